@@ -2,7 +2,7 @@
 """bench.py — headline benchmark of BASELINE.json: Gelements/s of fused Q->DQ, BFP[8|8]{16}(SN) ("BFP16,
 group 16"), on a 4096x4096 bf16 tensor, and % of the MI355X HBM roofline.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c2|llama-shard] [--replays R]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c2|llama-shard] [--dump-outputs DIR] [--full [--replays R]]
   python bench.py --workload layer --model opt125m|llama|whisper    one configured model layer end to end (tools/bench_layer.py)
   python bench.py --gpus 2|4|8 ...   starts its own N ranks: with no WORLD_SIZE in the environment the parent (which never
                                      touches the GPU) runs `python -m torch.distributed.run --nnodes=1 --nproc-per-node N
@@ -23,14 +23,17 @@ Workloads (one process per GPU, no data-path collective: SURVEY.md §8e)
   Outside the timed region the output shards are RCCL-all_gathered once and rank 0 asserts bit-equality with its own
   whole-tensor result (shard -> op -> concat == op on the whole).
 
-Timing: W eager warm-up steps; the K steps are enqueued either as K eager C-ABI calls (K <= 64) or as one replay of a
-hipGraph captured from them (larger K; one untimed replay first: graph upload).  Then R wall-clock regions of exactly K
-steps, each bracketed by barrier + synchronize on both sides, per region the MAX over ranks; `ms_per_step` / `value` come
-from the MEDIAN region (`config.replays`, `config.replay_ms` list them all).  Then R HIP-event regions of the same K steps
-for the roofline (events on the launch stream; a queued device-side delay in front of the first event keeps host enqueue
-latency out of the events).
+Timing: W eager warm-up steps; the K steps are enqueued either as K eager C-ABI calls (K <= 64) or as replays of hipGraphs
+captured from them (larger K: one graph of up to CHUNK steps replayed K // CHUNK times, one of the remaining steps; each replayed
+once untimed first: graph upload).  A plain run then times ONE wall-clock region of exactly K steps, bracketed by barrier +
+synchronize on both sides, the MAX over ranks: `ms_per_step` = region / K, `value` = elements / step time.  `--dump-outputs DIR`
+then writes what the last timed step computed (Workload.dump).
 
-The JSON line carries
+`--full` adds everything else: R wall-clock regions instead of one (`ms_per_step` / `value` from the MEDIAN region,
+`config.replays`, `config.replay_ms` list them all) after 10 untimed ones, the other `--sync` form, regions of 10 K steps, R
+HIP-event regions of the same K steps for the roofline (events on the launch stream; a queued device-side delay in front of the
+first event keeps host enqueue latency out of the events), the cache-resident rate, the output checks against the oracle and the
+reference's digests, the second tier (tools/bench_tier2.py) and the CPU baseline.  With --full the JSON line carries
   roofline     : algorithmic bytes per launch / average launch duration, measured with HIP events on the launch stream
                  over the same timed replays, vs 8.0 TB/s peak HBM.  `kernel` is what the library's dispatcher reports
                  for this call (dmxq_bfp_qdq_describe), `traffic` is labelled with its source.
@@ -46,6 +49,8 @@ import statistics
 import sys
 import time
 
+import numpy as np
+
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
@@ -55,6 +60,8 @@ ROWS = COLS = 4096
 BLOCK, PRECISION = 16, 8
 PEAK_HBM = 8.0e12  # B/s, MI355X HBM3E spec (/opt/skills/guides/MI355X_MICROARCH.md)
 BYTES_PER_ELEM = 4  # bf16 in + bf16 out (CastTo contract, numerical/cast.py:262,306)
+CHUNK = 2000        # steps per captured hipGraph: a larger K replays it K // CHUNK times (capture and upload stay bounded)
+DUMP_ELEMS = 1 << 23  # --dump-outputs: float32 elements written per rank and step at most (32 MiB)
 # Llama-3-8B decoder layer (hidden 4096, 32 heads / 8 KV heads, intermediate 14336): [out_features, in_features]
 LLAMA_LAYER = [("q_proj", 4096, 4096), ("k_proj", 1024, 4096), ("v_proj", 1024, 4096), ("o_proj", 4096, 4096),
                ("gate_proj", 14336, 4096), ("up_proj", 14336, 4096), ("down_proj", 4096, 14336)]
@@ -72,7 +79,13 @@ def parse():
     ap.add_argument("--op", choices=["hypernet", "hypernet-each", "bfp"], default="hypernet",
                     help="llama-shard only.  hypernet: the rank's seven weight shards in ONE launch (dmxq_weight_hypernet_multi); "
                          "hypernet-each: one dmxq_weight_hypernet launch per weight (rounds 2-3); bfp: plain BFP16_16 per weight")
-    ap.add_argument("--replays", type=int, default=15, help="timed replays of the K-step graph (median reported)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: repeated regions (median reported), roofline events, output checks, cache-resident "
+                         "rate, second tier, CPU baseline.  Off: set up, warm up, time the K steps once, dump, print the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy (float32; rows beyond a 32 MiB budget are a "
+                         "fixed, seeded sample)")
+    ap.add_argument("--replays", type=int, default=15, help="--full: timed regions of K steps (median reported)")
     ap.add_argument("--nbuf", type=int, default=20, help="c2: distinct in/out buffer pairs (20 x 64 MiB = 1.25 GiB)")
     ap.add_argument("--layers", type=int, default=2, help="llama-shard: distinct layer copies rotated over")
     ap.add_argument("--launch", choices=["auto", "graph", "eager"], default="auto",
@@ -372,6 +385,23 @@ class Workload:
             if rc != 0:
                 raise RuntimeError(f"{name} failed: {rc}")
 
+    def dump(self, slot, path):
+        """--dump-outputs: what step `slot` computed on this rank, as float32 DIR/<name>.npy (c2: `out`; llama-shard: one file per
+        weight shard, named after the weight; `_rank<r>` appended when N > 1).  A tensor beyond its share of DUMP_ELEMS is written as
+        a sample of whole rows: the row indices are drawn with a fixed seed and sorted, so every run writes the same rows."""
+        if self.args.workload in ("c2", "replica"):
+            outs = {"out": self.outs[slot % len(self.outs)]}
+        else:
+            outs = {nm: out for nm, _, _, _, _, _, out in self.layers[slot % len(self.layers)]}
+        os.makedirs(path, exist_ok=True)
+        tag = f"_rank{self.rank}" if self.world > 1 else ""
+        share = DUMP_ELEMS // len(outs)
+        for nm, t in outs.items():
+            if t.numel() > share:
+                rows = torch.randperm(t.shape[0], generator=torch.Generator().manual_seed(0))[:max(1, share // t.shape[1])]
+                t = t[rows.sort().values.to(t.device)]
+            np.save(os.path.join(path, nm + tag + ".npy"), t.float().cpu().numpy())
+
     def check(self, dist):
         """Outside the timed region.  (1) EVERY rotation slot is launched once more and its output compared, bit for bit, with
         the CPU oracle (oracle/oracle.c: the checker, never the thing measured) and -- for the portable inputs -- with the SHA-256
@@ -532,7 +562,7 @@ def main():
 
     L = _lib.lib()  # raises if libdmxq.so is missing: no fallback
     wl = Workload(args, L, _lib, rank, world, dev)
-    K, R = args.steps, max(1, args.replays)
+    K, R = args.steps, (max(1, args.replays) if args.full else 1)
     if args.no_graph:
         args.launch = "eager"
     if args.launch == "auto":
@@ -554,18 +584,26 @@ def main():
             wl.launch(i, sp)
         graph = None
         if not args.no_graph:
+            # a chunk is a whole number of rotations, so that chunk after chunk launches the slots K eager steps would
+            chunk = len(wl.calls) * max(1, CHUNK // len(wl.calls))
             torch.cuda.synchronize(dev)
-            graph = torch.cuda.CUDAGraph()
-            # thread_local: with RCCL initialised (N > 1) its watchdog thread polls events while we capture; only calls
-            # made by THIS thread belong to the capture
-            with torch.cuda.graph(graph, stream=stream, capture_error_mode="thread_local"):
-                for i in range(K):
-                    wl.launch(i, sp)
-            graph.replay()  # untimed: the first replay uploads the graph
+
+            def capture(n):
+                g = torch.cuda.CUDAGraph()
+                # thread_local: with RCCL initialised (N > 1) its watchdog thread polls events while we capture; only calls
+                # made by THIS thread belong to the capture
+                with torch.cuda.graph(g, stream=stream, capture_error_mode="thread_local"):
+                    for i in range(n):
+                        wl.launch(i, sp)
+                g.replay()  # untimed: the first replay uploads the graph
+                return g
+
+            graph = ([capture(chunk)] * (K // chunk) if K >= chunk else []) + ([capture(K % chunk)] if K % chunk else [])
             torch.cuda.synchronize(dev)
         def run_k():
             if graph is not None:
-                graph.replay()
+                for g in graph:
+                    g.replay()
             else:
                 for i in range(K):
                     wl.launch(i, sp)
@@ -591,15 +629,15 @@ def main():
         if args.workload in ("c2", "replica"):
             for i in range(args.preheat):   # untimed: the GPU sat idle while the host generated and checked inputs
                 wl.launch(i, sp)
-        for _ in range(10):          # untimed regions
+        for _ in range(10 if args.full else 0):   # untimed regions
             region(poll)
         for _ in range(R):
             walls.append(region(poll))
-        walls_alt = [region(not poll) for _ in range(R)]
+        walls_alt = [region(not poll) for _ in range(R if args.full else 0)]
         # (a') the same regions with 10 K steps (eager launches only): a region carries ~13 us that are not kernel time, 0.65 us per
         # step at the driver's K = 20 and 0.07 at 200 -- reported side by side, never as `value`
         walls_10x = []
-        if graph is None and K * 10 * wl.launches_per_step <= 4096:
+        if args.full and graph is None and K * 10 * wl.launches_per_step <= 4096:
             def region_10x():
                 barrier()
                 t0 = time.perf_counter()
@@ -615,24 +653,27 @@ def main():
         # short device-side delay is queued in front of the first event so that the host has finished enqueueing the
         # region before the GPU reaches it: the events then bracket back-to-back kernel execution and not the
         # host's graph-launch latency (~15 us per replay, i.e. ~0.8 us per step at K = 20, which (a) rightly includes)
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record(stream)
-        torch.cuda._sleep(2_000_000)
-        e1.record(stream)
-        torch.cuda.synchronize(dev)
-        cycles_per_us = 2_000_000 / max(e0.elapsed_time(e1) * 1e3, 1e-3)
-        delay = int(cycles_per_us * (60.0 if graph is not None else 15.0 * min(K, 200)))
-        for _ in range(R):
-            barrier()
-            torch.cuda._sleep(delay)
-            for i in range(args.preroll):
-                wl.launch(K + i, sp)
+        if args.full:
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             e0.record(stream)
-            run_k()
+            torch.cuda._sleep(2_000_000)
             e1.record(stream)
             torch.cuda.synchronize(dev)
-            evs.append(e0.elapsed_time(e1) / 1e3)
+            cycles_per_us = 2_000_000 / max(e0.elapsed_time(e1) * 1e3, 1e-3)
+            delay = int(cycles_per_us * (60.0 if graph is not None else 15.0 * min(K, 200)))
+            for _ in range(R):
+                barrier()
+                torch.cuda._sleep(delay)
+                for i in range(args.preroll):
+                    wl.launch(K + i, sp)
+                e0.record(stream)
+                run_k()
+                e1.record(stream)
+                torch.cuda.synchronize(dev)
+                evs.append(e0.elapsed_time(e1) / 1e3)
         barrier()
+    if args.dump_outputs:   # every later launch of a slot recomputes the same values: this is what step K - 1 computed
+        wl.dump(K - 1, args.dump_outputs)
 
     cdev = "cpu" if args.dist_backend == "gloo" else dev
     if walls_10x:
@@ -640,25 +681,30 @@ def main():
         if dist is not None:
             dist.all_reduce(t10, op=dist.ReduceOp.MAX)
         walls_10x = t10.tolist()
-    t = torch.tensor([walls, evs, walls_alt], device=cdev, dtype=torch.float64)
+    t = torch.tensor([walls, evs, walls_alt] if args.full else [walls], device=cdev, dtype=torch.float64)
     elems = torch.tensor([float(wl.elems_per_step_rank)], device=cdev, dtype=torch.float64)
-    # every rank's OWN median region and element count, side by side with the max-over-ranks figure (round 6): a straggler shows as a
-    # low per-rank minimum instead of only lowering the total
-    mine = torch.tensor([statistics.median(walls), statistics.median(evs), float(wl.elems_per_step_rank)], device=cdev, dtype=torch.float64)
-    per_rank = [mine]
-    if dist is not None:
-        per_rank = [torch.zeros_like(mine) for _ in range(world)]
-        dist.all_gather(per_rank, mine)
+    per_rank = None
+    if args.full:
+        # every rank's OWN median region and element count, side by side with the max-over-ranks figure (round 6): a straggler shows
+        # as a low per-rank minimum instead of only lowering the total
+        mine = torch.tensor([statistics.median(walls), statistics.median(evs), float(wl.elems_per_step_rank)], device=cdev, dtype=torch.float64)
+        per_rank = [mine]
+        if dist is not None:
+            per_rank = [torch.zeros_like(mine) for _ in range(world)]
+            dist.all_gather(per_rank, mine)
     if dist is not None:
         dist.all_reduce(t, op=dist.ReduceOp.MAX)   # per replay: the slowest rank
         dist.all_reduce(elems, op=dist.ReduceOp.SUM)
-    walls, evs, walls_alt = t[0].tolist(), t[1].tolist(), t[2].tolist()
-    wall_med, ev_med = statistics.median(walls), statistics.median(evs)
+    walls = t[0].tolist()
+    wall_med = statistics.median(walls)
+    if args.full:
+        evs, walls_alt = t[1].tolist(), t[2].tolist()
+        ev_med = statistics.median(evs)
     total_elems = float(elems[0])
 
     # cache-resident rate (one buffer pair, 64 MiB < 256 MiB Infinity Cache): always on record, never `value`
     resident = None
-    if args.workload in ("c2", "replica") and not args.no_resident:
+    if args.full and args.workload in ("c2", "replica") and not args.no_resident:
         with torch.cuda.stream(stream):
             for _ in range(50):
                 wl.launch(0, sp)
@@ -670,29 +716,11 @@ def main():
             torch.cuda.synchronize(dev)
         resident = wl.elems_per_step_rank * world / (r0.elapsed_time(r1) / 300 * 1e-3) / 1e9
 
-    checked = None if args.no_check else wl.check(dist)
+    checked = wl.check(dist) if args.full and not args.no_check else None
 
     if rank == 0:
         ms_per_step = wall_med * 1e3 / K
         value = total_elems / (wall_med / K) / 1e9
-        step_s = ev_med / K
-        launch_s = step_s / wl.launches_per_step
-        achieved = wl.bytes_per_step / step_s
-        traffic, traffic_src = None, None
-        for fn in ("r05_traffic.json", "r04_traffic.json", "r03_traffic.json", "r02_traffic.json", "r01_traffic.json"):
-            tp = os.path.join(ROOT, "profiles", fn)
-            if os.path.exists(tp) and args.workload != "llama-shard":
-                try:
-                    traffic = json.load(open(tp)).get("hbm_bytes_per_launch")
-                    traffic_src = f"profiles/{fn} (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE, separate passes, committed; NOT measured in this run)"
-                    break
-                except Exception:
-                    pass
-        kernel = None
-        if wl.describe_args is not None and hasattr(L, "dmxq_bfp_qdq_describe"):
-            buf = ctypes.create_string_buffer(256)
-            if L.dmxq_bfp_qdq_describe(*wl.describe_args, 1, buf, 256) == 0:
-                kernel = buf.value.decode()
         line = {
             "metric": "Gelements/s fused Q->DQ (BFP16, group=16) on 4096x4096 bf16" if args.workload != "llama-shard"
                       else "Gelements/s over row-sharded Llama-3-8B layer weights",
@@ -703,46 +731,69 @@ def main():
                        "buffers": (f"{args.nbuf} rotating in/out pairs = {args.nbuf * 2 * ROWS * COLS * 2 / 2**30:.2f} GiB per GPU "
                                    "(> 256 MiB Infinity Cache)") if args.workload != "llama-shard"
                                   else f"{args.layers} rotating layer copies ({wl.bytes_per_step / 2**20:.0f} MiB touched per step on this rank)",
-                       "launch": "K eager C-ABI calls per region" if args.no_graph else "one hipGraph replay of the K steps' C-ABI launches per region",
+                       "launch": ("K eager C-ABI calls per region" if args.no_graph else
+                                  f"hipGraph replays of the K steps' C-ABI launches per region ({len(graph)} of up to {CHUNK} steps)"),
                        "launches_per_step": wl.launches_per_step,
                        "replays": R,
                        "replay_ms": [round(w * 1e3, 4) for w in walls],
                        "sync": ("region end = hipStreamQuery spin until the stream is drained, then torch.cuda.synchronize()"
                                 if args.sync == "poll" else "region end = blocking torch.cuda.synchronize()"),
-                       "sync_alt": {"sync": "block" if args.sync == "poll" else "poll",
-                                    "ms_per_step": round(statistics.median(walls_alt) * 1e3 / K, 6),
-                                    "value": round(total_elems / (statistics.median(walls_alt) / K) / 1e9, 2)},
-                       "at_10x_steps": ({"steps": 10 * K, "ms_per_step": round(statistics.median(walls_10x) * 1e3 / (10 * K), 6),
-                                         "value": round(total_elems / (statistics.median(walls_10x) / (10 * K)) / 1e9, 2),
-                                         "note": "the same eager launches in regions of 10 K steps: the ~13 us a region carries besides "
-                                                 "kernel time weigh a tenth as much; informative, `value` is the K-step figure"}
-                                        if walls_10x else None),
                        "dist_backend": (args.dist_backend + (" (harness-only transport; ranks share GPUs: not a scaling figure)"
                                                              if args.dist_backend == "gloo" else " (RCCL)")) if dist is not None else None,
                        "input": ("tests/_data.py make('heavy', (4096, 4096), seed = 1000 rank + slot, bf16): counter-based, host-generated"
                                  if args.input == "portable" else "torch.randn on the device") if args.workload != "llama-shard"
                                 else ("layer copy 0: tests/_data.py make('heavy' | 'uniform', rows of the shard, seed = 7700 + t | 5000 + t, bf16), counter-based, "
                                       "host-generated; other copies: torch.randn on the device" if args.input == "portable" else "torch.randn on the device"),
-                       "timing": "one untimed replay, then R wall-clock regions of exactly K steps (barrier+sync, K steps, sync; "
-                                 "max over ranks; median region -> ms_per_step, value) and R HIP-event regions of the same K steps "
-                                 "(events on the launch stream, a queued device-side delay in front so that host launch latency is "
-                                 "not inside the events; median region -> roofline)",
-                       "per_gpu_elements_per_step": wl.elems_per_step_rank,
-                       "per_rank": {"value": [round(float(p[2]) / (float(p[0]) / K) / 1e9, 2) if float(p[2]) > 0 else 0.0 for p in per_rank],
-                                    "value_min": round(min((float(p[2]) / (float(p[0]) / K) / 1e9) for p in per_rank), 2),
-                                    "value_max": round(max((float(p[2]) / (float(p[0]) / K) / 1e9) for p in per_rank), 2),
-                                    "event_us_per_step": [round(float(p[1]) * 1e6 / K, 3) for p in per_rank],
-                                    "note": "each rank's own elements per step / its own median wall-clock region (Gelements/s); `value` is "
-                                            "all ranks' elements / the per-region maximum over ranks"},
-                       "check": checked},
-            "roofline": {"bound": "hbm", "achieved": round(achieved / 1e9, 1), "peak": PEAK_HBM / 1e9, "unit": "GB/s",
-                         "frac": round(achieved / PEAK_HBM, 4), "traffic": traffic, "traffic_source": traffic_src,
-                         "kernel": kernel, "kernel_source": "dmxq_bfp_qdq_describe (the dispatcher's own choice for this call)" if kernel else None,
-                         "algorithmic_bytes_per_launch": wl.bytes_per_step // wl.launches_per_step if wl.launches_per_step == 1 else None,
-                         "algorithmic_bytes_per_step": wl.bytes_per_step,
-                         "avg_launch_us": round(launch_s * 1e6, 3),
-                         "event_us_per_step": [round(e * 1e6 / K, 3) for e in evs]},
+                       "timing": ("one untimed replay of each graph, then R wall-clock regions of exactly K steps (barrier+sync, K steps, sync; "
+                                  "max over ranks; median region -> ms_per_step, value) and R HIP-event regions of the same K steps "
+                                  "(events on the launch stream, a queued device-side delay in front so that host launch latency is "
+                                  "not inside the events; median region -> roofline)") if args.full else
+                                 ("one untimed replay of each graph, then one wall-clock region of exactly K steps (barrier+sync, K steps, "
+                                  "sync; max over ranks) -> ms_per_step, value"),
+                       "per_gpu_elements_per_step": wl.elems_per_step_rank},
         }
+        if args.full:
+            step_s = ev_med / K
+            launch_s = step_s / wl.launches_per_step
+            achieved = wl.bytes_per_step / step_s
+            traffic, traffic_src = None, None
+            for fn in ("r05_traffic.json", "r04_traffic.json", "r03_traffic.json", "r02_traffic.json", "r01_traffic.json"):
+                tp = os.path.join(ROOT, "profiles", fn)
+                if os.path.exists(tp) and args.workload != "llama-shard":
+                    try:
+                        traffic = json.load(open(tp)).get("hbm_bytes_per_launch")
+                        traffic_src = f"profiles/{fn} (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE, separate passes, committed; NOT measured in this run)"
+                        break
+                    except Exception:
+                        pass
+            kernel = None
+            if wl.describe_args is not None and hasattr(L, "dmxq_bfp_qdq_describe"):
+                buf = ctypes.create_string_buffer(256)
+                if L.dmxq_bfp_qdq_describe(*wl.describe_args, 1, buf, 256) == 0:
+                    kernel = buf.value.decode()
+            line["config"].update({
+                "sync_alt": {"sync": "block" if args.sync == "poll" else "poll",
+                             "ms_per_step": round(statistics.median(walls_alt) * 1e3 / K, 6),
+                             "value": round(total_elems / (statistics.median(walls_alt) / K) / 1e9, 2)},
+                "at_10x_steps": ({"steps": 10 * K, "ms_per_step": round(statistics.median(walls_10x) * 1e3 / (10 * K), 6),
+                                  "value": round(total_elems / (statistics.median(walls_10x) / (10 * K)) / 1e9, 2),
+                                  "note": "the same eager launches in regions of 10 K steps: the ~13 us a region carries besides "
+                                          "kernel time weigh a tenth as much; informative, `value` is the K-step figure"}
+                                 if walls_10x else None),
+                "per_rank": {"value": [round(float(p[2]) / (float(p[0]) / K) / 1e9, 2) if float(p[2]) > 0 else 0.0 for p in per_rank],
+                             "value_min": round(min((float(p[2]) / (float(p[0]) / K) / 1e9) for p in per_rank), 2),
+                             "value_max": round(max((float(p[2]) / (float(p[0]) / K) / 1e9) for p in per_rank), 2),
+                             "event_us_per_step": [round(float(p[1]) * 1e6 / K, 3) for p in per_rank],
+                             "note": "each rank's own elements per step / its own median wall-clock region (Gelements/s); `value` is "
+                                     "all ranks' elements / the per-region maximum over ranks"},
+                "check": checked})
+            line["roofline"] = {"bound": "hbm", "achieved": round(achieved / 1e9, 1), "peak": PEAK_HBM / 1e9, "unit": "GB/s",
+                                "frac": round(achieved / PEAK_HBM, 4), "traffic": traffic, "traffic_source": traffic_src,
+                                "kernel": kernel, "kernel_source": "dmxq_bfp_qdq_describe (the dispatcher's own choice for this call)" if kernel else None,
+                                "algorithmic_bytes_per_launch": wl.bytes_per_step // wl.launches_per_step if wl.launches_per_step == 1 else None,
+                                "algorithmic_bytes_per_step": wl.bytes_per_step,
+                                "avg_launch_us": round(launch_s * 1e6, 3),
+                                "event_us_per_step": [round(e * 1e6 / K, 3) for e in evs]}
         if resident is not None:
             line["cache_resident_value"] = round(resident, 2)
         try:   # which library this line was measured on (tools/stamp.py: commit recorded in the build container, SHA-256 recomputed here)
@@ -753,7 +804,7 @@ def main():
             line["build"] = st.current()
         except Exception as e:   # noqa: BLE001
             line["build"] = {"error": repr(e)[:120]}
-        if world == 1 and args.workload == "c2" and not args.no_tier2:
+        if args.full and world == 1 and args.workload == "c2" and not args.no_tier2:
             # the second tier: configs 3 / 4 / 5's kernels and layers, AFTER the headline measurement above, in the
             # same process and the same driver-observed run; never raises (a failure is recorded in the entry it belongs to)
             try:
@@ -767,7 +818,7 @@ def main():
                                    log=lambda m: print("[tier2] " + m, file=sys.stderr, flush=True)))
             except Exception as e:   # noqa: BLE001
                 line["ops"] = {"error": f"{type(e).__name__}: {str(e)[:300]}"}
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(args.cpu_seconds)
         print(json.dumps(line), flush=True)
     if dist is not None:

@@ -276,7 +276,7 @@ def test_direct_entry_points_equal_the_dispatcher_ops(dmx, cuda):
 
 
 def test_bench_line_carries_the_second_tier_and_the_build_stamp():
-    """`python bench.py` at N = 1 times configs 3 / 4 / 5's kernels after the headline measurement and puts them into the ONE JSON line
+    """`python bench.py --full` at N = 1 times configs 3 / 4 / 5's kernels after the headline measurement and puts them into the ONE JSON line
     (`ops`: us / bytes / frac / check per op, each checked against the oracle outside the timed region), with the library's stamp
     (`build`).  Here with `--tier2-only basic` (one op) and no layers' worth of waiting."""
     import json
@@ -286,7 +286,7 @@ def test_bench_line_carries_the_second_tier_and_the_build_stamp():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
     p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "6", "--warmup", "2", "--replays", "3", "--nbuf", "4", "--preheat", "50",
-                        "--no-cpu-baseline", "--tier2-only", "basic"], cwd=root, env=env, capture_output=True, text=True, timeout=600)
+                        "--full", "--no-cpu-baseline", "--tier2-only", "basic"], cwd=root, env=env, capture_output=True, text=True, timeout=600)
     assert p.returncode == 0, p.stderr[-2000:]
     lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1
@@ -296,6 +296,39 @@ def test_bench_line_carries_the_second_tier_and_the_build_stamp():
     assert set(line["layers"]) == {"opt125m", "llama", "whisper"} and all("us_per_forward" in v for v in line["layers"].values())
     assert line["build"]["libdmxq_sha256"] and "4/4 slots == oracle" in line["config"]["check"]
     assert line["roofline"]["frac"] > 0 and line["value"] > 0
+
+
+def test_plain_bench_line_times_k_steps_once_and_dumps_the_last_step(oracle, tmp_path):
+    """`python bench.py` without --full: the headline fields, ONE timed region of exactly K steps, none of the --full extras, and
+    `--dump-outputs` writes what the last timed step computed: step K - 1 = rotation slot 5 % 4 = 1, a fixed sample of its rows,
+    bit-exact against the oracle on the same input rows."""
+    import json
+    import os
+    import subprocess
+    import sys
+
+    import numpy as np
+
+    from _data import make_chunked
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
+    p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "6", "--warmup", "2", "--nbuf", "4",
+                        "--dump-outputs", str(tmp_path)], cwd=root, env=env, capture_output=True, text=True, timeout=600)
+    assert p.returncode == 0, p.stderr[-2000:]
+    lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1
+    line = json.loads(lines[0])
+    assert line["steps"] == 6 and line["value"] > 0 and line["ms_per_step"] > 0 and line["unit"] == "Gelements/s"
+    assert line["higher_is_better"] is True and line["dtype"] == "f32" and line["metric"].startswith("Gelements/s")
+    assert line["config"]["replays"] == 1 and len(line["config"]["replay_ms"]) == 1
+    assert abs(line["config"]["replay_ms"][0] / 6 - line["ms_per_step"]) < 1e-3
+    assert not {"roofline", "ops", "layers", "cpu_baseline", "cache_resident_value"} & set(line) and "check" not in line["config"]
+    assert os.listdir(tmp_path) == ["out.npy"]
+    got = np.load(tmp_path / "out.npy")
+    assert got.dtype == np.float32 and got.shape == (2048, 4096)
+    rows = torch.randperm(4096, generator=torch.Generator().manual_seed(0))[:2048].sort().values
+    x = make_chunked("heavy", (4096, 4096), 1, torch.bfloat16)[rows]
+    assert bits_equal(torch.from_numpy(got), oracle.bfp_cast(x, 8, 16).to(torch.bfloat16).float()) == 0
 
 
 @pytest.mark.parametrize("binding", ["torch", "ctypes"])

@@ -1,9 +1,9 @@
 #!/usr/bin/env python3
 """tools/bench_tier2.py — the SECOND TIER of bench.py's line (round 6): the kernels BASELINE.json configs 3 / 4 / 5
-exercise, timed inside the driver's own `python bench.py` run right after the headline (config 2) measurement, so that their numbers
+exercise, timed inside a `python bench.py --full` run right after the headline (config 2) measurement, so that their numbers
 are driver-observed and not only builder-run tables under profiles/.
 
-    python bench.py                       -> the one JSON line gains  "ops": {name: {us, bytes, GB/s, frac, check, ...}}
+    python bench.py --full                -> the one JSON line gains  "ops": {name: {us, bytes, GB/s, frac, check, ...}}
                                                                       "layers": {model: {live: {eager, graph}, ...}}
     python tools/bench_tier2.py [--only c3,c5] [--no-layers]          the same dict, stand-alone (pretty-printed)
 

@@ -15,21 +15,21 @@ echo "$STAMP" > $OUT/STAMP.txt
 txt() { local f=$1; shift; { echo "$STAMP"; echo "# command: $*"; "$@" 2>&1 | grep -v amdgpu.ids; } > $OUT/$f; }
 # 1. bench lines: the driver's configuration (three runs), the default one, the sharded Llama workloads, the N > 1 path on real kernels with
 #    the box's single GPU (ranks share cuda:0 over gloo), a 1-rank torchrun (RCCL init path), the self-launch path
-python3 bench.py --steps 20 --warmup 5 > $OUT/bench_line_steps20.json 2> $OUT/bench.err
-for i in 2 3; do python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-tier2 > $OUT/bench_line_steps20_run$i.json 2>> $OUT/bench.err; done
-python3 bench.py --no-cpu-baseline --no-tier2 > $OUT/bench_line_default.json 2>> $OUT/bench.err
-python3 bench.py --gpus 2 --dist-backend gloo --steps 20 --warmup 5 --no-cpu-baseline > $OUT/bench_line_world2_gloo.json 2>> $OUT/bench.err
-python3 bench.py --gpus 8 --dist-backend gloo --nbuf 4 --steps 20 --warmup 5 --no-cpu-baseline > $OUT/bench_line_world8_gloo.json 2>> $OUT/bench.err
-python3 bench.py --gpus 8 --dist-backend gloo --workload llama-shard --op hypernet --layers 1 --steps 20 --warmup 5 --no-cpu-baseline > $OUT/bench_line_world8_gloo_llama_hypernet.json 2>> $OUT/bench.err
-python3 bench.py --workload llama-shard --steps 20 --warmup 5 --no-cpu-baseline > $OUT/bench_line_llama_hypernet.json 2>> $OUT/bench.err
-python3 bench.py --workload llama-shard --op bfp --steps 20 --warmup 5 --no-cpu-baseline > $OUT/bench_line_llama_bfp.json 2>> $OUT/bench.err
-python3 -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29511 bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --no-tier2 > $OUT/bench_line_torchrun1.json 2>> $OUT/bench.err
-python3 bench.py --gpus 1 --spawn --steps 20 --warmup 5 --no-cpu-baseline --no-tier2 > $OUT/bench_line_spawn1.json 2>> $OUT/bench.err
+python3 bench.py --full --steps 20 --warmup 5 > $OUT/bench_line_steps20.json 2> $OUT/bench.err
+for i in 2 3; do python3 bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-tier2 > $OUT/bench_line_steps20_run$i.json 2>> $OUT/bench.err; done
+python3 bench.py --full --no-cpu-baseline --no-tier2 > $OUT/bench_line_default.json 2>> $OUT/bench.err
+python3 bench.py --full --gpus 2 --dist-backend gloo --steps 20 --warmup 5 --no-cpu-baseline > $OUT/bench_line_world2_gloo.json 2>> $OUT/bench.err
+python3 bench.py --full --gpus 8 --dist-backend gloo --nbuf 4 --steps 20 --warmup 5 --no-cpu-baseline > $OUT/bench_line_world8_gloo.json 2>> $OUT/bench.err
+python3 bench.py --full --gpus 8 --dist-backend gloo --workload llama-shard --op hypernet --layers 1 --steps 20 --warmup 5 --no-cpu-baseline > $OUT/bench_line_world8_gloo_llama_hypernet.json 2>> $OUT/bench.err
+python3 bench.py --full --workload llama-shard --steps 20 --warmup 5 --no-cpu-baseline > $OUT/bench_line_llama_hypernet.json 2>> $OUT/bench.err
+python3 bench.py --full --workload llama-shard --op bfp --steps 20 --warmup 5 --no-cpu-baseline > $OUT/bench_line_llama_bfp.json 2>> $OUT/bench.err
+python3 -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29511 bench.py --full --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --no-tier2 > $OUT/bench_line_torchrun1.json 2>> $OUT/bench.err
+python3 bench.py --full --gpus 1 --spawn --steps 20 --warmup 5 --no-cpu-baseline --no-tier2 > $OUT/bench_line_spawn1.json 2>> $OUT/bench.err
 for mdl in opt125m llama whisper; do python3 bench.py --workload layer --model $mdl > $OUT/layer_$mdl.json 2>> $OUT/bench.err; done
 # 2. rocprofv3 kernel statistics of the driver's command (second tier included: its kernels are in the same table), and the two HBM
 #    traffic passes of the headline kernel (separate, --kernel-trace only)
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --stats -d $OUT/prof_bench -o run --output-format csv -- python3 $R/bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-resident --no-check > $OUT/prof_bench.log 2>&1
+rocprofv3 --kernel-trace --stats -d $OUT/prof_bench -o run --output-format csv -- python3 $R/bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-resident --no-check > $OUT/prof_bench.log 2>&1
 for mdl in opt125m llama whisper; do
   rocprofv3 --kernel-trace --stats -d $OUT/prof_layer_$mdl -o run --output-format csv -- python3 $R/bench.py --workload layer --model $mdl --layer-modes live > $OUT/prof_layer_$mdl.log 2>&1
   { echo "$STAMP"; python3 $R/tools/bench_layer.py --summarise $OUT/prof_layer_$mdl; } > $OUT/layer_shares_$mdl.txt 2>&1
@@ -64,7 +64,7 @@ for f in glob.glob(os.path.join(out, "prof_bench", "**", "*kernel_stats.csv"), r
     rows = list(csv.reader(open(f)))
     keep = [rows[0]] + [r for r in rows[1:] if "dmxq" in r[0]]
     with open(os.path.join(out, "bench_kernel_stats.csv"), "w") as g:
-        g.write(stamp + "\n# rocprofv3 --kernel-trace --stats -- python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-resident --no-check (second tier included)\n")
+        g.write(stamp + "\n# rocprofv3 --kernel-trace --stats -- python3 bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-resident --no-check (second tier included)\n")
         csv.writer(g).writerows(keep)
 PY
 rm -rf $OUT/prof_bench $OUT/pmc_fetch $OUT/pmc_write
