@@ -651,3 +651,43 @@ def norm_cast(x, cols, weight, bias, eps, kind, cast_in, cast_out, bfp_block=0, 
         check(L.dmxq_layernorm_cast(ptr(xc), ptr(out), dtype_code(xc.dtype), rows, cols, ptr(w), ptr(b), float(eps), *ptrs, stream_of(xc)),
               "dmxq_layernorm_cast")
     return out
+
+
+# ------------------------------------------------------------------------------------------------ GPTQ
+def _gptq_matrix(t, w, name):
+    if not (t.is_cuda and t.device == w.device and t.dtype == torch.float32 and t.dim() == 2 and (t.shape[1] <= 1 or t.stride(1) == 1)):
+        raise RuntimeError(f"gptq_block: {name} must be a float32 matrix with unit column stride on w's GPU")
+
+
+@_guarded
+def gptq_block(w, hinv, inv_d, microblock, fmt, scale, zero_point, q, err):
+    require_gpu(w, "gptq_block")
+    for t, name in ((w, "w"), (hinv, "hinv"), (q, "q"), (err, "err")):
+        _gptq_matrix(t, w, name)
+    if len(fmt) != 12:
+        raise RuntimeError("gptq_block: fmt is the 12 fields of dmxq_gptq_format")
+    if microblock < 1:
+        raise RuntimeError("gptq_block: microblock must be positive")
+    rows, count = w.shape
+    nmb = -(-count // microblock)
+    if tuple(q.shape) != (rows, count) or tuple(err.shape) != (rows, count) or tuple(hinv.shape) != (count, count):
+        raise RuntimeError("gptq_block: w, q, err must be [rows, count] and hinv [count, count]")
+    if not (inv_d.is_cuda and inv_d.device == w.device and inv_d.dtype == torch.float32 and inv_d.is_contiguous()
+            and inv_d.numel() == nmb * microblock * microblock):
+        raise RuntimeError(f"gptq_block: inv_d must be a contiguous float32 [{nmb}, {microblock}, {microblock}] tensor on w's GPU")
+    if scale is not None and not (scale.is_cuda and scale.device == w.device and scale.dtype == torch.float32 and scale.is_contiguous()):
+        raise RuntimeError("gptq_block: scale must be a contiguous float32 tensor on w's GPU")
+    if zero_point is not None and not (zero_point.is_cuda and zero_point.device == w.device and zero_point.dtype == torch.int64
+                                       and zero_point.is_contiguous()):
+        raise RuntimeError("gptq_block: zero_point must be a contiguous int64 tensor on w's GPU")
+    f = _lib.GptqFormat(*[int(v) for v in fmt])
+    if f.kind == _lib.GPTQ_FIXED:
+        need = rows if f.per_row else 1
+        if scale is None or zero_point is None or scale.numel() < need or zero_point.numel() < need:
+            raise RuntimeError("gptq_block: a fixed point cast needs its scale and zero point (one per row when per_row)")
+
+    def ld(t):
+        return max(t.stride(0), count) if t.shape[0] <= 1 else t.stride(0)
+
+    check(lib().dmxq_gptq_block(ptr(w), ld(w), ptr(q), ld(q), ptr(err), ld(err), rows, count, ptr(hinv), ld(hinv), ptr(inv_d), microblock,
+                                ctypes.byref(f), ptr(scale), ptr(zero_point), stream_of(w)), "dmxq_gptq_block")

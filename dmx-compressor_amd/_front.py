@@ -20,7 +20,7 @@ from ._lib import DmxqError, ROUNDING_CODE, require_gpu
 __all__ = [
     "bfp_qdq", "block_quantize", "bfp_qdq_multi", "bfp_pack", "bfp_unpack", "weight_hypernet", "weight_hypernet_multi", "input_hypernet", "binary_cast", "rope_cast", "relu_cast", "unary_cast", "unary_cast_table", "lut16_apply", "softmax_cast", "layernorm_cast", "rmsnorm_cast", "sbfp_qdq", "mxfp_qdq", "float_qdq", "float_qdq_multi", "fixed_qdq", "fixed_qdq_multi", "fixed_float_qdq_multi", "nm_mask", "nm_sparsify", "topk_mask", "topk_sparsify", "bernoulli_mask", "group_minmax", "group_minmax_accumulate", "qparams", "channel_maxabs",
     "smoothquant_scale", "scale_channels", "gelu", "silu", "quick_gelu", "exp", "silu_experimental", "rope", "softmax", "layernorm",
-    "rmsnorm", "histc",
+    "rmsnorm", "histc", "gptq_fields", "gptq_block",
 ]
 
 _ops = None   # the raw namespace: set by bind()
@@ -532,3 +532,33 @@ def rmsnorm_cast(x, normalized_shape, weight=None, eps: Optional[float] = None, 
                               int(then_bfp[1]) if then_bfp else 0, int(then_bfp[0]) if then_bfp else 0)
     except NotImplementedError:
         return None
+
+
+# ---------------------------------------------------------------------------------------------------- GPTQ
+def gptq_fields(fmt, per_row: bool = False):
+    """The dmxq_gptq_format fields (include/dmxq.h) of a weight format the fused GPTQ column kernel covers, or None: BFP (MXINT) with
+    nearest rounding and blocks of >= 2, FloatingPoint with nearest rounding and <= 22 mantissa bits, FixedPoint with nearest rounding
+    (per_row: one affine scale / zero point per output row, else one for the tensor)."""
+    from .format import BlockFloatingPoint, FixedPoint, FloatingPoint
+    if getattr(fmt, "rounding", None) != "nearest":
+        return None
+    if isinstance(fmt, BlockFloatingPoint):
+        if fmt.block_size < 2 or not 2 <= fmt.precision <= 22:
+            return None
+        return [0, fmt.precision, fmt.block_size, int(bool(fmt.symmetric)), 0, 0, 0, 0, 0, 0, 0, 0]
+    if isinstance(fmt, FloatingPoint):
+        if fmt.mantissa > 22:
+            return None
+        return [1, 0, 0, 0, fmt.mantissa, fmt.exponent, fmt.bias, int(bool(fmt.flush_subnormal)), int(bool(fmt.unsigned)), 0, 0, 0]
+    if isinstance(fmt, FixedPoint):
+        return [2, fmt.precision, 0, int(bool(fmt.symmetric)), 0, 0, 0, 0, 0, fmt.fraction, int(bool(fmt.clamp)), int(bool(per_row))]
+    return None
+
+
+def gptq_block(w, hinv, inv_d, q, err, microblock: int, fields, scale=None, zero_point=None):
+    """GPTQ's in-block column loop for one block of <= 128 columns in one launch (dmxq_gptq_block; layer_reconstruction.py:300-318):
+    w = W[:, i1:i2] (read only), hinv = Hinv[i1:i2, i1:i2], inv_d = the inverses of its diagonal microblocks [ceil(count / mb), mb, mb];
+    writes Q[:, i1:i2] into `q` and the error block into `err` (float32 views with unit column stride).  `fields`: gptq_fields(...).
+    NotImplementedError where the kernel does not take the format / microblock (the caller runs its own loop)."""
+    require_gpu(w, "gptq_block")
+    _ops.gptq_block(w, hinv, inv_d, int(microblock), [int(v) for v in fields], scale, zero_point, q, err)

@@ -69,6 +69,7 @@ SIGNATURES = {
     "dmxq_rope_cast": [_vp, _vp, _vp, _vp, _i32, _i64, _i64, _i64, _i64, _i32, _vp, _vp, _vp, _vp, _vp],
     "dmxq_softmax": [_vp, _vp, _i32, _i32, _i64, _i64, _f32, _vp],
     "dmxq_layernorm": [_vp, _vp, _i32, _i32, _i64, _i64, _vp, _vp, _i32, _f32, _vp],
+    "dmxq_gptq_block": [_vp, _i64, _vp, _i64, _vp, _i64, _i64, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp],
 }
 
 
@@ -90,6 +91,15 @@ class FloatFmt(ctypes.Structure):
 class AffineDesc(ctypes.Structure):
     """dmxq_affine_desc (include/dmxq.h)"""
     _fields_ = [("in_", _vp), ("out", _vp), ("scale", _vp), ("zero_point", _vp), ("outer", _i64), ("C", _i64), ("inner", _i64)]
+
+
+class GptqFormat(ctypes.Structure):
+    """dmxq_gptq_format (include/dmxq.h)"""
+    _fields_ = [("kind", _i32), ("precision", _i32), ("block_size", _i32), ("symmetric", _i32), ("man_bits", _i32), ("exp_bits", _i32),
+                ("exp_bias", _i32), ("flush_subnormal", _i32), ("unsigned_abs", _i32), ("fraction", _i32), ("clamp", _i32), ("per_row", _i32)]
+
+
+GPTQ_BFP, GPTQ_FLOAT, GPTQ_FIXED = 0, 1, 2
 
 
 class DmxqError(RuntimeError):

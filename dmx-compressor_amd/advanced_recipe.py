@@ -1,0 +1,51 @@
+"""ADVANCED-mode recipes (reference: advanced_recipe.py:14-40, 120-142): a hyperparameter generator maps a model to
+{DmxModule: hyperparams}, and `applied_to(model)` enters one module context manager per entry (an ExitStack), so that leaving the
+`with` block finishes every module's calibration / compression."""
+from contextlib import ExitStack, contextmanager
+from typing import Callable, Optional
+
+from .nn import DmxModule
+
+__all__ = ["DmxBaseRecipe", "DmxQuantizerCalibrationRecipe", "DmxSmoothQuantRecipe", "DmxGPTQRecipe"]
+
+
+class DmxBaseRecipe:
+    """hp_gen(model) -> {module: hyperparams}; subclasses set `recipe_context_manager` (an unbound DmxModule context manager)."""
+
+    def __init__(self, hp_gen: Callable, **kwargs):
+        self.generate_hyperparams = hp_gen
+        self.recipe_context_manager = None
+
+    @contextmanager
+    def applied_to(self, _model, save_checkpoint_to: Optional[str] = None):
+        _hyperparams = self.generate_hyperparams(_model)
+        with ExitStack() as stack:
+            try:
+                yield [stack.enter_context(self.recipe_context_manager(_m, _p)) for _m, _p in _hyperparams.items()]
+            finally:
+                if hasattr(_model, "_save_specific_layers_state_dict_and_register_urls"):
+                    _model._save_specific_layers_state_dict_and_register_urls(_hyperparams.keys(), save_checkpoint_to)
+
+
+class DmxQuantizerCalibrationRecipe(DmxBaseRecipe):
+    """fake quantizer calibration (DmxModule.calibrating_quantizers)"""
+
+    def __init__(self, hp_gen, **kwargs):
+        super().__init__(hp_gen, **kwargs)
+        self.recipe_context_manager = DmxModule.calibrating_quantizers
+
+
+class DmxSmoothQuantRecipe(DmxBaseRecipe):
+    """SmoothQuant calibration (DmxModule.calibrating_smoothquant)"""
+
+    def __init__(self, hp_gen, **kwargs):
+        super().__init__(hp_gen, **kwargs)
+        self.recipe_context_manager = DmxModule.calibrating_smoothquant
+
+
+class DmxGPTQRecipe(DmxBaseRecipe):
+    """GPTQ (DmxModule.optimal_brain_compressing)"""
+
+    def __init__(self, hp_gen, **kwargs):
+        super().__init__(hp_gen, **kwargs)
+        self.recipe_context_manager = DmxModule.optimal_brain_compressing

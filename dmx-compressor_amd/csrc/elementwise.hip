@@ -5,6 +5,7 @@
 //   * per-channel scaling      (numerical/smoothquant.py:255-283)
 // All share one skeleton: each lane moves 16 B of input per step (global_load_dwordx4), UNROLL steps in flight,
 // fp32 arithmetic, one RNE narrowing to the output dtype, 16-byte stores.  HBM-bound: 2+2 B/elem for 16-bit I/O.
+#include "fixedq.hpp"
 #include "floatq.hpp"
 #include "stream.hpp"
 #include "lastdim.hpp"
@@ -16,35 +17,7 @@ namespace dmxq {
 // ------------------------------------------------------------------------------------------------- float
 // (FloatFmt, float_q1 and the per-element cast of the fused modules: floatq.hpp)
 // ------------------------------------------------------------------------------------------------- fixed
-struct FixedFmt {
-  int sigma, clamp, rounding;
-  float t_min, t_max;
-  uint64_t seed;
-};
-
-// sim_helper.cpp:14-21 round(a, r, sigma): ldexp; a1 = (float)(a + r); nearbyint((double)a1 - 0.5) (half-even);
-// narrow to float; ldexp.  The fp32 add comes first — that is what makes 0.5 + 2^-24 round to 0 — and the
-// double subtraction is exact.  It is reproduced in fp32 only (no f64 VALU, half rate on gfx950):
-//   |a1| <  2^23 : a1 - 0.5f is exactly representable, rintf of it is the same integer;
-//   |a1| >= 2^23 : a1 is an integer, a1 - 0.5 is an exact tie between a1-1 and a1 -> the even one: a1 unless it
-//                  is odd (only possible below 2^24, where the mantissa LSB is the units bit), then a1 - 1.
-// sim_helper.cpp:24-38 for up (ceil) / down (floor).
-__device__ __forceinline__ float rne_minus_half(float a1) {
-  const float mag = fabsf(a1);
-  const float small = rintf(a1 - 0.5f);
-  const bool odd = (f2u(a1) & 1u) != 0u && mag < 16777216.0f;
-  const float big = odd ? a1 - 1.0f : a1;
-  return mag >= 8388608.0f ? big : small;
-}
-__device__ __forceinline__ float fixed_q1(float a, const FixedFmt& f, float r) {
-  a = ldexpf(a, -f.sigma);
-  if (f.rounding == DMXQ_ROUND_UP) a = ceilf(a);
-  else if (f.rounding == DMXQ_ROUND_DOWN) a = floorf(a);
-  else a = rne_minus_half(a + r);
-  a = ldexpf(a, f.sigma);
-  if (f.clamp) a = a > f.t_max ? f.t_max : (a < f.t_min ? f.t_min : a);
-  return a;
-}
+// (FixedFmt, fixed_q1: fixedq.hpp)
 
 __device__ __forceinline__ float rnd_unit(uint64_t seed, uint64_t idx) {
   return (float)(rnd_bits(seed, idx) >> 8) * (1.0f / 16777216.0f);

@@ -1,0 +1,237 @@
+// csrc/gptq.hip — GPTQ's in-block column loop (layer_reconstruction.py:300-318) for ONE column block of <= 128 columns in one launch.
+//
+// The reference runs that loop in Python: per microblock of columns, weight_hypernet on the [rows, m] slice, torch.linalg.inv of the
+// microblock's diagonal block of Hinv, two matmuls and slice copies -- at least 5 launches per column at microblock 1.  Here the host
+// keeps what is GEMM-shaped (Hessian, Cholesky factorisations, the batched inverse of the diagonal microblocks, the trailing update
+// W[:, i2:] -= E @ Hinv[i1:i2, i2:]) on torch's libraries, and this kernel does everything in between.
+//
+// Geometry: rows are independent given Hinv, so one LANE per weight row, one 64-lane wave per workgroup.  The workgroup's [64, count]
+// block of W is read along the rows into LDS (column-major, a lane's four columns in one 16-byte slot: the update reads and writes
+// them as one ds_read_b128 / ds_write_b128, conflict-free), next to the Hinv block (zero outside the upper triangle of
+// [count, count], read as wave-uniform broadcasts) and E; inv_d is read with wave-uniform loads; the current microblock (<= 64
+// columns) and its errors live in VGPRs.  Q overwrites W's columns as they become final, and Q and E leave along the rows at the
+// end.  No cross-lane traffic; 128 KiB of LDS per workgroup.  (A first form kept the whole row in VGPRs with the column loops
+// unrolled: at 128 columns the unroller gives up and the array goes to scratch.)
+//
+// Arithmetic order (every product and difference separately rounded: the library is built with -ffp-contract=off), with w the row's
+// block as it is updated, H = Hinv block, D = inv_d of the current microblock, m = min(MB, count - j1) the microblock's width:
+//   for each microblock j1 = 0, MB, 2 MB, ...:
+//     q_i   = cast(w[j1 .. j1 + m))_i                                  (the module's weight cast of the [rows, m] slice, bit for bit)
+//     d_i   = w_{j1+i} - q_i
+//     err_c = d_0 * D[0][c];  err_c = err_c + d_i * D[i][c]   for i = 1 .. m-1 in order
+//     for every later column k of the block:
+//       acc = err_0 * H[j1][k];  acc = acc + err_i * H[j1+i][k]   for i = 1 .. m-1 in order;  w_k = w_k - acc
+// At MB = 1 this is the reference's own order: q = cast(w_j), e = (w_j - q) * (1 / H[j][j]), w_k = w_k - e * H[j][k].
+// Formats (casts from bfp_math.hpp / floatq.hpp / fixedq.hpp, the literal reference forms; the per-column cast is a small share of
+// the O(count^2) update, so no fast forms are needed here):
+//   BFP    nearest rounding, symmetric or "(_N)"; blocks of `block_size` along the slice's columns from its first column (a ragged
+//          last microblock closes its last block early, torch.split semantics); block maxima are lane-local (one row per lane)
+//   FLOAT  nearest rounding
+//   FIXED  nearest rounding, affine x / sc + zp -> cast -> (x - zp) * sc with IEEE division (numerical/cast.py:278-296), the scale and
+//          zero point of the row (per-output-channel) or of the whole tensor
+#include "bfp_math.hpp"
+#include "fixedq.hpp"
+#include "floatq.hpp"
+
+namespace dmxq {
+
+constexpr int kGptqCols = 128;  // largest column block
+constexpr int kGptqRows = 64;   // rows per workgroup: one wave, one lane per row
+
+struct GptqCast {
+  int wl;         // BFP precision
+  uint64_t ends;  // BFP: bit i set <=> column i of a microblock closes a block
+  FloatFmt f;     // FLOAT
+  FixedFmt x;     // FIXED
+  int per_row;    // FIXED: scale / zero point indexed by row
+};
+
+// q[0 .. m) = cast of the slice w[0 .. m) of this lane's row
+template <int KIND, int MB, bool ASYM>
+__device__ __forceinline__ void gptq_cast(const float* w, int m, const GptqCast& c, float sc, float z, float* q) {
+  if constexpr (KIND == DMXQ_GPTQ_FLOAT) {
+#pragma unroll
+    for (int i = 0; i < MB; i++)
+      if (i < m) q[i] = float_q1<DMXQ_ROUND_NEAREST>(w[i], c.f, 0u);
+  } else if constexpr (KIND == DMXQ_GPTQ_FIXED) {
+#pragma unroll
+    for (int i = 0; i < MB; i++)
+      if (i < m) q[i] = (fixed_q1(w[i] / sc + z, c.x, 0.5f) - z) * sc;
+  } else {
+    // block maxima of |w| on the bit patterns (what the BFP kernels compare): a running maximum that restarts after each block end,
+    // then walked back so that every element sees the maximum of its whole block
+    uint32_t pm[MB];
+    uint32_t run = 0u;
+#pragma unroll
+    for (int i = 0; i < MB; i++) {
+      if (i < m) {
+        const uint32_t v = f2u(w[i]) & 0x7FFFFFFFu;
+        run = (i == 0 || ((c.ends >> (i - 1)) & 1u)) ? v : (run > v ? run : v);
+        pm[i] = run;
+      }
+    }
+    uint32_t bm = 0u;
+#pragma unroll
+    for (int i = MB - 1; i >= 0; i--) {
+      if (i < m) {
+        if (i == m - 1 || ((c.ends >> i) & 1u)) bm = pm[i];
+        const BfpBlockParams p = bfp_block_params<ASYM, false>(bm, c.wl);
+        q[i] = bfp_q1<DMXQ_ROUND_NEAREST, ASYM>(w[i], p, c.wl, DMXQ_ROUND_NEAREST, 0u);
+      }
+    }
+  }
+}
+
+template <int KIND, int MB, bool ASYM>
+__global__ __launch_bounds__(kGptqRows) void gptq_block_kernel(const float* __restrict__ wsrc, int64_t ldw, float* __restrict__ qdst,
+                                                             int64_t ldq, float* __restrict__ edst, int64_t lde, int64_t rows, int count,
+                                                             const float* __restrict__ hinv, int64_t ldh, const float* __restrict__ inv_d,
+                                                             const float* __restrict__ scale, const int64_t* __restrict__ zp, GptqCast c) {
+  __shared__ float4 hs[kGptqCols * kGptqCols / 4];  // Hinv block, row j = hs[j * 32 .. j * 32 + 32)
+  __shared__ float4 ws[kGptqCols / 4 * kGptqRows];  // the rows' block, columns 4 g .. 4 g + 3 of lane l at ws[g * 64 + l]; Q once final
+  __shared__ float es[kGptqCols * kGptqRows];       // E, column k of lane l at es[k * 64 + l]
+  float* const hf = (float*)hs;
+  float* const wf = (float*)ws;
+  const int lane = threadIdx.x;
+  const int64_t row0 = (int64_t)blockIdx.x * kGptqRows;
+  const int nr = rows - row0 < kGptqRows ? (int)(rows - row0) : kGptqRows;
+  // the Hinv block: upper triangle of rows j < count, columns k < count; zero elsewhere (rows >= count are never read)
+  for (int i = lane; i < count * kGptqCols; i += kGptqRows) {
+    const int j = i / kGptqCols, k = i % kGptqCols;
+    hf[i] = (k < count && k >= j) ? hinv[(int64_t)j * ldh + k] : 0.0f;
+  }
+  // the workgroup's rows, read along the rows (coalesced); rows past the last one, and the columns from `count` up to the next multiple
+  // of four (which the four-column update reads and writes, and nothing outputs), are zero
+  const int cpad = (count + 3) & ~3;
+  for (int i = lane; i < kGptqRows * cpad; i += kGptqRows) {
+    const int rl = i / cpad, k = i % cpad;
+    wf[((k >> 2) * kGptqRows + rl) * 4 + (k & 3)] = rl < nr && k < count ? wsrc[(row0 + rl) * ldw + k] : 0.0f;
+  }
+  float sc = 1.0f, z = 0.0f;
+  if constexpr (KIND == DMXQ_GPTQ_FIXED) {
+    const int64_t g = c.per_row ? row0 + (lane < nr ? lane : nr - 1) : 0;
+    sc = scale[g];
+    z = (float)zp[g];
+  }
+  __syncthreads();
+  auto col = [&](int k) -> float& { return wf[((k >> 2) * kGptqRows + lane) * 4 + (k & 3)]; };
+
+  for (int j1 = 0; j1 < count; j1 += MB) {
+    const int m = count - j1 < MB ? count - j1 : MB;
+    float x[MB], q[MB], e[MB];
+#pragma unroll
+    for (int i = 0; i < MB; i++) x[i] = i < m ? col(j1 + i) : 0.0f;
+    gptq_cast<KIND, MB, ASYM>(x, m, c, sc, z, q);
+#pragma unroll
+    for (int i = 0; i < MB; i++) {
+      if (i < m) col(j1 + i) = q[i];  // (the column is final: its slot now holds Q)
+      x[i] = i < m ? x[i] - q[i] : 0.0f;
+    }
+    const float* D = inv_d + (int64_t)(j1 / MB) * MB * MB;
+#pragma unroll
+    for (int cc = 0; cc < MB; cc++) {
+      e[cc] = 0.0f;
+      if (cc < m) {
+        float acc = x[0] * D[cc];
+#pragma unroll
+        for (int i = 1; i < MB; i++)
+          if (i < m) acc = acc + x[i] * D[i * MB + cc];
+        e[cc] = acc;
+        es[(j1 + cc) * kGptqRows + lane] = acc;
+      }
+    }
+    // the block's later columns, four at a time (only after a whole microblock: a ragged one is the block's last)
+    const int k1 = j1 + MB;
+    for (int k0 = k1 & ~3; k0 < count; k0 += 4) {
+      float acc[4];
+#pragma unroll
+      for (int i = 0; i < MB; i++) {
+        const float4 h = hs[(j1 + i) * (kGptqCols / 4) + (k0 >> 2)];
+        const float hv[4] = {h.x, h.y, h.z, h.w};
+#pragma unroll
+        for (int t = 0; t < 4; t++) acc[t] = i == 0 ? e[0] * hv[t] : acc[t] + e[i] * hv[t];
+      }
+      float4& wv = ws[(k0 >> 2) * kGptqRows + lane];
+      float4 v = wv;
+      float vv[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+      for (int t = 0; t < 4; t++)
+        if (k0 + t >= k1) vv[t] = vv[t] - acc[t];
+      wv = float4{vv[0], vv[1], vv[2], vv[3]};
+    }
+  }
+  __syncthreads();
+  // Q and E out, along the rows (coalesced)
+  for (int i = lane; i < nr * count; i += kGptqRows) {
+    const int rl = i / count, k = i % count;
+    qdst[(row0 + rl) * ldq + k] = wf[((k >> 2) * kGptqRows + rl) * 4 + (k & 3)];
+    edst[(row0 + rl) * lde + k] = es[k * kGptqRows + rl];
+  }
+}
+
+}  // namespace dmxq
+
+using namespace dmxq;
+
+extern "C" int dmxq_gptq_block(const float* w, int64_t ldw, float* q, int64_t ldq, float* err, int64_t lde, int64_t rows, int64_t count,
+                               const float* hinv, int64_t ldh, const float* inv_d, int64_t microblock, const dmxq_gptq_format* fmt,
+                               const float* scale, const int64_t* zero_point, void* stream) {
+  if (!fmt || rows < 0 || count < 0 || microblock < 1) return DMXQ_ERR_BAD_ARG;
+  if (fmt->kind != DMXQ_GPTQ_BFP && fmt->kind != DMXQ_GPTQ_FLOAT && fmt->kind != DMXQ_GPTQ_FIXED) return DMXQ_ERR_BAD_ARG;
+  if (rows == 0 || count == 0) return DMXQ_OK;
+  if (!w || !q || !err || !hinv || !inv_d || ldw < count || ldq < count || lde < count || ldh < count) return DMXQ_ERR_BAD_ARG;
+  if (rows >= ((int64_t)1 << 37)) return DMXQ_ERR_BAD_ARG;  // (grid of rows / 64 workgroups)
+  const int mb = (int)microblock;
+  if (count > kGptqCols || !(mb == 1 || mb == 8 || mb == 16 || mb == 32 || mb == 64)) return DMXQ_ERR_UNSUPPORTED;
+  GptqCast c{};
+  bool asym = false;
+  if (fmt->kind == DMXQ_GPTQ_BFP) {
+    const int B = fmt->block_size;
+    if (B < 2 || mb % B != 0 || fmt->precision < 2 || fmt->precision > 22) return DMXQ_ERR_UNSUPPORTED;
+    c.wl = fmt->precision;
+    for (int i = 0; i < mb; i++)
+      if ((i + 1) % B == 0) c.ends |= 1ull << i;
+    asym = fmt->symmetric == 0;
+  } else if (fmt->kind == DMXQ_GPTQ_FLOAT) {
+    if (fmt->exp_bits < 1 || fmt->exp_bits > 8 || fmt->man_bits < 0 || fmt->man_bits > 22) return DMXQ_ERR_UNSUPPORTED;
+    c.f = FloatFmt{fmt->man_bits, fmt->exp_bits, fmt->exp_bias, fmt->flush_subnormal ? 1 : 0, fmt->unsigned_abs ? 1 : 0,
+                   DMXQ_ROUND_NEAREST, 0ull};
+  } else {
+    if (!scale || !zero_point) return DMXQ_ERR_BAD_ARG;
+    if (fmt->precision < 1 || fmt->precision > 24) return DMXQ_ERR_UNSUPPORTED;
+    // sim_helper.cpp:5-12 fixed_min_max, evaluated on the host in the same float/double mix as dmxq_fixed_qdq
+    const int precision = fmt->precision, fraction = fmt->fraction, sigma = -fraction;
+    float t_min = (float)(-ldexp(1.0, precision - fraction - 1));
+    const float t_max = (float)(-(double)t_min - ldexp(1.0, sigma));
+    if (fmt->symmetric) t_min = (float)((double)t_min + ldexp(1.0, sigma));
+    c.x = FixedFmt{sigma, fmt->clamp ? 1 : 0, DMXQ_ROUND_NEAREST, t_min, t_max, 0ull};
+    c.per_row = fmt->per_row ? 1 : 0;
+  }
+  hipStream_t s = (hipStream_t)stream;
+  const dim3 grid((unsigned)((rows + kGptqRows - 1) / kGptqRows));
+#define DMXQ_GPTQ(K_, M_, A_) DMXQ_LAUNCH((gptq_block_kernel<K_, M_, A_>), grid, dim3(kGptqRows), 0, s, w, ldw, q, ldq, err, lde, rows, \
+                                          (int)count, hinv, ldh, inv_d, scale, zero_point, c)
+#define DMXQ_GPTQ_MB(K_, A_)                  \
+  switch (mb) {                               \
+    case 1: DMXQ_GPTQ(K_, 1, A_); break;      \
+    case 8: DMXQ_GPTQ(K_, 8, A_); break;      \
+    case 16: DMXQ_GPTQ(K_, 16, A_); break;    \
+    case 32: DMXQ_GPTQ(K_, 32, A_); break;    \
+    default: DMXQ_GPTQ(K_, 64, A_); break;    \
+  }
+  if (fmt->kind == DMXQ_GPTQ_FLOAT) {
+    DMXQ_GPTQ_MB(DMXQ_GPTQ_FLOAT, false);
+  } else if (fmt->kind == DMXQ_GPTQ_FIXED) {
+    DMXQ_GPTQ_MB(DMXQ_GPTQ_FIXED, false);
+  } else {
+    switch (mb) {  // (BFP blocks have >= 2 elements: no microblock of 1)
+      case 8: if (asym) DMXQ_GPTQ(DMXQ_GPTQ_BFP, 8, true); else DMXQ_GPTQ(DMXQ_GPTQ_BFP, 8, false); break;
+      case 16: if (asym) DMXQ_GPTQ(DMXQ_GPTQ_BFP, 16, true); else DMXQ_GPTQ(DMXQ_GPTQ_BFP, 16, false); break;
+      case 32: if (asym) DMXQ_GPTQ(DMXQ_GPTQ_BFP, 32, true); else DMXQ_GPTQ(DMXQ_GPTQ_BFP, 32, false); break;
+      default: if (asym) DMXQ_GPTQ(DMXQ_GPTQ_BFP, 64, true); else DMXQ_GPTQ(DMXQ_GPTQ_BFP, 64, false); break;
+    }
+  }
+#undef DMXQ_GPTQ_MB
+#undef DMXQ_GPTQ
+  return launch_status();
+}

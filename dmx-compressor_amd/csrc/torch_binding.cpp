@@ -817,6 +817,44 @@ Tensor norm_cast_meta(const Tensor& x, int64_t, const OptTensor&, const OptTenso
   return empty_like_shape(x, x.scalar_type());
 }
 
+// ------------------------------------------------------------------------------------------------ GPTQ
+// one column block of GPTQ's in-block loop (dmxq_gptq_block): q and err are written in place (views of the caller's Q and E)
+inline void gptq_matrix(const Tensor& t, const Tensor& w, const char* name) {
+  TORCH_CHECK(t.is_cuda() && t.device() == w.device() && t.scalar_type() == at::kFloat && t.dim() == 2 && (t.size(1) <= 1 || t.stride(1) == 1),
+              "gptq_block: ", name, " must be a float32 matrix with unit column stride on w's GPU");
+}
+void gptq_block(const Tensor& w, const Tensor& hinv, const Tensor& inv_d, int64_t microblock, at::IntArrayRef fmt, const OptTensor& scale,
+                const OptTensor& zero_point, Tensor q, Tensor err) {
+  TORCH_CHECK(w.is_cuda(), "gptq_block: tensor is on ", w.device(), "; dmx_compressor_amd runs on MI355X (HIP) tensors only and has no CPU fallback");
+  gptq_matrix(w, w, "w"); gptq_matrix(hinv, w, "hinv"); gptq_matrix(q, w, "q"); gptq_matrix(err, w, "err");
+  TORCH_CHECK(fmt.size() == 12, "gptq_block: fmt is the 12 fields of dmxq_gptq_format");
+  TORCH_CHECK(microblock >= 1, "gptq_block: microblock must be positive");
+  const int64_t rows = w.size(0), count = w.size(1), nmb = (count + microblock - 1) / microblock;
+  TORCH_CHECK(q.size(0) == rows && q.size(1) == count && err.size(0) == rows && err.size(1) == count && hinv.size(0) == count &&
+              hinv.size(1) == count, "gptq_block: w, q, err must be [rows, count] and hinv [count, count]");
+  TORCH_CHECK(inv_d.is_cuda() && inv_d.device() == w.device() && inv_d.scalar_type() == at::kFloat && inv_d.is_contiguous() &&
+              inv_d.numel() == nmb * microblock * microblock, "gptq_block: inv_d must be a contiguous float32 [", nmb, ", ", microblock, ", ",
+              microblock, "] tensor on w's GPU");
+  const bool has_sc = scale.has_value() && scale->defined(), has_zp = zero_point.has_value() && zero_point->defined();
+  TORCH_CHECK(!has_sc || (scale->is_cuda() && scale->device() == w.device() && scale->scalar_type() == at::kFloat && scale->is_contiguous()),
+              "gptq_block: scale must be a contiguous float32 tensor on w's GPU");
+  TORCH_CHECK(!has_zp || (zero_point->is_cuda() && zero_point->device() == w.device() && zero_point->scalar_type() == at::kLong &&
+              zero_point->is_contiguous()), "gptq_block: zero_point must be a contiguous int64 tensor on w's GPU");
+  const dmxq_gptq_format f{(int)fmt[0], (int)fmt[1], (int)fmt[2], (int)fmt[3], (int)fmt[4], (int)fmt[5], (int)fmt[6], (int)fmt[7],
+                           (int)fmt[8], (int)fmt[9], (int)fmt[10], (int)fmt[11]};
+  TORCH_CHECK(f.kind != DMXQ_GPTQ_FIXED || !f.per_row || (has_sc && has_zp && scale->numel() >= rows && zero_point->numel() >= rows),
+              "gptq_block: a per-row fixed point cast needs a scale and a zero point per row");
+  TORCH_CHECK(f.kind != DMXQ_GPTQ_FIXED || (has_sc && has_zp && scale->numel() >= 1 && zero_point->numel() >= 1),
+              "gptq_block: a fixed point cast needs its scale and zero point");
+  auto ld = [count](const Tensor& t) { return t.size(0) <= 1 ? std::max<int64_t>(t.stride(0), count) : t.stride(0); };
+  Launch l(w);
+  check(dmxq_gptq_block((const float*)w.data_ptr(), ld(w), (float*)q.data_ptr(), ld(q), (float*)err.data_ptr(), ld(err), rows, count,
+                        (const float*)hinv.data_ptr(), ld(hinv), (const float*)inv_d.data_ptr(), microblock, &f,
+                        has_sc ? (const float*)scale->data_ptr() : nullptr, has_zp ? (const int64_t*)zero_point->data_ptr() : nullptr, l.stream),
+        "dmxq_gptq_block");
+}
+void gptq_block_meta(const Tensor&, const Tensor&, const Tensor&, int64_t, at::IntArrayRef, const OptTensor&, const OptTensor&, Tensor, Tensor) {}
+
 }  // namespace
 
 TORCH_LIBRARY(dmxq, m) {
@@ -862,6 +900,7 @@ TORCH_LIBRARY(dmxq, m) {
   m.def("unary_cast_table(Tensor like, int kind, float param, int[] cast_in, int[] cast_out) -> Tensor");
   m.def("lut16_apply(Tensor x, Tensor table) -> Tensor");
   m.def("norm_cast(Tensor x, int cols, Tensor? weight, Tensor? bias, float eps, int kind, int[] cast_in, int[] cast_out, int bfp_block=0, int bfp_precision=0) -> Tensor");
+  m.def("gptq_block(Tensor w, Tensor hinv, Tensor inv_d, int microblock, int[] fmt, Tensor? scale, Tensor? zero_point, Tensor(a!) q, Tensor(b!) err) -> ()");
 }
 
 #define DMXQ_IMPL(m, name) m.impl(#name, &name)
@@ -870,7 +909,7 @@ TORCH_LIBRARY(dmxq, m) {
   X(m, bfp_qdq); X(m, block_quantize); X(m, bfp_qdq_multi); X(m, weight_hypernet_multi); X(m, bfp_pack); X(m, bfp_unpack); X(m, weight_hypernet); X(m, input_hypernet); X(m, binary_cast); X(m, relu_cast); X(m, sbfp_qdq); X(m, mxfp_qdq);   \
   X(m, float_qdq); X(m, float_qdq_multi); X(m, fixed_qdq); X(m, fixed_qdq_multi); X(m, fixed_float_qdq_multi); X(m, nm_mask); X(m, topk_mask); X(m, bernoulli_mask); X(m, group_minmax); X(m, qparams); \
   X(m, histc); X(m, channel_maxabs); X(m, smoothquant_scale); X(m, scale_channels); X(m, unary); X(m, rope); X(m, rope_cast); X(m, softmax); X(m, norm); \
-  X(m, unary_cast); X(m, unary_cast_table); X(m, lut16_apply); X(m, softmax_cast); X(m, norm_cast); X(m, group_minmax_accumulate)
+  X(m, unary_cast); X(m, unary_cast_table); X(m, lut16_apply); X(m, softmax_cast); X(m, norm_cast); X(m, group_minmax_accumulate); X(m, gptq_block)
 
 // "CUDA" is the dispatch key of HIP tensors in a ROCm build of PyTorch
 TORCH_LIBRARY_IMPL(dmxq, CUDA, m) {

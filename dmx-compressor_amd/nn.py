@@ -27,7 +27,7 @@ from .smoothquant import ActivationWeightSmoothQuant
 from .sparse import Dense, Sparsify
 
 __all__ = ["DmxModule", "DmxQuantizerCalibrationHyperparams", "DmxModuleQuantizerCalibrationHyperparams",
-           "DmxModuleSmoothQuantHyperparams", "Linear", "Conv1d", "Conv2d", "ResAdd", "ActActMatMul", "Softmax", "LayerNorm", "GELU", "ReLU", "SiLU", "QuickGELU", "Exp", "Mul", "RMSNorm", "ApplyRotaryPosEmb",
+           "DmxModuleSmoothQuantHyperparams", "DmxModuleGPTQHyperparams", "Linear", "Conv1d", "Conv2d", "ResAdd", "ActActMatMul", "Softmax", "LayerNorm", "GELU", "ReLU", "SiLU", "QuickGELU", "Exp", "Mul", "RMSNorm", "ApplyRotaryPosEmb",
            "MaxPool2d", "AvgPool2d", "Embedding", "ReLU6", "Tanh", "Dropout", "NewGELU", "FastGELU", "BloomGELU", "ClippedGELU", "AdaptiveAvgPool2d",
            "BatchNorm2d", "GroupNorm", "ConvTranspose2d", "BAddBMM", "ScaledDotProductAttention", "DmxConfigRule", "configure_model",
            "fold_weights_and_biases", "GraphedForward", "LiveWeightBatch", "link_consumer", "link_consumers_from_fx", "DmxTracer"]
@@ -75,6 +75,14 @@ class DmxModuleSmoothQuantHyperparams:
     fuse_to_weight: bool = False
 
 
+@dataclass
+class DmxModuleGPTQHyperparams:
+    """advanced_recipe.py:76-85"""
+    microblock_size: int = 1
+    block_size: int = 128
+    percdamp: float = 0.01
+
+
 def _shares_storage(a, b) -> bool:
     if not (isinstance(a, torch.Tensor) and isinstance(b, torch.Tensor)):
         return False
@@ -107,6 +115,8 @@ class DmxModule(FastAttr, torch.nn.Module):
     functional_forward = None
     ch_axis = win_ch_axis = wout_ch_axis = None
     has_accum = False
+    #: the OptimalBrainCompressor while `optimal_brain_compressing` is active (layer_reconstruction.py:24-27), else None
+    obc = None
 
     def _dmx_init(self, n_inputs: int = 1, input_names=("input_cast",), sparsifiable: bool = False):
         pnames = [n for n, _ in self.named_parameters(recurse=False)]
@@ -388,6 +398,31 @@ class DmxModule(FastAttr, torch.nn.Module):
         yield self
         self.enable_smoothquant_calib(False, hyperparams)
 
+    def enable_optimal_brain_compression(self, state: bool, hyperparams) -> None:
+        """layer_reconstruction.py:70-86: Linear and Conv2d only (any other module: nothing happens).  Entering measures the Hessian of
+        the unquantised inputs (fake quant off on the input casts and the weight cast); leaving switches both back on and runs GPTQ."""
+        if isinstance(self, (torch.nn.Linear, torch.nn.Conv2d)):
+            if state:
+                from .layer_reconstruction import OptimalBrainCompressor
+                self.obc = OptimalBrainCompressor(self)
+                self.input_casts.disable_fake_quant()
+                self.weight_cast.disable_fake_quant()
+            else:
+                self.input_casts.enable_fake_quant()
+                self.weight_cast.enable_fake_quant()
+                obc, self.obc = self.obc, None
+                obc.apply(**vars(hyperparams))
+
+    @contextmanager
+    def optimal_brain_compressing(self, hyperparams):
+        self.enable_optimal_brain_compression(True, hyperparams)
+        yield self
+        self.enable_optimal_brain_compression(False, hyperparams)
+
+    #: GPTQ's in-block column loop as one csrc/gptq.hip launch per column block when the weight format allows (False: the reference's
+    #: per-microblock loop, for A/B comparisons)
+    fuse_gptq = True
+
     #: use the single-kernel activation path (dmxq_input_hypernet) when the configuration allows it; results are bit-identical
     fuse_input_hypernet = True
 
@@ -610,6 +645,8 @@ class DmxModule(FastAttr, torch.nn.Module):
             _input, args, kwargs = self.input_casts(input, *args, first_done=True, **kwargs)
         else:
             _input, args, kwargs = self.input_casts(input, *args, **kwargs)
+        if self.obc is not None:
+            self.obc.measure_hessian(_input)
         _output = self._forward(_input, *args, **kwargs)
         # (a GEMM-bearing module's output cast is a launch of its own; when the linked consumer applies the SAME cast to this value as
         #  its first input cast -- inside its fused kernel -- the cast here is redundant: FloatingPoint casts are projections)

@@ -53,7 +53,8 @@ typedef enum {
 } dmxq_status;
 
 const char* dmxq_status_string(int status);
-/* ABI version: bumped on any signature change or addition.  4 = round 5: + dmxq_float_qdq_multi, dmxq_fixed_float_qdq_multi; 3 = round 4: + dmxq_weight_hypernet_multi,
+/* ABI version: bumped on any signature change.  Additions since 4 (dmxq_gptq_block) leave it at 4: a caller built against 4 runs on
+ * this library unchanged.  4 = round 5: + dmxq_float_qdq_multi, dmxq_fixed_float_qdq_multi; 3 = round 4: + dmxq_weight_hypernet_multi,
  * dmxq_unary_cast_table, dmxq_lut16_apply.  Nothing was ever removed or changed: a caller built against version n runs on any library >= n. */
 int dmxq_abi_version(void);
 
@@ -396,6 +397,36 @@ int dmxq_rmsnorm_cast_bfp(const void* in, void* out, int dtype, int64_t rows, in
  * vectors, unaligned pointers, >= 2^31 elements (the caller keeps torch's own ops). */
 int dmxq_rope(const void* x, const void* cos_tab, const void* sin_tab, void* out, int dtype, int64_t B, int64_t n1, int64_t n2,
               int64_t D, int broadcast_over_dim1, void* stream);
+
+/* GPTQ (optimal brain compression): the in-block column loop of ONE column block, in one launch.
+ * Replaces: layer_reconstruction.py:300-318 (per microblock of columns: weight_hypernet of the slice, (w - q) @ inv(Hinv block),
+ * slice copies, the update of the block's later columns), i.e. >= 5 launches per column at microblock 1.
+ * All float32.  w: the block W[:, i1:i2] (rows x count, row stride ldw; read only); q: Q[:, i1:i2] (row stride ldq); err: the error
+ * block E (rows x count, row stride lde); hinv: Hinv[i1:i2, i1:i2] (count x count, row stride ldh, the upper Cholesky factor of H^-1:
+ * only its upper triangle is read); inv_d: the inverses of the diagonal microblocks of hinv, ceil(count / microblock) matrices of
+ * microblock x microblock (a ragged last one padded with the identity; microblock 1: 1 / hinv[j][j]).  The trailing update
+ * W[:, i2:] -= E @ Hinv[i1:i2, i2:] is the caller's (a GEMM).
+ * Arithmetic (csrc/gptq.hip): every product and difference separately rounded; microblock 1: q = cast(w_j), e = (w_j - q) * inv_d[j],
+ * w_k = w_k - e * hinv[j][k]; microblock m > 1: q = cast(slice), err[c] = sum_i (w - q)[i] * inv_d[i][c] and
+ * w_k = w_k - sum_i err[i] * hinv[j1 + i][k], both sums accumulated in index order starting from the i = 0 product.
+ * The cast of each microblock slice is bit-identical to the module's weight cast of that [rows, m] slice:
+ *   DMXQ_GPTQ_BFP    BFP[precision|8]{block_size} with nearest rounding, symmetric or "(_N)", blocks along the slice's columns
+ *                    (block_size >= 2 divides microblock; 2 <= precision <= 22);
+ *   DMXQ_GPTQ_FLOAT  FP[..] with nearest rounding (man_bits <= 22), as dmxq_float_qdq;
+ *   DMXQ_GPTQ_FIXED  XP[precision, fraction] with nearest rounding and the affine wrapper x / scale + zp -> cast -> (x - zp) * scale,
+ *                    scale / zero_point per row (per_row = 1) or one for all rows (per_row = 0).
+ * count <= 128; microblock in {1, 8, 16, 32, 64} (BFP: not 1).  DMXQ_ERR_BAD_ARG: null pointers, sizes out of range, strides below
+ * count; DMXQ_ERR_UNSUPPORTED: a format, microblock or count outside the above (nothing launched: the caller runs its own loop). */
+typedef enum { DMXQ_GPTQ_BFP = 0, DMXQ_GPTQ_FLOAT = 1, DMXQ_GPTQ_FIXED = 2 } dmxq_gptq_kind;
+typedef struct {
+  int kind;                                                    /* dmxq_gptq_kind */
+  int precision, block_size, symmetric;                        /* BFP (precision, block_size, symmetric) and FIXED (precision, symmetric) */
+  int man_bits, exp_bits, exp_bias, flush_subnormal, unsigned_abs;   /* FLOAT */
+  int fraction, clamp, per_row;                                /* FIXED */
+} dmxq_gptq_format;
+int dmxq_gptq_block(const float* w, int64_t ldw, float* q, int64_t ldq, float* err, int64_t lde, int64_t rows, int64_t count,
+                    const float* hinv, int64_t ldh, const float* inv_d, int64_t microblock, const dmxq_gptq_format* fmt,
+                    const float* scale, const int64_t* zero_point, void* stream);
 
 #ifdef __cplusplus
 }

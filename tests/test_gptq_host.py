@@ -1,0 +1,129 @@
+"""GPTQ without a GPU: hyperparameters, recipes, the reference's argument asserts, the C ABI's argument checks, and the CPU
+restatements (tests/_gptq_ref.py) against the reference's own results (tests/golden/gptq.npz, tools/gen_golden_gptq.py)."""
+import ctypes
+
+import pytest
+import torch
+
+from _gptq_ref import block_fp32, inv_diag, slice_cast
+
+
+def test_hyperparameter_defaults(dmx):
+    hp = dmx.DmxModuleGPTQHyperparams()
+    assert (hp.microblock_size, hp.block_size, hp.percdamp) == (1, 128, 0.01)
+    assert dmx.nn.DmxModule.obc is None and dmx.nn.DmxModule.fuse_gptq is True
+
+
+def test_recipes_use_the_module_context_managers(dmx):
+    D = dmx.nn.DmxModule
+    assert dmx.DmxGPTQRecipe(dict).recipe_context_manager is D.optimal_brain_compressing
+    assert dmx.DmxQuantizerCalibrationRecipe(dict).recipe_context_manager is D.calibrating_quantizers
+    assert dmx.DmxSmoothQuantRecipe(dict).recipe_context_manager is D.calibrating_smoothquant
+    log = []
+    from contextlib import contextmanager
+
+    @contextmanager
+    def cm(m, p):
+        log.append(("enter", m, p))
+        yield m
+        log.append(("exit", m, p))
+
+    r = dmx.DmxGPTQRecipe(lambda model: {"a": 1, "b": 2})
+    r.recipe_context_manager = cm
+    with r.applied_to(object()) as ms:
+        assert ms == ["a", "b"] and log == [("enter", "a", 1), ("enter", "b", 2)]
+    assert log[2:] == [("exit", "b", 2), ("exit", "a", 1)]
+
+
+def test_entering_switches_fake_quant_and_other_modules_are_noops(dmx):
+    m = dmx.nn.Linear(16, 8)
+    m.configure({"weight_format": "BFP[8|8]{16}(SN)", "input_formats": ["BFP[8|8]{16}(SN)"]})
+    m.enable_optimal_brain_compression(True, dmx.DmxModuleGPTQHyperparams())
+    assert m.obc is not None
+    assert not m.input_casts.input_cast._flag("fake_quant_enabled") and not m.weight_cast._flag("fake_quant_enabled")
+    m.obc.measure_hessian(torch.randn(2, 5, 16))
+    m.obc.measure_hessian(torch.randn(5, 16))   # 2-D: one more sample, not five
+    assert m.obc.example_counter == 3 and m.obc.H.shape == (16, 16)
+    ln = dmx.nn.LayerNorm(16)
+    with ln.optimal_brain_compressing(dmx.DmxModuleGPTQHyperparams()):
+        assert ln.obc is None
+
+
+def test_reference_asserts(dmx):
+    from dmx_compressor_amd.layer_reconstruction import OptimalBrainCompressor
+
+    m = dmx.nn.Linear(32, 8)
+    m.configure({"weight_format": "BFP[8|8]{16}(SN)"})
+    o = OptimalBrainCompressor(m)
+    o.measure_hessian(torch.randn(4, 32))
+    with pytest.raises(AssertionError):
+        o.apply(microblock_size=3, block_size=128)   # block_size % microblock_size
+    with pytest.raises(AssertionError):
+        o.apply(microblock_size=8, block_size=128)   # microblock_size % format block size
+
+
+def test_abi_argument_checks(dmx):
+    L, lib = dmx._lib.lib(), dmx._lib
+    null, one = ctypes.c_void_p(None), ctypes.c_void_p(16)
+    f = lib.GptqFormat(lib.GPTQ_FLOAT, 0, 0, 0, 3, 4, 7, 0, 0, 0, 0, 0)
+    ok = (one, 64, one, 64, one, 64, 8, 64, one, 64, one)
+    assert L.dmxq_gptq_block(null, 64, null, 64, null, 64, 0, 64, null, 64, null, 1, ctypes.byref(f), null, null, null) == lib.OK
+    assert L.dmxq_gptq_block(*ok, 1, null, null, null, null) == lib.ERR_BAD_ARG                           # no format
+    assert L.dmxq_gptq_block(null, 64, one, 64, one, 64, 8, 64, one, 64, one, 1, ctypes.byref(f), null, null, null) == lib.ERR_BAD_ARG
+    assert L.dmxq_gptq_block(one, 32, one, 64, one, 64, 8, 64, one, 64, one, 1, ctypes.byref(f), null, null, null) == lib.ERR_BAD_ARG
+    assert L.dmxq_gptq_block(one, 256, one, 256, one, 256, 8, 200, one, 256, one, 1, ctypes.byref(f), null, null, null) == lib.ERR_UNSUPPORTED
+    assert L.dmxq_gptq_block(*ok, 3, ctypes.byref(f), null, null, null) == lib.ERR_UNSUPPORTED             # microblock 3
+    fx = lib.GptqFormat(lib.GPTQ_FIXED, 4, 0, 1, 0, 0, 0, 0, 0, 0, 1, 1)
+    assert L.dmxq_gptq_block(*ok, 1, ctypes.byref(fx), null, null, null) == lib.ERR_BAD_ARG                # fixed point without scale
+    bf = lib.GptqFormat(lib.GPTQ_BFP, 8, 16, 1, 0, 0, 0, 0, 0, 0, 0, 0)
+    assert L.dmxq_gptq_block(*ok, 8, ctypes.byref(bf), null, null, null) == lib.ERR_UNSUPPORTED            # blocks wider than the microblock
+    assert L.dmxq_abi_version() == 4
+
+
+def test_restatement_is_the_reference_loop_at_microblock_1(dmx, oracle):
+    """at mb 1 the kernel order IS the reference's (q = cast(w_j); e = (w_j - q) / d_j as a product with 1 / d_j; w_k -= e * H[j, k]),
+    so the restatement must equal the reference's loop (layer_reconstruction.py:300-318) evaluated in float32 on the CPU"""
+    fmt = dmx.Format.from_shorthand("FP[1|4|3,7](_N)")
+    cast = slice_cast(oracle, fmt)
+    g = torch.Generator().manual_seed(0)
+    W = torch.randn(24, 40, generator=g)
+    X = torch.randn(160, 40, generator=g)
+    H = X.t() @ X / 80 + 0.1 * torch.eye(40)
+    hinv = torch.linalg.cholesky(torch.cholesky_inverse(torch.linalg.cholesky(H)), upper=True)
+    Q, E = block_fp32(W, hinv, inv_diag(hinv, 1), 1, cast)
+    _W, _Q = W.clone(), torch.zeros_like(W)
+    for j in range(40):
+        q = cast(_W[:, j:j + 1].contiguous())
+        err = (_W[:, j:j + 1] - q) * (1.0 / hinv[j, j])
+        _Q[:, j:j + 1] = q
+        _W[:, j + 1:] -= err * hinv[j:j + 1, j + 1:]
+    assert torch.equal(Q, _Q)
+
+
+@pytest.mark.parametrize("name", ["a", "b", "c", "d", "e", "f"])
+def test_restatement_reproduces_reference_loss(dmx, oracle, name):
+    """the float64 restatement of apply() (the reference's loop, float64 linear algebra), on the fixture's seeded weight and inputs,
+    reaches the reference's loss within twice the largest float32 / float64 spread the generator measured over the cases"""
+    import os
+
+    import numpy as np
+
+    from _data import make
+    from _gptq_ref import CASES, apply_ref, case_cast, hessian64, loss
+
+    g = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "gptq.npz"))
+    eps = 2 * float(g["spread_f32_f64"].max())
+    c = CASES[name]
+    kind, fin, fout = c["module"]
+    m = dmx.nn.Linear(fin, fout) if kind == "linear" else dmx.nn.Conv2d(fin, fout, 3)
+    W = (make("normal", tuple(m.weight.shape), seed=c["seed"]) * 0.05).reshape(fout, -1)
+    xs = [make("normal", c["input"], seed=c["seed"] + 1 + b) for b in range(3)]
+    sc = torch.from_numpy(g[f"{name}_scale"]) if c.get("calib") else None
+    zp = torch.from_numpy(g[f"{name}_zero_point"]) if c.get("calib") else None
+    H = hessian64(kind, xs, m)
+    Hr = torch.from_numpy(g[f"{name}_H_rows"]).double()
+    assert torch.allclose(H[::8], Hr, rtol=0, atol=1e-5 * float(Hr.abs().max()))
+    Q = apply_ref(W, H, c["mb"], c["block"], case_cast(oracle, c, sc, zp), torch.float64)
+    lref = float(g[f"{name}_loss_ref"])
+    assert abs(loss(W, Q, H) - lref) <= eps * lref, (loss(W, Q, H), lref, eps)
+    assert lref < float(g[f"{name}_loss_rtn"])
