@@ -691,3 +691,45 @@ def gptq_block(w, hinv, inv_d, microblock, fmt, scale, zero_point, q, err):
 
     check(lib().dmxq_gptq_block(ptr(w), ld(w), ptr(q), ld(q), ptr(err), ld(err), rows, count, ptr(hinv), ld(hinv), ptr(inv_d), microblock,
                                 ctypes.byref(f), ptr(scale), ptr(zero_point), stream_of(w)), "dmxq_gptq_block")
+
+
+# ------------------------------------------------------------------------------------------------ HistogramObserver
+def _hist_state(t, like, dtype, numel, what, op):
+    if not (t.is_cuda and t.device == like.device and t.dtype == dtype and t.is_contiguous() and t.numel() == numel):
+        raise RuntimeError(f"{op}: {what} must be a contiguous {dtype} tensor of {numel} entries on the input's device")
+
+
+@_guarded
+def hist_observe(x, ch_axis, group_size, upsample_rate, hist, min_val, max_val, status, scratch):
+    xc = _prep(x, "hist_observe")
+    if group_size < 1 or upsample_rate < 1:
+        raise RuntimeError("hist_observe: group_size and upsample_rate must be positive")
+    outer, C, inner = _split(xc, ch_axis)
+    G = -(-C // group_size)
+    if not (G >= 1 and hist.numel() >= G and hist.numel() % G == 0):
+        raise RuntimeError(f"hist_observe: the histogram must hold {G} groups of bins")
+    _hist_state(hist, xc, torch.float32, hist.numel(), "hist", "hist_observe")
+    _hist_state(min_val, xc, torch.float32, G, "min_val", "hist_observe")
+    _hist_state(max_val, xc, torch.float32, G, "max_val", "hist_observe")
+    _hist_state(status, xc, torch.int32, 1, "status", "hist_observe")
+    if not (scratch.is_cuda and scratch.device == xc.device and scratch.is_contiguous()):
+        raise RuntimeError("hist_observe: scratch must be a contiguous tensor on the input's device")
+    check(lib().dmxq_hist_observe(ptr(xc), dtype_code(xc.dtype), outer, C, inner, group_size, hist.numel() // G, upsample_rate, ptr(hist),
+                                  ptr(min_val), ptr(max_val), ptr(status), ptr(scratch), scratch.numel() * scratch.element_size(),
+                                  stream_of(xc)), "dmxq_hist_observe")
+
+
+@_guarded
+def hist_qparams(hist, min_val, max_val, precision, qmin, qmax, symmetric_qscheme):
+    require_gpu(hist, "hist_qparams")
+    G = min_val.numel()
+    if not (G >= 1 and hist.numel() >= G and hist.numel() % G == 0):
+        raise RuntimeError(f"hist_qparams: the histogram must hold {G} groups of bins")
+    _hist_state(hist, hist, torch.float32, hist.numel(), "hist", "hist_qparams")
+    _hist_state(min_val, hist, torch.float32, G, "min_val", "hist_qparams")
+    _hist_state(max_val, hist, torch.float32, G, "max_val", "hist_qparams")
+    scale = torch.empty(G, dtype=torch.float32, device=hist.device)
+    zp = torch.empty(G, dtype=torch.int64, device=hist.device)
+    check(lib().dmxq_hist_qparams(ptr(hist), ptr(min_val), ptr(max_val), G, hist.numel() // G, precision, qmin, qmax, int(symmetric_qscheme),
+                                  ptr(scale), ptr(zp), stream_of(hist)), "dmxq_hist_qparams")
+    return scale, zp

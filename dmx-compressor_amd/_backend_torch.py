@@ -50,6 +50,8 @@ _FAST_NAMES = {"bfp_qdq_nograd": "bfp_qdq", "float_qdq_nograd": "float_qdq", "fi
                "mxfp_qdq_nograd": "mxfp_qdq", "weight_hypernet": "weight_hypernet", "input_hypernet": "input_hypernet", "binary_cast": "binary_cast",
                "relu_cast": "relu_cast", "scale_channels": "scale_channels", "rope_cast": "rope_cast", "unary_cast": "unary_cast",
                "lut16_apply": "lut16_apply", "softmax_cast": "softmax_cast", "norm_cast": "norm_cast"}
+# the calibration calls of the device HistogramObserver (no autograd to lose: they take the same route)
+_FAST_CALIBRATION_NAMES = {"hist_observe": "hist_observe", "hist_qparams": "hist_qparams"}
 FAST = None
 
 
@@ -79,7 +81,7 @@ if not os.environ.get("DMXQ_NO_FAST_CALLS"):
     except (ImportError, OSError, AttributeError):   # (a binding built without the entry points: the dispatcher serves everything)
         FAST = None
     if FAST is not None:
-        for _raw_name, _fast_name in _FAST_NAMES.items():
+        for _raw_name, _fast_name in {**_FAST_NAMES, **_FAST_CALIBRATION_NAMES}.items():
             setattr(RAW, _raw_name, _direct(getattr(FAST, _fast_name), getattr(RAW, _raw_name)))
         del _raw_name, _fast_name
 

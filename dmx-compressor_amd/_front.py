@@ -20,7 +20,7 @@ from ._lib import DmxqError, ROUNDING_CODE, require_gpu
 __all__ = [
     "bfp_qdq", "block_quantize", "bfp_qdq_multi", "bfp_pack", "bfp_unpack", "weight_hypernet", "weight_hypernet_multi", "input_hypernet", "binary_cast", "rope_cast", "relu_cast", "unary_cast", "unary_cast_table", "lut16_apply", "softmax_cast", "layernorm_cast", "rmsnorm_cast", "sbfp_qdq", "mxfp_qdq", "float_qdq", "float_qdq_multi", "fixed_qdq", "fixed_qdq_multi", "fixed_float_qdq_multi", "nm_mask", "nm_sparsify", "topk_mask", "topk_sparsify", "bernoulli_mask", "group_minmax", "group_minmax_accumulate", "qparams", "channel_maxabs",
     "smoothquant_scale", "scale_channels", "gelu", "silu", "quick_gelu", "exp", "silu_experimental", "rope", "softmax", "layernorm",
-    "rmsnorm", "histc", "gptq_fields", "gptq_block",
+    "rmsnorm", "histc", "gptq_fields", "gptq_block", "hist_observe", "hist_scratch_words", "hist_qparams",
 ]
 
 _ops = None   # the raw namespace: set by bind()
@@ -333,6 +333,27 @@ def histc(x, bins: int, lo: float = 0.0, hi: float = 0.0):
     if not (lo < hi and math.isfinite(lo) and math.isfinite(hi)):
         raise DmxqError(f"histc: needs a finite range with min < max, got [{lo}, {hi}]")
     return _ops.histc(x, int(bins), lo, hi)
+
+
+def hist_observe(x, ch_axis: int, group_size: int, upsample_rate: int, hist, min_val, max_val, status, scratch):
+    """One HistogramObserver observation of every group (slabs of `group_size` channels along ch_axis; per tensor: x.reshape(1, -1),
+    0, 1) in four launches, no host synchronisation (dmxq_hist_observe).  The state is updated IN PLACE: hist float32 [G, bins],
+    min_val / max_val float32 [G] (+inf / -inf before the first observation), status int32 [1] (0; 1 after an infinite extremum, 2
+    after a NaN: the observation the host code refuses with OverflowError / ValueError).  scratch: >= (2 + bins) * G words of device
+    memory (hist_scratch_words)."""
+    require_gpu(x, "hist_observe")
+    _ops.hist_observe(x, int(ch_axis), int(group_size), int(upsample_rate), hist, min_val, max_val, status, scratch)
+
+
+def hist_scratch_words(n_groups: int, bins: int) -> int:
+    return (2 + int(bins)) * int(n_groups)
+
+
+def hist_qparams(hist, min_val, max_val, precision: int, qmin: int, qmax: int, symmetric_qscheme: bool):
+    """HistogramObserver.calculate_qparams of every group in one launch (dmxq_hist_qparams): the L2 range search over the histogram,
+    then (scale float32 [G], zero_point int64 [G]); a group that observed nothing gets (1, 0)."""
+    require_gpu(hist, "hist_qparams")
+    return _ops.hist_qparams(hist, min_val, max_val, int(precision), int(qmin), int(qmax), bool(symmetric_qscheme))
 
 
 def channel_maxabs(x, ch_axis: int):

@@ -143,6 +143,8 @@ class CastTo(HostFlags, torch.nn.Module):
         else:
             self.enable_fake_quant()
             self.disable_observer()
+            if isinstance(self.activation_post_process, HistogramObserver):
+                self.activation_post_process.check_finite()   # the device path's delayed raise
 
     # ------------------------------------------------------------------ forward pieces
     def _observer_step(self, x):
@@ -150,8 +152,12 @@ class CastTo(HostFlags, torch.nn.Module):
         obs = self.activation_post_process
         obs.ch_axis = self.ch_axis
         obs.qscheme = self.qscheme
-        if self.group_size and not isinstance(obs, (MinMaxObserver, DummyObserver)):
-            # per-tensor-only observers (histogram): one instance per slab, as cast.py:185-213 does for every class
+        if self.group_size and isinstance(obs, HistogramObserver) and obs.device_path_ok(x, self.group_size):
+            # every slab's histogram in one observer and one call (dmxq_hist_observe), the searches in one launch
+            obs(x.detach(), self.group_size)
+            _scale, _zero_point = obs.calculate_qparams()
+        elif self.group_size and not isinstance(obs, (MinMaxObserver, DummyObserver)):
+            # per-tensor-only observers (the histogram's host code): one instance per slab, as cast.py:185-213 does for every class
             slabs = torch.split(x.detach(), self.group_size, dim=self.ch_axis)
             if len(getattr(self, "_group_observers", ())) != len(slabs):
                 self._group_observers = [obs.__class__(dtype=self.format, qscheme=self.qscheme, ch_axis=self.ch_axis)

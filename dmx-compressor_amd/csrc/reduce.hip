@@ -17,6 +17,7 @@
 
 #include "common.hpp"
 #include "gate_registry.hpp"
+#include "reduce_common.hpp"
 
 namespace dmxq {
 
@@ -274,35 +275,6 @@ __global__ __launch_bounds__(kThreads) void group_minmax_kernel(const void* __re
   block_minmax_finish<kThreads>(lo, hi, &mn[g], &mx[g], InitGate{nullptr, 0u, 0}, 0u, 0, [](int64_t) {});
 }
 
-// 8 consecutive elements, compile-time dtype: the RAW 16-byte vectors first (so that a batch of loads is issued back to
-// back), widened afterwards.  (The runtime-dtype load8_rt below wraps every load in a dtype branch whose conversion
-// waits for that load: one access in flight per lane.)
-template <int DT>
-struct Raw8 {
-  u32x4 a, b;  // b only for fp32
-};
-template <int DT>
-__device__ __forceinline__ Raw8<DT> load8_raw(const void* p, int64_t e) {
-  Raw8<DT> r;
-  // non-temporal: the reductions read their operand exactly once
-  if (DT == DMXQ_F32) { r.a = __builtin_nontemporal_load((const u32x4*)((const float*)p + e)); r.b = __builtin_nontemporal_load((const u32x4*)((const float*)p + e + 4)); }
-  else { r.a = __builtin_nontemporal_load((const u32x4*)((const uint16_t*)p + e)); r.b = r.a; }
-  return r;
-}
-template <int DT>
-__device__ __forceinline__ void widen8(const Raw8<DT>& r, float (&v)[8]) {
-  if (DT == DMXQ_F32) {
-#pragma unroll
-    for (int j = 0; j < 4; j++) { v[j] = u2f(r.a[j]); v[4 + j] = u2f(r.b[j]); }
-  } else {
-#pragma unroll
-    for (int j = 0; j < 4; j++) {
-      if (DT == DMXQ_BF16) { v[2 * j] = u2f(r.a[j] << 16); v[2 * j + 1] = u2f(r.a[j] & 0xFFFF0000u); }
-      else { v[2 * j] = half_lo(r.a[j]); v[2 * j + 1] = half_hi(r.a[j]); }
-    }
-  }
-}
-
 // 8 consecutive elements as fp32 (16-byte accesses; the address must be 16-byte aligned)
 __device__ __forceinline__ void load8_rt(const void* p, int dt, int64_t e, float (&v)[8]) {
   if (dt == DMXQ_F32) {
@@ -517,20 +489,7 @@ __global__ void qparams_kernel(const float* mn, const float* mx, int64_t G, int 
                                int64_t* zp) {
   const int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (g >= G) return;
-  const float eps = 1.1920928955078125e-07f;  // torch.finfo(torch.float32).eps (observer.py:37)
-  const float min_neg = fminf(mn[g], 0.0f);
-  const float max_pos = fmaxf(mx[g], 0.0f);
-  if (sym) {
-    const float m = fmaxf(-min_neg, max_pos);
-    scale[g] = fmaxf(m / ((float)(qmax - qmin) / 2.0f), eps);
-    zp[g] = 0;
-  } else {
-    const float s = fmaxf((max_pos - min_neg) / (float)(qmax - qmin), eps);
-    float z = (float)qmin - rintf(min_neg / s);
-    z = fminf(fmaxf(z, (float)qmin), (float)qmax);
-    scale[g] = s;
-    zp[g] = (int64_t)z;
-  }
+  qparams_one(mn[g], mx[g], qmin, qmax, sym, scale[g], zp[g]);
 }
 
 // grid = (ceil(C*inner / 256), splits over outer).  Lanes run along the contiguous (c, i) plane.
@@ -558,22 +517,6 @@ __global__ void smoothquant_scale_kernel(const float* a, const float* b, int64_t
 // counts, flushed with one global atomic per non-empty bin per workgroup; the counts become fp32 in a second tiny
 // launch that reuses the output buffer.  The bin of an element is ATen's fp32 expression, evaluated with IEEE
 // multiply and divide: (int64)((x - lo) * bins / (hi - lo)), right edge into the last bin, out-of-range and NaN dropped.
-constexpr int kHistThreads = 1024;
-constexpr int kHistMaxBins = 8192;  // 32 KiB of LDS counters
-// FAST: width in [2^-20, 2^20] (checked on the host): the quotient comes from div_for_clamped_int (common.hpp), which IS the IEEE
-// quotient for 2^-100 <= |n| <= 2^100; n = (v - lo) * bins is below 2^34 for an in-range v, and a smaller |n| truncates to bin 0
-// whatever its last bit is.  3 FMA-class operations instead of the ~14 of v_div_scale/fmas/fixup per element.
-// (Tried and measured slower on the same box, profiles/r02_histc_variants.txt: a branch-free add of 0 for out-of-range elements;
-// 2 / 4 / 8 interleaved copies of the counters against same-bin collisions; 128 or 512 workgroups.)
-template <bool FAST>
-__device__ __forceinline__ void hist_add(uint32_t* s, float v, float lo, float hi, float fb, const Recip& width, int bins) {
-  if (v >= lo && v <= hi) {
-    const float n = (v - lo) * fb;
-    int pos = (int)(FAST ? div_for_clamped_int(n, width) : n / width.d);
-    pos = pos < bins ? pos : bins - 1;
-    atomicAdd(&s[pos], 1u);
-  }
-}
 template <int DT, bool FAST, bool GATED>
 __global__ __launch_bounds__(kHistThreads) void histc_kernel(const void* __restrict__ in, int64_t n, int bins,
                                                              float lo, float hi, int vec, uint32_t* counts, const InitGate gate) {

@@ -855,6 +855,53 @@ void gptq_block(const Tensor& w, const Tensor& hinv, const Tensor& inv_d, int64_
 }
 void gptq_block_meta(const Tensor&, const Tensor&, const Tensor&, int64_t, at::IntArrayRef, const OptTensor&, const OptTensor&, Tensor, Tensor) {}
 
+// ------------------------------------------------------------------------------------------------ HistogramObserver
+// one observation of G groups (dmxq_hist_observe): hist [G, bins], min_val / max_val [G], status [1] (int32) are the observer's state,
+// updated in place; scratch: (2 + bins) * G words of any contiguous device tensor
+inline void hist_state(const Tensor& t, const Tensor& like, at::ScalarType dt, int64_t numel, const char* what) {
+  TORCH_CHECK(t.is_cuda() && t.device() == like.device() && t.scalar_type() == dt && t.is_contiguous() && t.numel() == numel,
+              "hist_observe: ", what, " must be a contiguous ", c10::toString(dt), " tensor of ", numel, " entries on the input's device");
+}
+void hist_observe(const Tensor& x, int64_t ch_axis, int64_t group_size, int64_t upsample_rate, Tensor hist, Tensor min_val, Tensor max_val,
+                  Tensor status, Tensor scratch) {
+  const Tensor xc = prep(x, "hist_observe");
+  TORCH_CHECK(group_size >= 1 && upsample_rate >= 1, "hist_observe: group_size and upsample_rate must be positive");
+  const Split3 s = split3(xc, ch_axis);
+  const int64_t G = (s.L + group_size - 1) / group_size;
+  TORCH_CHECK(G >= 1 && hist.numel() % G == 0 && hist.numel() >= G, "hist_observe: the histogram must hold ", G, " groups of bins");
+  hist_state(hist, xc, at::kFloat, hist.numel(), "hist");
+  hist_state(min_val, xc, at::kFloat, G, "min_val");
+  hist_state(max_val, xc, at::kFloat, G, "max_val");
+  hist_state(status, xc, at::kInt, 1, "status");
+  TORCH_CHECK(scratch.is_cuda() && scratch.device() == xc.device() && scratch.is_contiguous(), "hist_observe: scratch must be a contiguous tensor on the input's device");
+  Launch l(xc);
+  check(dmxq_hist_observe(xc.data_ptr(), dt_code(xc.scalar_type()), s.outer, s.L, s.inner, group_size, hist.numel() / G, upsample_rate,
+                          (float*)hist.data_ptr(), (float*)min_val.data_ptr(), (float*)max_val.data_ptr(), (int*)status.data_ptr(),
+                          scratch.data_ptr(), (int64_t)(scratch.numel() * scratch.element_size()), l.stream),
+        "dmxq_hist_observe");
+}
+void hist_observe_meta(const Tensor&, int64_t, int64_t, int64_t, Tensor, Tensor, Tensor, Tensor, Tensor) {}
+
+// the range search and (scale, zero_point) of every group (dmxq_hist_qparams): two [G] tensors
+std::tuple<Tensor, Tensor> hist_qparams(const Tensor& hist, const Tensor& min_val, const Tensor& max_val, int64_t precision, int64_t qmin,
+                                        int64_t qmax, bool symmetric_qscheme) {
+  TORCH_CHECK(hist.is_cuda(), "hist_qparams: tensor is on ", hist.device(), "; dmx_compressor_amd runs on MI355X (HIP) tensors only and has no CPU fallback");
+  const int64_t G = min_val.numel();
+  TORCH_CHECK(G >= 1 && hist.numel() % G == 0 && hist.numel() >= G, "hist_qparams: the histogram must hold ", G, " groups of bins");
+  hist_state(hist, hist, at::kFloat, hist.numel(), "hist");
+  hist_state(min_val, hist, at::kFloat, G, "min_val");
+  hist_state(max_val, hist, at::kFloat, G, "max_val");
+  Tensor scale = at::empty({G}, hist.options().dtype(at::kFloat)), zp = at::empty({G}, hist.options().dtype(at::kLong));
+  Launch l(hist);
+  check(dmxq_hist_qparams((const float*)hist.data_ptr(), (const float*)min_val.data_ptr(), (const float*)max_val.data_ptr(), G, hist.numel() / G,
+                          (int)precision, (int)qmin, (int)qmax, symmetric_qscheme, (float*)scale.data_ptr(), (int64_t*)zp.data_ptr(), l.stream),
+        "dmxq_hist_qparams");
+  return {scale, zp};
+}
+std::tuple<Tensor, Tensor> hist_qparams_meta(const Tensor& hist, const Tensor& min_val, const Tensor&, int64_t, int64_t, int64_t, bool) {
+  return {at::empty({min_val.numel()}, hist.options().dtype(at::kFloat)), at::empty({min_val.numel()}, hist.options().dtype(at::kLong))};
+}
+
 }  // namespace
 
 TORCH_LIBRARY(dmxq, m) {
@@ -901,6 +948,8 @@ TORCH_LIBRARY(dmxq, m) {
   m.def("lut16_apply(Tensor x, Tensor table) -> Tensor");
   m.def("norm_cast(Tensor x, int cols, Tensor? weight, Tensor? bias, float eps, int kind, int[] cast_in, int[] cast_out, int bfp_block=0, int bfp_precision=0) -> Tensor");
   m.def("gptq_block(Tensor w, Tensor hinv, Tensor inv_d, int microblock, int[] fmt, Tensor? scale, Tensor? zero_point, Tensor(a!) q, Tensor(b!) err) -> ()");
+  m.def("hist_observe(Tensor x, int ch_axis, int group_size, int upsample_rate, Tensor(a!) hist, Tensor(b!) min_val, Tensor(c!) max_val, Tensor(d!) status, Tensor(e!) scratch) -> ()");
+  m.def("hist_qparams(Tensor hist, Tensor min_val, Tensor max_val, int precision, int qmin, int qmax, bool symmetric_qscheme) -> (Tensor, Tensor)");
 }
 
 #define DMXQ_IMPL(m, name) m.impl(#name, &name)
@@ -909,7 +958,7 @@ TORCH_LIBRARY(dmxq, m) {
   X(m, bfp_qdq); X(m, block_quantize); X(m, bfp_qdq_multi); X(m, weight_hypernet_multi); X(m, bfp_pack); X(m, bfp_unpack); X(m, weight_hypernet); X(m, input_hypernet); X(m, binary_cast); X(m, relu_cast); X(m, sbfp_qdq); X(m, mxfp_qdq);   \
   X(m, float_qdq); X(m, float_qdq_multi); X(m, fixed_qdq); X(m, fixed_qdq_multi); X(m, fixed_float_qdq_multi); X(m, nm_mask); X(m, topk_mask); X(m, bernoulli_mask); X(m, group_minmax); X(m, qparams); \
   X(m, histc); X(m, channel_maxabs); X(m, smoothquant_scale); X(m, scale_channels); X(m, unary); X(m, rope); X(m, rope_cast); X(m, softmax); X(m, norm); \
-  X(m, unary_cast); X(m, unary_cast_table); X(m, lut16_apply); X(m, softmax_cast); X(m, norm_cast); X(m, group_minmax_accumulate); X(m, gptq_block)
+  X(m, unary_cast); X(m, unary_cast_table); X(m, lut16_apply); X(m, softmax_cast); X(m, norm_cast); X(m, group_minmax_accumulate); X(m, gptq_block); X(m, hist_observe); X(m, hist_qparams)
 
 // "CUDA" is the dispatch key of HIP tensors in a ROCm build of PyTorch
 TORCH_LIBRARY_IMPL(dmxq, CUDA, m) {
@@ -959,4 +1008,6 @@ PYBIND11_MODULE(dmxq_fast, m) {
         py::arg("bfp_precision") = 0);
   m.def("norm_cast", &norm_cast, py::arg("x"), py::arg("cols"), py::arg("weight"), py::arg("bias"), py::arg("eps"), py::arg("kind"), py::arg("cast_in"),
         py::arg("cast_out"), py::arg("bfp_block") = 0, py::arg("bfp_precision") = 0);
+  m.def("hist_observe", &hist_observe);
+  m.def("hist_qparams", &hist_qparams);
 }

@@ -1770,7 +1770,7 @@ class GraphedForward:
         `g(batch)` is one calibration step on that batch, with the observer state of the same steps run eagerly, bit for bit
         (numerical/cast.py:179-226, numerical/observer.py:173-193).  The warm-up forwards observe the example input (a running min / max
         is idempotent under repeats, but it must be a batch the calibration may see).  Only MinMax observers without a process group:
-        a HistogramObserver searches its thresholds on the host, a sharded exchange is a collective.  Default False: an enabled
+        a HistogramObserver is not yet admitted (its device path captures: tests/test_gpu_hist_observer.py), a sharded exchange is a collective.  Default False: an enabled
         observer in a model that is captured for inference is a mistake and is refused."""
         if not example_inputs or not all(isinstance(t, torch.Tensor) and t.is_cuda for t in example_inputs):
             raise ValueError("GraphedForward: tensor inputs on the GPU required")

@@ -3,9 +3,11 @@ path: MinMaxObserver (per-tensor / per-channel / per-group slabs) and `_calculat
 
 The reference creates one observer nn.Module per group in a Python loop (numerical/cast.py:185-213) and runs two
 ATen reductions per group; here ONE `dmxq_group_minmax` launch produces every group's min/max and one
-`dmxq_qparams` launch turns them into (scale, zero_point).  HistogramObserver keeps its two passes over the
-tensor on the device (min/max + `dmxq_histc`) and its bins-long bookkeeping and scalar search on the host.
+`dmxq_qparams` launch turns them into (scale, zero_point).  HistogramObserver runs on the device as a whole -- one observation of
+every group in four launches (`dmxq_hist_observe`), the range search and qparams of every group in one (`dmxq_hist_qparams`), no
+host synchronisation; its host code below stays as the specification and serves what the kernels do not take.
 """
+import os
 from typing import Optional, Tuple
 
 import torch
@@ -140,13 +142,31 @@ class MinMaxObserver(ObserverBase):
         return f"quant_min = {self.quant_min}, quant_max = {self.quant_max}, min_val = {self.min_val}, max_val = {self.max_val}"
 
 
+#: the largest state (groups x bins) the device path keeps; beyond it, and for more than 8192 bins, the host code runs (CastTo then
+#: observes group by group, one observer per slab, as before)
+HIST_DEVICE_MAX_STATE = 1 << 24
+HIST_DEVICE_MAX_BINS = 8192
+
+
+def hist_host_forced() -> bool:
+    """DMXQ_HIST_HOST=1: every HistogramObserver takes the host code (A/B measurements)"""
+    return os.environ.get("DMXQ_HIST_HOST", "") not in ("", "0")
+
+
 class HistogramObserver(ObserverBase):
     """Running histogram + L2-error range search (observer.py:213-583, itself adapted from torch.ao's observer).
 
-    Split by cost: the two passes over the observed tensor -- its min/max and `torch.histc` -- are device launches
-    (`dmxq_group_minmax`, `dmxq_histc`); everything that only touches the `bins`-long histogram (re-binning onto a
-    wider range, the quantile walk that picks the clipping range) is fp32 work on a host copy, with the same
-    operand types and order as the reference's tensor expressions so that the same bins win.  Per-tensor only.
+    On the device (`forward(x, group_size)` on a GPU tensor): every group -- slabs of `group_size` channels along ch_axis, or the
+    whole tensor -- in one `dmxq_hist_observe` call; the state stays on x's device (`histogram` [bins] or [G, bins], `min_val` /
+    `max_val` scalars or [G]) and `calculate_qparams()` returns device tensors from one `dmxq_hist_qparams` launch, nothing is read
+    back.  Bit for bit the host code below (csrc/hist_observer.hip), save the order of two fp32 sums ATen leaves open.
+    A non-finite extremum, which the host code refuses at once (`int()` raises), only raises a sticky flag on the device:
+    `check_finite()` -- called by `CastTo.enable_calibration(False)` -- raises the same exception type.
+
+    The host code (bins > 8192, groups x bins > HIST_DEVICE_MAX_STATE, DMXQ_HIST_HOST=1; per tensor only): the two passes over the
+    observed tensor -- its min/max and `torch.histc` -- are device launches (`dmxq_group_minmax`, `dmxq_histc`); everything that only
+    touches the `bins`-long histogram (re-binning onto a wider range, the quantile walk that picks the clipping range) is fp32 work
+    on a host copy, with the same operand types and order as the reference's tensor expressions so that the same bins win.
     Quirk kept: the histogram range is the observed min/max truncated toward zero by `int()`
     (observer.py:470-472, 489-491), so the fractional tails fall outside and are not counted."""
 
@@ -161,13 +181,73 @@ class HistogramObserver(ObserverBase):
         self.register_buffer("min_val", torch.tensor(float("inf")))
         self.register_buffer("max_val", torch.tensor(float("-inf")))
         self._device = None
+        self._status = None    # device path: int32 [1], the sticky non-finite flag
+        self._scratch = None   # device path: (2 + bins) * G words
 
-    # ------------------------------------------------------------------ observation (device passes + host merge)
+    # ------------------------------------------------------------------ observation on the device
+    def _n_groups(self, x, group_size) -> int:
+        if not group_size:
+            return 1
+        return -(-x.shape[self.ch_axis] // group_size) if x.dim() else 1
+
+    def device_path_ok(self, x, group_size=None) -> bool:
+        """whether forward(x, group_size) runs on the device"""
+        if hist_host_forced() or not x.is_cuda or self.bins > HIST_DEVICE_MAX_BINS or torch.compiler.is_compiling():
+            return False
+        G = self._n_groups(x, group_size)
+        return G <= 65535 and G * self.bins <= HIST_DEVICE_MAX_STATE
+
+    def _observe_device(self, xd, group_size):
+        if group_size:
+            view, axis, gs = xd, self.ch_axis, group_size
+            G = self._n_groups(xd, group_size)
+            hshape, rshape = (G, self.bins), (G,)
+        else:
+            view, axis, gs, G = xd.reshape(1, -1), 0, 1, 1
+            hshape, rshape = (self.bins,), ()
+        dev = xd.device
+        ok = lambda t, shape: (t.is_cuda and t.device == dev and tuple(t.shape) == shape and t.dtype == torch.float32 and t.is_contiguous())
+        if not (ok(self.histogram, hshape) and ok(self.min_val, rshape) and ok(self.max_val, rshape)):
+            if tuple(self.histogram.shape) == hshape and tuple(self.min_val.shape) == rshape and tuple(self.max_val.shape) == rshape:
+                # state of the same shape elsewhere (the host code's, on the CPU): carried over
+                self.histogram = self.histogram.to(device=dev, dtype=torch.float32).contiguous()
+                self.min_val = self.min_val.to(device=dev, dtype=torch.float32).contiguous()
+                self.max_val = self.max_val.to(device=dev, dtype=torch.float32).contiguous()
+            else:
+                self.histogram = torch.zeros(hshape, device=dev)
+                self.min_val = torch.full(rshape, float("inf"), device=dev)
+                self.max_val = torch.full(rshape, float("-inf"), device=dev)
+        if self._status is None or self._status.device != dev:
+            self._status = torch.zeros(1, dtype=torch.int32, device=dev)
+        need = ops.hist_scratch_words(G, self.bins)
+        if self._scratch is None or self._scratch.device != dev or self._scratch.numel() < need:
+            self._scratch = torch.empty(need, dtype=torch.int32, device=dev)
+        ops.hist_observe(view, axis, gs, self.upsample_rate, self.histogram, self.min_val, self.max_val, self._status, self._scratch)
+        self._device = dev
+
+    def check_finite(self):
+        """Raise what the host code would have raised during calibration: ValueError after a NaN, OverflowError after an infinity
+        (`int()` of the extremum).  One read of the device flag; the flag is cleared by the raise."""
+        if self._status is None:
+            return
+        code = int(self._status.item())
+        if code:
+            self._status.zero_()
+            if code == 2:
+                raise ValueError("HistogramObserver observed a NaN: cannot convert float NaN to integer")
+            raise OverflowError("HistogramObserver observed an infinite value: cannot convert float infinity to integer")
+
+    # ------------------------------------------------------------------ observation (host code: device passes + host merge)
     def _uninitialised(self):
         return float(self.min_val) == float("inf") and float(self.max_val) == float("-inf")
 
     def forward(self, x, group_size=None):
+        """group_size: slabs of `group_size` channels along ch_axis, each with its own histogram (device path only; the host
+        code observes the whole tensor)"""
         if x.numel() == 0:
+            return x
+        if self.device_path_ok(x, group_size):
+            self._observe_device(x.detach(), group_size)
             return x
         xd = x.detach()
         self._device = xd.device
@@ -264,7 +344,12 @@ class HistogramObserver(ObserverBase):
     def calculate_qparams(self):
         if self.quant_min is None:
             raise ValueError(f"{self.dtype!r} has no integer range: qparams are defined for XP[p,0](C..) formats only")
-        if self._uninitialised() or self._device is None:
+        if self._device is None:
+            return torch.tensor([1.0]), torch.tensor([0])
+        if self.histogram.is_cuda and self.bins <= HIST_DEVICE_MAX_BINS and (self.histogram.dim() == 2 or not hist_host_forced()):
+            return ops.hist_qparams(self.histogram, self.min_val.reshape(-1), self.max_val.reshape(-1), self.dtype.precision,
+                                    self.quant_min, self.quant_max, self.qscheme in _SYMMETRIC)
+        if self._uninitialised():
             return torch.tensor([1.0]), torch.tensor([0])
         assert self.bins == len(self.histogram), \
             "The number of bins in histogram should be equal to the number of bins supplied while making this observer"

@@ -53,7 +53,7 @@ typedef enum {
 } dmxq_status;
 
 const char* dmxq_status_string(int status);
-/* ABI version: bumped on any signature change.  Additions since 4 (dmxq_gptq_block) leave it at 4: a caller built against 4 runs on
+/* ABI version: bumped on any signature change.  Additions since 4 (dmxq_gptq_block, dmxq_hist_observe, dmxq_hist_qparams) leave it at 4: a caller built against 4 runs on
  * this library unchanged.  4 = round 5: + dmxq_float_qdq_multi, dmxq_fixed_float_qdq_multi; 3 = round 4: + dmxq_weight_hypernet_multi,
  * dmxq_unary_cast_table, dmxq_lut16_apply.  Nothing was ever removed or changed: a caller built against version n runs on any library >= n. */
 int dmxq_abi_version(void);
@@ -427,6 +427,24 @@ typedef struct {
 int dmxq_gptq_block(const float* w, int64_t ldw, float* q, int64_t ldq, float* err, int64_t lde, int64_t rows, int64_t count,
                     const float* hinv, int64_t ldh, const float* inv_d, int64_t microblock, const dmxq_gptq_format* fmt,
                     const float* scale, const int64_t* zero_point, void* stream);
+
+/* HistogramObserver on the device, for G = ceil(C / group_size) groups at once (slabs of group_size channels of the [outer, C, inner]
+ * view, as dmxq_group_minmax; per tensor: outer = C = 1, inner = n, group_size = 1).  csrc/hist_observer.hip; DESIGN.md §3.
+ * dmxq_hist_observe replaces numerical/observer.py:453-510 HistogramObserver.forward (min / max, torch.histc, the merge onto the
+ * running range, observer.py:400-458 re-binning) and the per-slab loop of numerical/cast.py:185-213; dmxq_hist_qparams replaces
+ * observer.py:331-397 _search_range and 59-115 _calculate_qparams.  Bit for bit the host code of dmx-compressor_amd/observer.py, save the
+ * two sums that ATen leaves unordered (torch.sum(hist), err.sum()): here fp64 in a fixed order, rounded once.
+ * State (caller-allocated, device, float32 unless said): hist [G, bins] and min_val / max_val [G] -- +inf / -inf before the first
+ * observation --, status: one int, 0 at first, raised to 1 (an infinite extremum: int(inf) raises OverflowError on the host) or 2 (a NaN:
+ * ValueError) by an observation that the host code would have refused; such a group's state is left unchanged.
+ * scratch: >= (2 + bins) * G * 4 bytes of device memory, contents free (scratch_bytes: its size).  bins <= 8192, upsample_rate <= 2^20.
+ * No host synchronisation, no allocation: both calls can be captured into a graph.  n == 0 changes nothing.
+ * dmxq_hist_qparams: levels = 2^precision; a group with min_val = +inf, max_val = -inf gets (1, 0). */
+int dmxq_hist_observe(const void* in, int dtype_in, int64_t outer, int64_t C, int64_t inner, int64_t group_size, int64_t bins,
+                      int64_t upsample_rate, float* hist, float* min_val, float* max_val, int* status, void* scratch, int64_t scratch_bytes,
+                      void* stream);
+int dmxq_hist_qparams(const float* hist, const float* min_val, const float* max_val, int64_t n_groups, int64_t bins, int precision, int qmin,
+                      int qmax, int symmetric_qscheme, float* scale, int64_t* zero_point, void* stream);
 
 #ifdef __cplusplus
 }
