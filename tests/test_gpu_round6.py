@@ -128,20 +128,21 @@ def test_sparsify_has_the_mask_of_its_initial_score(dmx, cuda, oracle):
 
 # ------------------------------------------------------------------------------------------------ bfp_slab.hip (LDS slabs / column tiles)
 SLAB_CASES = [
-    # shape, block_dim, B                      what it selects in csrc/bfp_slab.hip
-    ((4, 128, 14, 14), 1, 64),               # FLAT: rows of 392 bytes (not whole vectors), one contiguous slab per tile
-    ((2, 192, 14, 14), 1, 128),              # FLAT, 32 rows per lane, ragged last block (192 = 128 + 64)
-    ((3, 100, 14, 14), 1, 64),               # FLAT with a ragged last block of 36 rows
-    ((2, 128, 28, 28), 1, 64),               # SEGMENTED: two column tiles of 392
-    ((2, 64, 56, 56), 1, 64),                # SEGMENTED: eight column tiles
-    ((2, 48, 28, 28), 1, 16),                # B = 16: two lanes per column pair
-    ((2, 40, 28, 28), 1, 8),                 # B = 8: one lane per column pair
-    ((2, 96, 28, 28), 1, 32),
-    ((1, 512, 18, 18), 1, 256),              # B = 256: 64 rows per lane
-    ((2, 3, 224, 224), 1, 64),               # L = 3 < B / 2: one ragged block of three rows, B reduced to 8
-    ((2, 64, 10, 10), 1, 64),                # inner = 100
-    ((2, 64, 15, 15), 1, 64),                # odd inner: NOT the slab kernel (column kernel, unaligned form) -- same results
-    ((2, 12, 200, 64), -2, 64),              # attention operands blocked along the sequence: inner = 64
+    # shape, block_dim, B                      the kernel that computes it (tests/_strided_cases.py restates the routing; the cases that
+    #                                          assert which kernel ran, and every form of the slab kernel, are tests/test_gpu_strided_blocks.py)
+    ((4, 128, 14, 14), 1, 64),               # slab, 256 lanes: rows of 392 bytes (not whole vectors), one contiguous slab per tile
+    ((2, 192, 14, 14), 1, 128),              # slab, 256 lanes, 32 rows per lane, ragged last block (192 = 128 + 64)
+    ((3, 100, 14, 14), 1, 64),               # slab, 256 lanes, ragged last block of 36 rows
+    ((2, 128, 28, 28), 1, 64),               # slab, 1024 lanes: 98 KiB slabs, 4 tiles
+    ((2, 64, 56, 56), 1, 64),                # COLUMN kernel: 394 KiB slabs are refused (and whole-line rows are not slab-preferred)
+    ((2, 48, 28, 28), 1, 16),                # slab, B = 16: two lanes per column pair
+    ((2, 40, 28, 28), 1, 8),                 # COLUMN kernel: 12.25 KiB slabs are not slab-preferred (B = 8)
+    ((2, 96, 28, 28), 1, 32),                # slab, B = 32: four lanes per column pair
+    ((1, 512, 18, 18), 1, 256),              # generic kernel: a 168 KiB slab is over the 150 KiB cap, B = 256 is not the column kernel's
+    ((2, 3, 224, 224), 1, 64),               # COLUMN kernel, L = 3 < B / 2: one ragged block of three rows, B reduced to 8
+    ((2, 64, 10, 10), 1, 64),                # COLUMN kernel: inner = 100, 12.5 KiB slabs are not slab-preferred
+    ((2, 64, 15, 15), 1, 64),                # COLUMN kernel, unaligned form: odd inner
+    ((2, 12, 200, 64), -2, 64),              # COLUMN kernel: attention operands blocked along the sequence, rows of 128 bytes
     ((8, 1500, 64), -2, 64),                 # ... with a ragged last block (1500 = 23 x 64 + 28)
 ]
 
@@ -149,7 +150,7 @@ SLAB_CASES = [
 @pytest.mark.parametrize("dtype", [BF16, F16])
 @pytest.mark.parametrize("shape,dim,B", SLAB_CASES)
 def test_bfp_slab_kernel_vs_oracle(dmx, cuda, oracle, dtype, shape, dim, B):
-    """blocks along a strided dim through the LDS slab kernel: heavy-tailed data with special blocks (all zero, denormal maximum, Inf,
+    """blocks along a strided dim through the LDS slab kernel or, where the table above says so, the column kernel: heavy-tailed data with special blocks (all zero, denormal maximum, Inf,
     NaN, huge maximum: the literal path), symmetric and asymmetric, two precisions (single / double rounding builds), in place"""
     x = make("heavy", shape, seed=B + shape[1], dtype=dtype)
     flat = x.reshape(-1)
@@ -382,12 +383,18 @@ def test_graphed_module_captures_one_graph_per_input_signature(dmx, cuda):
 
 @pytest.mark.parametrize("chunk", range(3))
 def test_bfp_slab_random_cases(dmx, cuda, oracle, chunk):
-    """randomised differential cases drawn INSIDE the slab kernel's routing rule (rows that are not whole 128-byte lines, slabs of at
-    least 16 KiB): block sizes, ragged block dims, even inner extents, both 16-bit dtypes, precisions, symmetric / asymmetric"""
+    """randomised differential cases drawn inside the slab kernel's routing rule (rows that are not whole 128-byte lines, slabs of at
+    least 16 KiB): block sizes, ragged block dims, even inner extents, both 16-bit dtypes, precisions, symmetric / asymmetric.  Drawn
+    until 14 cases per chunk are ACCEPTED by the slab kernel (tests/_strided_cases.py restates its rules; the internal entry's return
+    code is asserted either way); the draws it refuses -- ragged tails that are not whole 16-byte vectors -- stay as cases of the
+    column kernel it falls back to."""
     import random
+
+    import _strided_cases as S
+    lib = dmx._lib.lib()
     rng = random.Random(6000 + chunk)
-    done = 0
-    while done < 14:
+    done = accepted = 0
+    while accepted < 14:
         B = rng.choice([8, 16, 32, 64, 64, 64, 128, 256])
         inner = 2 * rng.randrange(32, 620)
         if (inner * 2) % 128 == 0 or B * inner * 2 < 16 * 1024 or B * ((inner // 2 + 40)) * 4 > 150 * 1024:
@@ -400,10 +407,21 @@ def test_bfp_slab_random_cases(dmx, cuda, oracle, chunk):
         wl = rng.choice([2, 4, 8, 8, 8, 12, 15, 16, 20])
         sym = rng.random() < 0.7
         x = make(rng.choice(["normal", "heavy", "mixed_nd" if not sym else "mixed", "outlier", "ties"]), (outer, L, inner), seed=chunk * 100 + done, dtype=dtype, block=min(B, 64))
-        got = dmx.ops.bfp_qdq(x.to(cuda), wl, B, 1, sym)
+        what = (chunk, done, outer, L, inner, B, dtype, wl, sym)
+        xd = x.to(cuda)
+        got = dmx.ops.bfp_qdq(xd, wl, B, 1, sym)
         want = oracle.bfp_cast(x, wl, B, 1, sym).to(dtype)
-        assert mismatches_nan_aware(got, want) == 0, (chunk, done, outer, L, inner, B, dtype, wl, sym)
+        assert mismatches_nan_aware(got, want) == 0, what
+        geom = S.slab_geometry(outer, L, inner, B, wl)
+        assert S.slab_preferred(inner, B)
+        out = torch.zeros_like(xd)
+        rc = S.entry(lib, "slab", xd, out, outer, L, inner, B, wl, sym)
+        assert rc == (0 if geom.accepted else S.ERR_UNSUPPORTED), what + (geom.reason,)
+        if geom.accepted:
+            assert mismatches_nan_aware(out, want) == 0, ("slab entry",) + what
+            accepted += 1
         done += 1
+    assert done >= 14
 
 
 def test_plans_scaled_to_another_cu_count_give_the_same_bits(oracle):
