@@ -21,6 +21,9 @@ from .observer import DummyObserver, HistogramObserver, MinMaxObserver, Percenti
 from .smoothquant import ActivationWeightSmoothQuant
 from .config import apply_legacy_config, load_legacy_config
 from .sparse import Bernoulli, BlockTopK, Dense, Sparseness, Sparsify, TopK
+from . import benchmark
+from .benchmark import (compute_error, compute_maxdelta_error, compute_mse_error, format_sweep, gather_tensors,
+                        measure_model_error)
 
 __version__ = "0.1.0"
 

@@ -733,3 +733,42 @@ def hist_qparams(hist, min_val, max_val, precision, qmin, qmax, symmetric_qschem
     check(lib().dmxq_hist_qparams(ptr(hist), ptr(min_val), ptr(max_val), G, hist.numel() // G, precision, qmin, qmax, int(symmetric_qscheme),
                                   ptr(scale), ptr(zp), stream_of(hist)), "dmxq_hist_qparams")
     return scale, zp
+
+
+# ------------------------------------------------------------------------------------------------ error statistics
+def _error_rows(stats, scratch, like, rows, op):
+    if not (stats.is_cuda and stats.device == like.device and stats.dtype == torch.float64 and stats.is_contiguous() and stats.numel() == 4 * rows):
+        raise RuntimeError(f"{op}: stats must be a contiguous float64 tensor of {rows} x 4 entries on the input's device")
+    if not (scratch.is_cuda and scratch.device == like.device and scratch.is_contiguous()):
+        raise RuntimeError(f"{op}: scratch must be a contiguous tensor on the input's device")
+
+
+@_guarded
+def error_stats(ref, test, accumulate, stats, scratch):
+    rc, tc = _prep(ref, "error_stats"), _prep(test, "error_stats")
+    if rc.device != tc.device or rc.numel() != tc.numel():
+        raise RuntimeError("error_stats: ref and test must hold the same number of elements on one device")
+    _error_rows(stats, scratch, rc, 1, "error_stats")
+    check(lib().dmxq_error_stats(ptr(rc), dtype_code(rc.dtype), ptr(tc), dtype_code(tc.dtype), rc.numel(), int(bool(accumulate)), ptr(stats),
+                                 ptr(scratch), scratch.numel() * scratch.element_size(), stream_of(rc)), "dmxq_error_stats")
+
+
+@_guarded
+def cast_error(x, fmts, scale, zero_point, accumulate, stats, scratch):
+    xc = _prep(x, "cast_error")
+    if not fmts or len(fmts) % 12:
+        raise RuntimeError("cast_error: fmts is the 12 fields of dmxq_gptq_format per format")
+    K = len(fmts) // 12
+    _error_rows(stats, scratch, xc, K, "cast_error")
+    if scale is not None and not (scale.is_cuda and scale.device == xc.device and scale.dtype == torch.float32 and scale.is_contiguous()
+                                  and scale.numel() >= K):
+        raise RuntimeError("cast_error: scale must be a contiguous float32 tensor with an entry per format on x's GPU")
+    if zero_point is not None and not (zero_point.is_cuda and zero_point.device == xc.device and zero_point.dtype == torch.int64
+                                       and zero_point.is_contiguous() and zero_point.numel() >= K):
+        raise RuntimeError("cast_error: zero_point must be a contiguous int64 tensor with an entry per format on x's GPU")
+    f = (_lib.GptqFormat * K)(*[_lib.GptqFormat(*[int(v) for v in fmts[12 * k:12 * k + 12]]) for k in range(K)])
+    L = xc.shape[-1] if xc.dim() else 1
+    rows = xc.numel() // L if L else 0
+    check(lib().dmxq_cast_error(ptr(xc), dtype_code(xc.dtype), rows, L, ctypes.cast(f, ctypes.c_void_p), K, ptr(scale), ptr(zero_point),
+                                int(bool(accumulate)), ptr(stats), ptr(scratch), scratch.numel() * scratch.element_size(), stream_of(xc)),
+          "dmxq_cast_error")

@@ -20,7 +20,8 @@ from ._lib import DmxqError, ROUNDING_CODE, require_gpu
 __all__ = [
     "bfp_qdq", "block_quantize", "bfp_qdq_multi", "bfp_pack", "bfp_unpack", "weight_hypernet", "weight_hypernet_multi", "input_hypernet", "binary_cast", "rope_cast", "relu_cast", "unary_cast", "unary_cast_table", "lut16_apply", "softmax_cast", "layernorm_cast", "rmsnorm_cast", "sbfp_qdq", "mxfp_qdq", "float_qdq", "float_qdq_multi", "fixed_qdq", "fixed_qdq_multi", "fixed_float_qdq_multi", "nm_mask", "nm_sparsify", "topk_mask", "topk_sparsify", "bernoulli_mask", "group_minmax", "group_minmax_accumulate", "qparams", "channel_maxabs",
     "smoothquant_scale", "scale_channels", "gelu", "silu", "quick_gelu", "exp", "silu_experimental", "rope", "softmax", "layernorm",
-    "rmsnorm", "histc", "gptq_fields", "gptq_block", "hist_observe", "hist_scratch_words", "hist_qparams",
+    "rmsnorm", "histc", "gptq_fields", "gptq_block", "hist_observe", "hist_scratch_words", "hist_qparams", "error_stats", "cast_error",
+    "error_scratch_bytes",
 ]
 
 _ops = None   # the raw namespace: set by bind()
@@ -583,3 +584,132 @@ def gptq_block(w, hinv, inv_d, q, err, microblock: int, fields, scale=None, zero
     NotImplementedError where the kernel does not take the format / microblock (the caller runs its own loop)."""
     require_gpu(w, "gptq_block")
     _ops.gptq_block(w, hinv, inv_d, int(microblock), [int(v) for v in fields], scale, zero_point, q, err)
+
+
+# ---------------------------------------------------------------------------------------------------- error statistics
+ERR_MAX_FORMATS = 8   # formats per dmxq_cast_error call
+
+
+def error_scratch_bytes(n: int, n_formats: int = 1) -> int:
+    """dmxq_error_scratch_bytes: the scratch one dmxq_error_stats (n_formats = 1) or dmxq_cast_error call over n elements needs.  A host
+    query of the library itself, the same for both bindings."""
+    from ._lib import lib
+    return int(lib().dmxq_error_scratch_bytes(int(n), int(n_formats)))
+
+
+def _err_scratch(x, n_formats):
+    return torch.empty(max(error_scratch_bytes(x.numel(), n_formats), 8), dtype=torch.uint8, device=x.device)
+
+
+def _err_out(like, rows, out, accumulate, what):
+    if out is None:
+        if accumulate:
+            raise ValueError(f"{what}: accumulate=True merges into an existing row: pass it as out=")
+        return torch.empty((rows, 4) if rows is not None else (4,), dtype=torch.float64, device=like.device)
+    want = 4 * (rows if rows is not None else 1)
+    if not (out.is_cuda and out.device == like.device and out.dtype == torch.float64 and out.is_contiguous() and out.numel() == want):
+        raise ValueError(f"{what}: out must be a contiguous float64 tensor of {want} entries on the input's device")
+    return out
+
+
+def error_stats(ref, test, out=None, accumulate: bool = False):
+    """[sum_sq_err, sum_sq_ref, max_abs_err, count] between a reference and a test tensor of one shape (float32 / float16 / bfloat16 in any
+    combination) as a float64 [4] row ON THE DEVICE: one read of each tensor, no host synchronisation (dmxq_error_stats).
+    sum_sq_err = sum (float(ref) - float(test))^2 and sum_sq_ref = sum float(ref)^2 in fp64; max_abs_err is torch's
+    (ref - test).float().abs().max(); mse = row[0] / row[3], SQNR in dB = 10 log10(row[1] / row[0]).  accumulate=True merges into `out`
+    (sums add, max takes the max, count adds): statistics over many batches.  A non-dense view is copied to a contiguous tensor first."""
+    require_gpu(ref, "error_stats")
+    require_gpu(test, "error_stats")
+    if ref.shape != test.shape:
+        raise ValueError(f"error_stats: shapes differ: {tuple(ref.shape)} and {tuple(test.shape)}")
+    out = _err_out(ref, None, out, accumulate, "error_stats")
+    _ops.error_stats(ref.detach(), test.detach(), bool(accumulate), out, _err_scratch(ref, 1))
+    return out
+
+
+def _cast_error_entry(entry):
+    """a `formats` entry of cast_error -> (Format, scale, zero_point); FixedPoint: (format, scale, zero_point), numbers or 1-element tensors"""
+    from .format import FixedPoint, Format
+    fmt, scale, zp = entry if isinstance(entry, (tuple, list)) else (entry, None, None)
+    fmt = Format.from_shorthand(fmt)
+    if not isinstance(fmt, Format):
+        raise TypeError(f"cast_error: {fmt!r} is not a numerical format")
+    parts = [fmt] + [getattr(fmt, a) for a in ("block_format", "scaler_format", "element_format") if hasattr(fmt, a)]
+    if any(getattr(p, "rounding", None) == "stochastic" for p in parts):
+        raise NotImplementedError(f"cast_error: {fmt!r} rounds stochastically: its error is not a property of the format alone")
+    if scale is not None:
+        if not isinstance(fmt, FixedPoint):
+            raise ValueError(f"cast_error: only a FixedPoint entry takes a (format, scale, zero_point) triple, got {fmt!r}")
+        if any(isinstance(t, torch.Tensor) and t.numel() != 1 for t in (scale, zp)):
+            raise ValueError("cast_error: a FixedPoint entry takes ONE scale and zero point (per-channel / per-group: CastTo.measure_error)")
+    return fmt, scale, zp
+
+
+def _affine_tensor(v, dtype, like, default):
+    if isinstance(v, torch.Tensor):
+        return v.detach().to(device=like.device, dtype=dtype).reshape(1)
+    return torch.full((1,), default if v is None else v, dtype=dtype, device=like.device)   # (a fill launch: no host copy, capturable)
+
+
+def _cast_like_library(x, fmt, scale, zp, block_dim):
+    """the library's own cast of x to fmt, in x's dtype (what CastTo.forward returns)"""
+    from .format import FixedPoint
+    if isinstance(fmt, FixedPoint) and scale is not None:
+        return fixed_qdq(x, fmt.precision, fmt.fraction, fmt.clamp, fmt.symmetric, fmt.rounding,
+                         scale=_affine_tensor(scale, torch.float32, x, 1.0), zero_point=_affine_tensor(zp, torch.int64, x, 0), out_dtype=x.dtype)
+    return fmt.cast(x, block_dim, out_dtype=x.dtype)
+
+
+def cast_error(x, formats, block_dim: int = -1, out=None, accumulate: bool = False):
+    """The error_stats row between x and its cast to each of K formats -- float64 [K, 4] on the device -- WITHOUT materialising the casts
+    where the fused kernel covers them: x is read once per group of up to 8 formats and every cast is evaluated in registers
+    (dmxq_cast_error).  formats: Format objects or shorthands; a FixedPoint entry may be a (format, scale, zero_point)
+    triple (numbers or 1-element tensors: the affine wrapper of CastTo), else it is the bare fixed point cast.
+    Row k equals error_stats(x, CastTo(formats[k], block_dim=block_dim)(x)): count and max_abs_err bit for bit, the two sums up to the
+    order of an fp64 sum.  Fused: BFP / MXINT (nearest, blocks of 8 .. 128 along the last dim, dividing it), FloatingPoint (nearest) and
+    FixedPoint (nearest) on a tensor whose last dim is a multiple of 8.  Everything else -- a block dim other than the last, MXFP, SBFP,
+    ragged blocks, up / down rounding -- runs as the library's own cast followed by error_stats, under the same contract.  Stochastic
+    rounding is refused (NotImplementedError)."""
+    from .format import BlockFloatingPoint, FixedPoint, FloatingPoint
+    require_gpu(x, "cast_error")
+    entries = [_cast_error_entry(e) for e in formats]
+    K = len(entries)
+    if K == 0:
+        raise ValueError("cast_error: no formats")
+    out = _err_out(x, K, out, accumulate, "cast_error").view(K, 4)
+    xd = x.detach()
+    xd = xd if xd.is_contiguous() else xd.contiguous()
+    last = xd.dim() >= 1 and -xd.dim() <= block_dim < xd.dim() and block_dim % xd.dim() == xd.dim() - 1
+    fields = []
+    for fmt, scale, zp in entries:
+        f = gptq_fields(fmt) if xd.dim() >= 1 else None
+        if f is not None and isinstance(fmt, BlockFloatingPoint) and not last:
+            f = None
+        if f is not None and isinstance(fmt, FloatingPoint) and fmt.native_of() == xd.dtype:
+            f = None   # (Format.cast hands such a tensor through untouched)
+        fields.append(f)
+    fused = [i for i in range(K) if fields[i] is not None]
+    rest = [i for i in range(K) if fields[i] is None]
+    for c0 in range(0, len(fused), ERR_MAX_FORMATS):
+        idx = fused[c0:c0 + ERR_MAX_FORMATS]
+        dense = idx == list(range(idx[0], idx[0] + len(idx)))
+        rows = out[idx[0]:idx[0] + len(idx)] if dense else (torch.stack([out[i] for i in idx]) if accumulate else
+                                                            torch.empty((len(idx), 4), dtype=torch.float64, device=xd.device))
+        scale = zp = None
+        if any(isinstance(entries[i][0], FixedPoint) for i in idx):
+            scale = torch.cat([_affine_tensor(entries[i][1], torch.float32, xd, 1.0) for i in idx])
+            zp = torch.cat([_affine_tensor(entries[i][2], torch.int64, xd, 0) for i in idx])
+        try:
+            _ops.cast_error(xd, [int(v) for i in idx for v in fields[i]], scale, zp, bool(accumulate), rows, _err_scratch(xd, len(idx)))
+        except NotImplementedError:   # (DMXQ_ERR_UNSUPPORTED, nothing launched: a last dim that is no multiple of 8 or of a block size, ...)
+            rest += idx
+            continue
+        if not dense:
+            for j, i in enumerate(idx):
+                out[i].copy_(rows[j])
+    for i in sorted(rest):
+        fmt, scale, zp = entries[i]
+        with torch.no_grad():
+            y = _cast_like_library(xd, fmt, scale, zp, block_dim)
+        error_stats(xd, y, out=out[i], accumulate=accumulate)
+    return out

@@ -72,6 +72,9 @@ SIGNATURES = {
     "dmxq_gptq_block": [_vp, _i64, _vp, _i64, _vp, _i64, _i64, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp],
     "dmxq_hist_observe": [_vp, _i32, _i64, _i64, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _vp],
     "dmxq_hist_qparams": [_vp, _vp, _vp, _i64, _i64, _i32, _i32, _i32, _i32, _vp, _vp, _vp],
+    "dmxq_error_scratch_bytes": [_i64, _i32],
+    "dmxq_error_stats": [_vp, _i32, _vp, _i32, _i64, _i32, _vp, _vp, _i64, _vp],
+    "dmxq_cast_error": [_vp, _i32, _i64, _i64, _vp, _i32, _vp, _vp, _i32, _vp, _vp, _i64, _vp],
 }
 
 
@@ -126,6 +129,7 @@ def lib():
             fn.argtypes = argtypes
             fn.restype = ctypes.c_int
         L.dmxq_topk_workspace_bytes.restype = ctypes.c_int64
+        L.dmxq_error_scratch_bytes.restype = ctypes.c_int64
         L.dmxq_status_string.argtypes = [ctypes.c_int]
         L.dmxq_status_string.restype = ctypes.c_char_p
         L.dmxq_abi_version.restype = ctypes.c_int

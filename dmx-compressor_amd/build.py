@@ -15,7 +15,7 @@ LIB = os.path.join(HERE, "lib", "libdmxq.so")
 TORCH_LIB = os.path.join(HERE, "lib", "dmxq_torch.so")
 # "file.hip" or "file.hip#N": the file compiled with -DDMXQ_EW_PART=N into file_pN.o (elementwise.hip: three objects, approx.hip: two, in parallel);
 # the slowest compilations first (gptq.hip: 18 unrolled kernels)
-SOURCES = ["gptq.hip", "hist_observer.hip", "bfp.hip#1", "approx.hip#3", "approx.hip#5", "approx.hip#1", "approx.hip#2", "approx.hip#4", "elementwise.hip#2", "elementwise.hip#1", "elementwise.hip#3", "bfp_cols.hip#1", "bfp_cols.hip#2", "bfp_cols.hip#3", "bfp.hip#2", "bfp.hip#3", "bfp_urows.hip", "bfp_smallinner.hip", "bfp_slab.hip", "blockfmt.hip", "bfp_pack.hip", "hypernet.hip", "hypernet_multi.hip", "nm_mask.hip", "topk.hip", "reduce.hip", "unary.hip", "act_cast.hip", "lut16.hip", "fixed_multi.hip", "rope.hip"]
+SOURCES = ["gptq.hip", "hist_observer.hip", "error_stats.hip", "bfp.hip#1", "approx.hip#3", "approx.hip#5", "approx.hip#1", "approx.hip#2", "approx.hip#4", "elementwise.hip#2", "elementwise.hip#1", "elementwise.hip#3", "bfp_cols.hip#1", "bfp_cols.hip#2", "bfp_cols.hip#3", "bfp.hip#2", "bfp.hip#3", "bfp_urows.hip", "bfp_smallinner.hip", "bfp_slab.hip", "blockfmt.hip", "bfp_pack.hip", "hypernet.hip", "hypernet_multi.hip", "nm_mask.hip", "topk.hip", "reduce.hip", "unary.hip", "act_cast.hip", "lut16.hip", "fixed_multi.hip", "rope.hip"]
 # bit-exact fp32: no fast-math, no fma contraction; fp32 denormals stay on (gfx950 default).
 # --offload-compress (round 5): the gfx950 code objects are stored zstd-compressed inside the fat binary and unpacked by the HIP runtime at
 # load: libdmxq.so 88 MB -> 17 MB (what a gpurun snapshot pushes, what a wheel would ship), load time and kernels unchanged
@@ -32,7 +32,9 @@ FLAGS = ["--offload-arch=gfx950", "--offload-compress", "-mllvm", "-amdgpu-kerna
 # the compiler adds NO vector memory operation of its own, i.e. no scratch (a spill store can retire out of order against the loads on
 # gfx9): checked at build time from the compiler's own resource remarks -- a compiler upgrade or an edit that makes one of them spill
 # fails the build instead of silently reading registers before their data has landed.  source -> substrings of kernel names
-NO_SCRATCH = {"lut16.hip": ["lut16_apply_kernel"], "fixed_multi.hip": ["stream_multi2_kernel", "stream_multi_kernel"]}
+NO_SCRATCH = {"lut16.hip": ["lut16_apply_kernel"], "fixed_multi.hip": ["stream_multi2_kernel", "stream_multi_kernel"],
+              # the error statistics: a format table indexed in memory instead of registers shows as scratch (csrc/error_stats.hip ErrFmts)
+              "error_stats.hip": ["cast_error_kernel", "error_stats_kernel"]}
 
 
 def _check_no_scratch(src, remarks_file):
@@ -49,7 +51,8 @@ def _check_no_scratch(src, remarks_file):
             seen.add(cur)
             if int(m.group(2)) != 0:
                 raise RuntimeError(f"{src}: kernel {cur} uses {m.group(2)} bytes/lane of scratch (lut16: its hand-counted s_waitcnt would be "
-                                   f"wrong; the multi-tensor kernels: every wave of a launch pays for a spilling body) -- build.py NO_SCRATCH")
+                                   f"wrong; the multi-tensor kernels: every wave of a launch pays for a spilling body; "
+                                   f"the error statistics: the format table must stay in registers) -- build.py NO_SCRATCH")
     if not seen:
         raise RuntimeError(f"{src}: no kernel matching {wanted} in the compiler's resource remarks: the NO_SCRATCH check did not run")
 

@@ -270,6 +270,25 @@ class CastTo(HostFlags, torch.nn.Module):
             x, _ = self.apply_shaping_seq(x, inverse_shaping)
         return x.to(self.physical_dtype)
 
+    # ------------------------------------------------------------------ error of this cast
+    def measure_error(self, x):
+        """The row [sum_sq_err, sum_sq_ref, max_abs_err, count] (float64 [4] on x's device, ops.error_stats) between x and what this cast
+        makes of it: its format along its block_dim with its current scale / zero point.  Neither the observer nor the switches are
+        touched, and nothing is read back to the host.  BFP, FloatingPoint and per-tensor FixedPoint casts are measured without
+        materialising the cast (ops.cast_error); per-channel / per-group FixedPoint, and the formats cast_error does not fuse, as this
+        cast's own launch followed by ops.error_stats.  A cast with a pre_transform is not measured."""
+        if self.pre_transform:
+            raise NotImplementedError("CastTo.measure_error: a cast with a pre_transform (shaping / shortcut / pre-format)")
+        fmt, x = self.format, x.detach()
+        if not isinstance(fmt, Format) or isinstance(fmt, Same):
+            return ops.error_stats(x, x)
+        if isinstance(fmt, FixedPoint):
+            if self.group_size or self.is_per_channel or self.scale.numel() != 1:
+                with torch.no_grad():
+                    return ops.error_stats(x, self._quantize(x, x.dtype))
+            return ops.cast_error(x, [(fmt, self.scale, self.zero_point)], block_dim=self.block_dim)[0]
+        return ops.cast_error(x, [fmt], block_dim=self.block_dim)[0]
+
     # ------------------------------------------------------------------ introspection
     def get_precision(self) -> Optional[float]:
         if isinstance(self.format, Same):

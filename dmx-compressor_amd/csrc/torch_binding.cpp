@@ -902,6 +902,55 @@ std::tuple<Tensor, Tensor> hist_qparams_meta(const Tensor& hist, const Tensor& m
   return {at::empty({min_val.numel()}, hist.options().dtype(at::kFloat)), at::empty({min_val.numel()}, hist.options().dtype(at::kLong))};
 }
 
+// ------------------------------------------------------------------------------------------------ error statistics
+// rows of [sum_sq_err, sum_sq_ref, max_abs_err, count] (dmxq_error_stats, dmxq_cast_error): stats is float64 [.., 4], written (or merged
+// into) in place; scratch: dmxq_error_scratch_bytes bytes of any contiguous device tensor
+inline void error_rows(const Tensor& stats, const Tensor& scratch, const Tensor& like, int64_t rows, const char* op) {
+  TORCH_CHECK(stats.is_cuda() && stats.device() == like.device() && stats.scalar_type() == at::kDouble && stats.is_contiguous() &&
+              stats.numel() == 4 * rows, op, ": stats must be a contiguous float64 tensor of ", rows, " x 4 entries on the input's device");
+  TORCH_CHECK(scratch.is_cuda() && scratch.device() == like.device() && scratch.is_contiguous(), op,
+              ": scratch must be a contiguous tensor on the input's device");
+}
+void error_stats(const Tensor& ref, const Tensor& test, bool accumulate, Tensor stats, Tensor scratch) {
+  const Tensor rc = prep(ref, "error_stats"), tc = prep(test, "error_stats");
+  TORCH_CHECK(rc.device() == tc.device() && rc.numel() == tc.numel(), "error_stats: ref and test must hold the same number of elements on one device");
+  error_rows(stats, scratch, rc, 1, "error_stats");
+  Launch l(rc);
+  check(dmxq_error_stats(rc.data_ptr(), dt_code(rc.scalar_type()), tc.data_ptr(), dt_code(tc.scalar_type()), rc.numel(), accumulate,
+                         (double*)stats.data_ptr(), scratch.data_ptr(), (int64_t)(scratch.numel() * scratch.element_size()), l.stream),
+        "dmxq_error_stats");
+}
+void error_stats_meta(const Tensor&, const Tensor&, bool, Tensor, Tensor) {}
+
+// x: [rows, L] (any leading dims, blocks along the last); fmts: 12 fields of dmxq_gptq_format per format; scale / zero_point: one entry
+// per format (read for the fixed point ones)
+void cast_error(const Tensor& x, at::IntArrayRef fmts, const OptTensor& scale, const OptTensor& zero_point, bool accumulate, Tensor stats,
+                Tensor scratch) {
+  const Tensor xc = prep(x, "cast_error");
+  TORCH_CHECK(!fmts.empty() && fmts.size() % 12 == 0, "cast_error: fmts is the 12 fields of dmxq_gptq_format per format");
+  const int64_t K = (int64_t)fmts.size() / 12;
+  error_rows(stats, scratch, xc, K, "cast_error");
+  const bool has_sc = scale.has_value() && scale->defined(), has_zp = zero_point.has_value() && zero_point->defined();
+  TORCH_CHECK(!has_sc || (scale->is_cuda() && scale->device() == xc.device() && scale->scalar_type() == at::kFloat && scale->is_contiguous() &&
+              scale->numel() >= K), "cast_error: scale must be a contiguous float32 tensor with an entry per format on x's GPU");
+  TORCH_CHECK(!has_zp || (zero_point->is_cuda() && zero_point->device() == xc.device() && zero_point->scalar_type() == at::kLong &&
+              zero_point->is_contiguous() && zero_point->numel() >= K),
+              "cast_error: zero_point must be a contiguous int64 tensor with an entry per format on x's GPU");
+  std::vector<dmxq_gptq_format> f((size_t)K);
+  for (int64_t k = 0; k < K; k++) {
+    const int64_t* v = fmts.data() + 12 * k;
+    f[(size_t)k] = dmxq_gptq_format{(int)v[0], (int)v[1], (int)v[2], (int)v[3], (int)v[4], (int)v[5], (int)v[6], (int)v[7], (int)v[8], (int)v[9],
+                                    (int)v[10], (int)v[11]};
+  }
+  const int64_t L = xc.dim() ? xc.size(-1) : 1, rows = L ? xc.numel() / L : 0;
+  Launch l(xc);
+  check(dmxq_cast_error(xc.data_ptr(), dt_code(xc.scalar_type()), rows, L, f.data(), (int)K, has_sc ? (const float*)scale->data_ptr() : nullptr,
+                        has_zp ? (const int64_t*)zero_point->data_ptr() : nullptr, accumulate, (double*)stats.data_ptr(), scratch.data_ptr(),
+                        (int64_t)(scratch.numel() * scratch.element_size()), l.stream),
+        "dmxq_cast_error");
+}
+void cast_error_meta(const Tensor&, at::IntArrayRef, const OptTensor&, const OptTensor&, bool, Tensor, Tensor) {}
+
 }  // namespace
 
 TORCH_LIBRARY(dmxq, m) {
@@ -950,6 +999,8 @@ TORCH_LIBRARY(dmxq, m) {
   m.def("gptq_block(Tensor w, Tensor hinv, Tensor inv_d, int microblock, int[] fmt, Tensor? scale, Tensor? zero_point, Tensor(a!) q, Tensor(b!) err) -> ()");
   m.def("hist_observe(Tensor x, int ch_axis, int group_size, int upsample_rate, Tensor(a!) hist, Tensor(b!) min_val, Tensor(c!) max_val, Tensor(d!) status, Tensor(e!) scratch) -> ()");
   m.def("hist_qparams(Tensor hist, Tensor min_val, Tensor max_val, int precision, int qmin, int qmax, bool symmetric_qscheme) -> (Tensor, Tensor)");
+  m.def("error_stats(Tensor ref, Tensor test, bool accumulate, Tensor(a!) stats, Tensor(b!) scratch) -> ()");
+  m.def("cast_error(Tensor x, int[] fmts, Tensor? scale, Tensor? zero_point, bool accumulate, Tensor(a!) stats, Tensor(b!) scratch) -> ()");
 }
 
 #define DMXQ_IMPL(m, name) m.impl(#name, &name)
@@ -958,7 +1009,8 @@ TORCH_LIBRARY(dmxq, m) {
   X(m, bfp_qdq); X(m, block_quantize); X(m, bfp_qdq_multi); X(m, weight_hypernet_multi); X(m, bfp_pack); X(m, bfp_unpack); X(m, weight_hypernet); X(m, input_hypernet); X(m, binary_cast); X(m, relu_cast); X(m, sbfp_qdq); X(m, mxfp_qdq);   \
   X(m, float_qdq); X(m, float_qdq_multi); X(m, fixed_qdq); X(m, fixed_qdq_multi); X(m, fixed_float_qdq_multi); X(m, nm_mask); X(m, topk_mask); X(m, bernoulli_mask); X(m, group_minmax); X(m, qparams); \
   X(m, histc); X(m, channel_maxabs); X(m, smoothquant_scale); X(m, scale_channels); X(m, unary); X(m, rope); X(m, rope_cast); X(m, softmax); X(m, norm); \
-  X(m, unary_cast); X(m, unary_cast_table); X(m, lut16_apply); X(m, softmax_cast); X(m, norm_cast); X(m, group_minmax_accumulate); X(m, gptq_block); X(m, hist_observe); X(m, hist_qparams)
+  X(m, unary_cast); X(m, unary_cast_table); X(m, lut16_apply); X(m, softmax_cast); X(m, norm_cast); X(m, group_minmax_accumulate); X(m, gptq_block); X(m, hist_observe); X(m, hist_qparams); \
+  X(m, error_stats); X(m, cast_error)
 
 // "CUDA" is the dispatch key of HIP tensors in a ROCm build of PyTorch
 TORCH_LIBRARY_IMPL(dmxq, CUDA, m) {
@@ -1010,4 +1062,6 @@ PYBIND11_MODULE(dmxq_fast, m) {
         py::arg("cast_out"), py::arg("bfp_block") = 0, py::arg("bfp_precision") = 0);
   m.def("hist_observe", &hist_observe);
   m.def("hist_qparams", &hist_qparams);
+  m.def("error_stats", &error_stats);
+  m.def("cast_error", &cast_error);
 }

@@ -398,6 +398,19 @@ class DmxModule(FastAttr, torch.nn.Module):
         yield self
         self.enable_smoothquant_calib(False, hyperparams)
 
+    @contextmanager
+    def monitoring(self, records: list):
+        """modeling/nn/core.py:301-317: while active, every forward of this module appends {"input": (args, kwargs), "output": out} to
+        `records` (the tensors themselves, not copies); the forward hook is removed on exit.  benchmark.measure_model_error is built on it."""
+        def recorder(_module, args, kwargs, out) -> None:
+            records.append(dict(input=(args, kwargs), output=out))
+
+        handle = self.register_forward_hook(recorder, with_kwargs=True)
+        try:
+            yield self
+        finally:
+            handle.remove()
+
     def enable_optimal_brain_compression(self, state: bool, hyperparams) -> None:
         """layer_reconstruction.py:70-86: Linear and Conv2d only (any other module: nothing happens).  Entering measures the Hessian of
         the unquantised inputs (fake quant off on the input casts and the weight cast); leaving switches both back on and runs GPTQ."""

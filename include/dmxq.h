@@ -53,7 +53,8 @@ typedef enum {
 } dmxq_status;
 
 const char* dmxq_status_string(int status);
-/* ABI version: bumped on any signature change.  Additions since 4 (dmxq_gptq_block, dmxq_hist_observe, dmxq_hist_qparams) leave it at 4: a caller built against 4 runs on
+/* ABI version: bumped on any signature change.  Additions since 4 (dmxq_gptq_block, dmxq_hist_observe, dmxq_hist_qparams, dmxq_error_stats, dmxq_cast_error,
+ * dmxq_error_scratch_bytes) leave it at 4: a caller built against 4 runs on
  * this library unchanged.  4 = round 5: + dmxq_float_qdq_multi, dmxq_fixed_float_qdq_multi; 3 = round 4: + dmxq_weight_hypernet_multi,
  * dmxq_unary_cast_table, dmxq_lut16_apply.  Nothing was ever removed or changed: a caller built against version n runs on any library >= n. */
 int dmxq_abi_version(void);
@@ -445,6 +446,38 @@ int dmxq_hist_observe(const void* in, int dtype_in, int64_t outer, int64_t C, in
                       void* stream);
 int dmxq_hist_qparams(const float* hist, const float* min_val, const float* max_val, int64_t n_groups, int64_t bins, int precision, int qmin,
                       int qmax, int symmetric_qscheme, float* scale, int64_t* zero_point, void* stream);
+
+/* Quantization-error statistics on the device (csrc/error_stats.hip).  Replaces utils/benchmark.py:349-389
+ * compute_mse_error / compute_maxdelta_error (per tensor pair one mse_loss, one abs().max() and two .item() synchronisations) and, for a
+ * comparison of K formats on one tensor, K casts followed by 2 K torch reductions over temporaries.
+ * A row of statistics is double[4] in device memory: [sum_sq_err, sum_sq_ref, max_abs_err, count] for a reference r and a test t of n
+ * elements, with d = float(r) - float(t) (one fp32 subtraction): sum_sq_err = sum d^2 and sum_sq_ref = sum float(r)^2, every square
+ * formed exactly in fp64 and summed in fp64; max_abs_err = torch's (r - t).float().abs().max(), i.e. the largest |d| rounded to the
+ * promoted dtype of the pair (the dtype itself when both agree, else float32); count = n.  mse = row[0] / row[3],
+ * sqnr_db = 10 log10(row[1] / row[0]).  A NaN difference makes sum_sq_err and max_abs_err NaN.  No floating-point atomics: the same
+ * input twice gives the same bits.  accumulate != 0 merges into the row already in `stats` (sums add, max takes the max, count adds),
+ * so statistics run over many batches without a host read.  scratch: dmxq_error_scratch_bytes(n, n_formats) bytes of device memory,
+ * 8-byte aligned, contents free.  No allocation, no host synchronisation: both calls can be captured into a graph.  n == 0 writes the
+ * identity row [0, 0, 0, 0], or with accumulate leaves the row unchanged (nothing launched).
+ * dmxq_error_stats: ref / test of any dtype pair; 16-byte aligned pointers take the vector loads, others an element-wise kernel.
+ * dmxq_cast_error: `in` is [rows, L] contiguous and is read ONCE; row k of stats (double[n_formats][4]) is the row of dmxq_error_stats
+ * between `in` and the library's cast of that [rows, L] tensor to formats[k] -- blocks along L, the result rounded to `dtype` as
+ * CastTo.forward returns it -- bit for bit in count and max_abs_err (the sums differ only by the order of an fp64 sum).  Nothing is
+ * written but the statistics.  formats: a HOST array of dmxq_gptq_format with per_row = 0:
+ *   DMXQ_GPTQ_BFP    nearest rounding, symmetric or "(_N)", 2 <= precision <= 22, block_size in {8, 16, 32, 64, 128} dividing L;
+ *   DMXQ_GPTQ_FLOAT  nearest rounding, man_bits <= 22;
+ *   DMXQ_GPTQ_FIXED  nearest rounding with the affine wrapper, scale[k] / zero_point[k] (DEVICE arrays indexed like formats; may be NULL
+ *                    without a FIXED format).
+ * Status: DMXQ_ERR_BAD_ARG for an invalid dtype or format kind, n_formats < 1, or a scratch smaller than the query says;
+ * DMXQ_ERR_UNSUPPORTED, nothing launched, for everything else these entry points do not take -- a null pointer or a negative size,
+ * more than 8 formats, a format or block size outside the list, L % 8 != 0 or a block size that does not divide L, a misaligned
+ * pointer (dmxq_cast_error: `in` not 16-byte aligned): the caller then runs the library's cast followed by dmxq_error_stats. */
+int64_t dmxq_error_scratch_bytes(int64_t n, int n_formats);
+int dmxq_error_stats(const void* ref, int dtype_ref, const void* test, int dtype_test, int64_t n, int accumulate, double* stats,
+                     void* scratch, int64_t scratch_bytes, void* stream);
+int dmxq_cast_error(const void* in, int dtype, int64_t rows, int64_t L, const dmxq_gptq_format* formats, int n_formats,
+                    const float* scale, const int64_t* zero_point, int accumulate, double* stats, void* scratch, int64_t scratch_bytes,
+                    void* stream);
 
 #ifdef __cplusplus
 }
