@@ -772,3 +772,29 @@ def cast_error(x, fmts, scale, zero_point, accumulate, stats, scratch):
     check(lib().dmxq_cast_error(ptr(xc), dtype_code(xc.dtype), rows, L, ctypes.cast(f, ctypes.c_void_p), K, ptr(scale), ptr(zero_point),
                                 int(bool(accumulate)), ptr(stats), ptr(scratch), scratch.numel() * scratch.element_size(), stream_of(xc)),
           "dmxq_cast_error")
+
+
+# ------------------------------------------------------------------------------------------------ Hadamard rotation
+@_guarded
+def hadamard_qdq(x, size, inverse, fmt, scale, zero_point, out_dtype=None):
+    xc = _prep(x, "hadamard_qdq")
+    if fmt and len(fmt) != 12:
+        raise RuntimeError("hadamard_qdq: fmt is empty (rotation only) or the 12 fields of dmxq_gptq_format")
+    if xc.dim() < 1:
+        raise RuntimeError("hadamard_qdq: expects a tensor with at least one dimension")
+    out = torch.empty(xc.shape, dtype=out_dtype or xc.dtype, device=xc.device)
+    L = xc.shape[-1]
+    rows = xc.numel() // L if L else 0
+    f = _lib.GptqFormat(*[int(v) for v in fmt]) if fmt else None
+    if scale is not None and not (scale.is_cuda and scale.device == xc.device and scale.dtype == torch.float32 and scale.is_contiguous()):
+        raise RuntimeError("hadamard_qdq: scale must be a contiguous float32 tensor on x's GPU")
+    if zero_point is not None and not (zero_point.is_cuda and zero_point.device == xc.device and zero_point.dtype == torch.int64
+                                       and zero_point.is_contiguous()):
+        raise RuntimeError("hadamard_qdq: zero_point must be a contiguous int64 tensor on x's GPU")
+    if f is not None and f.kind == _lib.GPTQ_FIXED:
+        need = rows if f.per_row else 1
+        if scale is None or zero_point is None or scale.numel() < need or zero_point.numel() < need:
+            raise RuntimeError("hadamard_qdq: a fixed point cast needs its scale and zero point (one per row when per_row)")
+    check(lib().dmxq_hadamard_qdq(ptr(xc), ptr(out), dtype_code(xc.dtype), dtype_code(out.dtype), rows, L, size, int(bool(inverse)),
+                                  ctypes.byref(f) if f is not None else None, ptr(scale), ptr(zero_point), stream_of(xc)), "dmxq_hadamard_qdq")
+    return out

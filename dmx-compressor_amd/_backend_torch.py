@@ -51,7 +51,9 @@ _FAST_NAMES = {"bfp_qdq_nograd": "bfp_qdq", "float_qdq_nograd": "float_qdq", "fi
                "relu_cast": "relu_cast", "scale_channels": "scale_channels", "rope_cast": "rope_cast", "unary_cast": "unary_cast",
                "lut16_apply": "lut16_apply", "softmax_cast": "softmax_cast", "norm_cast": "norm_cast"}
 # the calibration calls of the device HistogramObserver and the error statistics (no autograd to lose: they take the same route)
-_FAST_CALIBRATION_NAMES = {"hist_observe": "hist_observe", "hist_qparams": "hist_qparams", "error_stats": "error_stats", "cast_error": "cast_error"}
+_FAST_CALIBRATION_NAMES = {"hist_observe": "hist_observe", "hist_qparams": "hist_qparams", "error_stats": "error_stats", "cast_error": "cast_error",
+                           # the Hadamard rotation: its backward is an autograd Function of the front end (_front.py), above the raw op
+                           "hadamard_qdq": "hadamard_qdq"}
 FAST = None
 
 

@@ -21,7 +21,7 @@ __all__ = [
     "bfp_qdq", "block_quantize", "bfp_qdq_multi", "bfp_pack", "bfp_unpack", "weight_hypernet", "weight_hypernet_multi", "input_hypernet", "binary_cast", "rope_cast", "relu_cast", "unary_cast", "unary_cast_table", "lut16_apply", "softmax_cast", "layernorm_cast", "rmsnorm_cast", "sbfp_qdq", "mxfp_qdq", "float_qdq", "float_qdq_multi", "fixed_qdq", "fixed_qdq_multi", "fixed_float_qdq_multi", "nm_mask", "nm_sparsify", "topk_mask", "topk_sparsify", "bernoulli_mask", "group_minmax", "group_minmax_accumulate", "qparams", "channel_maxabs",
     "smoothquant_scale", "scale_channels", "gelu", "silu", "quick_gelu", "exp", "silu_experimental", "rope", "softmax", "layernorm",
     "rmsnorm", "histc", "gptq_fields", "gptq_block", "hist_observe", "hist_scratch_words", "hist_qparams", "error_stats", "cast_error",
-    "error_scratch_bytes",
+    "error_scratch_bytes", "cast_error_entry", "hadamard", "hadamard_qdq", "hadamard_check_size", "HADAMARD_SIZES",
 ]
 
 _ops = None   # the raw namespace: set by bind()
@@ -645,6 +645,9 @@ def _cast_error_entry(entry):
     return fmt, scale, zp
 
 
+cast_error_entry = _cast_error_entry   # (benchmark.format_sweep parses its entries the same way)
+
+
 def _affine_tensor(v, dtype, like, default):
     if isinstance(v, torch.Tensor):
         return v.detach().to(device=like.device, dtype=dtype).reshape(1)
@@ -713,3 +716,196 @@ def cast_error(x, formats, block_dim: int = -1, out=None, accumulate: bool = Fal
             y = _cast_like_library(xd, fmt, scale, zp, block_dim)
         error_stats(xd, y, out=out[i], accumulate=accumulate)
     return out
+
+
+# ---------------------------------------------------------------------------------------------------- Hadamard rotation
+HADAMARD_SIZES = (8, 16, 32, 64, 128, 256)   # block widths of dmxq_hadamard_qdq
+
+
+def hadamard_check_size(size, what: str = "hadamard") -> int:
+    """the rotation width, or ValueError: a power of two from 8 to 256"""
+    if isinstance(size, bool) or not isinstance(size, int) or size not in HADAMARD_SIZES:
+        raise ValueError(f"{what}: the rotation size must be one of {HADAMARD_SIZES}, got {size!r}")
+    return size
+
+
+def _rot_dim(x, size, dim, what):
+    if x.dim() < 1 or not -x.dim() <= dim < x.dim():
+        raise ValueError(f"{what}: dimension {dim} of a tensor of shape {tuple(x.shape)}")
+    d = dim % x.dim()
+    if x.shape[d] % size:
+        raise ValueError(f"{what}: dimension {dim} has {x.shape[d]} elements, not a multiple of the rotation size {size}")
+    return d
+
+
+def _to_last(x, d):
+    """the rotated dimension as the contiguous last one (d not last: a transposing copy -- the SLOW path)"""
+    return x if d == x.dim() - 1 else x.movedim(d, -1).contiguous()
+
+
+def _from_last(y, d):
+    return y if d == y.dim() - 1 else y.movedim(-1, d).contiguous()
+
+
+def _rotate(x, size, d, out_dtype):
+    return _from_last(_ops.hadamard_qdq(_to_last(x.detach(), d), size, False, [], None, None, out_dtype), d)
+
+
+class _Rotation(torch.autograd.Function):
+    """R is symmetric and orthonormal: the gradient of R(x) is R(grad)"""
+
+    @staticmethod
+    def forward(ctx, x, size, d, out_dtype):
+        ctx.set_materialize_grads(False)
+        ctx.rot = (size, d, x.dtype)
+        return _rotate(x, size, d, out_dtype)
+
+    @staticmethod
+    def backward(ctx, g):
+        size, d, dt = ctx.rot
+        return (None if g is None else _rotate(g, size, d, dt)), None, None, None
+
+
+class _RotatedCast(torch.autograd.Function):
+    """rotate -> cast (-> rotate back): the cast is a straight-through estimator, so the backward is the identity with the inverse
+    rotation and R(grad) without it"""
+
+    @staticmethod
+    def forward(ctx, x, run, size, d, inverse):
+        ctx.set_materialize_grads(False)
+        ctx.rot = (size, d, x.dtype, inverse)
+        return run(x.detach())
+
+    @staticmethod
+    def backward(ctx, g):
+        size, d, dt, inverse = ctx.rot
+        if g is not None:
+            g = (g if g.dtype == dt else g.to(dt)) if inverse else _rotate(g, size, d, dt)
+        return g, None, None, None, None
+
+
+def hadamard(x, size: int, dim: int = -1, out_dtype: Optional[torch.dtype] = None):
+    """The orthonormal block-Hadamard rotation of blocks of `size` consecutive elements along `dim`, one launch (dmxq_hadamard_qdq without
+    a format): log2(size) butterfly stages of fp32 adds / subtracts, strides 1, 2, .., size / 2, then one multiply by
+    float32(1 / sqrt(size)); rounded once to out_dtype (default x.dtype).  Its own inverse.  size in HADAMARD_SIZES, dividing the
+    dimension (ValueError otherwise).  A `dim` other than the last is transposed to the last with a contiguous copy, rotated and
+    transposed back: a slow path.  Differentiable: the gradient is hadamard(grad)."""
+    hadamard_check_size(size, "hadamard")
+    require_gpu(x, "hadamard")
+    d = _rot_dim(x, size, dim, "hadamard")
+    out_dtype = out_dtype or x.dtype
+    if x.requires_grad and torch.is_grad_enabled():
+        return _Rotation.apply(x, size, d, out_dtype)
+    return _rotate(x, size, d, out_dtype)
+
+
+# dmxq_gptq_format kinds that fused=None sends to the three-launch chain although the kernel takes them.  The rule: the fused call moves
+# 4 B per bf16 element and the chain 20 B, so a format is routed to the kernel only when its fused call has been MEASURED under 5 x its
+# plain cast on [4096, 4096] and [14336, 4096] (tools/bench_hadamard.py).  profiles/r11_hadamard.txt: BFP[8|8]{16}, MXFP4[E2M1]{32} and
+# per-tensor XP[8,0] at H = 32 / 64 / 128 all between 1.98 x and 2.70 x -- every kind goes to the kernel (FloatingPoint, not in that
+# table, is the cheapest cast body of the four in the same kernel).
+HADAMARD_CHAIN_BY_DEFAULT = frozenset()
+
+
+def _hadamard_fields(fmt, per_row):
+    """the dmxq_gptq_format fields of a format the fused rotation kernel casts to (gptq_fields plus MXFP, kind 3), or None"""
+    from .format import MXFP, FloatingPoint
+    if isinstance(fmt, MXFP):
+        ef = fmt.element_format   # (MXFP.cast reads the element format's mantissa and exponent widths only)
+        if ef.mantissa > 22:
+            return None
+        return [3, 0, int(fmt.block_size), 0, int(ef.mantissa), int(ef.exponent), 0, 0, 0, 0, 0, 0]
+    f = gptq_fields(fmt, per_row)
+    if f is not None and isinstance(fmt, FloatingPoint) and fmt.native_of() == torch.float32:
+        return None   # (Format.cast hands a float32 tensor through untouched)
+    return f
+
+
+def hadamard_qdq(x, size: int, fmt, block_dim: int = -1, inverse: bool = True, scale=None, zero_point=None, per_row: bool = False,
+                 out_dtype: Optional[torch.dtype] = None, fused: Optional[bool] = None, ch_axis: Optional[int] = None,
+                 group_size: Optional[int] = None):
+    """Rotate, quantize, and rotate back (inverse=True) or stay in the rotated basis (inverse=False):
+        y = round_to(out_dtype, R(Q(R(x))))   or   round_to(out_dtype, Q(R(x)))
+    with R = hadamard(., size) along block_dim in float32 and Q the library's own cast of the rotated float32 tensor to `fmt` (a Format
+    or shorthand), blocks along the same dimension, float32 out; ONE rounding to out_dtype (default x.dtype) at the end.
+    ONE launch (dmxq_hadamard_qdq) for BFP / MXINT (nearest, a power-of-two block dividing size), MXFP (a power-of-two block dividing size),
+    FloatingPoint (nearest) and FixedPoint (nearest; scale / zero_point: one for the tensor -- numbers or 1-element tensors, default
+    scale 1 and zero point 0 through the same affine form on the kernel and on the chain, as ops.cast_error treats a bare FixedPoint
+    entry -- or with per_row one per row of the [rows, L] view, the rotated dimension being the last).
+    fused=None: the kernel where it applies (every fused format measured 2.0-2.7 x its plain cast, under the 5 x at which the chain
+    would be the better default: profiles/r11_hadamard.txt; HADAMARD_CHAIN_BY_DEFAULT would list the exceptions), else the chain hadamard (float32) -> the library's cast (float32) -> hadamard: the same
+    bits by construction, three launches.  The chain takes everything Format.cast takes -- SBFP, up / down / stochastic rounding (the usual
+    seed rules), blocks that do not divide size, and per-channel / per-group affine scales (ch_axis, group_size as ops.fixed_qdq; on the
+    chain only).  fused=True raises NotImplementedError instead of falling back; fused=False forces the chain.
+    A block_dim other than the last is transposed to the last with a contiguous copy and back: a slow path.
+    Autograd: the cast is a straight-through estimator -- the backward is the identity with inverse, hadamard(grad) without."""
+    from .format import FixedPoint, Format, Same
+    hadamard_check_size(size, "hadamard_qdq")
+    require_gpu(x, "hadamard_qdq")
+    fmt = Format.from_shorthand(fmt)
+    if not isinstance(fmt, Format):
+        raise TypeError(f"hadamard_qdq: {fmt!r} is not a numerical format")
+    d = _rot_dim(x, size, block_dim, "hadamard_qdq")
+    out_dtype = out_dtype or x.dtype
+    fixed = isinstance(fmt, FixedPoint)
+    if (scale is not None or zero_point is not None or per_row or ch_axis is not None or group_size) and not fixed:
+        raise ValueError(f"hadamard_qdq: only a FixedPoint format takes an affine scale / zero point, got {fmt!r}")
+    if per_row and (ch_axis is not None or group_size):
+        raise ValueError("hadamard_qdq: per_row or ch_axis / group_size, not both")
+    if per_row and d != x.dim() - 1:
+        raise ValueError("hadamard_qdq: per_row scales go with a rotation along the last dimension")
+    if (per_row or ch_axis is not None) and (scale is None or zero_point is None):
+        raise ValueError("hadamard_qdq: per-row / per-channel / per-group casts need their scale and zero_point tensors")
+    on_chain_only = ch_axis is not None or bool(group_size) or isinstance(fmt, Same)
+
+    def affine(xl):
+        if per_row or ch_axis is not None:
+            return (scale.detach().to(device=xl.device, dtype=torch.float32).reshape(-1).contiguous(),
+                    zero_point.detach().to(device=xl.device, dtype=torch.int64).reshape(-1).contiguous())
+        return _affine_tensor(scale, torch.float32, xl, 1.0), _affine_tensor(zero_point, torch.int64, xl, 0)
+
+    def cast(r, dt):   # the library's cast of the rotated float32 tensor r (rotated dimension last)
+        if not fixed:
+            y = fmt.cast(r, -1, out_dtype=dt)
+            return y if y.dtype == dt else y.to(dt)   # (SAME and FLOAT32 hand a float32 tensor through)
+        sc, zp = affine(r)
+        if per_row:
+            y = fixed_qdq(r.reshape(-1, r.shape[-1]), fmt.precision, fmt.fraction, fmt.clamp, fmt.symmetric, fmt.rounding, scale=sc,
+                          zero_point=zp, ch_axis=0, out_dtype=dt)
+            return y.reshape(r.shape)
+        ax = None
+        if ch_axis is not None:   # the channel axis after the rotated dimension moved to the end
+            a = ch_axis % x.dim()
+            ax = a if d == x.dim() - 1 or a < d else (x.dim() - 1 if a == d else a - 1)
+        return fixed_qdq(r, fmt.precision, fmt.fraction, fmt.clamp, fmt.symmetric, fmt.rounding, scale=sc, zero_point=zp, ch_axis=ax,
+                         group_size=group_size, out_dtype=dt)
+
+    def run(xd):
+        xl = _to_last(xd, d)
+        if fused is not False:
+            fields = None if on_chain_only else _hadamard_fields(fmt, per_row)
+            if fields is None and fused:
+                raise NotImplementedError(f"hadamard_qdq: no fused kernel for {fmt!r}"
+                                          + (" with per-channel / per-group scales" if on_chain_only else ""))
+            if fields is not None and fused is None and fields[0] in HADAMARD_CHAIN_BY_DEFAULT:
+                fields = None
+            if fields is not None:
+                sc, zp = affine(xl) if fixed else (None, None)
+                if per_row and (sc.numel() != xl.numel() // max(xl.shape[-1], 1) or zp.numel() != sc.numel()):
+                    raise ValueError("hadamard_qdq: per_row needs one scale and one zero point per row")
+                try:
+                    return _from_last(_ops.hadamard_qdq(xl, size, bool(inverse), fields, sc, zp, out_dtype), d)
+                except NotImplementedError:   # (DMXQ_ERR_UNSUPPORTED, nothing launched: a block that does not divide size, ...)
+                    if fused:
+                        raise
+        r = _ops.hadamard_qdq(xl, size, False, [], None, None, torch.float32)
+        if inverse:
+            y = _ops.hadamard_qdq(cast(r, torch.float32), size, False, [], None, None, out_dtype)
+        else:
+            y = cast(r, out_dtype)
+        return _from_last(y, d)
+
+    if x.requires_grad and torch.is_grad_enabled():
+        return _RotatedCast.apply(x, run, size, d, bool(inverse))
+    with torch.no_grad():
+        return run(x.detach())

@@ -75,6 +75,7 @@ SIGNATURES = {
     "dmxq_error_scratch_bytes": [_i64, _i32],
     "dmxq_error_stats": [_vp, _i32, _vp, _i32, _i64, _i32, _vp, _vp, _i64, _vp],
     "dmxq_cast_error": [_vp, _i32, _i64, _i64, _vp, _i32, _vp, _vp, _i32, _vp, _vp, _i64, _vp],
+    "dmxq_hadamard_qdq": [_vp, _vp, _i32, _i32, _i64, _i64, _i64, _i32, _vp, _vp, _vp, _vp],
 }
 
 
@@ -104,7 +105,7 @@ class GptqFormat(ctypes.Structure):
                 ("exp_bias", _i32), ("flush_subnormal", _i32), ("unsigned_abs", _i32), ("fraction", _i32), ("clamp", _i32), ("per_row", _i32)]
 
 
-GPTQ_BFP, GPTQ_FLOAT, GPTQ_FIXED = 0, 1, 2
+GPTQ_BFP, GPTQ_FLOAT, GPTQ_FIXED, GPTQ_MXFP = 0, 1, 2, 3   # (MXFP: dmxq_hadamard_qdq only)
 
 
 class DmxqError(RuntimeError):

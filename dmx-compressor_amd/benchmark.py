@@ -199,15 +199,49 @@ def _labels(formats):
     return out
 
 
-def format_sweep(model_or_tensor, formats, block_dim: Optional[int] = None):
+def _sweep_rows(x, formats, block_dim, hadamard):
+    """the error_stats rows [len(hadamard) * K, 4] of x against its cast to each of K formats, per rotation entry (None: no rotation:
+    ops.cast_error; a size: the rotated cast ops.hadamard_qdq(x, size, format) -- rotate, cast, rotate back -- then ops.error_stats)"""
+    rows = []
+    for h in hadamard:
+        if h is None:
+            rows.append(ops.cast_error(x, formats, block_dim=block_dim))
+            continue
+        r = torch.empty((len(formats), 4), dtype=torch.float64, device=x.device)
+        for k, entry in enumerate(formats):
+            fmt, scale, zp = ops.cast_error_entry(entry)
+            with torch.no_grad():
+                y = ops.hadamard_qdq(x.detach(), h, fmt, block_dim=block_dim, scale=scale, zero_point=zp)
+            ops.error_stats(x, y, out=r[k])
+        rows.append(r)
+    return torch.cat(rows)
+
+
+def _sweep_labels(formats, hadamard):
+    """(rotation entries, result keys) of format_sweep: "<format>" for the entry None, "<format> @H<size>" for a rotation size, entry by
+    entry in the order given"""
+    entries = list(hadamard) if isinstance(hadamard, (list, tuple)) else [hadamard]
+    if not entries:
+        raise ValueError("format_sweep: hadamard is a size, or a non-empty list of sizes and None")
+    for h in entries:
+        if h is not None:
+            ops.hadamard_check_size(h, "format_sweep")
+    return entries, [l if h is None else f"{l} @H{h}" for h in entries for l in _labels(formats)]
+
+
+def format_sweep(model_or_tensor, formats, block_dim: Optional[int] = None, hadamard=None):
     """SQNR in dB of every candidate format, from one read of each tensor per 8 formats (ops.cast_error).
     A tensor -> {format: dB}; a model -> {module name: {format: dB}} over the weight of every weighted DmxModule, blocks along the module's
     `weight_cast.block_dim` (or block_dim when given).  formats as in ops.cast_error; the keys are the shorthands given (repr() of Format
-    objects).  All rows stay on the device until ONE host read at the end.  An exact cast shows as inf."""
+    objects).  All rows stay on the device until ONE host read at the end.  An exact cast shows as inf.
+    hadamard: a rotation size, or a list of sizes that may include None -- every format is measured once per entry, None as it stands
+    and a size wrapped in the orthonormal block-Hadamard rotation of that width along the blocked dimension (ops.hadamard_qdq: rotate,
+    cast, rotate back; a FixedPoint entry's scale applies to the ROTATED tensor).  Keys: "<format>" for None, "<format> @H<size>"
+    otherwise, in the order of `hadamard`."""
     formats = list(formats)
-    labels = _labels(formats)
+    entries, labels = _sweep_labels(formats, hadamard)
     if isinstance(model_or_tensor, torch.Tensor):
-        db = sqnr_db_of(ops.cast_error(model_or_tensor, formats, block_dim=-1 if block_dim is None else block_dim)).cpu().tolist()
+        db = sqnr_db_of(_sweep_rows(model_or_tensor, formats, -1 if block_dim is None else block_dim, entries)).cpu().tolist()
         return dict(zip(labels, db))
     names, rows = [], []
     for n, m in _dmx_modules(model_or_tensor).items():
@@ -215,7 +249,7 @@ def format_sweep(model_or_tensor, formats, block_dim: Optional[int] = None):
         if w is None or m.weight_cast is None or not w.is_floating_point():
             continue
         names.append(n)
-        rows.append(sqnr_db_of(ops.cast_error(w, formats, block_dim=m.weight_cast.block_dim if block_dim is None else block_dim)))
+        rows.append(sqnr_db_of(_sweep_rows(w, formats, m.weight_cast.block_dim if block_dim is None else block_dim, entries)))
     if not names:
         return {}
     host: Dict[torch.device, list] = {}

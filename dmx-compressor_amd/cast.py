@@ -1,8 +1,8 @@
 """CastTo / CastToDict / CastToFormat — mirror of the reference's `numerical/cast.py` op containers.
 
 `CastTo.forward` keeps the reference's order of operations (cast.py:261-306: remember physical dtype ->
-pre_transform {shaping, noquant_shortcut, format} -> observer step -> [affine] -> format cast -> [inverse
-affine] -> shortcut restore -> inverse shaping -> `.to(physical_dtype)`), but the arithmetic part
+pre_transform {shaping, noquant_shortcut, format} -> [hadamard rotation: not in the reference, DESIGN.md §8] -> observer step ->
+[affine] -> format cast -> [inverse affine] -> [inverse rotation] -> shortcut restore -> inverse shaping -> `.to(physical_dtype)`), but the arithmetic part
 (`.float()`, `x/sc + zp`, the format cast, `(x - zp)*sc`, the final narrowing) is ONE kernel launch with the
 input and output in the tensor's own dtype, instead of 5-7 elementwise ATen passes around a chunked native call.
 """
@@ -51,6 +51,37 @@ class _FixedAffineCast(Function):
         if g is not None and g.dtype != ctx.in_dtype:
             g = g.to(ctx.in_dtype)
         return g, None, None, None, None, None, None
+
+
+class _RotatedSTE(Function):
+    """rotation -> observer step -> cast -> inverse rotation of a CastTo with a "hadamard" pre_transform, as ONE straight-through
+    estimator: R is its own inverse, so the backward is the identity (not R(R(g)), which is g only up to rounding)."""
+
+    @staticmethod
+    def forward(ctx, x, cast, had):
+        ctx.set_materialize_grads(False)
+        ctx.in_dtype = x.dtype
+        return cast._rotate_observe_cast(x.detach(), had)
+
+    @staticmethod
+    def backward(ctx, g):
+        if g is not None and g.dtype != ctx.in_dtype:
+            g = g.to(ctx.in_dtype)
+        return g, None, None
+
+
+def _parse_hadamard(spec):
+    """pre_transform["hadamard"]: 64 or {"size": 64, "inverse": False} -> {"size", "inverse"} (inverse defaults to True)"""
+    if isinstance(spec, dict):
+        extra = set(spec) - {"size", "inverse"}
+        if extra or "size" not in spec:
+            raise ValueError(f"pre_transform['hadamard']: expected {{'size': int, 'inverse': bool}}, got {spec!r}")
+        size, inverse = spec["size"], spec.get("inverse", True)
+    else:
+        size, inverse = spec, True
+    if not isinstance(inverse, bool):
+        raise ValueError(f"pre_transform['hadamard']: inverse must be a bool, got {inverse!r}")
+    return {"size": ops.hadamard_check_size(size, "pre_transform['hadamard']"), "inverse": inverse}
 
 
 class CastTo(HostFlags, torch.nn.Module):
@@ -122,6 +153,10 @@ class CastTo(HostFlags, torch.nn.Module):
         self.pre_transform = dict(pre_transform)
         if isinstance(self.pre_transform.get("format"), str):
             self.pre_transform["format"] = Format.from_shorthand(self.pre_transform["format"])
+        if "hadamard" in self.pre_transform:
+            # an orthonormal block-Hadamard rotation along block_dim around the cast (ops.hadamard_qdq): 64, or
+            # {"size": 64, "inverse": False} to leave the result in the rotated basis; a bad size raises ValueError here
+            self.pre_transform["hadamard"] = _parse_hadamard(self.pre_transform["hadamard"])
 
     def enable_calibration(self, state: bool = True, observer_cls: ObserverBase = HistogramObserver,
                            qscheme_to_overload: Optional[torch.qscheme] = None, group_size: int = None,
@@ -228,6 +263,39 @@ class CastTo(HostFlags, torch.nn.Module):
                 return y.permute(inv)
         return fmt.cast(x, self.block_dim, out_dtype=out_dtype)
 
+    # ------------------------------------------------------------------ hadamard pre_transform
+    def _hadamard_qdq(self, x, had, out_dtype):
+        """rotate -> this cast with its current scale / zero point -> [rotate back] as ONE ops.hadamard_qdq call (one launch where the
+        fused kernel covers the format)"""
+        fmt, kw = self.format, {}
+        if isinstance(fmt, FixedPoint):
+            kw = {"scale": self.scale, "zero_point": self.zero_point}
+            if self.group_size:
+                kw.update(ch_axis=self.ch_axis, group_size=self.group_size)
+            elif self.is_per_channel:
+                if x.dim() == 2 and self.ch_axis % 2 == 0 and self.block_dim % 2 == 1:
+                    kw["per_row"] = True   # (per output channel of a [rows, L] weight rotated along its rows: the fused kernel's case)
+                else:
+                    kw["ch_axis"] = self.ch_axis
+        return ops.hadamard_qdq(x, had["size"], fmt, self.block_dim, had["inverse"], out_dtype=out_dtype, **kw)
+
+    def _rotate_observe_cast(self, x, had):
+        """forward's steps rotation -> observer step (on the rotated float32 tensor: scales are calibrated in the rotated basis) -> cast
+        -> inverse rotation.  With fake-quant off nothing is cast: the input comes back as it is (inverse) or rotated (no inverse)."""
+        d = self.__dict__
+        fmt = self.format
+        r = ops.hadamard(x, had["size"], self.block_dim, out_dtype=torch.float32)
+        if d["_h_observer_enabled"] and not isinstance(fmt, Same):
+            self._observer_step(r)
+        if not d["_h_fake_quant_enabled"]:
+            return x if had["inverse"] else r
+        if not isinstance(fmt, Format):
+            raise TypeError("CastTo with a torch.dtype format is torch.ao's stock FakeQuantize path, "
+                            "not part of the accelerated hot path")
+        if not had["inverse"]:
+            return self._quantize(r, self.physical_dtype)
+        return ops.hadamard(self._quantize(r, torch.float32), had["size"], self.block_dim, out_dtype=self.physical_dtype)
+
     def forward(self, x):
         d = self.__dict__  # (plain attributes: nn.Module.__setattr__ costs several microseconds per assignment)
         d["physical_dtype"] = x.dtype
@@ -244,6 +312,10 @@ class CastTo(HostFlags, torch.nn.Module):
                 raise TypeError("CastTo with a torch.dtype format is torch.ao's stock FakeQuantize path, "
                                 "not part of the accelerated hot path")
             return self._quantize(x, x.dtype)
+        had = pt.get("hadamard")
+        if had is not None and len(pt) == 1 and d["_h_fake_quant_enabled"] and not d["_h_observer_enabled"] and isinstance(fmt, Format) \
+                and not isinstance(fmt, Same):
+            return self._hadamard_qdq(x, had, x.dtype)   # rotation, cast and inverse rotation: one call
         inverse_shaping = None
         shortcut = None
         if "shaping" in pt:
@@ -255,9 +327,14 @@ class CastTo(HostFlags, torch.nn.Module):
             shortcut = x[sc_idx].clone()
         if "format" in pt:
             x = CastToFormat.apply(x, pt["format"], self.block_dim, torch.float32)
-        if d["_h_observer_enabled"] and x is not None and not isinstance(fmt, Same):
+        if had is not None:
+            if had["inverse"] and torch.is_grad_enabled() and x.requires_grad:
+                x = _RotatedSTE.apply(x, self, had)
+            else:
+                x = self._rotate_observe_cast(x, had)   # (no inverse: the gradient is ops.hadamard(grad) through the pieces' own backward)
+        elif d["_h_observer_enabled"] and x is not None and not isinstance(fmt, Same):
             self._observer_step(x)
-        if d["_h_fake_quant_enabled"]:
+        if d["_h_fake_quant_enabled"] and had is None:
             if isinstance(fmt, Format):
                 x = self._quantize(x, self.physical_dtype)
             else:
@@ -276,10 +353,20 @@ class CastTo(HostFlags, torch.nn.Module):
         makes of it: its format along its block_dim with its current scale / zero point.  Neither the observer nor the switches are
         touched, and nothing is read back to the host.  BFP, FloatingPoint and per-tensor FixedPoint casts are measured without
         materialising the cast (ops.cast_error); per-channel / per-group FixedPoint, and the formats cast_error does not fuse, as this
-        cast's own launch followed by ops.error_stats.  A cast with a pre_transform is not measured."""
-        if self.pre_transform:
-            raise NotImplementedError("CastTo.measure_error: a cast with a pre_transform (shaping / shortcut / pre-format)")
+        cast's own launch followed by ops.error_stats.  A cast whose pre_transform is only "hadamard" is measured as the rotated cast
+        (ops.hadamard_qdq) followed by ops.error_stats against x; one with any other pre_transform key is not measured."""
+        if self.pre_transform and set(self.pre_transform) != {"hadamard"}:
+            raise NotImplementedError("CastTo.measure_error: a cast with a pre_transform other than hadamard (shaping / shortcut / pre-format)")
         fmt, x = self.format, x.detach()
+        if self.pre_transform:
+            had = self.pre_transform["hadamard"]
+            with torch.no_grad():
+                if isinstance(fmt, Format) and not isinstance(fmt, Same):
+                    y = self._hadamard_qdq(x, had, x.dtype)
+                else:
+                    y = ops.hadamard(x, had["size"], self.block_dim)
+                    y = ops.hadamard(y, had["size"], self.block_dim) if had["inverse"] else y
+            return ops.error_stats(x, y)
         if not isinstance(fmt, Format) or isinstance(fmt, Same):
             return ops.error_stats(x, x)
         if isinstance(fmt, FixedPoint):

@@ -1,0 +1,302 @@
+// csrc/hadamard.hip — orthonormal block-Hadamard rotation fused into a quantize-dequantize cast (include/dmxq.h dmxq_hadamard_qdq;
+// DESIGN.md §8).  Not in the reference: the rotate -> quantize -> rotate back recipe of QuaRot / SpinQuant and of the MXFP4 training
+// recipes, as ONE read and ONE write per element instead of a dense [H, H] matmul and two more passes around the cast.
+//
+// Arithmetic (the contract; tests/_hadamard_ref.py restates it in torch on the CPU), for a block of H = 2^k consecutive elements
+// along the rows, widened to fp32 (exact):
+//   for s = 1, 2, 4, .., H/2, in that order: for every i with bit s clear   v[i], v[i+s] = v[i] + v[i+s], v[i] - v[i+s]
+//   (old values on the right; every add and subtract ONE fp32 operation, lower index minus upper index), then ONE fp32 multiply by
+//   c = (float)(1 / sqrt((double)H)).  R_H is symmetric and orthonormal: the inverse rotation is R_H itself, scale included.
+//   y = round_to(dtype_out, R_H(Q(R_H(x))))   with `inverse`,   round_to(dtype_out, Q(R_H(x)))   without,   round_to(dtype_out, R_H(x))
+//   without a format; Q = the library's cast of the rotated fp32 tensor, fp32 in and out; one rounding to dtype_out at the very end.
+//   NaN / Inf simply propagate through the adds.  No FMA anywhere (-ffp-contract=off).
+//
+// Geometry: the tensor is flat -- L % H == 0, so the blocks of the flat index ARE the row blocks.  A lane holds one 16-byte vector of
+// the input (V = 8 sixteen-bit or 4 fp32 elements), a block is H / V neighbouring lanes of ONE wave (<= 64: a 256-wide fp32 block is a
+// whole wave; a wave's 64 vectors are a whole number of blocks for every H).  The stages with s < V run in registers, the others
+// across lanes with __shfl_xor: the lane whose bit is clear computes own + partner, the lane whose bit is set partner - own.  The
+// number of cross-lane stages is a run-time loop (one kernel per dtype pair, whatever H and the format are).  One vector per lane, one
+// tile per workgroup: the grid does not loop.  Lanes past the end re-read the last vector, meet only each other in the shuffles (the
+// tensor ends on a block boundary) and store nothing.  Every block is fully read before any of it is written (the stores depend on
+// the shuffles, which depend on every load of the block): in == out is fine when both dtypes have one width.
+// A pointer that is not 16-byte aligned takes the same kernel with element-wise loads and stores (a wave-uniform flag).
+//
+// Casts: the literal per-element forms of bfp_math.hpp / floatq.hpp / fixedq.hpp, as in gptq.hip and error_stats.hip (nearest
+// rounding), and the GENERAL path of blockfmt.hip's MXFP block (setup + apply: restated here literally, its fast paths are
+// bit-identical to it by construction), with float32 input rules (the rotated tensor is float32: the floor(log2 max) rule near powers
+// of two applies).  Block maxima are taken on the bit patterns of |x| over the cast's own block: inside the lane's vector when the
+// block is smaller than a vector (one pass of the cast body per sub-block, selected element by element: a rare shape, kept simple), with
+// DPP / shuffles across block_size / V lanes otherwise.
+#include <math.h>
+
+#include "bfp_math.hpp"
+#include "fixedq.hpp"
+#include "floatq.hpp"
+
+namespace dmxq {
+namespace {
+
+constexpr int kHadThreads = 256;
+constexpr int kHadRotateOnly = -1;   // HadCast::kind without a format
+
+struct HadCast {
+  int kind;      // dmxq_gptq_kind, or kHadRotateOnly
+  int inverse;   // rotate back after the cast
+  int blog;      // BFP / MXFP: log2(block_size)
+  int wl, asym;  // BFP: precision, "(_N)"
+  int per_row;   // FIXED: scale / zero point indexed by row
+  int man, exp_bits, bias, big_log2;   // MXFP (blockfmt.hip MxfpFmt)
+  float big;
+  FloatFmt f;    // FLOAT
+  FixedFmt x;    // FIXED
+};
+
+__device__ __forceinline__ uint32_t umax(uint32_t a, uint32_t b) { return a > b ? a : b; }
+
+// R_H of the block this lane's vector belongs to: `lanes` = H / V lanes per block (a power of two, wave-uniform)
+template <int V>
+__device__ __forceinline__ void had_rotate(float (&v)[V], int lanes, int lane, float c) {
+#pragma unroll
+  for (int s = 1; s < V; s <<= 1) {
+#pragma unroll
+    for (int i = 0; i < V; i++) {
+      if (!(i & s)) {
+        const float a = v[i], b = v[i + s];
+        v[i] = a + b;
+        v[i + s] = a - b;
+      }
+    }
+  }
+  for (int m = 1; m < lanes; m <<= 1) {   // (every lane of the wave takes part: `lanes` is uniform)
+    const bool upper = (lane & m) != 0;
+#pragma unroll
+    for (int i = 0; i < V; i++) {
+      const float p = __shfl_xor(v[i], m);
+      v[i] = upper ? p - v[i] : v[i] + p;
+    }
+  }
+#pragma unroll
+  for (int i = 0; i < V; i++) v[i] = v[i] * c;
+}
+
+// blockfmt.hip, restated literally: rne_bits, float_q_nearest, MxfpBlock::setup / apply (the general path), exact_exponent = 0
+__device__ __forceinline__ uint32_t had_rne_bits(uint32_t t, int man_bits) {  // quant_cpu.cpp:211-237, nearest
+  const int sh = 23 - man_bits;
+  const uint32_t mask = (1u << sh) - 1u;
+  return (t + (mask >> 1) + ((t >> sh) & 1u)) & ~mask;
+}
+__device__ __forceinline__ float had_float_q_nearest(float a, int man, int exp_bits, int bias, int flush) {  // quant_cpu.cpp:359-402
+  const uint32_t target = f2u(a);
+  const int target_exp = (int)((target & 0x7FFFFFFFu) >> 23) - 127;
+  const int min_exp = -(bias - 1);
+  if (target_exp < min_exp) {
+    if (flush) return 0.0f;
+    const float shift = u2f(((uint32_t)(127 + min_exp) << 23) | (target & 0x80000000u));
+    return u2f(had_rne_bits(f2u(a + shift), man)) - shift;
+  }
+  uint32_t qb = had_rne_bits(target, man);
+  const int max_e = (1 << (exp_bits - 1)) + 127;
+  if (qb != 0u && (int)((qb & 0x7FFFFFFFu) >> 23) > max_e)
+    qb = (target & 0x80000000u) | ((uint32_t)max_e << 23) | ((0x007FFFFFu >> (23 - man)) << (23 - man));
+  return u2f(qb);
+}
+struct HadMxfpBlock {
+  float scale;
+  bool zero;
+  __device__ __forceinline__ void setup(uint32_t maxbits, const HadCast& f) {
+    const float m = u2f(maxbits);
+    zero = m == 0.0f;
+    // the reference evaluates 2^floor(log2 m) / 2^(2^(e-1)) in fp32 (format.py:551-555).  No libm: a float32 log2 within an ulp
+    // of the truth crosses an integer only for m = 2^v (1 - j 2^-24) with j <= jmax(v) (the rule and its proof sketch are in
+    // oracle/oracle.c oracle_floor_log2f; checked against torch.log2 for every exponent, fixtures tests/golden/boundaries.npz)
+    int eb = (int)(maxbits >> 23);
+    if (eb >= 1 && eb <= 254) {
+      const uint32_t man = maxbits & 0x007FFFFFu;
+      const int v = eb - 126;  // floor(log2 m) + 1
+      if (man != 0u && v != 0) {
+        const uint32_t a = (uint32_t)(v < 0 ? -v : v), j = 0x00800000u - man;
+        const int c = 31 - __builtin_clz(a);
+        const int g = (v > 0 && (a & (a - 1u)) == 0u) ? 25 - c : 24 - c;  // 17 .. 25
+        // jmax = floor(2^24 (1 - 2^(-2^-g))): 88 44 22 11 | 5 2 1 | 0 0, as bytes of two constants
+        const uint32_t jmax = g <= 20 ? ((0x0B162C58u >> (8 * (g - 17))) & 0xFFu) : (g <= 23 ? ((0x00010205u >> (8 * (g - 21))) & 0xFFu) : 0u);
+        if (j <= jmax) eb += 1;
+      }
+      const int se = eb - f.big_log2;
+      if (eb == 255) scale = INFINITY;                      // 2^128: the reference's fp32 power overflows too
+      else if (se >= 1) scale = u2f((uint32_t)se << 23);
+      else scale = ldexpf(1.0f, se - 127);                  // a denormal (or zero) scale, exact
+    } else {
+      scale = exp2f(floorf(log2f(m))) / f.big;              // zero (see `zero`), denormal, Inf, NaN maxima
+    }
+  }
+  __device__ __forceinline__ float apply(float x, const HadCast& f) const {
+    if (zero) return x * 0.0f;
+    return had_float_q_nearest(x / scale, f.man, f.exp_bits, f.bias, 0) * scale;
+  }
+};
+
+// q = Q(x) for this lane's V elements of the rotated tensor.  Called by whole waves (the block maxima cross lanes).
+template <int V>
+__device__ __forceinline__ void had_cast(const float (&x)[V], float (&q)[V], const HadCast& c, float sc, float z) {
+  if (c.kind == DMXQ_GPTQ_FLOAT) {
+#pragma unroll
+    for (int j = 0; j < V; j++) q[j] = float_q1<DMXQ_ROUND_NEAREST>(x[j], c.f, 0u);
+  } else if (c.kind == DMXQ_GPTQ_FIXED) {
+#pragma unroll
+    for (int j = 0; j < V; j++) q[j] = (fixed_q1(x[j] / sc + z, c.x, 0.5f) - z) * sc;
+  } else {
+    // a block of >= V elements: ONE pass, the maximum over block_size / V lanes; a block smaller than the vector: one pass per sub-block,
+    // each keeping its own elements
+    const int B = 1 << c.blog;
+    const int passes = B >= V ? 1 : V >> c.blog;
+#pragma unroll
+    for (int j = 0; j < V; j++) q[j] = 0.0f;
+#pragma unroll 1
+    for (int g = 0; g < passes; g++) {
+      uint32_t bm = 0u;
+#pragma unroll
+      for (int j = 0; j < V; j++)
+        if (passes == 1 || (j >> c.blog) == g) bm = umax(bm, f2u(x[j]) & 0x7FFFFFFFu);
+      if (B > V) bm = group_max_u32(bm, B / V);   // (wave-uniform: blocks are aligned groups of B / V lanes)
+      if (c.kind == DMXQ_GPTQ_BFP) {
+        const BfpBlockParams p = bfp_block_params<true, false>(bm, c.wl);
+#pragma unroll
+        for (int j = 0; j < V; j++) {
+          float v = bfp_q1<DMXQ_ROUND_NEAREST, false>(x[j], p, c.wl, DMXQ_ROUND_NEAREST, 0u);
+          if (c.asym) v = (x[j] <= p.thr) ? p.neg_lim : v;   // bfp_q1<.., ASYM = true>, the flag at run time (wave-uniform)
+          q[j] = (passes == 1 || (j >> c.blog) == g) ? v : q[j];
+        }
+      } else {
+        HadMxfpBlock b;
+        b.setup(bm, c);
+#pragma unroll
+        for (int j = 0; j < V; j++) {
+          const float v = b.apply(x[j], c);
+          q[j] = (passes == 1 || (j >> c.blog) == g) ? v : q[j];
+        }
+      }
+    }
+  }
+}
+
+// nvec vectors of V elements; thread t of the grid takes vector t.  vec: both pointers 16-byte aligned.
+template <int DTI, int DTO>
+__global__ __launch_bounds__(kHadThreads) void hadamard_qdq_kernel(const void* in, void* out, int64_t nvec, int64_t L, int lanes, int vec,
+                                                                  float c, const float* __restrict__ scale,
+                                                                  const int64_t* __restrict__ zp, const HadCast cst) {
+  constexpr int V = 16 / Elem<DTI>::bytes;
+  const int lane = threadIdx.x & (kWave - 1);
+  const int64_t t = (int64_t)blockIdx.x * kHadThreads + threadIdx.x;
+  const bool act = t < nvec;
+  const int64_t e0 = (act ? t : nvec - 1) * V;   // (a lane past the end re-reads the last vector and stores nothing)
+  float x[V];
+  if (vec) {
+    load_vec<DTI, V>(in, e0, x);
+  } else {
+#pragma unroll
+    for (int j = 0; j < V; j++) x[j] = load1<DTI>(in, e0 + j);
+  }
+  had_rotate<V>(x, lanes, lane, c);
+  if (cst.kind != kHadRotateOnly) {
+    float sc = 1.0f, z = 0.0f;
+    if (cst.kind == DMXQ_GPTQ_FIXED) {
+      const int64_t g = cst.per_row ? e0 / L : 0;
+      sc = scale[g];
+      z = (float)zp[g];
+    }
+    float q[V];
+    had_cast<V>(x, q, cst, sc, z);
+#pragma unroll
+    for (int j = 0; j < V; j++) x[j] = q[j];
+    if (cst.inverse) had_rotate<V>(x, lanes, lane, c);
+  }
+  if (act) {
+    if (vec) {
+      store_vec<DTO, V>(out, e0, x);
+    } else {
+#pragma unroll
+      for (int j = 0; j < V; j++) store1<DTO>(out, e0 + j, x[j]);
+    }
+  }
+}
+
+inline bool pow2(int64_t v) { return v >= 1 && (v & (v - 1)) == 0; }
+inline int log2i(int64_t v) { int l = 0; while (((int64_t)1 << l) < v) l++; return l; }
+
+}  // namespace
+}  // namespace dmxq
+
+using namespace dmxq;
+
+extern "C" int dmxq_hadamard_qdq(const void* in, void* out, int dtype_in, int dtype_out, int64_t rows, int64_t L, int64_t size,
+                                 int inverse, const dmxq_gptq_format* fmt, const float* scale, const int64_t* zero_point, void* stream) {
+  if (!valid_dtype(dtype_in) || !valid_dtype(dtype_out) || rows < 0 || L < 0 || size < 0) return DMXQ_ERR_BAD_ARG;
+  if (fmt && fmt->kind != DMXQ_GPTQ_BFP && fmt->kind != DMXQ_GPTQ_FLOAT && fmt->kind != DMXQ_GPTQ_FIXED && fmt->kind != DMXQ_GPTQ_MXFP)
+    return DMXQ_ERR_BAD_ARG;
+  if (!fmt && inverse) return DMXQ_ERR_BAD_ARG;
+  if (!(size == 8 || size == 16 || size == 32 || size == 64 || size == 128 || size == 256) || L % size != 0) return DMXQ_ERR_UNSUPPORTED;
+  HadCast c{};
+  c.kind = kHadRotateOnly;
+  c.inverse = inverse ? 1 : 0;
+  if (fmt) {
+    c.kind = fmt->kind;
+    if (fmt->kind == DMXQ_GPTQ_BFP) {
+      const int B = fmt->block_size;
+      if (B < 2 || !pow2(B) || size % B != 0 || fmt->precision < 2 || fmt->precision > 22) return DMXQ_ERR_UNSUPPORTED;
+      c.blog = log2i(B);
+      c.wl = fmt->precision;
+      c.asym = fmt->symmetric == 0;
+    } else if (fmt->kind == DMXQ_GPTQ_MXFP) {
+      const int B = fmt->block_size;
+      if (B < 1 || !pow2(B) || size % B != 0 || fmt->exp_bits < 1 || fmt->exp_bits > 8 || fmt->man_bits < 0 || fmt->man_bits > 22)
+        return DMXQ_ERR_UNSUPPORTED;
+      c.blog = log2i(B);
+      c.man = fmt->man_bits;
+      c.exp_bits = fmt->exp_bits;
+      c.bias = (1 << (fmt->exp_bits - 1)) - 1;          // dmxq_mxfp_qdq's MxfpFmt, field by field
+      c.big_log2 = 1 << (fmt->exp_bits - 1);
+      c.big = (float)ldexp(1.0, 1 << (fmt->exp_bits - 1));
+    } else if (fmt->kind == DMXQ_GPTQ_FLOAT) {
+      if (fmt->exp_bits < 1 || fmt->exp_bits > 8 || fmt->man_bits < 0 || fmt->man_bits > 22) return DMXQ_ERR_UNSUPPORTED;
+      c.f = FloatFmt{fmt->man_bits, fmt->exp_bits, fmt->exp_bias, fmt->flush_subnormal ? 1 : 0, fmt->unsigned_abs ? 1 : 0,
+                     DMXQ_ROUND_NEAREST, 0ull};
+    } else {
+      if (fmt->precision < 1 || fmt->precision > 24) return DMXQ_ERR_UNSUPPORTED;
+      // sim_helper.cpp:5-12 fixed_min_max, evaluated on the host in the same float/double mix as dmxq_fixed_qdq
+      const int precision = fmt->precision, fraction = fmt->fraction, sigma = -fraction;
+      float t_min = (float)(-ldexp(1.0, precision - fraction - 1));
+      const float t_max = (float)(-(double)t_min - ldexp(1.0, sigma));
+      if (fmt->symmetric) t_min = (float)((double)t_min + ldexp(1.0, sigma));
+      c.x = FixedFmt{sigma, fmt->clamp ? 1 : 0, DMXQ_ROUND_NEAREST, t_min, t_max, 0ull};
+      c.per_row = fmt->per_row ? 1 : 0;
+    }
+  }
+  if (rows == 0 || L == 0) return DMXQ_OK;
+  if (!in || !out) return DMXQ_ERR_BAD_ARG;
+  if (fmt && fmt->kind == DMXQ_GPTQ_FIXED && (!scale || !zero_point)) return DMXQ_ERR_BAD_ARG;
+  const int bi = dtype_in == DMXQ_F32 ? 4 : 2, bo = dtype_out == DMXQ_F32 ? 4 : 2;
+  if (in == (const void*)out && bi != bo) return DMXQ_ERR_BAD_ARG;   // in place: equal widths only
+  if (rows > INT64_MAX / L) return DMXQ_ERR_BAD_ARG;
+  const int V = 16 / bi;
+  const int64_t nvec = rows * L / V;   // (size >= 8 >= V divides L)
+  const int64_t grid = (nvec + kHadThreads - 1) / kHadThreads;
+  if (grid > 0x7FFFFFFF) return DMXQ_ERR_BAD_ARG;
+  const int lanes = (int)(size / V);   // 1 .. 64
+  const int vec = aligned16(in) && aligned16(out) ? 1 : 0;
+  const float cs = (float)(1.0 / sqrt((double)size));
+  hipStream_t s = (hipStream_t)stream;
+#define DMXQ_HAD(I_, O_) \
+  if (dtype_in == I_ && dtype_out == O_) \
+    DMXQ_LAUNCH((hadamard_qdq_kernel<I_, O_>), dim3((unsigned)grid), dim3(kHadThreads), 0, s, in, out, nvec, L, lanes, vec, cs, scale, zero_point, c);
+  DMXQ_HAD(DMXQ_BF16, DMXQ_BF16)
+  DMXQ_HAD(DMXQ_F16, DMXQ_F16)
+  DMXQ_HAD(DMXQ_F32, DMXQ_F32)
+  DMXQ_HAD(DMXQ_BF16, DMXQ_F32)
+  DMXQ_HAD(DMXQ_F16, DMXQ_F32)
+  DMXQ_HAD(DMXQ_F32, DMXQ_BF16)
+  DMXQ_HAD(DMXQ_F32, DMXQ_F16)
+  DMXQ_HAD(DMXQ_BF16, DMXQ_F16)
+  DMXQ_HAD(DMXQ_F16, DMXQ_BF16)
+#undef DMXQ_HAD
+  return launch_status();
+}

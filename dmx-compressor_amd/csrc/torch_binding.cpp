@@ -951,6 +951,38 @@ void cast_error(const Tensor& x, at::IntArrayRef fmts, const OptTensor& scale, c
 }
 void cast_error_meta(const Tensor&, at::IntArrayRef, const OptTensor&, const OptTensor&, bool, Tensor, Tensor) {}
 
+// ------------------------------------------------------------------------------------------------ Hadamard rotation
+// x: [rows, L] (any leading dims; blocks of `size` along the last dim); fmt: empty = rotation only, else the 12 fields of dmxq_gptq_format;
+// scale / zero_point: one entry, or one per row when the format says per_row (read for a fixed point format)
+Tensor hadamard_qdq(const Tensor& x, int64_t size, bool inverse, at::IntArrayRef fmt, const OptTensor& scale, const OptTensor& zero_point,
+                    OptDtype out_dtype) {
+  const Tensor xc = prep(x, "hadamard_qdq");
+  TORCH_CHECK(fmt.empty() || fmt.size() == 12, "hadamard_qdq: fmt is empty (rotation only) or the 12 fields of dmxq_gptq_format");
+  TORCH_CHECK(xc.dim() >= 1, "hadamard_qdq: expects a tensor with at least one dimension");
+  Tensor out = empty_like_shape(xc, out_dtype);
+  const int64_t L = xc.size(-1), rows = L ? xc.numel() / L : 0;
+  dmxq_gptq_format f{};
+  if (!fmt.empty())
+    f = dmxq_gptq_format{(int)fmt[0], (int)fmt[1], (int)fmt[2], (int)fmt[3], (int)fmt[4], (int)fmt[5], (int)fmt[6], (int)fmt[7], (int)fmt[8],
+                         (int)fmt[9], (int)fmt[10], (int)fmt[11]};
+  const bool has_sc = scale.has_value() && scale->defined(), has_zp = zero_point.has_value() && zero_point->defined();
+  const int64_t need = (!fmt.empty() && f.kind == DMXQ_GPTQ_FIXED) ? (f.per_row ? rows : 1) : 0;
+  TORCH_CHECK(!has_sc || (scale->is_cuda() && scale->device() == xc.device() && scale->scalar_type() == at::kFloat && scale->is_contiguous()),
+              "hadamard_qdq: scale must be a contiguous float32 tensor on x's GPU");
+  TORCH_CHECK(!has_zp || (zero_point->is_cuda() && zero_point->device() == xc.device() && zero_point->scalar_type() == at::kLong &&
+              zero_point->is_contiguous()), "hadamard_qdq: zero_point must be a contiguous int64 tensor on x's GPU");
+  TORCH_CHECK(need == 0 || (has_sc && has_zp && scale->numel() >= need && zero_point->numel() >= need),
+              "hadamard_qdq: a fixed point cast needs its scale and zero point (one per row when per_row)");
+  Launch l(xc);
+  check(dmxq_hadamard_qdq(xc.data_ptr(), out.data_ptr(), dt_code(xc.scalar_type()), dt_code(out.scalar_type()), rows, L, size, inverse ? 1 : 0,
+                          fmt.empty() ? nullptr : &f, has_sc ? (const float*)scale->data_ptr() : nullptr,
+                          has_zp ? (const int64_t*)zero_point->data_ptr() : nullptr, l.stream), "dmxq_hadamard_qdq");
+  return out;
+}
+Tensor hadamard_qdq_meta(const Tensor& x, int64_t, bool, at::IntArrayRef, const OptTensor&, const OptTensor&, OptDtype out_dtype) {
+  return empty_like_shape(x, out_dtype);
+}
+
 }  // namespace
 
 TORCH_LIBRARY(dmxq, m) {
@@ -1001,6 +1033,7 @@ TORCH_LIBRARY(dmxq, m) {
   m.def("hist_qparams(Tensor hist, Tensor min_val, Tensor max_val, int precision, int qmin, int qmax, bool symmetric_qscheme) -> (Tensor, Tensor)");
   m.def("error_stats(Tensor ref, Tensor test, bool accumulate, Tensor(a!) stats, Tensor(b!) scratch) -> ()");
   m.def("cast_error(Tensor x, int[] fmts, Tensor? scale, Tensor? zero_point, bool accumulate, Tensor(a!) stats, Tensor(b!) scratch) -> ()");
+  m.def("hadamard_qdq(Tensor x, int size, bool inverse, int[] fmt, Tensor? scale, Tensor? zero_point, ScalarType? out_dtype=None) -> Tensor");
 }
 
 #define DMXQ_IMPL(m, name) m.impl(#name, &name)
@@ -1010,7 +1043,7 @@ TORCH_LIBRARY(dmxq, m) {
   X(m, float_qdq); X(m, float_qdq_multi); X(m, fixed_qdq); X(m, fixed_qdq_multi); X(m, fixed_float_qdq_multi); X(m, nm_mask); X(m, topk_mask); X(m, bernoulli_mask); X(m, group_minmax); X(m, qparams); \
   X(m, histc); X(m, channel_maxabs); X(m, smoothquant_scale); X(m, scale_channels); X(m, unary); X(m, rope); X(m, rope_cast); X(m, softmax); X(m, norm); \
   X(m, unary_cast); X(m, unary_cast_table); X(m, lut16_apply); X(m, softmax_cast); X(m, norm_cast); X(m, group_minmax_accumulate); X(m, gptq_block); X(m, hist_observe); X(m, hist_qparams); \
-  X(m, error_stats); X(m, cast_error)
+  X(m, error_stats); X(m, cast_error); X(m, hadamard_qdq)
 
 // "CUDA" is the dispatch key of HIP tensors in a ROCm build of PyTorch
 TORCH_LIBRARY_IMPL(dmxq, CUDA, m) {
@@ -1064,4 +1097,6 @@ PYBIND11_MODULE(dmxq_fast, m) {
   m.def("hist_qparams", &hist_qparams);
   m.def("error_stats", &error_stats);
   m.def("cast_error", &cast_error);
+  m.def("hadamard_qdq", &hadamard_qdq, py::arg("x"), py::arg("size"), py::arg("inverse"), py::arg("fmt"), py::arg("scale"), py::arg("zero_point"),
+        py::arg("out_dtype") = py::none());
 }

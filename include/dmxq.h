@@ -54,7 +54,7 @@ typedef enum {
 
 const char* dmxq_status_string(int status);
 /* ABI version: bumped on any signature change.  Additions since 4 (dmxq_gptq_block, dmxq_hist_observe, dmxq_hist_qparams, dmxq_error_stats, dmxq_cast_error,
- * dmxq_error_scratch_bytes) leave it at 4: a caller built against 4 runs on
+ * dmxq_error_scratch_bytes, dmxq_hadamard_qdq) leave it at 4: a caller built against 4 runs on
  * this library unchanged.  4 = round 5: + dmxq_float_qdq_multi, dmxq_fixed_float_qdq_multi; 3 = round 4: + dmxq_weight_hypernet_multi,
  * dmxq_unary_cast_table, dmxq_lut16_apply.  Nothing was ever removed or changed: a caller built against version n runs on any library >= n. */
 int dmxq_abi_version(void);
@@ -418,11 +418,13 @@ int dmxq_rope(const void* x, const void* cos_tab, const void* sin_tab, void* out
  *                    scale / zero_point per row (per_row = 1) or one for all rows (per_row = 0).
  * count <= 128; microblock in {1, 8, 16, 32, 64} (BFP: not 1).  DMXQ_ERR_BAD_ARG: null pointers, sizes out of range, strides below
  * count; DMXQ_ERR_UNSUPPORTED: a format, microblock or count outside the above (nothing launched: the caller runs its own loop). */
-typedef enum { DMXQ_GPTQ_BFP = 0, DMXQ_GPTQ_FLOAT = 1, DMXQ_GPTQ_FIXED = 2 } dmxq_gptq_kind;
+typedef enum { DMXQ_GPTQ_BFP = 0, DMXQ_GPTQ_FLOAT = 1, DMXQ_GPTQ_FIXED = 2,
+               DMXQ_GPTQ_MXFP = 3 /* dmxq_hadamard_qdq only: dmxq_gptq_block and dmxq_cast_error refuse it like any unknown kind */
+} dmxq_gptq_kind;
 typedef struct {
   int kind;                                                    /* dmxq_gptq_kind */
-  int precision, block_size, symmetric;                        /* BFP (precision, block_size, symmetric) and FIXED (precision, symmetric) */
-  int man_bits, exp_bits, exp_bias, flush_subnormal, unsigned_abs;   /* FLOAT */
+  int precision, block_size, symmetric;                        /* BFP (precision, block_size, symmetric) and FIXED (precision, symmetric); MXFP: block_size */
+  int man_bits, exp_bits, exp_bias, flush_subnormal, unsigned_abs;   /* FLOAT; MXFP: man_bits, exp_bits */
   int fraction, clamp, per_row;                                /* FIXED */
 } dmxq_gptq_format;
 int dmxq_gptq_block(const float* w, int64_t ldw, float* q, int64_t ldq, float* err, int64_t lde, int64_t rows, int64_t count,
@@ -478,6 +480,32 @@ int dmxq_error_stats(const void* ref, int dtype_ref, const void* test, int dtype
 int dmxq_cast_error(const void* in, int dtype, int64_t rows, int64_t L, const dmxq_gptq_format* formats, int n_formats,
                     const float* scale, const int64_t* zero_point, int accumulate, double* stats, void* scratch, int64_t scratch_bytes,
                     void* stream);
+
+/* Orthonormal block-Hadamard rotation fused into a quantize-dequantize cast (csrc/hadamard.hip).  Not in the reference:
+ * the rotate -> quantize -> rotate back companion of the 4- to 8-bit block formats (QuaRot, SpinQuant, the MXFP4 training recipes), one
+ * read and one write per element instead of a dense [size, size] matmul and two more passes around the cast.
+ * in / out: [rows, L] contiguous; blocks of `size` consecutive elements along L; size in {8, 16, 32, 64, 128, 256}, L % size == 0.
+ * R (one block, widened to fp32): butterfly stages of stride s = 1, 2, .., size / 2 in that order -- for every i with bit s clear
+ * v[i], v[i + s] = v[i] + v[i + s], v[i] - v[i + s] from the old values, each ONE fp32 operation -- then ONE fp32 multiply by
+ * (float)(1 / sqrt((double)size)).  R is symmetric and orthonormal: its own inverse.  NaN / Inf propagate through the adds.
+ *   fmt == NULL            out = round_to(dtype_out, R(x))  (inverse must be 0)
+ *   fmt, inverse == 0      out = round_to(dtype_out, Q(R(x)))
+ *   fmt, inverse != 0      out = round_to(dtype_out, R(Q(R(x))))
+ * Q: the library's cast of the rotated FLOAT32 tensor to fmt, float32 in and out, blocks along L, nearest rounding -- bit for bit
+ * dmxq_bfp_qdq / dmxq_float_qdq / dmxq_fixed_qdq / dmxq_mxfp_qdq on that tensor; ONE rounding to dtype_out at the very end.
+ *   DMXQ_GPTQ_BFP    symmetric or "(_N)", 2 <= precision <= 22, block_size a power of two >= 2 dividing size;
+ *   DMXQ_GPTQ_FLOAT  man_bits <= 22;
+ *   DMXQ_GPTQ_FIXED  the affine wrapper x / scale + zp -> cast -> (x - zp) * scale; per_row = 0: scale[0] / zero_point[0],
+ *                    per_row = 1: scale[rows] / zero_point[rows] (DEVICE arrays);
+ *   DMXQ_GPTQ_MXFP   man_bits <= 22, exp_bits, block_size a power of two dividing size (dmxq_mxfp_qdq's float32 rules, its
+ *                    floor(log2 max) rule near powers of two included; zero blocks stay zero).
+ * in == out is allowed when both dtypes have one width (every block is fully read before any of it is written); pointers need not be
+ * 16-byte aligned (such a call loads and stores element by element).  No allocation, no host synchronisation: the call can be captured
+ * into a graph.  DMXQ_ERR_BAD_ARG: null pointers, negative sizes, an invalid dtype or kind, inverse without a format, in == out with
+ * dtypes of different widths; DMXQ_ERR_UNSUPPORTED, nothing launched: a size outside the list, L % size != 0, a format or block size
+ * outside the above (the caller runs rotation, cast and rotation as three launches). */
+int dmxq_hadamard_qdq(const void* in, void* out, int dtype_in, int dtype_out, int64_t rows, int64_t L, int64_t size, int inverse,
+                      const dmxq_gptq_format* fmt, const float* scale, const int64_t* zero_point, void* stream);
 
 #ifdef __cplusplus
 }
