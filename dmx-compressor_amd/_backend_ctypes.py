@@ -798,3 +798,21 @@ def hadamard_qdq(x, size, inverse, fmt, scale, zero_point, out_dtype=None):
     check(lib().dmxq_hadamard_qdq(ptr(xc), ptr(out), dtype_code(xc.dtype), dtype_code(out.dtype), rows, L, size, int(bool(inverse)),
                                   ctypes.byref(f) if f is not None else None, ptr(scale), ptr(zero_point), stream_of(xc)), "dmxq_hadamard_qdq")
     return out
+
+
+# ------------------------------------------------------------------------------------------------ dynamic integer cast
+@_guarded
+def dynamic_fixed_qdq(x, segment, whole_rows, precision, fraction, clamp, symmetric, rounding, qmin, qmax, symmetric_qscheme, want_qparams,
+                      out_dtype=None):
+    xc = _prep(x, "dynamic_fixed_qdq")
+    if segment < 1 or xc.numel() % segment != 0:
+        raise RuntimeError("dynamic_fixed_qdq: the segment must divide the number of elements")
+    n = xc.numel() // segment
+    out = torch.empty(xc.shape, dtype=out_dtype or xc.dtype, device=xc.device)
+    sc = torch.empty(n if want_qparams else 0, dtype=torch.float32, device=xc.device)
+    zp = torch.empty(n if want_qparams else 0, dtype=torch.int64, device=xc.device)
+    check(lib().dmxq_dynamic_fixed_qdq(ptr(xc), ptr(out), dtype_code(xc.dtype), dtype_code(out.dtype), n, segment, int(bool(whole_rows)),
+                                       precision, fraction, int(bool(clamp)), int(bool(symmetric)), rounding, qmin, qmax,
+                                       int(bool(symmetric_qscheme)), ptr(sc) if want_qparams else None, ptr(zp) if want_qparams else None,
+                                       stream_of(xc)), "dmxq_dynamic_fixed_qdq")
+    return out, sc, zp

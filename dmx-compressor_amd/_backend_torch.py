@@ -53,7 +53,9 @@ _FAST_NAMES = {"bfp_qdq_nograd": "bfp_qdq", "float_qdq_nograd": "float_qdq", "fi
 # the calibration calls of the device HistogramObserver and the error statistics (no autograd to lose: they take the same route)
 _FAST_CALIBRATION_NAMES = {"hist_observe": "hist_observe", "hist_qparams": "hist_qparams", "error_stats": "error_stats", "cast_error": "cast_error",
                            # the Hadamard rotation: its backward is an autograd Function of the front end (_front.py), above the raw op
-                           "hadamard_qdq": "hadamard_qdq"}
+                           "hadamard_qdq": "hadamard_qdq",
+                           # the dynamic integer cast: straight-through above the raw op as well (cast.py)
+                           "dynamic_fixed_qdq": "dynamic_fixed_qdq"}
 FAST = None
 
 

@@ -22,6 +22,7 @@ __all__ = [
     "smoothquant_scale", "scale_channels", "gelu", "silu", "quick_gelu", "exp", "silu_experimental", "rope", "softmax", "layernorm",
     "rmsnorm", "histc", "gptq_fields", "gptq_block", "hist_observe", "hist_scratch_words", "hist_qparams", "error_stats", "cast_error",
     "error_scratch_bytes", "cast_error_entry", "hadamard", "hadamard_qdq", "hadamard_check_size", "HADAMARD_SIZES",
+    "dynamic_fixed_qdq", "dynamic_check", "dynamic_class", "DYNAMIC_GRANULARITIES", "DYNAMIC_CHAIN_BY_DEFAULT",
 ]
 
 _ops = None   # the raw namespace: set by bind()
@@ -907,5 +908,150 @@ def hadamard_qdq(x, size: int, fmt, block_dim: int = -1, inverse: bool = True, s
 
     if x.requires_grad and torch.is_grad_enabled():
         return _RotatedCast.apply(x, run, size, d, bool(inverse))
+    with torch.no_grad():
+        return run(x.detach())
+
+
+# ---------------------------------------------------------------------------------------------------- dynamic integer cast
+DYNAMIC_GRANULARITIES = ("per_token", "per_group", "per_tensor")
+DYNAMIC_MAX_ROW = 16384          # the longest segment dmxq_dynamic_fixed_qdq keeps in registers
+DYNAMIC_CHAIN_MAX_SEGMENTS = 65535   # groups of one dmxq_group_minmax call; more segments: the chain runs on pieces of ...
+DYNAMIC_CHAIN_PIECE = 32768          # ... this many segments (the kernel has no such limit)
+# Launch geometries of dmxq_dynamic_fixed_qdq (dynamic_class) that fused=None sends to the three-launch chain although the kernel takes
+# them.  The rule: a class goes to the kernel by default only where tools/bench_dynamic_quant.py MEASURED it faster than the chain on the
+# same buffers; a class that is not gets listed here with its row.  profiles/r12_dynamic_quant.txt (bf16 INT8, symmetric / affine, us per
+# call, kernel against chain): wave_row [8192,4096] 27.7 / 28.0 against 75.1 / 74.4, [2048,768] 3.7 / 3.8 against 20.4 / 20.3; block_row
+# [8192,14336] 85.9 / 84.4 against 143.1 / 143.2; group (128) [8192,4096] 28.3 / 31.2 against 1368 / 1370, [8192,14336] 77.3 / 83.6 against
+# 4757 / 4755, [2048,768] 3.3 / 3.5 against 67.4; short_row [60000,48] 36.3 / 38.5 against 287.3 / 287.6 (4 % of 8 TB/s: most lanes idle,
+# still 7.5-7.9 x the chain) -- every class is faster, none is listed.
+DYNAMIC_CHAIN_BY_DEFAULT = frozenset()
+# which route the calls of this front end took, counted on the host: private, for the tests (fused=True must have run the kernel)
+_dynamic_routes = {"fused": 0, "chain": 0}
+_DYNAMIC_CLASS_NAMES = {1: "group", 2: "short_row", 3: "wave_row", 4: "block_row"}   # dmxq_dynamic_geometry (include/dmxq.h)
+
+
+def dynamic_check(fmt, granularity, group_size=None, what: str = "dynamic_fixed_qdq"):
+    """-> (format, granularity, group_size) of a dynamic cast, or ValueError: a format with an integer range (observer.get_qmin_qmax), a
+    known granularity, a positive group size with per_group and none otherwise.  No GPU involved."""
+    from .format import Format
+    from .observer import get_qmin_qmax
+    fmt = Format.from_shorthand(fmt) if isinstance(fmt, str) else fmt
+    if not isinstance(fmt, Format) or get_qmin_qmax(fmt) == (None, None):
+        raise ValueError(f"{what}: a dynamic cast derives integer scales, so it needs a clamped FixedPoint format without fraction bits "
+                         f"(XP[p,0](C..)), got {fmt!r}")
+    if granularity not in DYNAMIC_GRANULARITIES:
+        raise ValueError(f"{what}: granularity must be one of {DYNAMIC_GRANULARITIES}, got {granularity!r}")
+    if granularity == "per_group":
+        if isinstance(group_size, bool) or not isinstance(group_size, int) or group_size < 1:
+            raise ValueError(f"{what}: per_group needs a positive integer group_size, got {group_size!r}")
+    elif group_size is not None:
+        raise ValueError(f"{what}: group_size goes with granularity 'per_group', got {granularity!r} with group_size {group_size!r}")
+    return fmt, granularity, group_size
+
+
+def dynamic_class(segment: int, dtype: torch.dtype, whole_rows: bool) -> Optional[str]:
+    """the launch geometry dmxq_dynamic_fixed_qdq picks for segments of `segment` elements of `dtype`, asked of the library itself
+    (dmxq_dynamic_class: the function that makes the choice inside the entry; no GPU involved), or None when it refuses them: "group"
+    (power-of-two segments of 16 .. 256 inside a wave), "short_row" (a wave per row of fewer than 64 vectors: lanes idle), "wave_row"
+    (a wave per row, up to 16 vectors per lane), "block_row" (a workgroup per row, up to 16384 elements)"""
+    from ._lib import dtype_code, lib
+    return _DYNAMIC_CLASS_NAMES.get(lib().dmxq_dynamic_class(dtype_code(dtype), int(segment), int(bool(whole_rows))))
+
+
+class _DynamicSTE(torch.autograd.Function):
+    """the dynamic cast as a straight-through estimator (cast.py _FixedAffineCast: the scales are not differentiated either)"""
+
+    @staticmethod
+    def forward(ctx, x, run):
+        ctx.set_materialize_grads(False)
+        ctx.in_dtype = x.dtype
+        out = run(x.detach())
+        if isinstance(out, tuple):
+            ctx.mark_non_differentiable(*out[1:])
+        return out
+
+    @staticmethod
+    def backward(ctx, g, *_):
+        if g is not None and g.dtype != ctx.in_dtype:
+            g = g.to(ctx.in_dtype)
+        return g, None
+
+
+def dynamic_fixed_qdq(x, fmt, granularity: str = "per_token", group_size: Optional[int] = None, symmetric_qscheme: bool = False,
+                      out_dtype: Optional[torch.dtype] = None, return_qparams: bool = False, fused: Optional[bool] = None, seed: Optional[int] = None):
+    """Integer Q->DQ with scales derived from the tensor itself on every call (not in the reference, whose integer casts
+    need a calibration pass).  A segment is S consecutive elements along the last dim of the contiguous tensor: the whole row with
+    "per_token" (per output channel of an [out, in] weight), `group_size` elements with "per_group" (it must divide the last dim), the
+    whole tensor with "per_tensor".  By definition, with (qmin, qmax) = observer.get_qmin_qmax(fmt):
+        x2 = x.reshape(-1, S);  mn, mx = group_minmax(x2, 0, 1);  sc, zp = qparams(mn, mx, qmin, qmax, symmetric_qscheme)
+        y = fixed_qdq(x2, fmt..., scale=sc, zero_point=zp, ch_axis=0, out_dtype=out_dtype).reshape(x.shape)
+    -- the reference's own formulas (numerical/observer.py:59-115, numerical/cast.py:278-296) per call; symmetric_qscheme as
+    MinMaxObserver.calculate_qparams decides it (True for torch.per_tensor_symmetric / per_channel_symmetric).  A row with a NaN gets
+    scale eps (qparams drops the NaN extrema); a row with an Inf gets scale Inf.  Nothing is read back to the host.
+    ONE launch (dmxq_dynamic_fixed_qdq: 4 B per bf16 element instead of 6, one launch instead of three) for a nearest-rounding format,
+    out_dtype == x.dtype, a 16-byte aligned tensor and S a power of two from 16 to 256 or -- per_token / per_tensor -- any multiple of a
+    16-byte vector up to 16384; the chain otherwise, same bits (on more than 65535 segments, what one group_minmax call takes, the chain
+    runs on pieces of 32768 segments and joins the results).  fused=None: the kernel where it applies and its geometry
+    (dynamic_class) is not listed in DYNAMIC_CHAIN_BY_DEFAULT; True: NotImplementedError instead of falling back; False: the chain.
+    seed: for a stochastic-rounding format (the chain only), as ops.fixed_qdq takes it; the draws are keyed by the element's index within
+    its piece of the chain.
+    return_qparams: (y, scale float32 [n_segments], zero_point int64 [n_segments]) on both routes.
+    ValueError (before any GPU use): a format without an integer range, an unknown granularity, a group_size that does not divide the
+    last dim.  Autograd: a straight-through estimator."""
+    from .observer import get_qmin_qmax
+    fmt, granularity, group_size = dynamic_check(fmt, granularity, group_size)
+    if x.dim() < 1:
+        raise ValueError("dynamic_fixed_qdq: expects a tensor with at least one dimension")
+    L = x.shape[-1]
+    if granularity == "per_group" and L % group_size:
+        raise ValueError(f"dynamic_fixed_qdq: the last dimension has {L} elements, not a multiple of the group size {group_size}")
+    require_gpu(x, "dynamic_fixed_qdq")
+    qmin, qmax = get_qmin_qmax(fmt)
+    sym = bool(symmetric_qscheme)
+    out_dtype = out_dtype or x.dtype
+    S = {"per_token": L, "per_group": group_size, "per_tensor": x.numel()}[granularity]
+    whole_rows = granularity != "per_group"
+
+    def run(xd):
+        xc = xd if xd.is_contiguous() else xd.contiguous()
+        if xc.numel() == 0:
+            y = torch.empty(xc.shape, dtype=out_dtype, device=xc.device)
+            return (y, y.new_empty(0, dtype=torch.float32), y.new_empty(0, dtype=torch.int64)) if return_qparams else y
+        if fused is not False:
+            cls = dynamic_class(S, xc.dtype, whole_rows) if (fmt.rounding == "nearest" and out_dtype == xc.dtype and fmt.precision <= 22
+                                                             and xc.data_ptr() % 16 == 0) else None
+            if cls is None and fused:
+                raise NotImplementedError(f"dynamic_fixed_qdq: no fused kernel for segments of {S} {xc.dtype} elements -> {out_dtype} "
+                                          f"with {fmt!r} (base address {xc.data_ptr() % 16} mod 16)")
+            if cls is not None and fused is None and cls in DYNAMIC_CHAIN_BY_DEFAULT:
+                cls = None
+            if cls is not None:
+                try:
+                    y, sc, zp = _ops.dynamic_fixed_qdq(xc, S, whole_rows, fmt.precision, fmt.fraction, bool(fmt.clamp), bool(fmt.symmetric),
+                                                       ROUNDING_CODE[fmt.rounding], qmin, qmax, sym, bool(return_qparams), out_dtype)
+                    _dynamic_routes["fused"] += 1
+                    return (y, sc, zp) if return_qparams else y
+                except NotImplementedError:   # (DMXQ_ERR_UNSUPPORTED, nothing launched)
+                    if fused:
+                        raise
+        _dynamic_routes["chain"] += 1
+        x2 = xc.reshape(-1, S)
+
+        def three(part):
+            mn, mx = _ops.group_minmax(part, 0, 1)
+            sc, zp = _ops.qparams(mn, mx, qmin, qmax, sym)
+            return fixed_qdq(part, fmt.precision, fmt.fraction, fmt.clamp, fmt.symmetric, fmt.rounding, scale=sc, zero_point=zp, ch_axis=0,
+                             out_dtype=out_dtype, seed=seed), sc, zp
+
+        if x2.shape[0] <= DYNAMIC_CHAIN_MAX_SEGMENTS:
+            y, sc, zp = three(x2)
+        else:   # (dmxq_group_minmax takes 65535 groups: segments are independent, so the chain runs on pieces and the results are joined)
+            parts = [three(x2[i:i + DYNAMIC_CHAIN_PIECE]) for i in range(0, x2.shape[0], DYNAMIC_CHAIN_PIECE)]
+            y, sc, zp = (torch.cat([p[k] for p in parts]) for k in range(3))
+        y = y.reshape(xc.shape)
+        return (y, sc, zp) if return_qparams else y
+
+    if x.requires_grad and torch.is_grad_enabled():
+        return _DynamicSTE.apply(x, run)
     with torch.no_grad():
         return run(x.detach())

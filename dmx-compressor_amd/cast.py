@@ -15,7 +15,7 @@ from torch.autograd import Function
 from . import ops
 from ._flags import HostFlags
 from .format import FixedPoint, Format, Same
-from .observer import _PER_CHANNEL, DummyObserver, HistogramObserver, MinMaxObserver, ObserverBase
+from .observer import _PER_CHANNEL, _SYMMETRIC, DummyObserver, HistogramObserver, MinMaxObserver, ObserverBase
 
 __all__ = ["CastToFormat", "CastTo", "CastToDict"]
 
@@ -84,6 +84,20 @@ def _parse_hadamard(spec):
     return {"size": ops.hadamard_check_size(size, "pre_transform['hadamard']"), "inverse": inverse}
 
 
+def _parse_dynamic(granularity, group_size=None):
+    """set_dynamic's arguments -> None or (granularity, group_size): None / False, "per_token", "per_tensor", ("per_group", g) or
+    {"per_group": g}"""
+    if granularity is None or granularity is False:
+        if group_size is not None:
+            raise ValueError(f"set_dynamic: group_size {group_size!r} without a granularity")
+        return None
+    if isinstance(granularity, dict):
+        if set(granularity) != {"per_group"} or group_size is not None:
+            raise ValueError(f"set_dynamic: expected {{'per_group': int}}, got {granularity!r}")
+        granularity, group_size = "per_group", granularity["per_group"]
+    return granularity, group_size
+
+
 class CastTo(HostFlags, torch.nn.Module):
     """Simulated numerical cast to a target format (cast.py:136-162).  Buffers and switches follow
     torch.ao's FakeQuantize, which the reference subclasses: scale, zero_point, fake_quant_enabled,
@@ -99,6 +113,9 @@ class CastTo(HostFlags, torch.nn.Module):
     #: instead of being copied to a contiguous tensor first.  Same values; set by modules whose `_forward` takes any strides
     #: (ActActMatMul: q / k^T / v of an attention arrive as transposed views -- k^T blocked along -2 is k blocked along its LAST dim).
     keep_layout = False
+    #: None, or (granularity, group_size): scale and zero point are derived from every tensor itself (set_dynamic).  A plain
+    #: attribute, not a buffer: the state_dict of a module does not change.
+    _dynamic = None
 
     def __init__(self, format="SAME", observer=DummyObserver, group_size=None, block_dim=-1,
                  qscheme=torch.per_tensor_affine, ch_axis=-1, **observer_kwargs):
@@ -139,6 +156,8 @@ class CastTo(HostFlags, torch.nn.Module):
     def set_format(self, format: Union[str, torch.dtype, Format]):
         if isinstance(format, str):
             format = Format.from_shorthand(format)
+        if self._dynamic is not None and not isinstance(format, Same):
+            ops.dynamic_check(format, *self._dynamic, what="CastTo.set_format on a dynamic cast")
         self.format = format
         if hasattr(self, "activation_post_process"):
             self.activation_post_process.dtype = format
@@ -157,6 +176,34 @@ class CastTo(HostFlags, torch.nn.Module):
             # an orthonormal block-Hadamard rotation along block_dim around the cast (ops.hadamard_qdq): 64, or
             # {"size": 64, "inverse": False} to leave the result in the rotated basis; a bad size raises ValueError here
             self.pre_transform["hadamard"] = _parse_hadamard(self.pre_transform["hadamard"])
+
+    def set_dynamic(self, granularity=None, group_size=None):
+        """Dynamic scales (not in the reference): with fake-quant on and the observer off, an integer format is cast with a
+        scale and zero point derived from the tensor itself on every forward (ops.dynamic_fixed_qdq; this cast's qscheme decides symmetric
+        or affine) -- one per row of the last dimension ("per_token"; per output channel of an [out, in] weight), per `group_size`
+        consecutive elements of it ("per_group", or {"per_group": g}) or for the whole tensor ("per_tensor").  The scale / zero_point
+        buffers and the observer are neither read nor written.  None switches back to the stored scales.  While the observer is enabled the
+        calibration path runs as ever.  ValueError for an unknown granularity and for a format without an integer range -- here, or in
+        set_format when the format comes later (a cast that is still SAME accepts the setting)."""
+        dyn = _parse_dynamic(granularity, group_size)
+        if dyn is not None:
+            if isinstance(self.format, Same):
+                ops.dynamic_check("XP[8,0](CSN)", *dyn, what="CastTo.set_dynamic")   # (the granularity alone)
+            else:
+                ops.dynamic_check(self.format, *dyn, what="CastTo.set_dynamic")
+        self._dynamic = dyn
+
+    @property
+    def dynamic(self):
+        """None, "per_token", "per_tensor" or {"per_group": g} (set_dynamic)"""
+        dyn = self._dynamic
+        if dyn is None:
+            return None
+        return {"per_group": dyn[1]} if dyn[0] == "per_group" else dyn[0]
+
+    def _dynamic_cast(self, x, out_dtype):
+        g, gs = self._dynamic
+        return ops.dynamic_fixed_qdq(x, self.format, g, gs, symmetric_qscheme=self.qscheme in _SYMMETRIC, out_dtype=out_dtype)
 
     def enable_calibration(self, state: bool = True, observer_cls: ObserverBase = HistogramObserver,
                            qscheme_to_overload: Optional[torch.qscheme] = None, group_size: int = None,
@@ -238,6 +285,8 @@ class CastTo(HostFlags, torch.nn.Module):
         fmt = self.format
         # the autograd wrappers only matter when a gradient will flow (straight-through estimator); inference skips them
         ste = torch.is_grad_enabled() and x.requires_grad
+        if self._dynamic is not None and isinstance(fmt, FixedPoint) and not self.__dict__["_h_observer_enabled"]:
+            return self._dynamic_cast(x, out_dtype)   # (a straight-through estimator under autograd by itself)
         if isinstance(fmt, FixedPoint):
             # per-tensor: one scale; per-channel: scale[c]; per-group: scale[c // group_size] (cast.py:279-293)
             if self.group_size:
@@ -314,7 +363,7 @@ class CastTo(HostFlags, torch.nn.Module):
             return self._quantize(x, x.dtype)
         had = pt.get("hadamard")
         if had is not None and len(pt) == 1 and d["_h_fake_quant_enabled"] and not d["_h_observer_enabled"] and isinstance(fmt, Format) \
-                and not isinstance(fmt, Same):
+                and not isinstance(fmt, Same) and self._dynamic is None:   # (a dynamic cast: the step-by-step route below)
             return self._hadamard_qdq(x, had, x.dtype)   # rotation, cast and inverse rotation: one call
         inverse_shaping = None
         shortcut = None
@@ -358,6 +407,17 @@ class CastTo(HostFlags, torch.nn.Module):
         if self.pre_transform and set(self.pre_transform) != {"hadamard"}:
             raise NotImplementedError("CastTo.measure_error: a cast with a pre_transform other than hadamard (shaping / shortcut / pre-format)")
         fmt, x = self.format, x.detach()
+        if self._dynamic is not None and isinstance(fmt, FixedPoint):
+            # a dynamic cast: the cast itself (between the two rotations of a "hadamard" pre_transform), then ops.error_stats
+            with torch.no_grad():
+                had = self.pre_transform.get("hadamard")
+                if had is None:
+                    y = self._dynamic_cast(x, x.dtype)
+                else:
+                    r = ops.hadamard(x, had["size"], self.block_dim, out_dtype=torch.float32)
+                    y = (ops.hadamard(self._dynamic_cast(r, torch.float32), had["size"], self.block_dim, out_dtype=x.dtype)
+                         if had["inverse"] else self._dynamic_cast(r, x.dtype))
+            return ops.error_stats(x, y)
         if self.pre_transform:
             had = self.pre_transform["hadamard"]
             with torch.no_grad():
@@ -386,7 +446,8 @@ class CastTo(HostFlags, torch.nn.Module):
 
     def extra_repr(self):
         return f"format = dtype = {self.format!r}, qscheme = {self.qscheme}, ch_axis = {self.ch_axis}, " \
-               f"group_size = {self.group_size}, block_dim = {self.block_dim}"
+               f"group_size = {self.group_size}, block_dim = {self.block_dim}" \
+               + (f", dynamic = {self.dynamic!r}" if self._dynamic is not None else "")
 
 
 class CastToDict(torch.nn.ModuleDict):
@@ -425,6 +486,25 @@ class CastToDict(torch.nn.ModuleDict):
     def set_pre_transform(self, pre_transforms):
         for k, t in self.pack_to_dict(pre_transforms).items():
             self[k].set_pre_transform(t)
+
+    def set_dynamic(self, dynamic):
+        """one setting (None, "per_token", "per_tensor", {"per_group": g}) for every cast, or a list / dict of settings over the casts the
+        way set_pre_transform takes them"""
+        if dynamic is None or isinstance(dynamic, str) or (isinstance(dynamic, dict) and set(dynamic) == {"per_group"}
+                                                           and "per_group" not in self.keys()):
+            for c in self.values():
+                c.set_dynamic(dynamic)
+            return
+        if isinstance(dynamic, (tuple, list)):   # (not pack_to_dict: it spells a None entry "SAME", a format)
+            if len(dynamic) != len(self):
+                raise ValueError(f"set_dynamic: {len(dynamic)} settings for {len(self)} casts")
+            dynamic = dict(zip(self.keys(), dynamic))
+        elif not isinstance(dynamic, dict):
+            raise ValueError(f"set_dynamic: expected a setting, or a list or dict of settings, got {dynamic!r}")
+        for k, t in dynamic.items():
+            if k not in self.keys():
+                raise RuntimeError(f"No CastTo with key {k}!")
+            self[k].set_dynamic(t)
 
     def set_format(self, format):
         for k, f in self.pack_to_dict(format).items():

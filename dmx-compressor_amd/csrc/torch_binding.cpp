@@ -983,6 +983,31 @@ Tensor hadamard_qdq_meta(const Tensor& x, int64_t, bool, at::IntArrayRef, const 
   return empty_like_shape(x, out_dtype);
 }
 
+// ------------------------------------------------------------------------------------------------ dynamic integer cast
+// x: contiguous, numel % segment == 0; -> (out, scale [n_segments] float32, zero_point [n_segments] int64), the last two empty unless
+// want_qparams.  DMXQ_ERR_UNSUPPORTED (NotImplementedError, nothing launched): the front end runs the three-launch chain.
+std::tuple<Tensor, Tensor, Tensor> dynamic_fixed_qdq(const Tensor& x, int64_t segment, bool whole_rows, int64_t precision, int64_t fraction,
+                                                     bool clamp, bool symmetric, int64_t rounding, int64_t qmin, int64_t qmax,
+                                                     bool symmetric_qscheme, bool want_qparams, OptDtype out_dtype) {
+  const Tensor xc = prep(x, "dynamic_fixed_qdq");
+  TORCH_CHECK(segment >= 1 && xc.numel() % segment == 0, "dynamic_fixed_qdq: the segment must divide the number of elements");
+  const int64_t n = xc.numel() / segment;
+  Tensor out = empty_like_shape(xc, out_dtype);
+  Tensor sc = at::empty({want_qparams ? n : 0}, xc.options().dtype(at::kFloat));
+  Tensor zp = at::empty({want_qparams ? n : 0}, xc.options().dtype(at::kLong));
+  Launch l(xc);
+  check(dmxq_dynamic_fixed_qdq(xc.data_ptr(), out.data_ptr(), dt_code(xc.scalar_type()), dt_code(out.scalar_type()), n, segment, whole_rows ? 1 : 0,
+                               (int)precision, (int)fraction, clamp ? 1 : 0, symmetric ? 1 : 0, (int)rounding, (int)qmin, (int)qmax,
+                               symmetric_qscheme ? 1 : 0, want_qparams ? (float*)sc.data_ptr() : nullptr,
+                               want_qparams ? (int64_t*)zp.data_ptr() : nullptr, l.stream), "dmxq_dynamic_fixed_qdq");
+  return std::make_tuple(out, sc, zp);
+}
+std::tuple<Tensor, Tensor, Tensor> dynamic_fixed_qdq_meta(const Tensor& x, int64_t segment, bool, int64_t, int64_t, bool, bool, int64_t, int64_t,
+                                                          int64_t, bool, bool want_qparams, OptDtype out_dtype) {
+  const int64_t n = (want_qparams && segment >= 1) ? x.numel() / segment : 0;
+  return std::make_tuple(empty_like_shape(x, out_dtype), at::empty({n}, x.options().dtype(at::kFloat)), at::empty({n}, x.options().dtype(at::kLong)));
+}
+
 }  // namespace
 
 TORCH_LIBRARY(dmxq, m) {
@@ -1034,6 +1059,7 @@ TORCH_LIBRARY(dmxq, m) {
   m.def("error_stats(Tensor ref, Tensor test, bool accumulate, Tensor(a!) stats, Tensor(b!) scratch) -> ()");
   m.def("cast_error(Tensor x, int[] fmts, Tensor? scale, Tensor? zero_point, bool accumulate, Tensor(a!) stats, Tensor(b!) scratch) -> ()");
   m.def("hadamard_qdq(Tensor x, int size, bool inverse, int[] fmt, Tensor? scale, Tensor? zero_point, ScalarType? out_dtype=None) -> Tensor");
+  m.def("dynamic_fixed_qdq(Tensor x, int segment, bool whole_rows, int precision, int fraction, bool clamp, bool symmetric, int rounding, int qmin, int qmax, bool symmetric_qscheme, bool want_qparams, ScalarType? out_dtype=None) -> (Tensor, Tensor, Tensor)");
 }
 
 #define DMXQ_IMPL(m, name) m.impl(#name, &name)
@@ -1043,7 +1069,7 @@ TORCH_LIBRARY(dmxq, m) {
   X(m, float_qdq); X(m, float_qdq_multi); X(m, fixed_qdq); X(m, fixed_qdq_multi); X(m, fixed_float_qdq_multi); X(m, nm_mask); X(m, topk_mask); X(m, bernoulli_mask); X(m, group_minmax); X(m, qparams); \
   X(m, histc); X(m, channel_maxabs); X(m, smoothquant_scale); X(m, scale_channels); X(m, unary); X(m, rope); X(m, rope_cast); X(m, softmax); X(m, norm); \
   X(m, unary_cast); X(m, unary_cast_table); X(m, lut16_apply); X(m, softmax_cast); X(m, norm_cast); X(m, group_minmax_accumulate); X(m, gptq_block); X(m, hist_observe); X(m, hist_qparams); \
-  X(m, error_stats); X(m, cast_error); X(m, hadamard_qdq)
+  X(m, error_stats); X(m, cast_error); X(m, hadamard_qdq); X(m, dynamic_fixed_qdq)
 
 // "CUDA" is the dispatch key of HIP tensors in a ROCm build of PyTorch
 TORCH_LIBRARY_IMPL(dmxq, CUDA, m) {
@@ -1099,4 +1125,7 @@ PYBIND11_MODULE(dmxq_fast, m) {
   m.def("cast_error", &cast_error);
   m.def("hadamard_qdq", &hadamard_qdq, py::arg("x"), py::arg("size"), py::arg("inverse"), py::arg("fmt"), py::arg("scale"), py::arg("zero_point"),
         py::arg("out_dtype") = py::none());
+  m.def("dynamic_fixed_qdq", &dynamic_fixed_qdq, py::arg("x"), py::arg("segment"), py::arg("whole_rows"), py::arg("precision"), py::arg("fraction"),
+        py::arg("clamp"), py::arg("symmetric"), py::arg("rounding"), py::arg("qmin"), py::arg("qmax"), py::arg("symmetric_qscheme"),
+        py::arg("want_qparams"), py::arg("out_dtype") = py::none());
 }

@@ -72,8 +72,8 @@ class OptimalBrainCompressor:
         wc, st = m.weight_cast, m.weight_storage_cast
         if st is not None and not (isinstance(st.format, Same) and not st.pre_transform):
             return None
-        if wc.pre_transform or not wc._flag("fake_quant_enabled") or wc._flag("observer_enabled"):
-            return None
+        if wc.pre_transform or wc.dynamic is not None or not wc._flag("fake_quant_enabled") or wc._flag("observer_enabled"):
+            return None   # (a dynamic cast: its scale buffers are not what it casts with)
         per_row = False
         if isinstance(wc.format, FixedPoint):
             if wc.group_size:

@@ -155,6 +155,14 @@ class DmxModule(FastAttr, torch.nn.Module):
             self.output_casts.set_format(config["output_formats"])
         if "pre_output_transform" in config:
             self.output_casts.set_pre_transform(config["pre_output_transform"])
+        # dynamic scales for the integer casts (CastTo.set_dynamic): None, "per_token", "per_tensor" or {"per_group": g} -- one setting
+        # for every cast of the group, or a list / dict over them; after the formats of the same config, which they are checked against
+        if "input_dynamic" in config:
+            self.input_casts.set_dynamic(config["input_dynamic"])
+        if "output_dynamic" in config:
+            self.output_casts.set_dynamic(config["output_dynamic"])
+        if self.weight_cast is not None and "weight_dynamic" in config:
+            self.weight_cast.set_dynamic(config["weight_dynamic"])   # (per_token: per output channel of the [out, in] view)
         if self.accum_cast is not None and "accum_format" in config:
             self.accum_cast.set_format(config["accum_format"])
         if self.weight_storage_cast is not None and "weight_storage_format" in config:
@@ -1477,14 +1485,15 @@ def _weight_batches(mods):
     INT8 / INT4 per tensor or per row group) through `ops.bfp_qdq_multi` / `ops.fixed_qdq_multi`;
     hyper: {(weight dtype, device, score dtype, K, M, has SmoothQuant scale, precision, block size, symmetric): [(module, score, scale), ...]}
     -- the fused N:M mask / SmoothQuant scale -> BFP chain along the last dim through `ops.weight_hypernet_multi`.
-    Everything else (other sparsifiers, storage formats, pre-transforms, per-channel affine casts) is the module's own business."""
+    Everything else (other sparsifiers, storage formats, pre-transforms, per-channel affine casts, dynamic casts -- their scale buffers
+    are stale by design) is the module's own business."""
     from .format import BlockFloatingPoint, FixedPoint
     from .sparse import Dense
     groups = {}
     with torch.no_grad():
         for m in mods:
             wc, st, sp, sq = m.weight_cast, m.weight_storage_cast, m.weight_sparsifier, m.smoothquant
-            if (wc is None or wc.pre_transform or not wc._flag("fake_quant_enabled") or wc._flag("observer_enabled") or not m.weight.is_cuda
+            if (wc is None or wc.pre_transform or wc.dynamic is not None or not wc._flag("fake_quant_enabled") or wc._flag("observer_enabled") or not m.weight.is_cuda
                     or (sp is not None and not isinstance(sp.sparseness, Dense))
                     or (sq is not None and not sq._flag("fused_to_weight") and sq._flag("enabled"))
                     or (st is not None and not (isinstance(st.format, Same) and not st.pre_transform))):

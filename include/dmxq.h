@@ -54,7 +54,7 @@ typedef enum {
 
 const char* dmxq_status_string(int status);
 /* ABI version: bumped on any signature change.  Additions since 4 (dmxq_gptq_block, dmxq_hist_observe, dmxq_hist_qparams, dmxq_error_stats, dmxq_cast_error,
- * dmxq_error_scratch_bytes, dmxq_hadamard_qdq) leave it at 4: a caller built against 4 runs on
+ * dmxq_error_scratch_bytes, dmxq_hadamard_qdq, dmxq_dynamic_fixed_qdq, dmxq_dynamic_class) leave it at 4: a caller built against 4 runs on
  * this library unchanged.  4 = round 5: + dmxq_float_qdq_multi, dmxq_fixed_float_qdq_multi; 3 = round 4: + dmxq_weight_hypernet_multi,
  * dmxq_unary_cast_table, dmxq_lut16_apply.  Nothing was ever removed or changed: a caller built against version n runs on any library >= n. */
 int dmxq_abi_version(void);
@@ -506,6 +506,28 @@ int dmxq_cast_error(const void* in, int dtype, int64_t rows, int64_t L, const dm
  * outside the above (the caller runs rotation, cast and rotation as three launches). */
 int dmxq_hadamard_qdq(const void* in, void* out, int dtype_in, int dtype_out, int64_t rows, int64_t L, int64_t size, int inverse,
                       const dmxq_gptq_format* fmt, const float* scale, const int64_t* zero_point, void* stream);
+
+/* Dynamic integer cast (csrc/dynamic_quant.hip): every segment of `segment` consecutive elements of the contiguous
+ * [n_segments, segment] tensor takes its scale and zero point from its OWN minimum and maximum, on every call, in ONE launch.  Not in
+ * the reference (its integer casts read what a calibration run stored); the arithmetic is the reference's, applied per call:
+ *   (mn, mx)     the segment's extrema as dmxq_group_minmax reports them (one NaN makes both NaN, which the next step's fminf / fmaxf drop);
+ *   (scale, zp)  dmxq_qparams(mn, mx, qmin, qmax, symmetric_qscheme)  (numerical/observer.py:59-115);
+ *   out          dmxq_fixed_qdq with that one (scale, zp) per segment  (numerical/cast.py:278-296), nearest rounding.
+ * Bit for bit that three-launch chain, scale_out / zp_out included (each NULL, or a DEVICE array of n_segments entries).
+ * whole_rows != 0: the segments are the rows of the caller's tensor (per token / per output channel) -- any segment % V == 0 up to
+ * 16384, V = 8 sixteen-bit or 4 fp32 elements; whole_rows == 0: groups inside rows -- a power of two from 16 to 256 only.
+ * DMXQ_ERR_UNSUPPORTED, nothing launched (the caller runs the chain): dtype_in != dtype_out, a segment outside the above, a base that
+ * is not 16-byte aligned, rounding other than nearest, fraction != 0, no clamp, precision > 22.  DMXQ_ERR_BAD_ARG: null data
+ * pointers, negative sizes, invalid dtype / rounding, qmax <= qmin.  No workspace, no allocation, no host synchronisation: capturable. */
+/* The launch geometry dmxq_dynamic_fixed_qdq picks for segments of `segment` elements of `dtype` (no GPU involved; the same function
+ * makes the choice inside the entry): NONE = refused (DMXQ_ERR_UNSUPPORTED), GROUP = power-of-two segments of 16 .. 256 inside a wave,
+ * SHORT_ROW = a wave per row of fewer than 64 vectors (lanes idle), WAVE_ROW = a wave per row of 64 .. 1024 vectors, BLOCK_ROW = a
+ * 256-thread workgroup per row.  Returns the enum value, not a status. */
+typedef enum { DMXQ_DYN_NONE = 0, DMXQ_DYN_GROUP = 1, DMXQ_DYN_SHORT_ROW = 2, DMXQ_DYN_WAVE_ROW = 3, DMXQ_DYN_BLOCK_ROW = 4 } dmxq_dynamic_geometry;
+int dmxq_dynamic_class(int dtype, int64_t segment, int whole_rows);
+int dmxq_dynamic_fixed_qdq(const void* in, void* out, int dtype_in, int dtype_out, int64_t n_segments, int64_t segment, int whole_rows,
+                           int precision, int fraction, int clamp, int symmetric, int rounding, int qmin, int qmax,
+                           int symmetric_qscheme, float* scale_out, int64_t* zp_out, void* stream);
 
 #ifdef __cplusplus
 }
