@@ -693,6 +693,40 @@ def gptq_block(w, hinv, inv_d, microblock, fmt, scale, zero_point, q, err):
                                 ctypes.byref(f), ptr(scale), ptr(zero_point), stream_of(w)), "dmxq_gptq_block")
 
 
+@_guarded
+def gptq_block_dynamic(w, hinv, inv_d, microblock, fmt, rounding, group, qmin, qmax, symmetric_qscheme, q, err, scale_out, zp_out):
+    what = "gptq_block_dynamic"
+    require_gpu(w, what)
+    for t, name in ((w, "w"), (hinv, "hinv"), (q, "q"), (err, "err"), (scale_out, "scale_out")):
+        if not (t.is_cuda and t.device == w.device and t.dtype == torch.float32 and t.dim() == 2 and (t.shape[1] <= 1 or t.stride(1) == 1)):
+            raise RuntimeError(f"{what}: {name} must be a float32 matrix with unit column stride on w's GPU")
+    if len(fmt) != 12:
+        raise RuntimeError(f"{what}: fmt is the 12 fields of dmxq_gptq_format")
+    if microblock < 1 or group < 1:
+        raise RuntimeError(f"{what}: microblock and group must be positive")
+    rows, count = w.shape
+    nmb, ng = -(-count // microblock), count // group
+    if tuple(q.shape) != (rows, count) or tuple(err.shape) != (rows, count) or tuple(hinv.shape) != (count, count):
+        raise RuntimeError(f"{what}: w, q, err must be [rows, count] and hinv [count, count]")
+    if not (inv_d.is_cuda and inv_d.device == w.device and inv_d.dtype == torch.float32 and inv_d.is_contiguous()
+            and inv_d.numel() == nmb * microblock * microblock):
+        raise RuntimeError(f"{what}: inv_d must be a contiguous float32 [{nmb}, {microblock}, {microblock}] tensor on w's GPU")
+    if not (zp_out.is_cuda and zp_out.device == w.device and zp_out.dtype == torch.int64 and zp_out.dim() == 2
+            and (zp_out.shape[1] <= 1 or zp_out.stride(1) == 1)):
+        raise RuntimeError(f"{what}: zp_out must be an int64 matrix with unit column stride on w's GPU")
+    if tuple(scale_out.shape) != (rows, ng) or tuple(zp_out.shape) != (rows, ng):
+        raise RuntimeError(f"{what}: scale_out and zp_out must be [rows, count / group] = [{rows}, {ng}]")
+    f = _lib.GptqFormat(*[int(v) for v in fmt])
+
+    def ld(t, n):
+        return max(t.stride(0), n) if t.shape[0] <= 1 else t.stride(0)
+
+    check(lib().dmxq_gptq_block_dynamic(ptr(w), ld(w, count), ptr(q), ld(q, count), ptr(err), ld(err, count), rows, count, ptr(hinv),
+                                        ld(hinv, count), ptr(inv_d), microblock, ctypes.byref(f), int(rounding), int(group), int(qmin), int(qmax),
+                                        int(bool(symmetric_qscheme)), ptr(scale_out), ld(scale_out, ng), ptr(zp_out), ld(zp_out, ng),
+                                        stream_of(w)), "dmxq_gptq_block_dynamic")
+
+
 # ------------------------------------------------------------------------------------------------ HistogramObserver
 def _hist_state(t, like, dtype, numel, what, op):
     if not (t.is_cuda and t.device == like.device and t.dtype == dtype and t.is_contiguous() and t.numel() == numel):

@@ -20,7 +20,7 @@ from ._lib import DmxqError, ROUNDING_CODE, require_gpu
 __all__ = [
     "bfp_qdq", "block_quantize", "bfp_qdq_multi", "bfp_pack", "bfp_unpack", "weight_hypernet", "weight_hypernet_multi", "input_hypernet", "binary_cast", "rope_cast", "relu_cast", "unary_cast", "unary_cast_table", "lut16_apply", "softmax_cast", "layernorm_cast", "rmsnorm_cast", "sbfp_qdq", "mxfp_qdq", "float_qdq", "float_qdq_multi", "fixed_qdq", "fixed_qdq_multi", "fixed_float_qdq_multi", "nm_mask", "nm_sparsify", "topk_mask", "topk_sparsify", "bernoulli_mask", "group_minmax", "group_minmax_accumulate", "qparams", "channel_maxabs",
     "smoothquant_scale", "scale_channels", "gelu", "silu", "quick_gelu", "exp", "silu_experimental", "rope", "softmax", "layernorm",
-    "rmsnorm", "histc", "gptq_fields", "gptq_block", "hist_observe", "hist_scratch_words", "hist_qparams", "error_stats", "cast_error",
+    "rmsnorm", "histc", "gptq_fields", "gptq_block", "gptq_block_dynamic", "hist_observe", "hist_scratch_words", "hist_qparams", "error_stats", "cast_error",
     "error_scratch_bytes", "cast_error_entry", "hadamard", "hadamard_qdq", "hadamard_check_size", "HADAMARD_SIZES",
     "dynamic_fixed_qdq", "dynamic_check", "dynamic_class", "DYNAMIC_GRANULARITIES", "DYNAMIC_CHAIN_BY_DEFAULT",
 ]
@@ -585,6 +585,23 @@ def gptq_block(w, hinv, inv_d, q, err, microblock: int, fields, scale=None, zero
     NotImplementedError where the kernel does not take the format / microblock (the caller runs its own loop)."""
     require_gpu(w, "gptq_block")
     _ops.gptq_block(w, hinv, inv_d, int(microblock), [int(v) for v in fields], scale, zero_point, q, err)
+
+
+def gptq_block_dynamic(w, hinv, inv_d, q, err, scale_out, zp_out, microblock: int, group: int, fmt, symmetric_qscheme: bool = False):
+    """gptq_block for an integer format with DYNAMIC per-group scales (dmxq_gptq_block_dynamic): at every column j of the
+    block with j % group == 0 each row takes (scale, zero point) = qparams(group_minmax(w[:, j:j + group])) of its values as the loop
+    has updated them, casts the group's columns with it as gptq_block casts with a per-row scale, and records it in
+    scale_out / zp_out (float32 / int64 [rows, count // group] views with unit column stride).  fmt: a clamped XP[p,0] format (or its
+    shorthand); symmetric_qscheme as ops.qparams takes it.  ValueError for a format without an integer range; NotImplementedError
+    where the kernel does not take the group (16, 32, 64, 128; it divides count and is a multiple of the microblock), the microblock
+    or the format (the caller runs its own loop; nothing was launched)."""
+    from .observer import get_qmin_qmax
+    fmt, _, group = dynamic_check(fmt, "per_group", group, what="gptq_block_dynamic")
+    require_gpu(w, "gptq_block_dynamic")
+    qmin, qmax = get_qmin_qmax(fmt)
+    fields = [2, fmt.precision, 0, int(bool(fmt.symmetric)), 0, 0, 0, 0, 0, fmt.fraction, int(bool(fmt.clamp)), 1]
+    _ops.gptq_block_dynamic(w, hinv, inv_d, int(microblock), fields, ROUNDING_CODE[fmt.rounding], int(group), qmin, qmax,
+                            bool(symmetric_qscheme), q, err, scale_out, zp_out)
 
 
 # ---------------------------------------------------------------------------------------------------- error statistics

@@ -70,6 +70,8 @@ SIGNATURES = {
     "dmxq_softmax": [_vp, _vp, _i32, _i32, _i64, _i64, _f32, _vp],
     "dmxq_layernorm": [_vp, _vp, _i32, _i32, _i64, _i64, _vp, _vp, _i32, _f32, _vp],
     "dmxq_gptq_block": [_vp, _i64, _vp, _i64, _vp, _i64, _i64, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp],
+    "dmxq_gptq_block_dynamic": [_vp, _i64, _vp, _i64, _vp, _i64, _i64, _i64, _vp, _i64, _vp, _i64, _vp, _i32, _i64, _i32, _i32, _i32, _vp, _i64,
+                                _vp, _i64, _vp],
     "dmxq_hist_observe": [_vp, _i32, _i64, _i64, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _vp],
     "dmxq_hist_qparams": [_vp, _vp, _vp, _i64, _i64, _i32, _i32, _i32, _i32, _vp, _vp, _vp],
     "dmxq_error_scratch_bytes": [_i64, _i32],

@@ -44,7 +44,8 @@ class DmxSmoothQuantRecipe(DmxBaseRecipe):
 
 
 class DmxGPTQRecipe(DmxBaseRecipe):
-    """GPTQ (DmxModule.optimal_brain_compressing)"""
+    """GPTQ (DmxModule.optimal_brain_compressing); every field of a module's DmxModuleGPTQHyperparams, `act_order` included, reaches
+    OptimalBrainCompressor.apply"""
 
     def __init__(self, hp_gen, **kwargs):
         super().__init__(hp_gen, **kwargs)

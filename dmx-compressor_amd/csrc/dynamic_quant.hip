@@ -44,22 +44,18 @@ struct DynFmt {
 __device__ __forceinline__ uint32_t dyn_key(float f) { const uint32_t b = f2u(f); return b ^ ((uint32_t)((int32_t)b >> 31) | 0x80000000u); }
 __device__ __forceinline__ float dyn_key_inv(uint32_t k) { return u2f(k ^ ((k & 0x80000000u) ? 0x80000000u : 0xFFFFFFFFu)); }
 
-struct DynExt {
-  float lo, hi;
-  uint32_t am;   // max of the |x| bit patterns: above +Inf's pattern <=> a NaN was seen (fminf / fmaxf drop it)
-  __device__ __forceinline__ void init() { lo = INFINITY; hi = -INFINITY; am = 0u; }
+struct DynExt : FloatExtrema {   // (reduce_common.hpp: the float accumulation and the NaN rule, shared with GPTQ's group scan)
   template <int DT, int V>
   __device__ __forceinline__ void add(const u32x4& raw) {
     float x[V];
     widen<DT, V>(raw, x);
 #pragma unroll
-    for (int k = 0; k < V; k++) { lo = fminf(lo, x[k]); hi = fmaxf(hi, x[k]); am = max(am, f2u(x[k]) & 0x7FFFFFFFu); }
+    for (int k = 0; k < V; k++) FloatExtrema::add(x[k]);
   }
   // -> keys; a NaN anywhere: (-NaN, +NaN), which win every min / max of the combine
   __device__ __forceinline__ void keys(uint32_t& klo, uint32_t& khi) const {
-    const bool nan = am > 0x7F800000u;
-    klo = nan ? dyn_key(u2f(0xFFC00000u)) : dyn_key(lo);
-    khi = nan ? dyn_key(u2f(0x7FC00000u)) : dyn_key(hi);
+    klo = dyn_key(mn());
+    khi = dyn_key(mx());
   }
 };
 

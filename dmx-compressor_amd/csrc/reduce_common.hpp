@@ -1,6 +1,8 @@
 // csrc/reduce_common.hpp -- pieces of the calibration reductions shared by csrc/reduce.hip (dmxq_group_minmax, dmxq_histc) and
 // csrc/hist_observer.hip (the device HistogramObserver): raw 16-byte loads widened to fp32, and torch.histc's bin rule.
 #pragma once
+#include <math.h>
+
 #include "common.hpp"
 
 namespace dmxq {
@@ -50,6 +52,20 @@ __device__ __forceinline__ void hist_add(uint32_t* s, float v, float lo, float h
     atomicAdd(&s[pos], 1u);
   }
 }
+
+// Running minimum and maximum of float VALUES with dmxq_group_minmax's NaN rule, for the kernels that derive a segment's scale themselves
+// (csrc/dynamic_quant.hip, csrc/gptq_cols.hpp): fminf / fmaxf drop a NaN operand, so a NaN is noticed on the |x| bit patterns instead
+// (above +Inf's pattern <=> a NaN was seen) and makes BOTH extrema NaN (torch.amin / amax propagate it; reduce.hip nan_to_both), which
+// qparams_one's fminf / fmaxf then drop in turn.
+struct FloatExtrema {
+  float lo, hi;
+  uint32_t am;   // max of the |x| bit patterns
+  __device__ __forceinline__ void init() { lo = INFINITY; hi = -INFINITY; am = 0u; }
+  __device__ __forceinline__ void add(float x) { lo = fminf(lo, x); hi = fmaxf(hi, x); am = max(am, f2u(x) & 0x7FFFFFFFu); }
+  __device__ __forceinline__ bool nan() const { return am > 0x7F800000u; }
+  __device__ __forceinline__ float mn() const { return nan() ? u2f(0xFFC00000u) : lo; }   // (-NaN, +NaN): they win every later min / max
+  __device__ __forceinline__ float mx() const { return nan() ? u2f(0x7FC00000u) : hi; }
+};
 
 // (min, max) -> (scale, zero_point) of one group (numerical/observer.py:59-115 _calculate_qparams): dmxq_qparams and the
 // HistogramObserver's search kernel (csrc/hist_observer.hip)

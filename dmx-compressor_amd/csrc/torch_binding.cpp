@@ -855,6 +855,37 @@ void gptq_block(const Tensor& w, const Tensor& hinv, const Tensor& inv_d, int64_
 }
 void gptq_block_meta(const Tensor&, const Tensor&, const Tensor&, int64_t, at::IntArrayRef, const OptTensor&, const OptTensor&, Tensor, Tensor) {}
 
+// the same block with dynamic per-group integer scales (dmxq_gptq_block_dynamic): scale_out / zp_out [rows, count / group] are written in
+// place as well (views of the caller's [rows, ncols / group] tensors)
+void gptq_block_dynamic(const Tensor& w, const Tensor& hinv, const Tensor& inv_d, int64_t microblock, at::IntArrayRef fmt, int64_t rounding,
+                        int64_t group, int64_t qmin, int64_t qmax, bool symmetric_qscheme, Tensor q, Tensor err, Tensor scale_out, Tensor zp_out) {
+  TORCH_CHECK(w.is_cuda(), "gptq_block_dynamic: tensor is on ", w.device(), "; dmx_compressor_amd runs on MI355X (HIP) tensors only and has no CPU fallback");
+  gptq_matrix(w, w, "w"); gptq_matrix(hinv, w, "hinv"); gptq_matrix(q, w, "q"); gptq_matrix(err, w, "err"); gptq_matrix(scale_out, w, "scale_out");
+  TORCH_CHECK(fmt.size() == 12, "gptq_block_dynamic: fmt is the 12 fields of dmxq_gptq_format");
+  TORCH_CHECK(microblock >= 1 && group >= 1, "gptq_block_dynamic: microblock and group must be positive");
+  const int64_t rows = w.size(0), count = w.size(1), nmb = (count + microblock - 1) / microblock, ng = count / group;
+  TORCH_CHECK(q.size(0) == rows && q.size(1) == count && err.size(0) == rows && err.size(1) == count && hinv.size(0) == count &&
+              hinv.size(1) == count, "gptq_block_dynamic: w, q, err must be [rows, count] and hinv [count, count]");
+  TORCH_CHECK(inv_d.is_cuda() && inv_d.device() == w.device() && inv_d.scalar_type() == at::kFloat && inv_d.is_contiguous() &&
+              inv_d.numel() == nmb * microblock * microblock, "gptq_block_dynamic: inv_d must be a contiguous float32 [", nmb, ", ", microblock,
+              ", ", microblock, "] tensor on w's GPU");
+  TORCH_CHECK(zp_out.is_cuda() && zp_out.device() == w.device() && zp_out.scalar_type() == at::kLong && zp_out.dim() == 2 &&
+              (zp_out.size(1) <= 1 || zp_out.stride(1) == 1), "gptq_block_dynamic: zp_out must be an int64 matrix with unit column stride on w's GPU");
+  TORCH_CHECK(scale_out.size(0) == rows && scale_out.size(1) == ng && zp_out.size(0) == rows && zp_out.size(1) == ng,
+              "gptq_block_dynamic: scale_out and zp_out must be [rows, count / group] = [", rows, ", ", ng, "]");
+  const dmxq_gptq_format f{(int)fmt[0], (int)fmt[1], (int)fmt[2], (int)fmt[3], (int)fmt[4], (int)fmt[5], (int)fmt[6], (int)fmt[7],
+                           (int)fmt[8], (int)fmt[9], (int)fmt[10], (int)fmt[11]};
+  auto ld = [](const Tensor& t, int64_t n) { return t.size(0) <= 1 ? std::max<int64_t>(t.stride(0), n) : t.stride(0); };
+  Launch l(w);
+  check(dmxq_gptq_block_dynamic((const float*)w.data_ptr(), ld(w, count), (float*)q.data_ptr(), ld(q, count), (float*)err.data_ptr(), ld(err, count),
+                                rows, count, (const float*)hinv.data_ptr(), ld(hinv, count), (const float*)inv_d.data_ptr(), microblock, &f,
+                                (int)rounding, group, (int)qmin, (int)qmax, symmetric_qscheme ? 1 : 0, (float*)scale_out.data_ptr(),
+                                ld(scale_out, ng), (int64_t*)zp_out.data_ptr(), ld(zp_out, ng), l.stream),
+        "dmxq_gptq_block_dynamic");
+}
+void gptq_block_dynamic_meta(const Tensor&, const Tensor&, const Tensor&, int64_t, at::IntArrayRef, int64_t, int64_t, int64_t, int64_t, bool, Tensor,
+                             Tensor, Tensor, Tensor) {}
+
 // ------------------------------------------------------------------------------------------------ HistogramObserver
 // one observation of G groups (dmxq_hist_observe): hist [G, bins], min_val / max_val [G], status [1] (int32) are the observer's state,
 // updated in place; scratch: (2 + bins) * G words of any contiguous device tensor
@@ -1054,6 +1085,7 @@ TORCH_LIBRARY(dmxq, m) {
   m.def("lut16_apply(Tensor x, Tensor table) -> Tensor");
   m.def("norm_cast(Tensor x, int cols, Tensor? weight, Tensor? bias, float eps, int kind, int[] cast_in, int[] cast_out, int bfp_block=0, int bfp_precision=0) -> Tensor");
   m.def("gptq_block(Tensor w, Tensor hinv, Tensor inv_d, int microblock, int[] fmt, Tensor? scale, Tensor? zero_point, Tensor(a!) q, Tensor(b!) err) -> ()");
+  m.def("gptq_block_dynamic(Tensor w, Tensor hinv, Tensor inv_d, int microblock, int[] fmt, int rounding, int group, int qmin, int qmax, bool symmetric_qscheme, Tensor(a!) q, Tensor(b!) err, Tensor(c!) scale_out, Tensor(d!) zp_out) -> ()");
   m.def("hist_observe(Tensor x, int ch_axis, int group_size, int upsample_rate, Tensor(a!) hist, Tensor(b!) min_val, Tensor(c!) max_val, Tensor(d!) status, Tensor(e!) scratch) -> ()");
   m.def("hist_qparams(Tensor hist, Tensor min_val, Tensor max_val, int precision, int qmin, int qmax, bool symmetric_qscheme) -> (Tensor, Tensor)");
   m.def("error_stats(Tensor ref, Tensor test, bool accumulate, Tensor(a!) stats, Tensor(b!) scratch) -> ()");
@@ -1069,7 +1101,7 @@ TORCH_LIBRARY(dmxq, m) {
   X(m, float_qdq); X(m, float_qdq_multi); X(m, fixed_qdq); X(m, fixed_qdq_multi); X(m, fixed_float_qdq_multi); X(m, nm_mask); X(m, topk_mask); X(m, bernoulli_mask); X(m, group_minmax); X(m, qparams); \
   X(m, histc); X(m, channel_maxabs); X(m, smoothquant_scale); X(m, scale_channels); X(m, unary); X(m, rope); X(m, rope_cast); X(m, softmax); X(m, norm); \
   X(m, unary_cast); X(m, unary_cast_table); X(m, lut16_apply); X(m, softmax_cast); X(m, norm_cast); X(m, group_minmax_accumulate); X(m, gptq_block); X(m, hist_observe); X(m, hist_qparams); \
-  X(m, error_stats); X(m, cast_error); X(m, hadamard_qdq); X(m, dynamic_fixed_qdq)
+  X(m, error_stats); X(m, cast_error); X(m, hadamard_qdq); X(m, dynamic_fixed_qdq); X(m, gptq_block_dynamic)
 
 // "CUDA" is the dispatch key of HIP tensors in a ROCm build of PyTorch
 TORCH_LIBRARY_IMPL(dmxq, CUDA, m) {

@@ -5,6 +5,14 @@
 column loop is ONE launch of csrc/gptq.hip per block when the weight cast is a format that kernel covers (ops.gptq_block), the
 trailing update W[:, i2:] -= E @ Hinv[i1:i2, i2:] a GEMM; any other format runs the reference-shaped loop (the module's own
 `weight_hypernet` on each slice, torch linear algebra) on the GPU.
+
+Not in the reference ("GPTQ with dynamic scales and activation order"):
+  * a DYNAMIC integer weight cast (`weight_dynamic`): per_group g takes the scale of every group of g input columns inside the column
+    loop, from the row's current, already error-compensated values -- one csrc/gptq_dynamic.hip launch per block
+    (ops.gptq_block_dynamic), or the torch loop `_loop_dynamic` with the same definition; per_token / per_tensor take their scale once
+    from W and run the static kernel.  apply() then records the scales in `module.gptq_qparams` and switches the weight cast's
+    fake quantisation off (see apply);
+  * `act_order`: the columns are visited in order of decreasing diag(H).
 """
 import math
 
@@ -62,6 +70,54 @@ class OptimalBrainCompressor:
             raise DmxqError("GPTQ with SmoothQuant enabled and not fused to the weight is not supported (the reference's slices do not "
                             "broadcast against its scale)")
 
+    def _dynamic_plan(self, block_size):
+        """None when the weight cast casts with stored scales (or not at all); (granularity, group_size) for a dynamic integer weight
+        cast, after the checks of what GPTQ supports with one.  No GPU involved, nothing modified."""
+        from .format import FixedPoint, Same
+        m = self.module
+        wc = m.weight_cast
+        if wc is None or wc._dynamic is None or not isinstance(wc.format, FixedPoint):
+            return None
+        if not wc._flag("fake_quant_enabled") or wc._flag("observer_enabled"):
+            return None   # (the cast does not run dynamically in this state: cast.py _quantize)
+        gran, g = wc._dynamic
+        if not isinstance(m, torch.nn.Linear) or m.weight.dim() != 2:
+            raise DmxqError(f"GPTQ with a dynamic weight cast ({wc.dynamic!r}) supports Linear modules with a 2-D weight only: on a "
+                            f"{type(m).__name__} weight of shape {tuple(m.weight.shape)} the segments of the cast are not runs of GPTQ's columns")
+        if wc.pre_transform:
+            raise DmxqError(f"GPTQ with a dynamic weight cast ({wc.dynamic!r}) and a pre_transform {sorted(wc.pre_transform)} is not supported")
+        st = m.weight_storage_cast
+        if st is not None and not (isinstance(st.format, Same) and not st.pre_transform):
+            raise DmxqError(f"GPTQ with a dynamic weight cast ({wc.dynamic!r}) needs a weight_storage_cast of SAME")
+        if wc.format.rounding != "nearest":
+            raise DmxqError(f"GPTQ with a dynamic weight cast ({wc.dynamic!r}) needs nearest rounding, got {wc.format!r}")
+        if gran == "per_group":
+            ncols = m.weight.shape[1]
+            if ncols % g != 0 or block_size % g != 0:
+                raise ValueError(f"GPTQ with weight_dynamic per_group {g}: the group size must divide the {ncols} input columns and the "
+                                 f"block size {block_size} (groups do not straddle column blocks)")
+        return gran, g
+
+    def _check_act_order(self, act_order):
+        """activation order permutes the columns: allowed where the cast of a column depends on per-row or per-tensor parameters only"""
+        from .format import FixedPoint
+        if not isinstance(act_order, bool):
+            raise TypeError(f"act_order must be a bool, got {act_order!r}")
+        if not act_order:
+            return
+        wc = self.module.weight_cast
+        if wc.pre_transform:
+            raise DmxqError(f"GPTQ with act_order and a weight cast pre_transform {sorted(wc.pre_transform)} is not supported: a rotation or a "
+                            "shaping of the slice mixes neighbouring input columns, which the permutation tears apart")
+        if getattr(wc.format, "blocked", False):
+            raise DmxqError(f"GPTQ with act_order and the blocked weight format {wc.format!r} is not supported: its blocks are runs of "
+                            "neighbouring input columns, which the permutation tears apart")
+        if isinstance(wc.format, FixedPoint) and (wc._dynamic is None or wc._flag("observer_enabled")):
+            if wc.group_size:
+                raise DmxqError("GPTQ with act_order and static group scales is not supported (the scales would have to follow the columns)")
+            if wc.is_per_channel and wc.ch_axis % 2 != 0:
+                raise DmxqError("GPTQ with act_order and per-input-channel scales is not supported (the scales would have to follow the columns)")
+
     def _fused_fields(self):
         """dmxq_gptq_format fields when the kernel reproduces this module's weight cast of a slice, else None"""
         from . import ops
@@ -88,8 +144,26 @@ class OptimalBrainCompressor:
             return None
         return ops.gptq_fields(wc.format, per_row)
 
-    def apply(self, microblock_size=1, block_size=128, percdamp=0.01):
+    def apply(self, microblock_size=1, block_size=128, percdamp=0.01, act_order=False):
+        """GPTQ of the module's weight, in place.  act_order (not in the reference): after the dead-column fix and before damping the
+        columns of W and the rows and columns of H are permuted by perm = argsort(diag(H), descending, stable), everything runs on the
+        permuted problem and Q is un-permuted at the end; DmxqError for a blocked format (BFP, MXINT, MXFP, SBFP), for static group
+        or per-input-channel scales, whose parameters belong to runs of neighbouring columns, and for a weight cast with a pre_transform.
+
+        A DYNAMIC integer weight cast (weight_dynamic; Linear only, nearest rounding, no pre_transform, storage cast SAME -- DmxqError
+        otherwise): per_group g (it divides the column count and block_size, ValueError otherwise) derives each group's scale inside
+        the column loop from the row's current values (ops.gptq_block_dynamic per block where g is 16 / 32 / 64 / 128 and a multiple of
+        the microblock, `_loop_dynamic` otherwise and with fuse_gptq = False); per_token / per_tensor take theirs once from W after
+        the dead columns are zeroed.  SIDE EFFECT for such a cast, and the reason: a dynamic cast is not idempotent on Q -- a group's
+        extrema move after its scale was fixed, so re-deriving the scale from Q on the next forward would put Q on ANOTHER grid.
+        Therefore apply() (1) records
+            module.gptq_qparams = {"scale": float32 [rows, G], "zero_point": int64 [rows, G], "group_size": g or None, "perm": perm or None}
+        (G = columns / g groups in PROCESSING order, i.e. groups of permuted columns under act_order; G = 1 and group_size None for
+        per_token / per_tensor; a plain attribute, no state_dict key), and (2) switches the weight cast's fake_quant_enabled flag OFF, so
+        that forwards use Q as written.  Static casts behave as before: nothing recorded, no switch touched."""
         self._check(microblock_size, block_size)
+        self._check_act_order(act_order)
+        dyn = self._dynamic_plan(block_size)
         m = self.module
         weight = m.weight
         W = weight.data.clone()
@@ -102,6 +176,11 @@ class OptimalBrainCompressor:
         dead = torch.diag(H) == 0
         H[dead, dead] = 1
         W[:, dead] = 0
+        perm = None
+        if act_order:
+            perm = torch.argsort(torch.diag(H), descending=True, stable=True)
+            W = W[:, perm].contiguous()
+            H = H[perm][:, perm].contiguous()
         Q = torch.zeros_like(W)
         damp = percdamp * torch.mean(torch.diag(H))
         diag = torch.arange(ncols, device=H.device)
@@ -110,15 +189,25 @@ class OptimalBrainCompressor:
         H = torch.cholesky_inverse(H)
         Hinv = torch.linalg.cholesky(H, upper=True).contiguous()   # (LAPACK hands back column-major strides; the kernel reads rows)
 
-        fields = self._fused_fields() if block_size <= 128 else None
-        if fields is not None:
-            done = self._fused(W, Q, Hinv, microblock_size, block_size, fields)
-            if not done:
-                fields = None
-        if fields is None:
-            self._loop(W, Q, Hinv, microblock_size, block_size)
+        qparams = None
+        if dyn is not None:
+            qparams = self._dynamic(W, Q, Hinv, microblock_size, block_size, *dyn)
+        else:
+            fields = self._fused_fields() if block_size <= 128 else None
+            if fields is not None:
+                done = self._fused(W, Q, Hinv, microblock_size, block_size, fields)
+                if not done:
+                    fields = None
+            if fields is None:
+                self._loop(W, Q, Hinv, microblock_size, block_size)
+        if perm is not None:
+            Qp, Q = Q, torch.empty_like(Q)
+            Q[:, perm] = Qp
         with torch.no_grad():
             weight.copy_(Q.reshape(weight.shape).to(weight.dtype))
+        if qparams is not None:
+            m.gptq_qparams = {"scale": qparams[0], "zero_point": qparams[1], "group_size": dyn[1], "perm": perm}
+            m.weight_cast.disable_fake_quant()
 
     @staticmethod
     def _inv_diag(Hinv, mb):
@@ -138,11 +227,11 @@ class OptimalBrainCompressor:
         blocks = P.view(nmb, mb, nmb, mb).diagonal(dim1=0, dim2=2).permute(2, 0, 1)   # [nmb, mb, mb]: the diagonal microblocks
         return torch.linalg.inv(blocks).contiguous()
 
-    def _fused(self, W, Q, Hinv, mb, block_size, fields):
+    def _fused(self, W, Q, Hinv, mb, block_size, fields, sc=None, zp=None):
+        """sc / zp: the scales of a FIXED cast when they are not the weight cast's buffers (a dynamic per_token / per_tensor cast)"""
         from . import ops
         wc = self.module.weight_cast
-        sc = zp = None
-        if fields[0] == 2:
+        if fields[0] == 2 and sc is None:
             sc = wc.scale.detach().float().contiguous()
             zp = wc.zero_point.detach().to(torch.int64).contiguous()
         ncols = W.shape[1]
@@ -184,3 +273,127 @@ class OptimalBrainCompressor:
                 _E[:, j1:j2] = err
             Q[:, i1:i2] = _Q
             W[:, i2:] -= _E.matmul(Hinv[i1:i2, i2:])
+
+    # ------------------------------------------------------------------------------------------------ dynamic integer weight casts
+    @staticmethod
+    def _segment_qparams(x2, qmin, qmax, sym):
+        """(scale float32 [n], zero point int64 [n]) of the rows of the contiguous [n, S] tensor: ops.group_minmax -> ops.qparams, the two
+        steps that define the dynamic cast (ops.dynamic_fixed_qdq), in pieces of what one group_minmax call takes"""
+        from . import ops
+        from ._front import DYNAMIC_CHAIN_PIECE as piece
+        out = []
+        for i in range(0, x2.shape[0], piece):
+            mn, mx = ops.group_minmax(x2[i:i + piece], 0, 1)
+            out.append(ops.qparams(mn, mx, qmin, qmax, sym))
+        if len(out) == 1:
+            return out[0]
+        return torch.cat([o[0] for o in out]), torch.cat([o[1] for o in out])
+
+    def _dynamic(self, W, Q, Hinv, mb, block_size, gran, g):
+        """the column loop for a dynamic integer weight cast -> (scale [rows, G], zero_point [rows, G]) in processing order"""
+        from . import ops
+        from .observer import _SYMMETRIC, get_qmin_qmax
+        m = self.module
+        wc = m.weight_cast
+        fmt = wc.format
+        qmin, qmax = get_qmin_qmax(fmt)
+        sym = wc.qscheme in _SYMMETRIC
+        rows, ncols = W.shape
+        fuse = getattr(m, "fuse_gptq", True) and block_size <= 128
+        if gran != "per_group":
+            # one scale per output channel (a weight row is a "token") or for the tensor, taken ONCE from W as GPTQ sees it; the static
+            # kernel does the rest
+            per_row = gran == "per_token"
+            sc, zp = self._segment_qparams(W if per_row else W.reshape(1, -1), qmin, qmax, sym)
+            done = False
+            if fuse:
+                fields = ops.gptq_fields(fmt, per_row)
+                done = fields is not None and self._fused(W, Q, Hinv, mb, block_size, fields, sc, zp)
+            if not done:
+                self._loop_dynamic(W, Q, Hinv, mb, block_size, None, sc, zp, per_row, qmin, qmax, sym)
+            return sc.reshape(-1, 1).expand(rows, 1).contiguous(), zp.reshape(-1, 1).expand(rows, 1).contiguous()
+        scale = torch.empty(rows, ncols // g, dtype=torch.float32, device=W.device)
+        zp = torch.empty(rows, ncols // g, dtype=torch.int64, device=W.device)
+        done = False
+        if fuse and g % mb == 0 and g in (16, 32, 64, 128):
+            done = self._fused_dynamic(W, Q, Hinv, mb, block_size, g, scale, zp, sym)
+        if not done:
+            self._loop_dynamic(W, Q, Hinv, mb, block_size, g, scale, zp, True, qmin, qmax, sym)
+        return scale, zp
+
+    def _fused_dynamic(self, W, Q, Hinv, mb, block_size, g, scale, zp, sym):
+        """one ops.gptq_block_dynamic launch per column block; the trailing GEMM as in _fused"""
+        from . import ops
+        fmt = self.module.weight_cast.format
+        ncols = W.shape[1]
+        invd = self._inv_diag(Hinv, mb)
+        E = torch.empty(W.shape[0], min(block_size, ncols), dtype=torch.float32, device=W.device)
+        for i1 in range(0, ncols, block_size):
+            i2 = min(i1 + block_size, ncols)
+            e = E[:, :i2 - i1]
+            d = invd[i1:i2] if mb == 1 else invd[i1 // mb:-(-i2 // mb)]
+            try:
+                ops.gptq_block_dynamic(W[:, i1:i2], Hinv[i1:i2, i1:i2], d, Q[:, i1:i2], e, scale[:, i1 // g:i2 // g], zp[:, i1 // g:i2 // g],
+                                       mb, g, fmt, sym)
+            except NotImplementedError:
+                if i1 == 0:
+                    return False   # (a microblock / format the kernel does not take: nothing done yet, the loop runs instead)
+                raise
+            if i2 < ncols:
+                W[:, i2:].addmm_(e, Hinv[i1:i2, i2:], alpha=-1)
+        return True
+
+    def _loop_dynamic(self, W, Q, Hinv, mb, block_size, g, scale, zp, per_row, qmin, qmax, sym):
+        """The column loop for a dynamic integer weight cast in torch: the A/B partner of the fused kernels and the route for what they
+        do not take.  Same definition AND same arithmetic order as the kernels (csrc/gptq.hip: every product and difference its own
+        elementwise op, sums in index order from the first product; the diagonal microblocks inverted by `_inv_diag`; the trailing
+        update the same addmm_), so that the two routes derive the same group scales: a scale follows its group's extremum to the last
+        bit, and one bit of it moves every element of the group.
+        g None: `scale` / `zp` are given ([rows] when per_row, else [1]) and every slice is cast with them.  g: at the start of each
+        microblock, every group of g columns that STARTS inside it takes (scale, zp) = qparams(group_minmax(W[:, j:j + g])) of the
+        current values, written to scale[:, j // g] / zp[:, j // g]; a column is cast with its group's pair (a microblock wider than a
+        group is cast group by group, all with scales from the microblock's start)."""
+        from . import ops
+        fmt = self.module.weight_cast.format
+        ncols = W.shape[1]
+        invd = self._inv_diag(Hinv, mb)
+
+        def cast(w, sc, z):
+            return ops.fixed_qdq(w.contiguous(), fmt.precision, fmt.fraction, fmt.clamp, fmt.symmetric, fmt.rounding, scale=sc, zero_point=z,
+                                 ch_axis=0 if per_row else None)
+
+        for i1 in range(0, ncols, block_size):
+            i2 = min(i1 + block_size, ncols)
+            count = i2 - i1
+            _W = W[:, i1:i2].clone()
+            _E = torch.empty_like(_W)
+            _Hinv = Hinv[i1:i2, i1:i2]
+            for j1 in range(0, count, mb):
+                j2 = min(j1 + mb, count)
+                n = j2 - j1
+                w = _W[:, j1:j2]
+                if g is None:
+                    q = cast(w, scale, zp)
+                else:   # (block_size % g == 0: a group never straddles a block, and i1 is a group start)
+                    for s in range(-(-j1 // g) * g, j2, g):
+                        sc, z = self._segment_qparams(_W[:, s:s + g].contiguous(), qmin, qmax, sym)
+                        scale[:, (i1 + s) // g], zp[:, (i1 + s) // g] = sc, z
+                    q = torch.empty_like(w)
+                    for s in range(j1 // g * g, j2, g):   # the pieces of the microblock, one per group it touches
+                        a, b = max(s, j1), min(s + g, j2)
+                        k = (i1 + s) // g
+                        q[:, a - j1:b - j1] = cast(_W[:, a:b], scale[:, k].contiguous(), zp[:, k].contiguous())
+                d = w - q
+                D = invd[i1 + j1].reshape(1, 1) if mb == 1 else invd[(i1 + j1) // mb]
+                err = d[:, 0:1] * D[0, :n]
+                for i in range(1, n):
+                    err = err + d[:, i:i + 1] * D[i, :n]
+                Q[:, i1 + j1:i1 + j2] = q
+                _E[:, j1:j2] = err
+                if j2 < count:
+                    acc = err[:, 0:1] * _Hinv[j1, j2:]
+                    for i in range(1, n):
+                        acc = acc + err[:, i:i + 1] * _Hinv[j1 + i, j2:]
+                    _W[:, j2:] -= acc
+            if i2 < ncols:
+                W[:, i2:].addmm_(_E, Hinv[i1:i2, i2:], alpha=-1)

@@ -77,10 +77,12 @@ class DmxModuleSmoothQuantHyperparams:
 
 @dataclass
 class DmxModuleGPTQHyperparams:
-    """advanced_recipe.py:76-85"""
+    """advanced_recipe.py:76-85; act_order (not in the reference): visit the columns in order of decreasing Hessian diagonal
+    (OptimalBrainCompressor.apply)"""
     microblock_size: int = 1
     block_size: int = 128
     percdamp: float = 0.01
+    act_order: bool = False
 
 
 def _shares_storage(a, b) -> bool:

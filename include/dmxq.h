@@ -54,7 +54,7 @@ typedef enum {
 
 const char* dmxq_status_string(int status);
 /* ABI version: bumped on any signature change.  Additions since 4 (dmxq_gptq_block, dmxq_hist_observe, dmxq_hist_qparams, dmxq_error_stats, dmxq_cast_error,
- * dmxq_error_scratch_bytes, dmxq_hadamard_qdq, dmxq_dynamic_fixed_qdq, dmxq_dynamic_class) leave it at 4: a caller built against 4 runs on
+ * dmxq_error_scratch_bytes, dmxq_hadamard_qdq, dmxq_dynamic_fixed_qdq, dmxq_dynamic_class, dmxq_gptq_block_dynamic) leave it at 4: a caller built against 4 runs on
  * this library unchanged.  4 = round 5: + dmxq_float_qdq_multi, dmxq_fixed_float_qdq_multi; 3 = round 4: + dmxq_weight_hypernet_multi,
  * dmxq_unary_cast_table, dmxq_lut16_apply.  Nothing was ever removed or changed: a caller built against version n runs on any library >= n. */
 int dmxq_abi_version(void);
@@ -430,6 +430,30 @@ typedef struct {
 int dmxq_gptq_block(const float* w, int64_t ldw, float* q, int64_t ldq, float* err, int64_t lde, int64_t rows, int64_t count,
                     const float* hinv, int64_t ldh, const float* inv_d, int64_t microblock, const dmxq_gptq_format* fmt,
                     const float* scale, const int64_t* zero_point, void* stream);
+
+/* dmxq_gptq_block with DYNAMIC per-group integer scales (csrc/gptq_dynamic.hip): the scale of a group of `group` input
+ * columns is found while the column loop runs, from the row's current, already error-compensated values.  Not in the reference, whose
+ * group quantisation groups output channels and whose GPTQ reads scales that a calibration run fixed.
+ * Arguments as dmxq_gptq_block's with fmt->kind == DMXQ_GPTQ_FIXED (per_row is ignored: every row has its own scales), plus the
+ * format's rounding, and qmin / qmax / symmetric_qscheme as dmxq_qparams takes them.  Per row, with w the row's block as the loop
+ * updates it:
+ *   at every column j with j % group == 0, before the microblock that starts there is cast:
+ *     (mn, mx)  dmxq_group_minmax of the float32 values w[j .. j + group) as they stand at that moment (the updates of all earlier
+ *               microblocks and -- through the caller's trailing updates -- earlier blocks included; one NaN makes both NaN);
+ *     (sc, zp)  dmxq_qparams(mn, mx, qmin, qmax, symmetric_qscheme), in its float32 operations;
+ *     scale_out[row * lds + j / group] = sc, zp_out[row * ldz + j / group] = zp  (DEVICE arrays [rows, count / group]);
+ *   every column of the group is cast with that (sc, zp) exactly as DMXQ_GPTQ_FIXED casts with a per-row scale:
+ *   (cast(w / sc + zp) - zp) * sc with IEEE division and nearest rounding.
+ * Everything else -- the inv_d products, the update of the later columns, q and err -- is dmxq_gptq_block's, in its order.
+ * DMXQ_ERR_UNSUPPORTED, nothing launched (the caller runs its own loop): group not in {16, 32, 64, 128}; count % group != 0 or
+ * group % microblock != 0 (a microblock never straddles a group; microblock == group is allowed); count > 128; microblock not in
+ * {1, 8, 16, 32, 64}; rounding other than nearest; fraction != 0; no clamp; precision outside 1 .. 22.
+ * DMXQ_ERR_BAD_ARG: dmxq_gptq_block's rules, a kind other than DMXQ_GPTQ_FIXED, an invalid rounding, group < 1, qmax <= qmin, null
+ * scale_out / zp_out, lds or ldz below count / group.  No workspace, no allocation, no host synchronisation: capturable. */
+int dmxq_gptq_block_dynamic(const float* w, int64_t ldw, float* q, int64_t ldq, float* err, int64_t lde, int64_t rows, int64_t count,
+                            const float* hinv, int64_t ldh, const float* inv_d, int64_t microblock, const dmxq_gptq_format* fmt,
+                            int rounding, int64_t group, int qmin, int qmax, int symmetric_qscheme, float* scale_out, int64_t lds,
+                            int64_t* zp_out, int64_t ldz, void* stream);
 
 /* HistogramObserver on the device, for G = ceil(C / group_size) groups at once (slabs of group_size channels of the [outer, C, inner]
  * view, as dmxq_group_minmax; per tensor: outer = C = 1, inner = n, group_size = 1).  csrc/hist_observer.hip; DESIGN.md §3.

@@ -1,0 +1,179 @@
+"""GPTQ with dynamic per-group integer scales and activation order, without a GPU: the CPU restatement (tests/_gptq_group_ref.py) against
+the checkers it must agree with, the C ABI's argument checks of dmxq_gptq_block_dynamic (null stream, nothing launched), and the
+argument checks of OptimalBrainCompressor.apply that run before any GPU work."""
+import ctypes
+
+import pytest
+import torch
+
+from _data import bits_equal
+from _dynamic_ref import dynamic_ref
+from _gptq_group_ref import act_perm, apply_ref_dynamic, block_fp32_dynamic
+from _gptq_ref import block_fp32, inv_diag
+
+
+def _hinv(count, seed):
+    g = torch.Generator().manual_seed(seed)
+    X = torch.randn(4 * count, count, generator=g)
+    H = 2.0 / X.shape[0] * (X.t() @ X)
+    H += 0.01 * torch.mean(torch.diag(H)) * torch.eye(count)
+    return torch.linalg.cholesky(torch.cholesky_inverse(torch.linalg.cholesky(H)), upper=True).contiguous()
+
+
+@pytest.mark.parametrize("mb,precision,fsym,qsym", [(16, 4, True, True), (32, 3, False, False), (8, 8, True, False)])
+def test_microblock_equal_to_group_is_the_dynamic_cast_of_each_slice(oracle, mb, precision, fsym, qsym):
+    """mb == g: every microblock is one group whose scale comes from the slice being cast, i.e. block_fp32 with the slice's dynamic cast"""
+    gen = torch.Generator().manual_seed(mb)
+    W = torch.randn(20, 4 * mb, generator=gen) * 0.05
+    hinv = _hinv(4 * mb, seed=3)
+    invd = inv_diag(hinv, mb)
+    Q, E, sc, zp = block_fp32_dynamic(W, hinv, invd, mb, mb, precision, fsym, qsym, oracle)
+    Qr, Er = block_fp32(W, hinv, invd, mb, lambda x: dynamic_ref(oracle, x, precision, fsym, mb, qsym)[0])
+    assert bits_equal(Q, Qr) == 0 and bits_equal(E, Er) == 0
+    assert sc.shape == zp.shape == (20, 4) and zp.dtype == torch.int64
+    qmin, qmax = -(2 ** (precision - 1)) + (1 if fsym else 0), 2 ** (precision - 1) - 1
+    assert (zp == 0).all() if qsym else bool(((zp >= qmin) & (zp <= qmax)).all())
+    assert (sc > 0).all()
+
+
+@pytest.mark.parametrize("mb,g,qsym", [(1, 32, True), (8, 16, False), (16, 64, True)])
+def test_diagonal_hinv_is_the_dynamic_cast_of_the_block(oracle, mb, g, qsym):
+    """a diagonal Hinv updates nothing: Q is the per-group dynamic cast of the whole block, scales included, and E = (W - Q) / diag"""
+    gen = torch.Generator().manual_seed(g)
+    W = torch.randn(9, 128, generator=gen) * 0.1
+    d = torch.rand(128, generator=gen) + 0.5
+    hinv = torch.diag(d)
+    Q, E, sc, zp = block_fp32_dynamic(W, hinv, inv_diag(hinv, mb), mb, g, 4, True, qsym, oracle)
+    y, scr, zpr = dynamic_ref(oracle, W, 4, True, g, qsym)
+    assert bits_equal(Q, y) == 0
+    assert bits_equal(sc.reshape(-1), scr) == 0 and torch.equal(zp.reshape(-1), zpr)
+    if mb == 1:
+        assert bits_equal(E, (W - Q) * (1.0 / d)) == 0
+
+
+def test_abi_status_codes(dmx):
+    """every refusal of dmxq_gptq_block_dynamic, with a null stream: nothing is launched (no GPU here)"""
+    L, lib = dmx._lib.lib(), dmx._lib
+    null, one = ctypes.c_void_p(None), ctypes.c_void_p(16)
+    fx = lib.GptqFormat(lib.GPTQ_FIXED, 4, 0, 1, 0, 0, 0, 0, 0, 0, 1, 1)
+    N = lib.ROUND_NEAREST
+
+    def call(w=one, ldw=128, q=one, ldq=128, err=one, lde=128, rows=8, count=128, hinv=one, ldh=128, inv_d=one, mb=1, fmt=fx, rounding=N,
+             group=128, qmin=-7, qmax=7, sym=1, so=one, lds=1, zo=one, ldz=1):
+        return L.dmxq_gptq_block_dynamic(w, ldw, q, ldq, err, lde, rows, count, hinv, ldh, inv_d, mb,
+                                         ctypes.byref(fmt) if fmt is not None else null, rounding, group, qmin, qmax, sym, so, lds, zo, ldz, null)
+
+    assert call(rows=0, w=null, q=null, err=null, hinv=null, inv_d=null, so=null, zo=null) == lib.OK     # nothing to do
+    assert call(count=0) == lib.OK
+    # ---- DMXQ_ERR_UNSUPPORTED: the caller runs its own loop
+    for g in (8, 24, 48, 256, 1):
+        assert call(group=g, count=g * 2 if g < 64 else 128) == lib.ERR_UNSUPPORTED, g               # group not in {16, 32, 64, 128}
+    assert call(group=64, count=96, lds=2, ldz=2) == lib.ERR_UNSUPPORTED                              # count % group
+    assert call(group=32, count=48, lds=2, ldz=2) == lib.ERR_UNSUPPORTED
+    assert call(group=16, mb=32, count=64, lds=4, ldz=4) == lib.ERR_UNSUPPORTED                       # microblock wider than a group
+    assert call(group=16, mb=64, count=64, lds=4, ldz=4) == lib.ERR_UNSUPPORTED
+    for mb in (2, 3, 4, 128):
+        assert call(mb=mb) == lib.ERR_UNSUPPORTED, mb                                                 # microblock outside {1, 8, 16, 32, 64}
+    assert call(count=256, ldw=256, ldq=256, lde=256, ldh=256, lds=2, ldz=2) == lib.ERR_UNSUPPORTED   # count > 128
+    for r in (lib.ROUND_UP, lib.ROUND_DOWN, lib.ROUND_STOCHASTIC):
+        assert call(rounding=r) == lib.ERR_UNSUPPORTED, r                                             # rounding other than nearest
+    assert call(fmt=lib.GptqFormat(lib.GPTQ_FIXED, 4, 0, 1, 0, 0, 0, 0, 0, 1, 1, 1)) == lib.ERR_UNSUPPORTED   # fraction != 0
+    assert call(fmt=lib.GptqFormat(lib.GPTQ_FIXED, 4, 0, 1, 0, 0, 0, 0, 0, 0, 0, 1)) == lib.ERR_UNSUPPORTED   # no clamp
+    assert call(fmt=lib.GptqFormat(lib.GPTQ_FIXED, 23, 0, 1, 0, 0, 0, 0, 0, 0, 1, 1)) == lib.ERR_UNSUPPORTED  # precision > 22
+    # ---- DMXQ_ERR_BAD_ARG: dmxq_gptq_block's rules ...
+    assert call(fmt=None) == lib.ERR_BAD_ARG
+    assert call(w=null) == lib.ERR_BAD_ARG and call(q=null) == lib.ERR_BAD_ARG and call(err=null) == lib.ERR_BAD_ARG
+    assert call(hinv=null) == lib.ERR_BAD_ARG and call(inv_d=null) == lib.ERR_BAD_ARG
+    assert call(ldw=64) == lib.ERR_BAD_ARG and call(ldq=64) == lib.ERR_BAD_ARG and call(lde=64) == lib.ERR_BAD_ARG and call(ldh=64) == lib.ERR_BAD_ARG
+    assert call(rows=-1) == lib.ERR_BAD_ARG and call(count=-1) == lib.ERR_BAD_ARG and call(mb=0) == lib.ERR_BAD_ARG
+    assert call(rows=1 << 37) == lib.ERR_BAD_ARG
+    # ... plus its own: only FIXED, a valid rounding, a group, an integer range, both outputs with strides that hold a row's groups
+    assert call(fmt=lib.GptqFormat(lib.GPTQ_FLOAT, 0, 0, 0, 3, 4, 7, 0, 0, 0, 0, 0)) == lib.ERR_BAD_ARG
+    assert call(fmt=lib.GptqFormat(lib.GPTQ_BFP, 8, 16, 1, 0, 0, 0, 0, 0, 0, 0, 0), mb=16) == lib.ERR_BAD_ARG
+    assert call(rounding=9) == lib.ERR_BAD_ARG and call(group=0) == lib.ERR_BAD_ARG
+    assert call(qmin=7, qmax=7) == lib.ERR_BAD_ARG and call(qmin=8, qmax=-8) == lib.ERR_BAD_ARG
+    assert call(so=null) == lib.ERR_BAD_ARG and call(zo=null) == lib.ERR_BAD_ARG
+    assert call(group=32, lds=3, ldz=4) == lib.ERR_BAD_ARG and call(group=32, lds=4, ldz=3) == lib.ERR_BAD_ARG
+    assert L.dmxq_abi_version() == 4
+
+
+def test_hyperparameter_and_recipe_carry_act_order(dmx):
+    hp = dmx.DmxModuleGPTQHyperparams()
+    assert hp.act_order is False and (hp.microblock_size, hp.block_size, hp.percdamp) == (1, 128, 0.01)
+    hp = dmx.DmxModuleGPTQHyperparams(act_order=True)
+    assert vars(hp) == dict(microblock_size=1, block_size=128, percdamp=0.01, act_order=True)
+    seen = []
+
+    class Obc:
+        def apply(self, **kw):
+            seen.append(kw)
+
+    m = dmx.nn.Linear(16, 8)
+    recipe = dmx.DmxGPTQRecipe(lambda model: {model: hp})
+    with recipe.applied_to(m):
+        m.obc = Obc()          # what leaving the context hands the hyperparameters to
+    assert seen == [vars(hp)] and m.obc is None
+
+
+def _compressor(dmx, module, config, x):
+    from dmx_compressor_amd.layer_reconstruction import OptimalBrainCompressor
+
+    module.configure(config)
+    o = OptimalBrainCompressor(module)
+    o.measure_hessian(x)
+    return o
+
+
+def test_apply_argument_checks_come_before_any_work(dmx):
+    """the refusals need no GPU (they precede every device call) and leave the weight, the Hessian and the switches alone"""
+    def refused(module, config, x, exc, match, pre=None, **kw):
+        w0 = module.weight.detach().clone()
+        o = _compressor(dmx, module, config, x)
+        if pre is not None:
+            pre(module)
+        with pytest.raises(exc, match=match):
+            o.apply(**kw)
+        assert o.H is not None and torch.equal(module.weight.detach(), w0)
+        assert not hasattr(module, "gptq_qparams") and module.weight_cast._flag("fake_quant_enabled")
+
+    x64 = torch.randn(4, 64)
+    refused(dmx.nn.Linear(64, 8), {"weight_format": "BFP[8|8]{64}(SN)"}, x64, dmx.DmxqError, "act_order", microblock_size=64, act_order=True)
+    refused(dmx.nn.Linear(64, 8), {"weight_format": "MXINT4{32}"}, x64, dmx.DmxqError, "act_order", microblock_size=32, act_order=True)
+    refused(dmx.nn.Linear(64, 8), {"weight_format": "FP[1|4|3,7](_N)"}, x64, TypeError, "act_order", act_order=1)
+
+    refused(dmx.nn.Linear(64, 8), {"weight_format": "FP[1|4|3,7](_N)"}, x64, dmx.DmxqError, "pre_transform", act_order=True,
+            pre=lambda m: m.weight_cast.set_pre_transform({"hadamard": 32}))
+
+    def static_groups(m):
+        m.weight_cast.group_size = 4
+    refused(dmx.nn.Linear(64, 8), {"weight_format": "XP[4,0](CSN)"}, x64, dmx.DmxqError, "act_order", pre=static_groups, act_order=True)
+    # a group wider than a column block; columns that are not whole groups
+    refused(dmx.nn.Linear(256, 8), {"weight_format": "XP[4,0](CSN)", "weight_dynamic": {"per_group": 256}}, torch.randn(4, 256), ValueError,
+            "group", block_size=128)
+    refused(dmx.nn.Linear(96, 8), {"weight_format": "XP[4,0](CSN)", "weight_dynamic": {"per_group": 64}}, torch.randn(4, 96), ValueError, "group")
+    refused(dmx.nn.Conv2d(4, 8, 3), {"weight_format": "XP[4,0](CSN)", "weight_dynamic": "per_token"}, torch.randn(2, 4, 6, 6), dmx.DmxqError,
+            "Conv2d")
+    refused(dmx.nn.Linear(64, 8), {"weight_format": "XP[4,0](CSN)", "weight_dynamic": {"per_group": 32}}, x64, dmx.DmxqError, "pre_transform",
+            pre=lambda m: m.weight_cast.set_pre_transform({"hadamard": 32}))
+
+
+@pytest.mark.parametrize("g", [None, 32])
+def test_permutation_round_trip_on_the_float64_restatement(oracle, g):
+    """a diagonal Hessian compensates nothing, so act_order only reorders: per_token scales do not depend on the order (Q is the
+    per-token cast of W); per-group scales are those of groups of PERMUTED columns, and Q comes back in the original order"""
+    gen = torch.Generator().manual_seed(7)
+    W = torch.randn(12, 64, generator=gen) * 0.1
+    H = torch.diag(torch.rand(64, generator=gen) + 0.1).double()
+    Q, sc, zp, perm = apply_ref_dynamic(W, H, 1, 64, g, 4, True, True, oracle, torch.float64, act_order=True)
+    assert torch.equal(perm, act_perm(H)) and not torch.equal(perm, torch.arange(64))
+    assert sorted(perm.tolist()) == list(range(64))
+    if g is None:
+        y, scr, _ = dynamic_ref(oracle, W, 4, True, 64, True)
+        assert bits_equal(Q.float(), y) == 0 and bits_equal(sc.reshape(-1), scr) == 0
+    else:
+        y, scr, _ = dynamic_ref(oracle, W[:, perm].contiguous(), 4, True, g, True)
+        assert bits_equal(Q.float()[:, perm].contiguous(), y) == 0 and bits_equal(sc.reshape(-1), scr) == 0
+        y0, _, _ = dynamic_ref(oracle, W, 4, True, g, True)
+        assert bits_equal(Q.float(), y0) != 0                          # (not the cast of the unpermuted groups)
+    Q0, _, _, p0 = apply_ref_dynamic(W, H, 1, 64, g, 4, True, True, oracle, torch.float64, act_order=False)
+    assert p0 is None and Q0.shape == Q.shape
