@@ -654,6 +654,13 @@ def norm_cast(x, cols, weight, bias, eps, kind, cast_in, cast_out, bfp_block=0, 
 
 
 # ------------------------------------------------------------------------------------------------ GPTQ
+def _gptq_format(fmt, what):
+    """the 12 fields of a dmxq_gptq_format in the struct's order: one format, or one format's slice of a list"""
+    if len(fmt) != 12:
+        raise RuntimeError(f"{what}: fmt is the 12 fields of dmxq_gptq_format")
+    return _lib.GptqFormat(*[int(v) for v in fmt])
+
+
 def _gptq_matrix(t, w, name):
     if not (t.is_cuda and t.device == w.device and t.dtype == torch.float32 and t.dim() == 2 and (t.shape[1] <= 1 or t.stride(1) == 1)):
         raise RuntimeError(f"gptq_block: {name} must be a float32 matrix with unit column stride on w's GPU")
@@ -664,8 +671,7 @@ def gptq_block(w, hinv, inv_d, microblock, fmt, scale, zero_point, q, err):
     require_gpu(w, "gptq_block")
     for t, name in ((w, "w"), (hinv, "hinv"), (q, "q"), (err, "err")):
         _gptq_matrix(t, w, name)
-    if len(fmt) != 12:
-        raise RuntimeError("gptq_block: fmt is the 12 fields of dmxq_gptq_format")
+    f = _gptq_format(fmt, "gptq_block")
     if microblock < 1:
         raise RuntimeError("gptq_block: microblock must be positive")
     rows, count = w.shape
@@ -680,7 +686,6 @@ def gptq_block(w, hinv, inv_d, microblock, fmt, scale, zero_point, q, err):
     if zero_point is not None and not (zero_point.is_cuda and zero_point.device == w.device and zero_point.dtype == torch.int64
                                        and zero_point.is_contiguous()):
         raise RuntimeError("gptq_block: zero_point must be a contiguous int64 tensor on w's GPU")
-    f = _lib.GptqFormat(*[int(v) for v in fmt])
     if f.kind == _lib.GPTQ_FIXED:
         need = rows if f.per_row else 1
         if scale is None or zero_point is None or scale.numel() < need or zero_point.numel() < need:
@@ -700,8 +705,7 @@ def gptq_block_dynamic(w, hinv, inv_d, microblock, fmt, rounding, group, qmin, q
     for t, name in ((w, "w"), (hinv, "hinv"), (q, "q"), (err, "err"), (scale_out, "scale_out")):
         if not (t.is_cuda and t.device == w.device and t.dtype == torch.float32 and t.dim() == 2 and (t.shape[1] <= 1 or t.stride(1) == 1)):
             raise RuntimeError(f"{what}: {name} must be a float32 matrix with unit column stride on w's GPU")
-    if len(fmt) != 12:
-        raise RuntimeError(f"{what}: fmt is the 12 fields of dmxq_gptq_format")
+    f = _gptq_format(fmt, what)
     if microblock < 1 or group < 1:
         raise RuntimeError(f"{what}: microblock and group must be positive")
     rows, count = w.shape
@@ -716,7 +720,6 @@ def gptq_block_dynamic(w, hinv, inv_d, microblock, fmt, rounding, group, qmin, q
         raise RuntimeError(f"{what}: zp_out must be an int64 matrix with unit column stride on w's GPU")
     if tuple(scale_out.shape) != (rows, ng) or tuple(zp_out.shape) != (rows, ng):
         raise RuntimeError(f"{what}: scale_out and zp_out must be [rows, count / group] = [{rows}, {ng}]")
-    f = _lib.GptqFormat(*[int(v) for v in fmt])
 
     def ld(t, n):
         return max(t.stride(0), n) if t.shape[0] <= 1 else t.stride(0)
@@ -800,7 +803,7 @@ def cast_error(x, fmts, scale, zero_point, accumulate, stats, scratch):
     if zero_point is not None and not (zero_point.is_cuda and zero_point.device == xc.device and zero_point.dtype == torch.int64
                                        and zero_point.is_contiguous() and zero_point.numel() >= K):
         raise RuntimeError("cast_error: zero_point must be a contiguous int64 tensor with an entry per format on x's GPU")
-    f = (_lib.GptqFormat * K)(*[_lib.GptqFormat(*[int(v) for v in fmts[12 * k:12 * k + 12]]) for k in range(K)])
+    f = (_lib.GptqFormat * K)(*[_gptq_format(fmts[12 * k:12 * k + 12], "cast_error") for k in range(K)])
     L = xc.shape[-1] if xc.dim() else 1
     rows = xc.numel() // L if L else 0
     check(lib().dmxq_cast_error(ptr(xc), dtype_code(xc.dtype), rows, L, ctypes.cast(f, ctypes.c_void_p), K, ptr(scale), ptr(zero_point),
@@ -819,7 +822,7 @@ def hadamard_qdq(x, size, inverse, fmt, scale, zero_point, out_dtype=None):
     out = torch.empty(xc.shape, dtype=out_dtype or xc.dtype, device=xc.device)
     L = xc.shape[-1]
     rows = xc.numel() // L if L else 0
-    f = _lib.GptqFormat(*[int(v) for v in fmt]) if fmt else None
+    f = _gptq_format(fmt, "hadamard_qdq") if fmt else None
     if scale is not None and not (scale.is_cuda and scale.device == xc.device and scale.dtype == torch.float32 and scale.is_contiguous()):
         raise RuntimeError("hadamard_qdq: scale must be a contiguous float32 tensor on x's GPU")
     if zero_point is not None and not (zero_point.is_cuda and zero_point.device == xc.device and zero_point.dtype == torch.int64

@@ -1,4 +1,5 @@
-// csrc/bfp_math.hpp — per-block / per-element BFP arithmetic shared by bfp.hip and tools/tune_bfp.hip.
+// csrc/bfp_math.hpp — per-block / per-element BFP arithmetic shared by the BFP kernels (bfp*.hip), tools/tune_bfp.hip and the kernels
+// that cast inside another loop (gptq_cols.hpp, hadamard.hip, error_stats.hip).
 //
 // Reference sequence (quant_cpu.cpp:239-275, oracle/oracle.c bfp_q1), per block with max|x| = m:
 //   E = bits(m) & 0x7F800000 ; base = 6 * float(E)
@@ -96,6 +97,14 @@ __device__ __forceinline__ float bfp_q1(float x, const BfpBlockParams& p, int wl
   q = u2f(qb);
   if (ASYM) q = (x <= p.thr) ? p.neg_lim : q;
   return q;
+}
+
+// the literal path with nearest rounding and "(_N)" as a (wave-uniform) run-time flag, for the kernels that take the format as data
+// (csrc/hadamard.hip, csrc/error_stats.hip); p from bfp_block_params<true, false>
+__device__ __forceinline__ float bfp_q1_nearest_rt(float x, const BfpBlockParams& p, int wl, bool asym) {
+  float v = bfp_q1<DMXQ_ROUND_NEAREST, false>(x, p, wl, DMXQ_ROUND_NEAREST, 0u);
+  if (asym) v = (x <= p.thr) ? p.neg_lim : v;
+  return v;
 }
 
 // (5) the other rounding modes (down / up / stochastic act on t's bit pattern) keep the literal rounding and only

@@ -9,33 +9,16 @@
 
 #include <cmath>
 
-#include "floatq.hpp"
+#include "fixedq.hpp"
+#include "mxfp_math.hpp"
 #include "stream.hpp"
 
 namespace dmxq {
 
-// per-element pieces shared with elementwise.hip (kept local: tiny, and it avoids a header for three functions)
-__device__ __forceinline__ uint32_t rne_bits(uint32_t t, int man_bits) {  // quant_cpu.cpp:211-237, nearest
-  const int sh = 23 - man_bits;
-  const uint32_t mask = (1u << sh) - 1u;
-  return (t + (mask >> 1) + ((t >> sh) & 1u)) & ~mask;
-}
-__device__ __forceinline__ float float_q_nearest(float a, int man, int exp_bits, int bias, int flush) {  // quant_cpu.cpp:359-402
-  const uint32_t target = f2u(a);
-  const int target_exp = (int)((target & 0x7FFFFFFFu) >> 23) - 127;
-  const int min_exp = -(bias - 1);
-  if (target_exp < min_exp) {
-    if (flush) return 0.0f;
-    const float shift = u2f(((uint32_t)(127 + min_exp) << 23) | (target & 0x80000000u));
-    return u2f(rne_bits(f2u(a + shift), man)) - shift;
-  }
-  uint32_t qb = rne_bits(target, man);
-  const int max_e = (1 << (exp_bits - 1)) + 127;
-  if (qb != 0u && (int)((qb & 0x7FFFFFFFu) >> 23) > max_e)
-    qb = (target & 0x80000000u) | ((uint32_t)max_e << 23) | ((0x007FFFFFu >> (23 - man)) << (23 - man));
-  return u2f(qb);
-}
-__device__ __forceinline__ float fixed_rne(float a) {  // sim_helper.cpp:14-21 with sigma = 0 (see elementwise.hip)
+// sim_helper.cpp:14-21 with sigma = 0: fixedq.hpp rne_minus_half(a + 0.5f), with its selects spelled as nested conditionals -- the
+// spelling decides the instruction order of the SBFP rows kernels, and two of them take one more VGPR through the shared one
+// (profiles/literal_cast_codegen.txt)
+__device__ __forceinline__ float fixed_rne(float a) {
   const float a1 = a + 0.5f;
   const float mag = fabsf(a1);
   const bool odd = (f2u(a1) & 1u) != 0u && mag < 16777216.0f;
@@ -51,7 +34,7 @@ struct SbfpBlock {
   bool fast;  // clamped codes and a block scale whose reciprocal carries the exact-quotient argument of common.hpp
   __device__ __forceinline__ void setup(uint32_t maxbits, const SbfpFmt& f) {
     s = u2f(maxbits) / f.man_scaling;
-    sc = fabsf(float_q_nearest(s, f.man, f.exp_bits, f.bias, f.flush));
+    sc = fabsf(float_q1<DMXQ_ROUND_NEAREST>(s, FloatFmt{f.man, f.exp_bits, f.bias, f.flush, 0, DMXQ_ROUND_NEAREST, 0ull}, 0u));
     rs = 1.0f / s;
     fast = f.clamp != 0 && recip_ok(s);
   }
@@ -116,7 +99,7 @@ struct MxfpBlock {
   //     saturation           maxv  = max_val * scale
   // 12 VALU per element instead of ~20 (no x * inv, no per-element range check -- every element is <= the block maximum --, no zero
   // select, no * scale), and the block set-up shrinks to ~10 operations.  Blocks it does not cover (zero / Inf / NaN maxima, scales below
-  // 2^(bias - 127) or maxima from 2^105 up, float32 maxima within 88 ulps below a power of two -- the log2 rounding rule of setup()) make
+  // 2^(bias - 127) or maxima from 2^105 up, float32 maxima within 88 ulps below a power of two -- the log2 rounding rule of mxfp_math.hpp mxfp_block_scale) make
   // the WAVE take the general path: one wave-uniform branch per vector.
   uint32_t tbits, k1;
   float maxv;
@@ -143,38 +126,14 @@ struct MxfpBlock {
     }
   }
   __device__ __forceinline__ void setup(uint32_t maxbits, const MxfpFmt& f) {
-    const float m = u2f(maxbits);
-    zero = m == 0.0f;
-    // the reference evaluates 2^floor(log2 m) / 2^(2^(e-1)) in fp32 (format.py:551-555).  No libm: a float32 log2 within an ulp
-    // of the truth crosses an integer only for m = 2^v (1 - j 2^-24) with j <= jmax(v) (the rule and its proof sketch are in
-    // oracle/oracle.c oracle_floor_log2f; checked against torch.log2 for every exponent, fixtures tests/golden/boundaries.npz);
-    // a maximum with at most 11 significant bits (bf16 / fp16 inputs) has j >= 2^13 and never does.
-    int eb = (int)(maxbits >> 23);
-    if (eb >= 1 && eb <= 254) {
-      const uint32_t man = maxbits & 0x007FFFFFu;
-      const int v = eb - 126;  // floor(log2 m) + 1
-      if (!f.exact_exponent && man != 0u && v != 0) {
-        const uint32_t a = (uint32_t)(v < 0 ? -v : v), j = 0x00800000u - man;
-        const int c = 31 - __builtin_clz(a);
-        const int g = (v > 0 && (a & (a - 1u)) == 0u) ? 25 - c : 24 - c;  // 17 .. 25
-        // jmax = floor(2^24 (1 - 2^(-2^-g))): 88 44 22 11 | 5 2 1 | 0 0, as bytes of two constants
-        const uint32_t jmax = g <= 20 ? ((0x0B162C58u >> (8 * (g - 17))) & 0xFFu) : (g <= 23 ? ((0x00010205u >> (8 * (g - 21))) & 0xFFu) : 0u);
-        if (j <= jmax) eb += 1;
-      }
-      const int se = eb - f.big_log2;
-      if (eb == 255) scale = INFINITY;                      // 2^128: the reference's fp32 power overflows too
-      else if (se >= 1) scale = u2f((uint32_t)se << 23);
-      else scale = ldexpf(1.0f, se - 127);                  // a denormal (or zero) scale, exact
-    } else {
-      scale = exp2f(floorf(log2f(m))) / f.big;              // zero (see `zero`), denormal, Inf, NaN maxima
-    }
+    zero = u2f(maxbits) == 0.0f;
+    scale = mxfp_block_scale(maxbits, f.big_log2, f.big, f.exact_exponent);   // (the log2 rounding rule near powers of two: mxfp_math.hpp)
     const uint32_t sb = f2u(scale);
     pow2 = (sb & 0x007FFFFFu) == 0u && (sb >> 23) >= 1u && (sb >> 23) <= 253u;
     inv = u2f((254u - (sb >> 23)) << 23);
   }
   __device__ __forceinline__ float apply(float x, const MxfpFmt& f) const {
-    if (zero) return x * 0.0f;
-    return float_q_nearest(x / scale, f.man, f.exp_bits, f.bias, 0) * scale;
+    return mxfp_q1(x, scale, zero, f.man, f.exp_bits, f.bias);
   }
   // a whole lane-vector; the branch-free element form when the wave's blocks and values allow it (floatq.hpp)
   template <int N>
@@ -289,10 +248,8 @@ extern "C" int dmxq_sbfp_qdq(const void* in, void* out, int dtype_in, int dtype_
   if (scaler_man_bits > 22) return DMXQ_ERR_UNSUPPORTED;
   if (outer * L * inner == 0) return DMXQ_OK;
   if (!in || !out) return DMXQ_ERR_BAD_ARG;
-  float t_min = (float)(-ldexp(1.0, precision - 1));            // sim_helper.cpp:5-12 with fl = 0
-  const float t_max = (float)(-(double)t_min - 1.0);
-  if (symmetric) t_min = (float)((double)t_min + 1.0);
-  const SbfpFmt f{precision, clamp ? 1 : 0, t_min, t_max, (float)((1 << (precision - 1)) - 1), scaler_man_bits,
+  const FixedFmt x = make_fixed_fmt(precision, 0, clamp, symmetric, DMXQ_ROUND_NEAREST, 0ull);
+  const SbfpFmt f{precision, x.clamp, x.t_min, x.t_max, (float)((1 << (precision - 1)) - 1), scaler_man_bits,
                   scaler_exp_bits, scaler_exp_bias, scaler_flush_subnormal ? 1 : 0};
   return dispatch_blockfmt<SbfpFmt, SbfpBlock>(in, out, dtype_in, dtype_out, outer, L, inner, block_size, f, (hipStream_t)stream);
 }
@@ -304,9 +261,8 @@ extern "C" int dmxq_mxfp_qdq(const void* in, void* out, int dtype_in, int dtype_
   if (man_bits > 22) return DMXQ_ERR_UNSUPPORTED;
   if (outer * L * inner == 0) return DMXQ_OK;
   if (!in || !out) return DMXQ_ERR_BAD_ARG;
-  MxfpFmt f{man_bits, exp_bits, (1 << (exp_bits - 1)) - 1, (float)ldexp(1.0, 1 << (exp_bits - 1)),
-            make_float_fast(man_bits, exp_bits, (1 << (exp_bits - 1)) - 1), 1 << (exp_bits - 1),
-            dtype_in != DMXQ_F32 ? 1 : 0, 0};
+  const MxfpConsts k = make_mxfp_consts(exp_bits);
+  MxfpFmt f{man_bits, exp_bits, k.bias, k.big, make_float_fast(man_bits, exp_bits, k.bias), k.big_log2, dtype_in != DMXQ_F32 ? 1 : 0, 0};
   f.xdomain = (f.fast.usable && std::isfinite(f.fast.max_val) && f.bias >= 1) ? 1 : 0;  // MxfpBlock::try_fast
   return dispatch_blockfmt<MxfpFmt, MxfpBlock>(in, out, dtype_in, dtype_out, outer, L, inner, block_size, f, (hipStream_t)stream);
 }

@@ -19,6 +19,7 @@ constexpr int kMaxBlocks = 256 * 8;  // memory-bound grid cap: 256 CUs x 8 workg
 
 __device__ __forceinline__ uint32_t f2u(float f) { return __float_as_uint(f); }
 __device__ __forceinline__ float u2f(uint32_t u) { return __uint_as_float(u); }
+__device__ __forceinline__ uint32_t umax(uint32_t a, uint32_t b) { return a > b ? a : b; }
 
 // hash32(seed, linear element index): the same counter-based stream as oracle/oracle.c rnd_bits, so the
 // stochastic modes are reproducible and kernel-vs-oracle bit-exact (the reference's RNG is an unseeded

@@ -4,7 +4,7 @@
 // reference's two formulas (numerical/observer.py:59-115 -> reduce_common.hpp qparams_one; numerical/cast.py:278-296 -> FixedOp).
 //
 // The contract is the library's own three-launch chain on x.reshape(-1, S), bit for bit, scale and zero point included:
-//   dmxq_group_minmax (one group per segment) -> dmxq_qparams -> dmxq_fixed_qdq (one scale per segment), restated:
+//   dmxq_group_minmax (one group per segment) -> dmxq_qparams -> dmxq_fixed_qdq (one scale per segment), that is:
 //   * (mn, mx) = the segment's minimum and maximum as VALUES (the sign of a zero extremum cannot reach the result: qparams_one takes
 //     fminf(mn, 0) / fmaxf(mx, 0), whose zero ends up in a sum, a quotient that rounds to 0, or below eps); ONE NaN anywhere in the
 //     segment makes BOTH extrema NaN (torch.amin / amax propagate it; reduce.hip nan_to_both), which qparams_one's fminf / fmaxf then
@@ -19,7 +19,7 @@
 // Geometry.  A lane moves 16-byte vectors (V = 8 sixteen-bit or 4 fp32 elements), held RAW in registers between the extrema pass and
 // the cast: one read and one write per element.
 //   * segments inside a wave (S = 16 .. 256, a power of two): flat, S / V adjacent lanes per segment, extrema by DPP / xor shuffles
-//     over those lanes on order-preserving keys (reduce.hip fkey, restated); a wave takes U x 64 consecutive vectors, the grid does not
+//     over those lanes on order-preserving keys (reduce_common.hpp fkey); a wave takes U x 64 consecutive vectors, the grid does not
 //     loop.  Lanes past the end re-read the last vector, meet only each other (the tensor ends on a segment boundary) and store nothing.
 //   * whole rows (any S % V == 0 up to 16384): a wave per row while the row fits 16 vectors per lane (S <= 1024 V), four rows per
 //     workgroup; a 256-thread workgroup per row above that, the four waves' extrema exchanged through LDS.  The vector count per lane
@@ -27,6 +27,7 @@
 // Every segment is read completely before any of it is written.  No workspace, no synchronisation with the host: capturable.
 #include <math.h>
 
+#include "fixedq.hpp"
 #include "reduce_common.hpp"
 
 namespace dmxq {
@@ -40,10 +41,6 @@ struct DynFmt {
   int qmin, qmax, sym;
 };
 
-// reduce.hip's order-preserving keys: unsigned order == float order, -NaN below -Inf, +NaN above +Inf
-__device__ __forceinline__ uint32_t dyn_key(float f) { const uint32_t b = f2u(f); return b ^ ((uint32_t)((int32_t)b >> 31) | 0x80000000u); }
-__device__ __forceinline__ float dyn_key_inv(uint32_t k) { return u2f(k ^ ((k & 0x80000000u) ? 0x80000000u : 0xFFFFFFFFu)); }
-
 struct DynExt : FloatExtrema {   // (reduce_common.hpp: the float accumulation and the NaN rule, shared with GPTQ's group scan)
   template <int DT, int V>
   __device__ __forceinline__ void add(const u32x4& raw) {
@@ -54,8 +51,8 @@ struct DynExt : FloatExtrema {   // (reduce_common.hpp: the float accumulation a
   }
   // -> keys; a NaN anywhere: (-NaN, +NaN), which win every min / max of the combine
   __device__ __forceinline__ void keys(uint32_t& klo, uint32_t& khi) const {
-    klo = dyn_key(mn());
-    khi = dyn_key(mx());
+    klo = fkey(mn());
+    khi = fkey(mx());
   }
 };
 
@@ -83,7 +80,7 @@ struct DynSeg {
   float sc, rs, z;
   int64_t zp;
   __device__ __forceinline__ void setup(uint32_t klo, uint32_t khi, const DynFmt& f) {
-    qparams_one(dyn_key_inv(klo), dyn_key_inv(khi), f.qmin, f.qmax, f.sym, sc, zp);
+    qparams_one(fkey_inv(klo), fkey_inv(khi), f.qmin, f.qmax, f.sym, sc, zp);
     z = (float)zp;
     rs = 1.0f / sc;
   }
@@ -287,11 +284,8 @@ extern "C" int dmxq_dynamic_fixed_qdq(const void* in, void* out, int dtype_in, i
   if (n_segments == 0 || segment == 0) return DMXQ_OK;
   if (!aligned16(in) || !aligned16(out)) return DMXQ_ERR_UNSUPPORTED;
   if (n_segments > INT64_MAX / (segment * 4)) return DMXQ_ERR_UNSUPPORTED;
-  // sim_helper.cpp:5-12 fixed_min_max with fraction 0, as dmxq_fixed_qdq evaluates it
-  float t_min = (float)(-ldexp(1.0, precision - 1));
-  const float t_max = (float)(-(double)t_min - 1.0);
-  if (symmetric) t_min = (float)((double)t_min + 1.0);
-  const DynFmt f{t_min, t_max, qmin, qmax, symmetric_qscheme ? 1 : 0};
+  const FixedFmt x = make_fixed_fmt(precision, 0, 1, symmetric, DMXQ_ROUND_NEAREST, 0ull);
+  const DynFmt f{x.t_min, x.t_max, qmin, qmax, symmetric_qscheme ? 1 : 0};
   hipStream_t s = (hipStream_t)stream;
   if (dtype_in == DMXQ_BF16) return dyn_launch<DMXQ_BF16>(in, out, n_segments, segment, whole_rows != 0, f, scale_out, zp_out, s);
   if (dtype_in == DMXQ_F16) return dyn_launch<DMXQ_F16>(in, out, n_segments, segment, whole_rows != 0, f, scale_out, zp_out, s);

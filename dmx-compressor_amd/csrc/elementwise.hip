@@ -900,12 +900,7 @@ extern "C" int dmxq_fixed_qdq(const void* in, void* out, int dtype_in, int dtype
   const int64_t n = outer * C * inner;
   if (n == 0) return DMXQ_OK;
   if (!in || !out) return DMXQ_ERR_BAD_ARG;
-  // sim_helper.cpp:5-12 fixed_min_max, evaluated on the host in the same float/double mix
-  const int sigma = -fraction;
-  float t_min = (float)(-ldexp(1.0, precision - fraction - 1));
-  const float t_max = (float)(-(double)t_min - ldexp(1.0, sigma));
-  if (symmetric) t_min = (float)((double)t_min + ldexp(1.0, sigma));
-  const FixedFmt f{sigma, clamp ? 1 : 0, rounding, t_min, t_max, seed};
+  const FixedFmt f = make_fixed_fmt(precision, fraction, clamp, symmetric, rounding, seed);
   const ChannelMap cm = make_channel_map(C, inner, group_size, n);
   hipStream_t s = (hipStream_t)stream;
   const bool simple = fraction == 0 && clamp && rounding == DMXQ_ROUND_NEAREST && precision <= 22;  // |t| <= 2^21

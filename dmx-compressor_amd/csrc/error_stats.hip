@@ -23,16 +23,15 @@
 // dmxq_cast_error, geometry: the tensor is flat -- L is a multiple of every block size, so the blocks of the flat index ARE the row
 // blocks.  A lane holds 8 consecutive elements (16 bytes of a 16-bit tensor), a wave 512: blocks of 8 .. 128 elements are 1 .. 16
 // neighbouring lanes, whose maxima (on the bit patterns of |x|, what the BFP kernels compare) are one lane-local maximum and up to
-// four xor shuffles per vector and format.  The casts are the literal forms shared with gptq.hip (bfp_block_params /
-// bfp_q1, float_q1, fixed_q1 with the affine wrapper in IEEE arithmetic): bit for bit the library's casts, then rounded to the tensor's
+// four xor shuffles per vector and format.  The casts are the literal per-element leaves (bfp_math.hpp bfp_block_params /
+// bfp_q1_nearest_rt, floatq.hpp float_q1, fixedq.hpp fixed_affine_q1 with its IEEE division): bit for bit the library's casts, then rounded to the tensor's
 // dtype as CastTo.forward returns them.  The format loop runs over descriptors held in the kernel arguments and is NOT unrolled (one
 // copy of the three cast bodies whatever K is; no spills at K = 8): a batch of vectors stays in registers across the loop, every
 // format folds the batch into a register pair and then into its lane's slot in LDS (K * 12 bytes per lane).
 #include <math.h>
 
 #include "bfp_math.hpp"
-#include "fixedq.hpp"
-#include "floatq.hpp"
+#include "format_desc.hpp"
 #include "reduce_common.hpp"
 
 namespace dmxq {
@@ -44,8 +43,6 @@ constexpr int kErrWgPerCu = 8;      // the largest grid: 8 workgroups of 4 waves
 constexpr int kErrMaxFormats = 8;
 constexpr int kErrBatch = 4;        // 16-byte loads in flight per lane and operand
 constexpr int kErrRow = 4;          // doubles per partial row: sum_sq_err, sum_sq_ref, bits of max |d|, unused
-
-__device__ __forceinline__ uint32_t umax(uint32_t a, uint32_t b) { return a > b ? a : b; }
 
 struct ErrAcc {
   double sse, ssr;
@@ -166,9 +163,7 @@ __device__ __forceinline__ void err_cast8(const float (&x)[8], uint32_t bm, cons
     const BfpBlockParams p = bfp_block_params<true, false>(bm, wl);
 #pragma unroll
     for (int j = 0; j < 8; j++) {
-      float v = bfp_q1<DMXQ_ROUND_NEAREST, false>(x[j], p, wl, DMXQ_ROUND_NEAREST, 0u);
-      if (f.c) v = (x[j] <= p.thr) ? p.neg_lim : v;   // bfp_q1<.., ASYM = true>, the flag at run time (wave-uniform)
-      q[j] = round_to<DT>(v);
+      q[j] = round_to<DT>(bfp_q1_nearest_rt(x[j], p, wl, f.c != 0));
     }
   } else if (f.kind == DMXQ_GPTQ_FLOAT) {
     const FloatFmt ff{f.a, f.b, f.c, f.d, f.e, DMXQ_ROUND_NEAREST, 0ull};
@@ -177,7 +172,7 @@ __device__ __forceinline__ void err_cast8(const float (&x)[8], uint32_t bm, cons
   } else {
     const FixedFmt fx{f.a, f.b, DMXQ_ROUND_NEAREST, u2f((uint32_t)f.c), u2f((uint32_t)f.d), 0ull};
 #pragma unroll
-    for (int j = 0; j < 8; j++) q[j] = round_to<DT>((fixed_q1(x[j] / sc + z, fx, 0.5f) - z) * sc);
+    for (int j = 0; j < 8; j++) q[j] = round_to<DT>(fixed_affine_q1(x[j], sc, z, fx));
   }
 }
 
@@ -353,27 +348,21 @@ extern "C" int dmxq_cast_error(const void* in, int dtype, int64_t rows, int64_t 
   for (int k = 0; k < n_formats; k++) {
     const dmxq_gptq_format& g = formats[k];
     ErrFmt e{g.kind, 0, 0, 0, 0, 0};
-    if (g.per_row) return DMXQ_ERR_UNSUPPORTED;
+    FormatDesc d;
+    if (g.per_row || format_desc(g, &d) != DMXQ_OK) return DMXQ_ERR_UNSUPPORTED;
     if (g.kind == DMXQ_GPTQ_BFP) {
       const int B = g.block_size;
-      if (!(B == 8 || B == 16 || B == 32 || B == 64 || B == 128) || g.precision < 2 || g.precision > 22) return DMXQ_ERR_UNSUPPORTED;
-      if (L % B != 0) return DMXQ_ERR_UNSUPPORTED;
-      e.a = g.precision;
+      if (!(B == 8 || B == 16 || B == 32 || B == 64 || B == 128) || L % B != 0) return DMXQ_ERR_UNSUPPORTED;
+      e.a = d.wl;
       e.b = B == 8 ? 0 : B == 16 ? 1 : B == 32 ? 2 : B == 64 ? 3 : 4;
-      e.c = g.symmetric == 0;
+      e.c = d.asym;
     } else if (g.kind == DMXQ_GPTQ_FLOAT) {
-      if (g.exp_bits < 1 || g.exp_bits > 8 || g.man_bits < 0 || g.man_bits > 22) return DMXQ_ERR_UNSUPPORTED;
-      e.a = g.man_bits; e.b = g.exp_bits; e.c = g.exp_bias; e.d = g.flush_subnormal ? 1 : 0; e.e = g.unsigned_abs ? 1 : 0;
+      e.a = d.f.man; e.b = d.f.exp_bits; e.c = d.f.bias; e.d = d.f.flush; e.e = d.f.unsigned_abs;
     } else {
-      if (!scale || !zero_point || g.precision < 1 || g.precision > 24) return DMXQ_ERR_UNSUPPORTED;
-      // sim_helper.cpp:5-12 fixed_min_max, evaluated on the host in the same float/double mix as dmxq_fixed_qdq
-      const int sigma = -g.fraction;
-      float t_min = (float)(-ldexp(1.0, g.precision - g.fraction - 1));
-      const float t_max = (float)(-(double)t_min - ldexp(1.0, sigma));
-      if (g.symmetric) t_min = (float)((double)t_min + ldexp(1.0, sigma));
-      e.a = sigma; e.b = g.clamp ? 1 : 0;
-      memcpy(&e.c, &t_min, 4);
-      memcpy(&e.d, &t_max, 4);
+      if (!scale || !zero_point) return DMXQ_ERR_UNSUPPORTED;
+      e.a = d.x.sigma; e.b = d.x.clamp;
+      memcpy(&e.c, &d.x.t_min, 4);
+      memcpy(&e.d, &d.x.t_max, 4);
     }
     fm.kind[k] = e.kind; fm.a[k] = e.a; fm.b[k] = e.b; fm.c[k] = e.c; fm.d[k] = e.d; fm.e[k] = e.e;
   }

@@ -47,10 +47,7 @@ extern "C" int dmxq_fixed_qdq_multi(const dmxq_affine_desc* tensors, int64_t n_t
   hipStream_t s = (hipStream_t)stream;
   const int epl = dtype_in == DMXQ_F32 ? 4 : 8;
   const bool simple = fraction == 0 && clamp && rounding == DMXQ_ROUND_NEAREST && precision <= 22;
-  float t_min = (float)(-ldexp(1.0, precision - 1));   // sim_helper.cpp:5-12 fixed_min_max at fraction 0
-  const float t_max = (float)(-(double)t_min - 1.0);
-  if (symmetric) t_min = (float)((double)t_min + 1.0);
-  const FixedFmt f{0, 1, DMXQ_ROUND_NEAREST, t_min, t_max, 0ull};
+  const FixedFmt f = make_fixed_fmt(precision, 0, 1, symmetric, DMXQ_ROUND_NEAREST, 0ull);   // (read by the batched, SIMPLE tensors only)
   using OP = FixedOp<kUniform, true>;
   StreamMultiArgs<OP> a;
   a.n = 0;
@@ -162,10 +159,7 @@ extern "C" int dmxq_fixed_float_qdq_multi(const dmxq_affine_desc* fixed, int64_t
     combined = n > 0 && t.in && t.out && n % epl == 0 && n < ((int64_t)1 << 31) && aligned16(t.in) && aligned16(t.out);
   }
   if (combined) {
-    float t_min = (float)(-ldexp(1.0, precision - 1));
-    const float t_max = (float)(-(double)t_min - 1.0);
-    if (symmetric) t_min = (float)((double)t_min + 1.0);
-    const FixedFmt f{0, 1, DMXQ_ROUND_NEAREST, t_min, t_max, 0ull};
+    const FixedFmt f = make_fixed_fmt(precision, 0, 1, symmetric, DMXQ_ROUND_NEAREST, 0ull);
     const FloatFmt ff{man_bits, exp_bits, exp_bias, flush_subnormal ? 1 : 0, unsigned_abs ? 1 : 0, DMXQ_ROUND_NEAREST, seed};
     const OPB opb{ff, make_float_fast(ff.man, ff.exp_bits, ff.bias), make_flush_fast(ff.man, ff.exp_bits, ff.bias, ff.flush && !ff.unsigned_abs)};
     Args a;

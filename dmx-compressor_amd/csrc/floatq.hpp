@@ -1,5 +1,8 @@
-// csrc/floatq.hpp — branch-free nearest-even quantisation to a low-bit float format, shared by the elementwise float
-// cast (elementwise.hip) and the MX block formats (blockfmt.hip).  Reference: quant_cpu.cpp:359-402, bit_helper.cpp:4-22.
+// csrc/floatq.hpp — quantisation of one element to a low-bit float format (quant_cpu.cpp:359-402, bit_helper.cpp:4-22): the branch-free
+// nearest-even forms and the bit-level form of every rounding mode.  Used by the elementwise float cast and the fused modules
+// (elementwise.hip, fixed_multi.hip, approx.hip, act_cast.hip, rope.hip, lut16.hip), the block formats (blockfmt.hip through
+// mxfp_math.hpp), and through format_desc.hpp the GPTQ column kernels (gptq_cols.hpp), the fused rotation (hadamard.hip) and the error
+// sweep (error_stats.hip).
 #pragma once
 #include <math.h>
 #include <string.h>

@@ -58,29 +58,20 @@ extern "C" int dmxq_gptq_block(const float* w, int64_t ldw, float* q, int64_t ld
   if (rows >= ((int64_t)1 << 37)) return DMXQ_ERR_BAD_ARG;  // (grid of rows / 64 workgroups)
   const int mb = (int)microblock;
   if (count > kGptqCols || !(mb == 1 || mb == 8 || mb == 16 || mb == 32 || mb == 64)) return DMXQ_ERR_UNSUPPORTED;
+  if (fmt->kind == DMXQ_GPTQ_FIXED && (!scale || !zero_point)) return DMXQ_ERR_BAD_ARG;
+  FormatDesc d;
+  if (format_desc(*fmt, &d) != DMXQ_OK) return DMXQ_ERR_UNSUPPORTED;
   GptqCast c{};
-  bool asym = false;
+  c.wl = d.wl;
+  c.f = d.f;
+  c.x = d.x;
+  c.per_row = fmt->kind == DMXQ_GPTQ_FIXED && fmt->per_row ? 1 : 0;
+  const bool asym = d.asym != 0;
   if (fmt->kind == DMXQ_GPTQ_BFP) {
     const int B = fmt->block_size;
-    if (B < 2 || mb % B != 0 || fmt->precision < 2 || fmt->precision > 22) return DMXQ_ERR_UNSUPPORTED;
-    c.wl = fmt->precision;
+    if (B < 2 || mb % B != 0) return DMXQ_ERR_UNSUPPORTED;
     for (int i = 0; i < mb; i++)
       if ((i + 1) % B == 0) c.ends |= 1ull << i;
-    asym = fmt->symmetric == 0;
-  } else if (fmt->kind == DMXQ_GPTQ_FLOAT) {
-    if (fmt->exp_bits < 1 || fmt->exp_bits > 8 || fmt->man_bits < 0 || fmt->man_bits > 22) return DMXQ_ERR_UNSUPPORTED;
-    c.f = FloatFmt{fmt->man_bits, fmt->exp_bits, fmt->exp_bias, fmt->flush_subnormal ? 1 : 0, fmt->unsigned_abs ? 1 : 0,
-                   DMXQ_ROUND_NEAREST, 0ull};
-  } else {
-    if (!scale || !zero_point) return DMXQ_ERR_BAD_ARG;
-    if (fmt->precision < 1 || fmt->precision > 24) return DMXQ_ERR_UNSUPPORTED;
-    // sim_helper.cpp:5-12 fixed_min_max, evaluated on the host in the same float/double mix as dmxq_fixed_qdq
-    const int precision = fmt->precision, fraction = fmt->fraction, sigma = -fraction;
-    float t_min = (float)(-ldexp(1.0, precision - fraction - 1));
-    const float t_max = (float)(-(double)t_min - ldexp(1.0, sigma));
-    if (fmt->symmetric) t_min = (float)((double)t_min + ldexp(1.0, sigma));
-    c.x = FixedFmt{sigma, fmt->clamp ? 1 : 0, DMXQ_ROUND_NEAREST, t_min, t_max, 0ull};
-    c.per_row = fmt->per_row ? 1 : 0;
   }
   hipStream_t s = (hipStream_t)stream;
   const dim3 grid((unsigned)((rows + kGptqRows - 1) / kGptqRows));

@@ -8,6 +8,7 @@
 #include "bfp_math.hpp"
 #include "fixedq.hpp"
 #include "floatq.hpp"
+#include "format_desc.hpp"
 #include "reduce_common.hpp"
 
 namespace dmxq {
@@ -46,7 +47,7 @@ __device__ __forceinline__ void gptq_cast(const float* w, int m, const GptqCast&
   } else if constexpr (KIND == DMXQ_GPTQ_FIXED) {
 #pragma unroll
     for (int i = 0; i < MB; i++)
-      if (i < m) q[i] = (fixed_q1(w[i] / sc + z, c.x, 0.5f) - z) * sc;
+      if (i < m) q[i] = fixed_affine_q1(w[i], sc, z, c.x);
   } else {
     // block maxima of |w| on the bit patterns (what the BFP kernels compare): a running maximum that restarts after each block end,
     // then walked back so that every element sees the maximum of its whole block

@@ -41,15 +41,12 @@ extern "C" int dmxq_gptq_block_dynamic(const float* w, int64_t ldw, float* q, in
   const int mb = (int)microblock;
   if (count > kGptqCols || !(mb == 1 || mb == 8 || mb == 16 || mb == 32 || mb == 64)) return DMXQ_ERR_UNSUPPORTED;
   if (!(group == 16 || group == 32 || group == 64 || group == 128) || count % group != 0 || group % mb != 0) return DMXQ_ERR_UNSUPPORTED;
-  if (rounding != DMXQ_ROUND_NEAREST || fmt->fraction != 0 || !fmt->clamp || fmt->precision < 1 || fmt->precision > 22)
-    return DMXQ_ERR_UNSUPPORTED;
+  FormatDesc d;
+  if (format_desc(*fmt, &d) != DMXQ_OK) return DMXQ_ERR_UNSUPPORTED;
+  if (rounding != DMXQ_ROUND_NEAREST || fmt->fraction != 0 || !fmt->clamp || fmt->precision > 22) return DMXQ_ERR_UNSUPPORTED;
   if (lds < count / group || ldz < count / group) return DMXQ_ERR_BAD_ARG;
   GptqCast c{};
-  // sim_helper.cpp:5-12 fixed_min_max with fraction 0, as dmxq_gptq_block evaluates it
-  float t_min = (float)(-ldexp(1.0, fmt->precision - 1));
-  const float t_max = (float)(-(double)t_min - 1.0);
-  if (fmt->symmetric) t_min = (float)((double)t_min + 1.0);
-  c.x = FixedFmt{0, 1, DMXQ_ROUND_NEAREST, t_min, t_max, 0ull};
+  c.x = d.x;
   c.per_row = 1;
   int l2 = 4;
   while (((int64_t)1 << l2) < group) l2++;

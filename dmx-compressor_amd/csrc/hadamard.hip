@@ -21,17 +21,15 @@
 // the shuffles, which depend on every load of the block): in == out is fine when both dtypes have one width.
 // A pointer that is not 16-byte aligned takes the same kernel with element-wise loads and stores (a wave-uniform flag).
 //
-// Casts: the literal per-element forms of bfp_math.hpp / floatq.hpp / fixedq.hpp, as in gptq.hip and error_stats.hip (nearest
-// rounding), and the GENERAL path of blockfmt.hip's MXFP block (setup + apply: restated here literally, its fast paths are
-// bit-identical to it by construction), with float32 input rules (the rotated tensor is float32: the floor(log2 max) rule near powers
-// of two applies).  Block maxima are taken on the bit patterns of |x| over the cast's own block: inside the lane's vector when the
-// block is smaller than a vector (one pass of the cast body per sub-block, selected element by element: a rare shape, kept simple), with
-// DPP / shuffles across block_size / V lanes otherwise.
+// Casts: the literal per-element leaves of bfp_math.hpp / floatq.hpp / fixedq.hpp (nearest rounding) and the general path of the MXFP
+// block (mxfp_math.hpp: blockfmt.hip's fast paths are bit-identical to it by construction), with float32 input rules (the rotated
+// tensor is float32: the floor(log2 max) rule near powers of two applies).  Block maxima are taken on the bit patterns of |x| over the
+// cast's own block: inside the lane's vector when the block is smaller than a vector (one pass of the cast body per sub-block, selected
+// element by element: a rare shape, kept simple), with DPP / shuffles across block_size / V lanes otherwise.
 #include <math.h>
 
 #include "bfp_math.hpp"
-#include "fixedq.hpp"
-#include "floatq.hpp"
+#include "format_desc.hpp"
 
 namespace dmxq {
 namespace {
@@ -43,15 +41,9 @@ struct HadCast {
   int kind;      // dmxq_gptq_kind, or kHadRotateOnly
   int inverse;   // rotate back after the cast
   int blog;      // BFP / MXFP: log2(block_size)
-  int wl, asym;  // BFP: precision, "(_N)"
   int per_row;   // FIXED: scale / zero point indexed by row
-  int man, exp_bits, bias, big_log2;   // MXFP (blockfmt.hip MxfpFmt)
-  float big;
-  FloatFmt f;    // FLOAT
-  FixedFmt x;    // FIXED
+  FormatDesc d;  // the format as the leaves take it (format_desc.hpp)
 };
-
-__device__ __forceinline__ uint32_t umax(uint32_t a, uint32_t b) { return a > b ? a : b; }
 
 // R_H of the block this lane's vector belongs to: `lanes` = H / V lanes per block (a power of two, wave-uniform)
 template <int V>
@@ -79,71 +71,15 @@ __device__ __forceinline__ void had_rotate(float (&v)[V], int lanes, int lane, f
   for (int i = 0; i < V; i++) v[i] = v[i] * c;
 }
 
-// blockfmt.hip, restated literally: rne_bits, float_q_nearest, MxfpBlock::setup / apply (the general path), exact_exponent = 0
-__device__ __forceinline__ uint32_t had_rne_bits(uint32_t t, int man_bits) {  // quant_cpu.cpp:211-237, nearest
-  const int sh = 23 - man_bits;
-  const uint32_t mask = (1u << sh) - 1u;
-  return (t + (mask >> 1) + ((t >> sh) & 1u)) & ~mask;
-}
-__device__ __forceinline__ float had_float_q_nearest(float a, int man, int exp_bits, int bias, int flush) {  // quant_cpu.cpp:359-402
-  const uint32_t target = f2u(a);
-  const int target_exp = (int)((target & 0x7FFFFFFFu) >> 23) - 127;
-  const int min_exp = -(bias - 1);
-  if (target_exp < min_exp) {
-    if (flush) return 0.0f;
-    const float shift = u2f(((uint32_t)(127 + min_exp) << 23) | (target & 0x80000000u));
-    return u2f(had_rne_bits(f2u(a + shift), man)) - shift;
-  }
-  uint32_t qb = had_rne_bits(target, man);
-  const int max_e = (1 << (exp_bits - 1)) + 127;
-  if (qb != 0u && (int)((qb & 0x7FFFFFFFu) >> 23) > max_e)
-    qb = (target & 0x80000000u) | ((uint32_t)max_e << 23) | ((0x007FFFFFu >> (23 - man)) << (23 - man));
-  return u2f(qb);
-}
-struct HadMxfpBlock {
-  float scale;
-  bool zero;
-  __device__ __forceinline__ void setup(uint32_t maxbits, const HadCast& f) {
-    const float m = u2f(maxbits);
-    zero = m == 0.0f;
-    // the reference evaluates 2^floor(log2 m) / 2^(2^(e-1)) in fp32 (format.py:551-555).  No libm: a float32 log2 within an ulp
-    // of the truth crosses an integer only for m = 2^v (1 - j 2^-24) with j <= jmax(v) (the rule and its proof sketch are in
-    // oracle/oracle.c oracle_floor_log2f; checked against torch.log2 for every exponent, fixtures tests/golden/boundaries.npz)
-    int eb = (int)(maxbits >> 23);
-    if (eb >= 1 && eb <= 254) {
-      const uint32_t man = maxbits & 0x007FFFFFu;
-      const int v = eb - 126;  // floor(log2 m) + 1
-      if (man != 0u && v != 0) {
-        const uint32_t a = (uint32_t)(v < 0 ? -v : v), j = 0x00800000u - man;
-        const int c = 31 - __builtin_clz(a);
-        const int g = (v > 0 && (a & (a - 1u)) == 0u) ? 25 - c : 24 - c;  // 17 .. 25
-        // jmax = floor(2^24 (1 - 2^(-2^-g))): 88 44 22 11 | 5 2 1 | 0 0, as bytes of two constants
-        const uint32_t jmax = g <= 20 ? ((0x0B162C58u >> (8 * (g - 17))) & 0xFFu) : (g <= 23 ? ((0x00010205u >> (8 * (g - 21))) & 0xFFu) : 0u);
-        if (j <= jmax) eb += 1;
-      }
-      const int se = eb - f.big_log2;
-      if (eb == 255) scale = INFINITY;                      // 2^128: the reference's fp32 power overflows too
-      else if (se >= 1) scale = u2f((uint32_t)se << 23);
-      else scale = ldexpf(1.0f, se - 127);                  // a denormal (or zero) scale, exact
-    } else {
-      scale = exp2f(floorf(log2f(m))) / f.big;              // zero (see `zero`), denormal, Inf, NaN maxima
-    }
-  }
-  __device__ __forceinline__ float apply(float x, const HadCast& f) const {
-    if (zero) return x * 0.0f;
-    return had_float_q_nearest(x / scale, f.man, f.exp_bits, f.bias, 0) * scale;
-  }
-};
-
 // q = Q(x) for this lane's V elements of the rotated tensor.  Called by whole waves (the block maxima cross lanes).
 template <int V>
 __device__ __forceinline__ void had_cast(const float (&x)[V], float (&q)[V], const HadCast& c, float sc, float z) {
   if (c.kind == DMXQ_GPTQ_FLOAT) {
 #pragma unroll
-    for (int j = 0; j < V; j++) q[j] = float_q1<DMXQ_ROUND_NEAREST>(x[j], c.f, 0u);
+    for (int j = 0; j < V; j++) q[j] = float_q1<DMXQ_ROUND_NEAREST>(x[j], c.d.f, 0u);
   } else if (c.kind == DMXQ_GPTQ_FIXED) {
 #pragma unroll
-    for (int j = 0; j < V; j++) q[j] = (fixed_q1(x[j] / sc + z, c.x, 0.5f) - z) * sc;
+    for (int j = 0; j < V; j++) q[j] = fixed_affine_q1(x[j], sc, z, c.d.x);
   } else {
     // a block of >= V elements: ONE pass, the maximum over block_size / V lanes; a block smaller than the vector: one pass per sub-block,
     // each keeping its own elements
@@ -159,19 +95,18 @@ __device__ __forceinline__ void had_cast(const float (&x)[V], float (&q)[V], con
         if (passes == 1 || (j >> c.blog) == g) bm = umax(bm, f2u(x[j]) & 0x7FFFFFFFu);
       if (B > V) bm = group_max_u32(bm, B / V);   // (wave-uniform: blocks are aligned groups of B / V lanes)
       if (c.kind == DMXQ_GPTQ_BFP) {
-        const BfpBlockParams p = bfp_block_params<true, false>(bm, c.wl);
+        const BfpBlockParams p = bfp_block_params<true, false>(bm, c.d.wl);
 #pragma unroll
         for (int j = 0; j < V; j++) {
-          float v = bfp_q1<DMXQ_ROUND_NEAREST, false>(x[j], p, c.wl, DMXQ_ROUND_NEAREST, 0u);
-          if (c.asym) v = (x[j] <= p.thr) ? p.neg_lim : v;   // bfp_q1<.., ASYM = true>, the flag at run time (wave-uniform)
+          const float v = bfp_q1_nearest_rt(x[j], p, c.d.wl, c.d.asym != 0);
           q[j] = (passes == 1 || (j >> c.blog) == g) ? v : q[j];
         }
       } else {
-        HadMxfpBlock b;
-        b.setup(bm, c);
+        const float bs = mxfp_block_scale(bm, c.d.k.big_log2, c.d.k.big, 0);
+        const bool zero = u2f(bm) == 0.0f;
 #pragma unroll
         for (int j = 0; j < V; j++) {
-          const float v = b.apply(x[j], c);
+          const float v = mxfp_q1(x[j], bs, zero, c.d.man, c.d.exp_bits, c.d.k.bias);
           q[j] = (passes == 1 || (j >> c.blog) == g) ? v : q[j];
         }
       }
@@ -239,37 +174,14 @@ extern "C" int dmxq_hadamard_qdq(const void* in, void* out, int dtype_in, int dt
   c.kind = kHadRotateOnly;
   c.inverse = inverse ? 1 : 0;
   if (fmt) {
+    if (format_desc(*fmt, &c.d) != DMXQ_OK) return DMXQ_ERR_UNSUPPORTED;
     c.kind = fmt->kind;
-    if (fmt->kind == DMXQ_GPTQ_BFP) {
+    if (fmt->kind == DMXQ_GPTQ_BFP || fmt->kind == DMXQ_GPTQ_MXFP) {   // blocks: a power of two dividing the rotation's (BFP: >= 2)
       const int B = fmt->block_size;
-      if (B < 2 || !pow2(B) || size % B != 0 || fmt->precision < 2 || fmt->precision > 22) return DMXQ_ERR_UNSUPPORTED;
+      if (B < (fmt->kind == DMXQ_GPTQ_BFP ? 2 : 1) || !pow2(B) || size % B != 0) return DMXQ_ERR_UNSUPPORTED;
       c.blog = log2i(B);
-      c.wl = fmt->precision;
-      c.asym = fmt->symmetric == 0;
-    } else if (fmt->kind == DMXQ_GPTQ_MXFP) {
-      const int B = fmt->block_size;
-      if (B < 1 || !pow2(B) || size % B != 0 || fmt->exp_bits < 1 || fmt->exp_bits > 8 || fmt->man_bits < 0 || fmt->man_bits > 22)
-        return DMXQ_ERR_UNSUPPORTED;
-      c.blog = log2i(B);
-      c.man = fmt->man_bits;
-      c.exp_bits = fmt->exp_bits;
-      c.bias = (1 << (fmt->exp_bits - 1)) - 1;          // dmxq_mxfp_qdq's MxfpFmt, field by field
-      c.big_log2 = 1 << (fmt->exp_bits - 1);
-      c.big = (float)ldexp(1.0, 1 << (fmt->exp_bits - 1));
-    } else if (fmt->kind == DMXQ_GPTQ_FLOAT) {
-      if (fmt->exp_bits < 1 || fmt->exp_bits > 8 || fmt->man_bits < 0 || fmt->man_bits > 22) return DMXQ_ERR_UNSUPPORTED;
-      c.f = FloatFmt{fmt->man_bits, fmt->exp_bits, fmt->exp_bias, fmt->flush_subnormal ? 1 : 0, fmt->unsigned_abs ? 1 : 0,
-                     DMXQ_ROUND_NEAREST, 0ull};
-    } else {
-      if (fmt->precision < 1 || fmt->precision > 24) return DMXQ_ERR_UNSUPPORTED;
-      // sim_helper.cpp:5-12 fixed_min_max, evaluated on the host in the same float/double mix as dmxq_fixed_qdq
-      const int precision = fmt->precision, fraction = fmt->fraction, sigma = -fraction;
-      float t_min = (float)(-ldexp(1.0, precision - fraction - 1));
-      const float t_max = (float)(-(double)t_min - ldexp(1.0, sigma));
-      if (fmt->symmetric) t_min = (float)((double)t_min + ldexp(1.0, sigma));
-      c.x = FixedFmt{sigma, fmt->clamp ? 1 : 0, DMXQ_ROUND_NEAREST, t_min, t_max, 0ull};
-      c.per_row = fmt->per_row ? 1 : 0;
     }
+    c.per_row = fmt->kind == DMXQ_GPTQ_FIXED && fmt->per_row ? 1 : 0;
   }
   if (rows == 0 || L == 0) return DMXQ_OK;
   if (!in || !out) return DMXQ_ERR_BAD_ARG;

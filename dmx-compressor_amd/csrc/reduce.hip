@@ -215,11 +215,9 @@ __global__ void fill2_kernel(float* a, float va, float* b, float vb, int64_t n) 
   }
 }
 
-// (lo, hi) of every lane -> one pair per workgroup -> the float atomics, on ORDER-PRESERVING KEYS: key(f) = bits ^ (sign ? ~0 : 1 << 31)
-// orders like the floats as an unsigned integer, puts -NaN below -Inf and +NaN above +Inf -- so a lane that saw a NaN (and carries
-// (-NaN, +NaN)) wins every unsigned min / max of the combine with no special case and no branch, like it wins the atomics.
-__device__ __forceinline__ uint32_t fkey(float f) { const uint32_t b = f2u(f); return b ^ ((uint32_t)((int32_t)b >> 31) | 0x80000000u); }
-__device__ __forceinline__ float fkey_inv(uint32_t k) { return u2f(k ^ ((k & 0x80000000u) ? 0x80000000u : 0xFFFFFFFFu)); }
+// (lo, hi) of every lane -> one pair per workgroup -> the float atomics, on the order-preserving keys of reduce_common.hpp (fkey): a
+// lane that saw a NaN (and carries (-NaN, +NaN)) wins every unsigned min / max of the combine with no special case and no branch, like
+// it wins the atomics.
 __device__ __forceinline__ void wave_minmax_keys(uint32_t& lo, uint32_t& hi) {
   // 16-lane rows by DPP (no LDS crossbar), then two xor shuffles across the rows
 #define DMXQ_MM_DPP(ctrl)                                                                                   \

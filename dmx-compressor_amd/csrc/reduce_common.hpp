@@ -67,6 +67,12 @@ struct FloatExtrema {
   __device__ __forceinline__ float mx() const { return nan() ? u2f(0x7FC00000u) : hi; }
 };
 
+// ORDER-PRESERVING KEYS of float values: key(f) = bits ^ (sign ? ~0 : 1 << 31) orders like the floats as an unsigned integer and puts
+// -NaN below -Inf and +NaN above +Inf, so a minimum / maximum across lanes is an integer one (DPP, shuffles, LDS) and a (-NaN, +NaN)
+// pair wins it.  csrc/reduce.hip (dmxq_group_minmax) and csrc/dynamic_quant.hip (a segment's extrema).
+__device__ __forceinline__ uint32_t fkey(float f) { const uint32_t b = f2u(f); return b ^ ((uint32_t)((int32_t)b >> 31) | 0x80000000u); }
+__device__ __forceinline__ float fkey_inv(uint32_t k) { return u2f(k ^ ((k & 0x80000000u) ? 0x80000000u : 0xFFFFFFFFu)); }
+
 // (min, max) -> (scale, zero_point) of one group (numerical/observer.py:59-115 _calculate_qparams): dmxq_qparams and the
 // HistogramObserver's search kernel (csrc/hist_observer.hip)
 __device__ __forceinline__ void qparams_one(float mn, float mx, int qmin, int qmax, int sym, float& scale, int64_t& zp) {

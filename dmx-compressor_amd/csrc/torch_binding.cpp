@@ -818,6 +818,13 @@ Tensor norm_cast_meta(const Tensor& x, int64_t, const OptTensor&, const OptTenso
 }
 
 // ------------------------------------------------------------------------------------------------ GPTQ
+// the 12 fields of a dmxq_gptq_format in the struct's order, as every raw op that takes a format passes them: one format, or one
+// format's slice of a list
+inline dmxq_gptq_format gptq_format_of(at::IntArrayRef v, const char* what) {
+  TORCH_CHECK(v.size() == 12, what, ": fmt is the 12 fields of dmxq_gptq_format");
+  return dmxq_gptq_format{(int)v[0], (int)v[1], (int)v[2], (int)v[3], (int)v[4], (int)v[5], (int)v[6], (int)v[7], (int)v[8], (int)v[9], (int)v[10],
+                          (int)v[11]};
+}
 // one column block of GPTQ's in-block loop (dmxq_gptq_block): q and err are written in place (views of the caller's Q and E)
 inline void gptq_matrix(const Tensor& t, const Tensor& w, const char* name) {
   TORCH_CHECK(t.is_cuda() && t.device() == w.device() && t.scalar_type() == at::kFloat && t.dim() == 2 && (t.size(1) <= 1 || t.stride(1) == 1),
@@ -827,7 +834,7 @@ void gptq_block(const Tensor& w, const Tensor& hinv, const Tensor& inv_d, int64_
                 const OptTensor& zero_point, Tensor q, Tensor err) {
   TORCH_CHECK(w.is_cuda(), "gptq_block: tensor is on ", w.device(), "; dmx_compressor_amd runs on MI355X (HIP) tensors only and has no CPU fallback");
   gptq_matrix(w, w, "w"); gptq_matrix(hinv, w, "hinv"); gptq_matrix(q, w, "q"); gptq_matrix(err, w, "err");
-  TORCH_CHECK(fmt.size() == 12, "gptq_block: fmt is the 12 fields of dmxq_gptq_format");
+  const dmxq_gptq_format f = gptq_format_of(fmt, "gptq_block");
   TORCH_CHECK(microblock >= 1, "gptq_block: microblock must be positive");
   const int64_t rows = w.size(0), count = w.size(1), nmb = (count + microblock - 1) / microblock;
   TORCH_CHECK(q.size(0) == rows && q.size(1) == count && err.size(0) == rows && err.size(1) == count && hinv.size(0) == count &&
@@ -840,8 +847,6 @@ void gptq_block(const Tensor& w, const Tensor& hinv, const Tensor& inv_d, int64_
               "gptq_block: scale must be a contiguous float32 tensor on w's GPU");
   TORCH_CHECK(!has_zp || (zero_point->is_cuda() && zero_point->device() == w.device() && zero_point->scalar_type() == at::kLong &&
               zero_point->is_contiguous()), "gptq_block: zero_point must be a contiguous int64 tensor on w's GPU");
-  const dmxq_gptq_format f{(int)fmt[0], (int)fmt[1], (int)fmt[2], (int)fmt[3], (int)fmt[4], (int)fmt[5], (int)fmt[6], (int)fmt[7],
-                           (int)fmt[8], (int)fmt[9], (int)fmt[10], (int)fmt[11]};
   TORCH_CHECK(f.kind != DMXQ_GPTQ_FIXED || !f.per_row || (has_sc && has_zp && scale->numel() >= rows && zero_point->numel() >= rows),
               "gptq_block: a per-row fixed point cast needs a scale and a zero point per row");
   TORCH_CHECK(f.kind != DMXQ_GPTQ_FIXED || (has_sc && has_zp && scale->numel() >= 1 && zero_point->numel() >= 1),
@@ -861,7 +866,7 @@ void gptq_block_dynamic(const Tensor& w, const Tensor& hinv, const Tensor& inv_d
                         int64_t group, int64_t qmin, int64_t qmax, bool symmetric_qscheme, Tensor q, Tensor err, Tensor scale_out, Tensor zp_out) {
   TORCH_CHECK(w.is_cuda(), "gptq_block_dynamic: tensor is on ", w.device(), "; dmx_compressor_amd runs on MI355X (HIP) tensors only and has no CPU fallback");
   gptq_matrix(w, w, "w"); gptq_matrix(hinv, w, "hinv"); gptq_matrix(q, w, "q"); gptq_matrix(err, w, "err"); gptq_matrix(scale_out, w, "scale_out");
-  TORCH_CHECK(fmt.size() == 12, "gptq_block_dynamic: fmt is the 12 fields of dmxq_gptq_format");
+  const dmxq_gptq_format f = gptq_format_of(fmt, "gptq_block_dynamic");
   TORCH_CHECK(microblock >= 1 && group >= 1, "gptq_block_dynamic: microblock and group must be positive");
   const int64_t rows = w.size(0), count = w.size(1), nmb = (count + microblock - 1) / microblock, ng = count / group;
   TORCH_CHECK(q.size(0) == rows && q.size(1) == count && err.size(0) == rows && err.size(1) == count && hinv.size(0) == count &&
@@ -873,8 +878,6 @@ void gptq_block_dynamic(const Tensor& w, const Tensor& hinv, const Tensor& inv_d
               (zp_out.size(1) <= 1 || zp_out.stride(1) == 1), "gptq_block_dynamic: zp_out must be an int64 matrix with unit column stride on w's GPU");
   TORCH_CHECK(scale_out.size(0) == rows && scale_out.size(1) == ng && zp_out.size(0) == rows && zp_out.size(1) == ng,
               "gptq_block_dynamic: scale_out and zp_out must be [rows, count / group] = [", rows, ", ", ng, "]");
-  const dmxq_gptq_format f{(int)fmt[0], (int)fmt[1], (int)fmt[2], (int)fmt[3], (int)fmt[4], (int)fmt[5], (int)fmt[6], (int)fmt[7],
-                           (int)fmt[8], (int)fmt[9], (int)fmt[10], (int)fmt[11]};
   auto ld = [](const Tensor& t, int64_t n) { return t.size(0) <= 1 ? std::max<int64_t>(t.stride(0), n) : t.stride(0); };
   Launch l(w);
   check(dmxq_gptq_block_dynamic((const float*)w.data_ptr(), ld(w, count), (float*)q.data_ptr(), ld(q, count), (float*)err.data_ptr(), ld(err, count),
@@ -968,11 +971,7 @@ void cast_error(const Tensor& x, at::IntArrayRef fmts, const OptTensor& scale, c
               zero_point->is_contiguous() && zero_point->numel() >= K),
               "cast_error: zero_point must be a contiguous int64 tensor with an entry per format on x's GPU");
   std::vector<dmxq_gptq_format> f((size_t)K);
-  for (int64_t k = 0; k < K; k++) {
-    const int64_t* v = fmts.data() + 12 * k;
-    f[(size_t)k] = dmxq_gptq_format{(int)v[0], (int)v[1], (int)v[2], (int)v[3], (int)v[4], (int)v[5], (int)v[6], (int)v[7], (int)v[8], (int)v[9],
-                                    (int)v[10], (int)v[11]};
-  }
+  for (int64_t k = 0; k < K; k++) f[(size_t)k] = gptq_format_of(fmts.slice(12 * k, 12), "cast_error");
   const int64_t L = xc.dim() ? xc.size(-1) : 1, rows = L ? xc.numel() / L : 0;
   Launch l(xc);
   check(dmxq_cast_error(xc.data_ptr(), dt_code(xc.scalar_type()), rows, L, f.data(), (int)K, has_sc ? (const float*)scale->data_ptr() : nullptr,
@@ -993,9 +992,7 @@ Tensor hadamard_qdq(const Tensor& x, int64_t size, bool inverse, at::IntArrayRef
   Tensor out = empty_like_shape(xc, out_dtype);
   const int64_t L = xc.size(-1), rows = L ? xc.numel() / L : 0;
   dmxq_gptq_format f{};
-  if (!fmt.empty())
-    f = dmxq_gptq_format{(int)fmt[0], (int)fmt[1], (int)fmt[2], (int)fmt[3], (int)fmt[4], (int)fmt[5], (int)fmt[6], (int)fmt[7], (int)fmt[8],
-                         (int)fmt[9], (int)fmt[10], (int)fmt[11]};
+  if (!fmt.empty()) f = gptq_format_of(fmt, "hadamard_qdq");
   const bool has_sc = scale.has_value() && scale->defined(), has_zp = zero_point.has_value() && zero_point->defined();
   const int64_t need = (!fmt.empty() && f.kind == DMXQ_GPTQ_FIXED) ? (f.per_row ? rows : 1) : 0;
   TORCH_CHECK(!has_sc || (scale->is_cuda() && scale->device() == xc.device() && scale->scalar_type() == at::kFloat && scale->is_contiguous()),

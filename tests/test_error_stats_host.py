@@ -71,6 +71,24 @@ def test_entry_points_validate_without_a_device(dmx):
               (lib.GPTQ_BFP, 1, 16, 1) + (0,) * 8, (lib.GPTQ_FLOAT, 0, 0, 0, 23, 8, 127, 0, 0, 0, 0, 0), int8[:11] + (1,)):
         k, ptr = fmts(f)
         assert call(ptr, 1, L_=256, scale=p, zp=p) == lib.ERR_UNSUPPORTED, f
+    # the range checks every user of dmxq_gptq_format shares, each reached through this entry point
+    for f in ((lib.GPTQ_FIXED, 0, 0, 1, 0, 0, 0, 0, 0, 0, 1, 0), (lib.GPTQ_FIXED, 25, 0, 1, 0, 0, 0, 0, 0, 0, 1, 0),
+              (lib.GPTQ_FLOAT, 0, 0, 0, 3, 0, 7, 0, 0, 0, 0, 0), (lib.GPTQ_FLOAT, 0, 0, 0, 3, 9, 7, 0, 0, 0, 0, 0),
+              (lib.GPTQ_FLOAT, 0, 0, 0, -1, 4, 7, 0, 0, 0, 0, 0)):
+        k, ptr = fmts(f)
+        assert call(ptr, 1, L_=256, scale=p, zp=p) == lib.ERR_UNSUPPORTED, f
+    k, ptr = fmts((lib.GPTQ_MXFP, 0, 32, 0, 1, 2, 0, 0, 0, 0, 0, 0))
+    assert call(ptr, 1, L_=256) == lib.ERR_BAD_ARG                                # MXFP: refused like any unknown kind
+    # a shared range check and a rule of this entry point broken at once: every format's kind is judged first, the format's ranges
+    # before the input pointer and before the size of the scratch
+    k, ptr = fmts((lib.GPTQ_FLOAT, 0, 0, 0, 23, 8, 127, 0, 0, 0, 0, 0), (9,) + bfp[1:])
+    assert call(ptr, 2, L_=256) == lib.ERR_BAD_ARG
+    k, ptr = fmts((lib.GPTQ_FLOAT, 0, 0, 0, 23, 8, 127, 0, 0, 0, 0, 0))
+    assert L.dmxq_cast_error(p, lib.BF16, 4, 256, ptr, 1, null, null, 0, p, p, 8, null) == lib.ERR_UNSUPPORTED
+    k, ptr = fmts(bfp)
+    assert L.dmxq_cast_error(p, lib.BF16, 4, 256, ptr, 1, null, null, 0, p, p, 8, null) == lib.ERR_BAD_ARG
+    k, ptr = fmts((lib.GPTQ_FIXED, 25, 0, 1, 0, 0, 0, 0, 0, 0, 1, 1))
+    assert call(ptr, 1, L_=256, in_=null) == lib.ERR_UNSUPPORTED
     keepi, fixed = fmts(int8)
     assert call(fixed, 1) == lib.ERR_UNSUPPORTED                                  # a fixed point format without its scale / zero point
     assert call(one, 1, rows=0, acc=1) == lib.OK                                  # n == 0 merged into a row: no-op

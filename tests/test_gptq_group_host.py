@@ -80,6 +80,14 @@ def test_abi_status_codes(dmx):
     assert call(fmt=lib.GptqFormat(lib.GPTQ_FIXED, 4, 0, 1, 0, 0, 0, 0, 0, 1, 1, 1)) == lib.ERR_UNSUPPORTED   # fraction != 0
     assert call(fmt=lib.GptqFormat(lib.GPTQ_FIXED, 4, 0, 1, 0, 0, 0, 0, 0, 0, 0, 1)) == lib.ERR_UNSUPPORTED   # no clamp
     assert call(fmt=lib.GptqFormat(lib.GPTQ_FIXED, 23, 0, 1, 0, 0, 0, 0, 0, 0, 1, 1)) == lib.ERR_UNSUPPORTED  # precision > 22
+    # the fixed point range check every user of dmxq_gptq_format shares, reached through this entry point; broken together with one of
+    # this entry point's own rules, the format is judged before the output strides and after the output pointers
+    for prec in (0, 25):
+        bad = lib.GptqFormat(lib.GPTQ_FIXED, prec, 0, 1, 0, 0, 0, 0, 0, 0, 1, 1)
+        assert call(fmt=bad) == lib.ERR_UNSUPPORTED, prec
+        assert call(fmt=bad, group=32, lds=3, ldz=3) == lib.ERR_UNSUPPORTED, prec
+        assert call(fmt=bad, so=null) == lib.ERR_BAD_ARG, prec
+        assert call(fmt=bad, rows=0) == lib.OK, prec
     # ---- DMXQ_ERR_BAD_ARG: dmxq_gptq_block's rules ...
     assert call(fmt=None) == lib.ERR_BAD_ARG
     assert call(w=null) == lib.ERR_BAD_ARG and call(q=null) == lib.ERR_BAD_ARG and call(err=null) == lib.ERR_BAD_ARG

@@ -77,6 +77,23 @@ def test_abi_argument_checks(dmx):
     assert L.dmxq_gptq_block(*ok, 1, ctypes.byref(fx), null, null, null) == lib.ERR_BAD_ARG                # fixed point without scale
     bf = lib.GptqFormat(lib.GPTQ_BFP, 8, 16, 1, 0, 0, 0, 0, 0, 0, 0, 0)
     assert L.dmxq_gptq_block(*ok, 8, ctypes.byref(bf), null, null, null) == lib.ERR_UNSUPPORTED            # blocks wider than the microblock
+    # the range checks every user of dmxq_gptq_format shares, each reached through this entry point
+    for bad in ((lib.GPTQ_FIXED, 0, 0, 1, 0, 0, 0, 0, 0, 0, 1, 0), (lib.GPTQ_FIXED, 25, 0, 1, 0, 0, 0, 0, 0, 0, 1, 0),
+                (lib.GPTQ_FLOAT, 0, 0, 0, 3, 0, 7, 0, 0, 0, 0, 0), (lib.GPTQ_FLOAT, 0, 0, 0, 3, 9, 7, 0, 0, 0, 0, 0),
+                (lib.GPTQ_FLOAT, 0, 0, 0, 23, 8, 127, 0, 0, 0, 0, 0), (lib.GPTQ_FLOAT, 0, 0, 0, -1, 4, 7, 0, 0, 0, 0, 0),
+                (lib.GPTQ_BFP, 1, 8, 1, 0, 0, 0, 0, 0, 0, 0, 0), (lib.GPTQ_BFP, 23, 8, 1, 0, 0, 0, 0, 0, 0, 0, 0)):
+        assert L.dmxq_gptq_block(*ok, 8, ctypes.byref(lib.GptqFormat(*bad)), one, one, null) == lib.ERR_UNSUPPORTED, bad
+    mx = lib.GptqFormat(lib.GPTQ_MXFP, 0, 8, 0, 1, 2, 0, 0, 0, 0, 0, 0)
+    assert L.dmxq_gptq_block(*ok, 8, ctypes.byref(mx), null, null, null) == lib.ERR_BAD_ARG                # MXFP: like any unknown kind
+    # a shared range check and a rule of this entry point broken at once: pointers, strides and a fixed point format's scale are judged
+    # before the format's ranges, the kind before everything but the sizes' signs
+    wide = lib.GptqFormat(lib.GPTQ_FLOAT, 0, 0, 0, 23, 8, 127, 0, 0, 0, 0, 0)
+    assert L.dmxq_gptq_block(null, 64, one, 64, one, 64, 8, 64, one, 64, one, 1, ctypes.byref(wide), null, null, null) == lib.ERR_BAD_ARG
+    assert L.dmxq_gptq_block(one, 32, one, 64, one, 64, 8, 64, one, 64, one, 1, ctypes.byref(wide), null, null, null) == lib.ERR_BAD_ARG
+    fx25 = lib.GptqFormat(lib.GPTQ_FIXED, 25, 0, 1, 0, 0, 0, 0, 0, 0, 1, 1)
+    assert L.dmxq_gptq_block(*ok, 1, ctypes.byref(fx25), null, null, null) == lib.ERR_BAD_ARG
+    assert L.dmxq_gptq_block(null, 64, null, 64, null, 64, 0, 64, null, 64, null, 1, ctypes.byref(wide), null, null, null) == lib.OK   # nothing to do
+    assert L.dmxq_gptq_block(*ok, 0, ctypes.byref(mx), null, null, null) == lib.ERR_BAD_ARG
     assert L.dmxq_abi_version() == 4
 
 

@@ -123,6 +123,20 @@ def test_c_abi_argument_validation(dmx):
     assert call(one, one, lib.BF16, lib.BF16, 4, 64, 64, 1, fmt(lib.GPTQ_MXFP, 0, 48, 0, 1, 2, 0, 0, 0, 0, 0, 0), null, null, null) == lib.ERR_UNSUPPORTED
     assert call(one, one, lib.BF16, lib.BF16, 4, 64, 64, 1, fmt(lib.GPTQ_MXFP, 0, 32, 0, 23, 8, 0, 0, 0, 0, 0, 0), null, null, null) == lib.ERR_UNSUPPORTED
     assert call(one, one, lib.BF16, lib.BF16, 4, 64, 64, 1, fmt(lib.GPTQ_FLOAT, 0, 0, 0, 23, 8, 127, 0, 0, 0, 0, 0), null, null, null) == lib.ERR_UNSUPPORTED
+    # the range checks every user of dmxq_gptq_format shares, each reached through this entry point
+    sc = one
+    for bad in ((lib.GPTQ_FIXED, 0, 0, 1, 0, 0, 0, 0, 0, 0, 1, 0), (lib.GPTQ_FIXED, 25, 0, 1, 0, 0, 0, 0, 0, 0, 1, 0),
+                (lib.GPTQ_FLOAT, 0, 0, 0, 3, 0, 7, 0, 0, 0, 0, 0), (lib.GPTQ_FLOAT, 0, 0, 0, 3, 9, 7, 0, 0, 0, 0, 0),
+                (lib.GPTQ_FLOAT, 0, 0, 0, -1, 4, 7, 0, 0, 0, 0, 0),
+                (lib.GPTQ_MXFP, 0, 32, 0, 1, 0, 0, 0, 0, 0, 0, 0), (lib.GPTQ_MXFP, 0, 32, 0, 1, 9, 0, 0, 0, 0, 0, 0),
+                (lib.GPTQ_MXFP, 0, 32, 0, -1, 2, 0, 0, 0, 0, 0, 0)):
+        assert call(one, one, lib.BF16, lib.BF16, 4, 64, 64, 1, fmt(*bad), sc, sc, null) == lib.ERR_UNSUPPORTED, bad
+    # a shared range check and a rule of this entry point broken at once: the format is judged before the pointers and before "nothing to do"
+    assert call(null, null, lib.BF16, lib.BF16, 4, 64, 64, 1, fmt(lib.GPTQ_FLOAT, 0, 0, 0, 23, 8, 127, 0, 0, 0, 0, 0), null, null, null) == lib.ERR_UNSUPPORTED
+    assert call(one, one, lib.BF16, lib.BF16, 4, 64, 64, 1, fmt(lib.GPTQ_FIXED, 25, 0, 1, 0, 0, 0, 0, 0, 0, 1, 0), null, null, null) == lib.ERR_UNSUPPORTED
+    assert call(null, null, lib.BF16, lib.BF16, 0, 64, 64, 1, fmt(lib.GPTQ_BFP, 23, 16, 1, 0, 0, 0, 0, 0, 0, 0, 0), null, null, null) == lib.ERR_UNSUPPORTED
+    # ... but after the block size of the rotation and the format's kind
+    assert call(one, one, lib.BF16, lib.BF16, 4, 1536, 48, 1, fmt(4, 23, 16, 1, 0, 0, 0, 0, 0, 0, 0, 0), null, null, null) == lib.ERR_BAD_ARG
     # the other users of dmxq_gptq_format answer kind 3 as they answer any unknown kind
     assert L.dmxq_cast_error(one, lib.BF16, 4, 64, ctypes.cast(ctypes.pointer(lib.GptqFormat(lib.GPTQ_MXFP, 0, 32, 0, 1, 2, 0, 0, 0, 0, 0, 0)),
                                                                 ctypes.c_void_p), 1, null, null, 0, one, one, 1 << 20, null) == lib.ERR_BAD_ARG

@@ -203,6 +203,49 @@ def main():
         lambda i: L.dmxq_mxfp_qdq(vp(xs[i].data_ptr()), vp(ys[i].data_ptr()), _lib.BF16, _lib.BF16, R, C, 1, 32, 3, 4, sp), k, n * 4)
     run("mxfp_qdq bf16 MXFP4[E2M1]{32}",
         lambda i: L.dmxq_mxfp_qdq(vp(xs[i].data_ptr()), vp(ys[i].data_ptr()), _lib.BF16, _lib.BF16, R, C, 1, 32, 1, 2, sp), k, n * 4)
+    run("sbfp_qdq float32 SBFP12_16",
+        lambda i: L.dmxq_sbfp_qdq(vp(f32a[i % 6].data_ptr()), vp(f32o[i % 6].data_ptr()), _lib.F32, _lib.F32, R, C, 1, 16, 4, 1, 1, 4, 4, 7, 1, sp), 6, n * 8)
+    run("mxfp_qdq float32 MXFP8[E4M3]{32}",
+        lambda i: L.dmxq_mxfp_qdq(vp(f32a[i % 6].data_ptr()), vp(f32o[i % 6].data_ptr()), _lib.F32, _lib.F32, R, C, 1, 32, 3, 4, sp), 6, n * 8)
+    # ---------------------------------------------------------------- the casts that run inside another kernel's loop
+    GF = _lib.GptqFormat
+    bfp8 = GF(_lib.GPTQ_BFP, 8, 16, 1, 0, 0, 0, 0, 0, 0, 0, 0)
+    mxfp4 = GF(_lib.GPTQ_MXFP, 0, 32, 0, 1, 2, 0, 0, 0, 0, 0, 0)
+    for nm, gf in (("BFP[8|8]{16}(SN)", bfp8), ("MXFP4[E2M1]{32}", mxfp4)):
+        run(f"hadamard_qdq bf16 H=64 rotate -> {nm} -> rotate back",
+            lambda i: L.dmxq_hadamard_qdq(vp(xs[i].data_ptr()), vp(ys[i].data_ptr()), _lib.BF16, _lib.BF16, R, C, 64, 1, ctypes.byref(gf), None, None, sp), k, n * 4)
+    sweep = (GF * 8)(bfp8, GF(_lib.GPTQ_BFP, 4, 32, 1, 0, 0, 0, 0, 0, 0, 0, 0), GF(_lib.GPTQ_BFP, 8, 64, 0, 0, 0, 0, 0, 0, 0, 0, 0),
+                     GF(_lib.GPTQ_BFP, 6, 128, 1, 0, 0, 0, 0, 0, 0, 0, 0), GF(_lib.GPTQ_FLOAT, 0, 0, 0, 3, 4, 7, 0, 0, 0, 0, 0),
+                     GF(_lib.GPTQ_FLOAT, 0, 0, 0, 2, 5, 15, 0, 0, 0, 0, 0), GF(_lib.GPTQ_FIXED, 8, 0, 1, 0, 0, 0, 0, 0, 0, 1, 0),
+                     GF(_lib.GPTQ_FIXED, 4, 0, 1, 0, 0, 0, 0, 0, 0, 1, 0))
+    esc = torch.full((8,), 0.05, device=dev)
+    ezp = torch.zeros(8, dtype=torch.int64, device=dev)
+    est = torch.zeros(8, 4, dtype=torch.float64, device=dev)
+    ews = torch.empty(L.dmxq_error_scratch_bytes(n, 8) // 8 + 1, dtype=torch.float64, device=dev)
+    run("cast_error bf16 K=8 (4 BFP, 2 float, 2 integer formats from one read)",
+        lambda i: L.dmxq_cast_error(vp(xs[i].data_ptr()), _lib.BF16, R, C, ctypes.cast(sweep, vp), 8, vp(esc.data_ptr()), vp(ezp.data_ptr()), 0,
+                                    vp(est.data_ptr()), vp(ews.data_ptr()), ews.numel() * 8, sp), k, n * 2)
+    run("dynamic_fixed_qdq bf16 INT8 per-token (rows of 4096)",
+        lambda i: L.dmxq_dynamic_fixed_qdq(vp(xs[i].data_ptr()), vp(ys[i].data_ptr()), _lib.BF16, _lib.BF16, R, C, 1, 8, 0, 1, 1, 2, -127, 127, 1, None, None, sp), k, n * 4)
+    run("dynamic_fixed_qdq bf16 INT4 per-group of 128",
+        lambda i: L.dmxq_dynamic_fixed_qdq(vp(xs[i].data_ptr()), vp(ys[i].data_ptr()), _lib.BF16, _lib.BF16, n // 128, 128, 0, 4, 0, 1, 1, 2, -7, 7, 1, None, None, sp), k, n * 4)
+    slabs = [(_lib.AffineDesc * 4)(*[_lib.AffineDesc(vp(xs[i][j * (R // 4):].data_ptr()), vp(ys[i][j * (R // 4):].data_ptr()), vp(sc.data_ptr()), vp(zp.data_ptr()),
+                                                      1, R // 4, C) for j in range(4)]) for i in range(k)]
+    run("fixed_qdq_multi bf16 INT8 group_size=128, four [R/4, C] weights in one launch",
+        lambda i: L.dmxq_fixed_qdq_multi(ctypes.cast(slabs[i], vp), 4, _lib.BF16, _lib.BF16, 8, 0, 1, 1, 2, 128, 0, sp), k, n * 4)
+    gw = torch.randn(R, 128, device=dev) * 0.05
+    gq, ge = torch.empty_like(gw), torch.empty_like(gw)
+    ghinv = (torch.triu(torch.randn(128, 128, device=dev)) * 0.01 + torch.eye(128, device=dev)).contiguous()
+    ginvd = (1.0 / torch.diagonal(ghinv)).contiguous()
+    gsc = torch.full((R,), 0.02, device=dev)
+    gzp = torch.zeros(R, dtype=torch.int64, device=dev)
+    gso, gzo = torch.empty(R, 1, device=dev), torch.empty(R, 1, dtype=torch.int64, device=dev)
+    int4 = GF(_lib.GPTQ_FIXED, 4, 0, 1, 0, 0, 0, 0, 0, 0, 1, 1)
+    gargs = (vp(gw.data_ptr()), 128, vp(gq.data_ptr()), 128, vp(ge.data_ptr()), 128, R, 128, vp(ghinv.data_ptr()), 128, vp(ginvd.data_ptr()), 1, ctypes.byref(int4))
+    run("gptq_block float32 [R, 128] columns, microblock 1, INT4 per-row scales",
+        lambda i: L.dmxq_gptq_block(*gargs, vp(gsc.data_ptr()), vp(gzp.data_ptr()), sp), 1, R * 128 * 12)
+    run("gptq_block_dynamic float32 [R, 128] columns, microblock 1, INT4 group 128",
+        lambda i: L.dmxq_gptq_block_dynamic(*gargs, 2, 128, -7, 7, 1, vp(gso.data_ptr()), 1, vp(gzo.data_ptr()), 1, sp), 1, R * 128 * 12)
     mant = [torch.empty(R, C, dtype=torch.int8, device=dev) for _ in range(k)]
     exps = [torch.empty(R, C // 16, dtype=torch.uint8, device=dev) for _ in range(k)]
     run("bfp_pack bf16 -> int8 codes + uint8 exponents, B=16",
