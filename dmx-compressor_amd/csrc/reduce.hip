@@ -405,20 +405,26 @@ __global__ __launch_bounds__(kFlatThreads) void group_minmax_flat_kernel(const v
 // partial maxima are combined through LDS and ONE wave issues the integer atomics.
 constexpr int kMaxabsThreads = 1024;  // 16 waves over rows per column strip: parallelism without more atomics
 constexpr int kMaxabsRows = 8;        // rows in flight per lane
-template <int DT, int U, bool GATED>
+// BIG (planes of 2^31 columns and more): one strip per workgroup would be a grid of 2^22 workgroups of 1024 lanes and more -- 2^32 work
+// items, which the launch does not take (the count wraps and only the first strips run) -- so the launcher caps the strips of the grid
+// at nx.d and a workgroup walks strips bx, bx + nx.d, ... of the plane.  Never gated.  BIG == false: one strip, the code as it was.
+template <int DT, int U, bool GATED, bool BIG = false>
 __global__ __launch_bounds__(kMaxabsThreads) void channel_maxabs_vec_kernel(const void* __restrict__ in,
                                                                            int64_t outer, int64_t C, int64_t inner,
                                                                            float* out, const InitGate gate, const FastDivU32 nx /* column strips */,
                                                                            uint32_t ny /* row splits */) {
+  static_assert(!(BIG && GATED), "the strip loop is not gated");
   constexpr int W = kMaxabsThreads / kWave;
   auto init = [&](int64_t i) { gate_store(&out[i], 0.0f); };
   uint32_t wid;
   if (gate_open<GATED>(gate, C, init, wid)) return;
-  const uint32_t by = nx.div(wid), bx = wid - by * nx.d;
+  const uint32_t by = nx.div(wid), bx0 = wid - by * nx.d;
   unsigned seen = ~gate.epoch;   // not the epoch: a workgroup that never peeks must wait
   const int lane = threadIdx.x & (kWave - 1), w = threadIdx.x / kWave;
-  const int64_t col0 = ((int64_t)bx * kWave + lane) * 8;
   const int64_t plane = C * inner;
+  const int64_t strips = BIG ? (plane / 8 + kWave - 1) / kWave : 0;
+  for (int64_t bx = bx0;; bx += nx.d) {
+  const int64_t col0 = (bx * kWave + lane) * 8;
   const bool ok = col0 < plane;
   // a workgroup takes W * U consecutive rows per pass: wave w rows w, w + W, ...; the U row loads of a lane are all in flight
   // before the first is consumed (tools/tune_reduce.hip: W16 x U8 = 9.4 us on 4096 x 4096 bf16 against 11.6 us with 4 loads per
@@ -462,7 +468,7 @@ __global__ __launch_bounds__(kMaxabsThreads) void channel_maxabs_vec_kernel(cons
   // the strip's 512 columns over the first 512 threads (8 waves), each combining the W partial maxima of its column
   if (threadIdx.x < 8 * kWave) {
     const int c = threadIdx.x;                 // column c of the strip = element c % 8 of lane c / 8
-    const int64_t col = (int64_t)bx * (kWave * 8) + c;
+    const int64_t col = bx * (kWave * 8) + c;
     if (col < plane) {
       const int l = c >> 3, e = c & 7;
       uint32_t r;
@@ -480,6 +486,9 @@ __global__ __launch_bounds__(kMaxabsThreads) void channel_maxabs_vec_kernel(cons
       const int64_t ch = inner == 1 ? col : (plane < (1ll << 31) ? (int64_t)((uint32_t)col / (uint32_t)inner) : col / inner);
       atomicMax((int*)&out[ch], (int)r);  // |x| patterns: int order == float order, a NaN pattern is above +Inf's
     }
+  }
+  if (!BIG || bx + nx.d >= strips) break;
+  __syncthreads();   // (the next strip's partial maxima go through the same LDS)
   }
 }
 
@@ -650,6 +659,8 @@ extern "C" int dmxq_channel_maxabs(const void* in, int dtype_in, int64_t outer, 
   hipStream_t s = (hipStream_t)stream;
   const int64_t plane = C * inner;
   const bool vec = outer * plane > 0 && in && aligned16(in) && plane % 8 == 0;
+  // (the scalar kernel, for unaligned or ragged planes, has no strip loop: 2^32 work items along x would wrap)
+  if (!vec && outer * plane > 0 && in && plane >= ((int64_t)1 << 32)) return DMXQ_ERR_UNSUPPORTED;
   InitGate gate{nullptr, 0u, 0};
   if (vec) gate = take_gate(s, C);   // zeros by the kernel's first workgroup (the init gate above), else by a launch in front
   if (!gate.on) DMXQ_LAUNCH(fill2_kernel, dim3((unsigned)((C + 255) / 256)), dim3(256), 0, s, out, 0.0f, (float*)nullptr, 0.0f, C);
@@ -672,6 +683,24 @@ extern "C" int dmxq_channel_maxabs(const void* in, int dtype_in, int64_t outer, 
     }
     if (gy > 65535) gy = 65535;
     if (vec && gx * gy > 0x7FFFFFF0ll) gy = 0x7FFFFFF0ll / gx > 0 ? 0x7FFFFFF0ll / gx : 1;   // (one-dimensional grid: strips x row splits)
+    // a launch takes fewer than 2^32 work items: from 2^22 workgroups of 1024 lanes on (a plane of 2^31 columns with one row split) the
+    // grid is capped at 2^20 strips x the row splits that fit, and the workgroups walk the plane's strips (the BIG kernel; no gate)
+    constexpr int64_t kMaxabsGridMax = ((int64_t)1 << 32) / kMaxabsThreads - 1;
+    if (vec && gx * gy + (gate.on ? 1 : 0) > kMaxabsGridMax) {
+      if (gate.on) {   // (the gate was taken for a launch that is not coming: the fill launch serves, the slot's epoch just moves on)
+        gate = InitGate{nullptr, 0u, 0};
+        DMXQ_LAUNCH(fill2_kernel, dim3((unsigned)((C + 255) / 256)), dim3(256), 0, s, out, 0.0f, (float*)nullptr, 0.0f, C);
+      }
+      const int64_t sx = gx < ((int64_t)1 << 20) ? gx : ((int64_t)1 << 20);
+      const int64_t rows_per_pass = (kMaxabsThreads / kWave) * kMaxabsRows;
+      int64_t sy = (outer + rows_per_pass - 1) / rows_per_pass;
+      if (sy > 64) sy = 64;
+      if (sx * sy > kMaxabsGridMax) sy = kMaxabsGridMax / sx;
+#define DMXQ_MAB(D_) DMXQ_LAUNCH((channel_maxabs_vec_kernel<D_, kMaxabsRows, false, true>), dim3((unsigned)(sx * sy)), dim3(kMaxabsThreads), 0, s, in, outer, C, inner, out, gate, make_fastdiv_u32(sx), (uint32_t)sy)
+      if (dtype_in == DMXQ_F32) DMXQ_MAB(DMXQ_F32); else if (dtype_in == DMXQ_F16) DMXQ_MAB(DMXQ_F16); else DMXQ_MAB(DMXQ_BF16);
+#undef DMXQ_MAB
+      return launch_status();
+    }
     if (vec)
 #define DMXQ_MAU1(D_, U_, G_) DMXQ_LAUNCH((channel_maxabs_vec_kernel<D_, U_, G_>), dim3((unsigned)(gx * gy + ((G_) ? 1 : 0))), dim3(kMaxabsThreads), 0, s, in, outer, C, inner, out, gate, make_fastdiv_u32(gx), (uint32_t)gy)
 #define DMXQ_MAU(D_, U_) do { if (gate.on) DMXQ_MAU1(D_, U_, true); else DMXQ_MAU1(D_, U_, false); } while (0)

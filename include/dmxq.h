@@ -213,7 +213,8 @@ int dmxq_qparams(const float* mn, const float* mx, int64_t n_groups, int qmin, i
  * the caller) and bins <= 8192.  hist: float[bins] device buffer, fully overwritten. */
 int dmxq_histc(const void* in, int dtype_in, int64_t n, int64_t bins, float lo, float hi, float* hist, void* stream);
 
-/* Per-channel max|x| (SmoothQuant).  Replaces numerical/smoothquant.py:285-299 _maxabs. out: float[C]. */
+/* Per-channel max|x| (SmoothQuant).  Replaces numerical/smoothquant.py:285-299 _maxabs. out: float[C].
+ * DMXQ_ERR_UNSUPPORTED: a plane of C * inner >= 2^32 elements that is not whole 16-byte vectors from an aligned pointer. */
 int dmxq_channel_maxabs(const void* in, int dtype_in, int64_t outer, int64_t C, int64_t inner, float* out, void* stream);
 
 /* SmoothQuant scale = clamp(a^alpha / clamp(b, min)^(1-alpha), min).  Replaces smoothquant.py:301-321. */

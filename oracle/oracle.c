@@ -119,13 +119,19 @@ static inline float float_q1(float a, int man, int exp_bits, int bias, int flush
 }
 
 /* returns 0 ok, 1 bad argument (man outside 0..22: the reference's behaviour at man=23 is undefined) */
-int oracle_float_qdq(const float* in, float* out, int64_t n, int man, int exp_bits, int bias, int flush,
-                     int rounding, uint64_t seed) {
+/* start: the linear index of in[0] within the tensor it was cut from -- the stochastic draws are keyed by (seed, start + i), so a slice
+ * of a tensor of more than 2^32 elements is checked without the rest of it */
+int oracle_float_qdq_at(const float* in, float* out, int64_t n, int man, int exp_bits, int bias, int flush,
+                        int rounding, uint64_t seed, uint64_t start) {
   if (man < 0 || man > 22 || exp_bits < 1 || exp_bits > 8) return 1;
 #pragma omp parallel for schedule(static)
   for (int64_t i = 0; i < n; i++)
-    out[i] = float_q1(in[i], man, exp_bits, bias, flush, rounding, rounding == R_STOCHASTIC ? rnd_bits(seed, (uint64_t)i) : 0u);
+    out[i] = float_q1(in[i], man, exp_bits, bias, flush, rounding, rounding == R_STOCHASTIC ? rnd_bits(seed, start + (uint64_t)i) : 0u);
   return 0;
+}
+int oracle_float_qdq(const float* in, float* out, int64_t n, int man, int exp_bits, int bias, int flush,
+                     int rounding, uint64_t seed) {
+  return oracle_float_qdq_at(in, out, n, man, exp_bits, bias, flush, rounding, seed, 0);
 }
 
 /* ------------------------------------------------------------------------------------------- block floating point
@@ -243,9 +249,11 @@ static inline float rnd_unit(uint64_t seed, uint64_t idx) { /* [0,1) with 24 ran
  * x is viewed as [outer, C, inner] (C = size along ch_axis); channel c uses scale[c / group_size]
  * (repeat_interleave(sc, group_size)[:C], cast.py:281-292).  scale == NULL -> no affine (bare Format.cast).
  * Per-tensor: C = 1 (outer*inner = numel), group_size = 1, one scale.  Per-channel: group_size = 1. */
-int oracle_fixed_qdq(const float* in, float* out, int64_t outer, int64_t C, int64_t inner, int wl, int fl,
-                     int clamp, int symmetric, int rounding, const float* scale, const int64_t* zp,
-                     int64_t group_size, uint64_t seed) {
+/* start: the linear index of in[0] within the [outer, C, inner] tensor it was cut from (n = outer * C * inner elements FROM there):
+ * channel and stochastic draw of element i are those of index start + i */
+int oracle_fixed_qdq_at(const float* in, float* out, int64_t outer, int64_t C, int64_t inner, int wl, int fl,
+                        int clamp, int symmetric, int rounding, const float* scale, const int64_t* zp,
+                        int64_t group_size, uint64_t seed, uint64_t start) {
   if (wl < 1 || group_size < 1) return 1;
   float t_min, t_max;
   fixed_min_max(wl, fl, symmetric, &t_min, &t_max);
@@ -253,7 +261,7 @@ int oracle_fixed_qdq(const float* in, float* out, int64_t outer, int64_t C, int6
   const int64_t n = outer * C * inner;
 #pragma omp parallel for schedule(static)
   for (int64_t i = 0; i < n; i++) {
-    const int64_t c = (i / inner) % C;
+    const int64_t c = (int64_t)(((start + (uint64_t)i) / (uint64_t)inner) % (uint64_t)C);
     float v = in[i], sc = 1.0f, z = 0.0f;
     if (scale) {
       sc = scale[c / group_size];
@@ -261,13 +269,18 @@ int oracle_fixed_qdq(const float* in, float* out, int64_t outer, int64_t C, int6
       v = v / sc + z;
     }
     float r = 0.5f;
-    if (rounding == R_STOCHASTIC) r = rnd_unit(seed, (uint64_t)i);
+    if (rounding == R_STOCHASTIC) r = rnd_unit(seed, start + (uint64_t)i);
     float q = fixed_q1(v, sigma, rounding, r);
     if (clamp) q = clampf(q, t_min, t_max);
     if (scale) q = (q - z) * sc;
     out[i] = q;
   }
   return 0;
+}
+int oracle_fixed_qdq(const float* in, float* out, int64_t outer, int64_t C, int64_t inner, int wl, int fl,
+                     int clamp, int symmetric, int rounding, const float* scale, const int64_t* zp,
+                     int64_t group_size, uint64_t seed) {
+  return oracle_fixed_qdq_at(in, out, outer, C, inner, wl, fl, clamp, symmetric, rounding, scale, zp, group_size, seed, 0);
 }
 
 static void fixed_min_max(int wl, int fl, int symmetric, float* t_min, float* t_max);
@@ -483,10 +496,13 @@ int oracle_histc(const float* x, int64_t n, int64_t bins, float lo, float hi, fl
 
 /* sparse.py:201-221 Bernoulli.forward with the counter-based stream of rnd_bits in place of torch.bernoulli's global
  * generator: mask = (u < score), u = (rnd >> 8) * 2^-24 in [0, 1). */
-int oracle_bernoulli_mask(const float* score, float* mask, int64_t n, uint64_t seed) {
+int oracle_bernoulli_mask_at(const float* score, float* mask, int64_t n, uint64_t seed, uint64_t start) {
   for (int64_t i = 0; i < n; i++) {
-    const float u = (float)(rnd_bits(seed, (uint64_t)i) >> 8) * (1.0f / 16777216.0f);
+    const float u = (float)(rnd_bits(seed, start + (uint64_t)i) >> 8) * (1.0f / 16777216.0f);
     mask[i] = u < score[i] ? 1.0f : 0.0f;
   }
   return 0;
+}
+int oracle_bernoulli_mask(const float* score, float* mask, int64_t n, uint64_t seed) {
+  return oracle_bernoulli_mask_at(score, mask, n, seed, 0);
 }

@@ -51,8 +51,13 @@ def lib():
         L.oracle_channel_maxabs.argtypes = [fp, i64, i64, i64, fp]
         L.oracle_histc.argtypes = [fp, i64, i64, ctypes.c_float, ctypes.c_float, fp]
         L.oracle_bernoulli_mask.argtypes = [fp, fp, i64, u64]
+        # the same three with the linear index of the first element (a slice of a larger tensor: index-keyed random streams)
+        L.oracle_float_qdq_at.argtypes = L.oracle_float_qdq.argtypes + [u64]
+        L.oracle_fixed_qdq_at.argtypes = L.oracle_fixed_qdq.argtypes + [u64]
+        L.oracle_bernoulli_mask_at.argtypes = L.oracle_bernoulli_mask.argtypes + [u64]
         for f in ("oracle_sbfp_qdq", "oracle_mxfp_qdq", "oracle_float_qdq", "oracle_bfp_qdq", "oracle_fixed_qdq", "oracle_nm_mask",
-                  "oracle_group_minmax", "oracle_qparams", "oracle_channel_maxabs", "oracle_histc", "oracle_bernoulli_mask"):
+                  "oracle_group_minmax", "oracle_qparams", "oracle_channel_maxabs", "oracle_histc", "oracle_bernoulli_mask",
+                  "oracle_float_qdq_at", "oracle_fixed_qdq_at", "oracle_bernoulli_mask_at"):
             getattr(L, f).restype = ctypes.c_int
         _lib = L
     return _lib
@@ -73,12 +78,13 @@ def _check(rc, what):
 
 
 # ------------------------------------------------------------------------------------------------ formats
-def float_quantize(x, man, exp, bias, flush_subnormal, rounding="nearest", seed=0):
-    """quant/quant_function.py:120-152 -> quant_cpu.cpp:359-402.  fp32 in -> fp32 out."""
+def float_quantize(x, man, exp, bias, flush_subnormal, rounding="nearest", seed=0, start=0):
+    """quant/quant_function.py:120-152 -> quant_cpu.cpp:359-402.  fp32 in -> fp32 out.  start: the linear index of x's first element
+    in the tensor it was sliced from (the stochastic draws are keyed by the element index)."""
     xi = _f32c(x)
     out = torch.empty_like(xi)
-    _check(lib().oracle_float_qdq(_ptr(xi), _ptr(out), xi.numel(), man, exp, bias, int(flush_subnormal),
-                                  ROUNDING[rounding], seed), "float_qdq")
+    _check(lib().oracle_float_qdq_at(_ptr(xi), _ptr(out), xi.numel(), man, exp, bias, int(flush_subnormal),
+                                     ROUNDING[rounding], seed, start), "float_qdq")
     return out
 
 
@@ -161,12 +167,12 @@ def bfp_pack(x, precision, block_size, symmetric=True):
     return mant, exps
 
 
-def fixed_point_cast(x, precision, fraction, clamp=True, symmetric=True, rounding="nearest", seed=0):
-    """numerical/format.py:134-142 FixedPoint.cast -> quant_cpu.cpp:148-167."""
+def fixed_point_cast(x, precision, fraction, clamp=True, symmetric=True, rounding="nearest", seed=0, start=0):
+    """numerical/format.py:134-142 FixedPoint.cast -> quant_cpu.cpp:148-167.  start: as float_quantize."""
     xi = _f32c(x)
     out = torch.empty_like(xi)
-    _check(lib().oracle_fixed_qdq(_ptr(xi), _ptr(out), 1, 1, xi.numel(), precision, fraction, int(clamp),
-                                  int(symmetric), ROUNDING[rounding], None, None, 1, seed), "fixed_qdq")
+    _check(lib().oracle_fixed_qdq_at(_ptr(xi), _ptr(out), 1, 1, xi.numel(), precision, fraction, int(clamp),
+                                     int(symmetric), ROUNDING[rounding], None, None, 1, seed, start), "fixed_qdq")
     return out
 
 
@@ -292,10 +298,11 @@ def topk_mask(score, density):
     return torch.from_numpy(mask).reshape(score.shape).to(score.dtype)
 
 
-def bernoulli_mask(score, seed):
+def bernoulli_mask(score, seed, start=0):
+    """start: the linear index of score's first element in the tensor it was sliced from (the draws are keyed by the element index)"""
     sc = _f32c(score)
     out = torch.empty_like(sc)
-    _check(lib().oracle_bernoulli_mask(_ptr(sc), _ptr(out), sc.numel(), seed), "bernoulli_mask")
+    _check(lib().oracle_bernoulli_mask_at(_ptr(sc), _ptr(out), sc.numel(), seed, start), "bernoulli_mask")
     return out.to(score.dtype)
 
 

@@ -7,7 +7,10 @@ script by the child processes of test_gpu_strided_blocks.py (DMXQ_PLAN_CUS / DMX
 Nothing here needs a GPU to be imported; torch is imported by the functions that use it.
 
 Not covered anywhere, on purpose: the column kernel's 64-bit index form (ColsIdx.small == 0, bfp_cols.hip launch_cols_geom) needs
-2^31 lane slots -- at 8 elements per lane and B <= 128 that is a tensor of tens of GiB, more than a test may allocate."""
+2^31 lane slots -- at 8 elements per lane and B <= 128 that is a tensor of tens of GiB, more than a test may allocate.  The other
+kernels' 64-bit index forms run in tests/test_gpu_large_index.py (table: tests/_large_cases.py), which leaves out, for the same
+reason or because they take a process of their own: hist_observer.hip:98 narrow == false (2^32 16-byte vectors), stream.hpp:452 (the
+stream kernels' tile count beyond 32 bits) and DMXQ_INPUT_HYPERNET_TILED (read once per process)."""
 from collections import namedtuple
 
 ERR_UNSUPPORTED = 2

@@ -393,19 +393,28 @@ def test_inplace_through_the_c_abi(dmx, cuda, oracle):
 
 def test_more_than_2_to_the_31_elements(dmx, cuda):
     """64-bit sizes (the reference's kernels take `int size`): a 2^31 + 2^20 element bf16 tensor; the rows beyond the
-    32-bit boundary must equal the same rows quantised on their own (shard invariance, no oracle needed)."""
+    32-bit boundary must equal the same rows quantised on their own (shard invariance, no oracle needed).
+    The input has no period (random, generated on the device, with a NaN, an Inf, a denormal block and an all-zero block beyond
+    element 2^31): the old one, 256 rows repeated, had a period of 2^20 elements, so a read at e mod 2^32 returned what a read at e
+    does.  And the WHOLE output is compared, chunk by chunk, through the harness of tests/_large_cases.py (the other ops and the
+    row lengths that are no power of two: tests/test_gpu_large_index.py)."""
+    import _large_cases as LC
     free, _ = torch.cuda.mem_get_info()
     n_rows = (1 << 19) + 256           # x 4096 columns = 2^31 + 2^20 elements, 4 GiB per tensor
-    if free < 3 * n_rows * 4096 * 2:
+    c = LC.case("bfp_rows_4096", "bfp_qdq", (n_rows, 4096))
+    if free < LC.peak_bytes(c) + n_rows * 4096 * 2:       # (two full-size outputs here)
         pytest.skip("not enough free device memory")
-    base = make("heavy", (256, 4096), seed=11, dtype=torch.bfloat16).to(cuda)
-    x = base.repeat(n_rows // 256, 1)
+    x = LC.device_input("heavy", c.shape, torch.bfloat16, 11, cuda)
+    LC.plant_specials(x, c)
     assert x.numel() > 2 ** 31
     q = dmx.ops.bfp_qdq(x, 8, 16)
-    ref = dmx.ops.bfp_qdq(base, 8, 16)
-    assert torch.equal(q[-256:], ref) and torch.equal(q[:256], ref) and torch.equal(q[(1 << 19) - 256:(1 << 19)], ref)
     f = dmx.ops.float_qdq(x, 10, 5, 15, True)
-    assert torch.equal(f[-256:], dmx.ops.float_qdq(base, 10, 5, 15, True))
+    for a, b in ((n_rows - 256, n_rows), (0, 256), ((1 << 19) - 256, 1 << 19)):
+        assert torch.equal(q[a:b].view(torch.int16), dmx.ops.bfp_qdq(x[a:b], 8, 16).view(torch.int16)), (a, b)
+    assert torch.equal(f[-256:].view(torch.int16), dmx.ops.float_qdq(x[-256:], 10, 5, 15, True).view(torch.int16))
+    LC.check_chunks(c, lambda v, ab: (dmx.ops.bfp_qdq(v[0], 8, 16),), [x], (q,))
+    LC.check_chunks(c, lambda v, ab: (dmx.ops.float_qdq(v[0], 10, 5, 15, True),), [x], (f,))
+    assert bool(torch.isnan(q[LC.special_rows(c)[0]].float()).any())      # the planted NaN poisons its block, beyond element 2^31
     del x, q, f
     torch.cuda.empty_cache()
 
