@@ -853,3 +853,34 @@ def dynamic_fixed_qdq(x, segment, whole_rows, precision, fraction, clamp, symmet
                                        int(bool(symmetric_qscheme)), ptr(sc) if want_qparams else None, ptr(zp) if want_qparams else None,
                                        stream_of(xc)), "dmxq_dynamic_fixed_qdq")
     return out, sc, zp
+
+
+# ------------------------------------------------------------------------------------------------ dynamic scaled float cast
+DYNF_GROUP, DYNF_ROWS, DYNF_TILE = 0, 1, 2   # dmxq_dynamic_float_mode (include/dmxq.h)
+
+
+@_guarded
+def dynamic_float_qdq(x, mode, segment, man, exp, bias, flush_subnormal, rounding, pow2_scale, want_scale, out_dtype=None):
+    """-> (out, scale): scale float32 [n_segments] ([..., R / g, C / g] for tiles), empty unless want_scale"""
+    xc = _prep(x, "dynamic_float_qdq")
+    if segment < 1:
+        raise RuntimeError("dynamic_float_qdq: the segment must be positive")
+    rows = cols = 0
+    if mode == DYNF_TILE:
+        if xc.dim() < 2 or xc.shape[-2] % segment or xc.shape[-1] % segment:
+            raise RuntimeError("dynamic_float_qdq: the tile size must divide the last two dimensions")
+        cols = xc.shape[-1]
+        rows = xc.numel() // cols
+        sc_shape = tuple(xc.shape[:-2]) + (xc.shape[-2] // segment, cols // segment)
+        n = (rows // segment) * (cols // segment)
+    else:
+        if xc.numel() % segment != 0:
+            raise RuntimeError("dynamic_float_qdq: the segment must divide the number of elements")
+        n = xc.numel() // segment
+        sc_shape = (n,)
+    out = torch.empty(xc.shape, dtype=out_dtype or xc.dtype, device=xc.device)
+    sc = torch.empty(sc_shape if want_scale else 0, dtype=torch.float32, device=xc.device)
+    check(lib().dmxq_dynamic_float_qdq(ptr(xc), ptr(out), dtype_code(xc.dtype), dtype_code(out.dtype), mode, n, segment, rows, cols, man, exp,
+                                       bias, int(bool(flush_subnormal)), rounding, int(bool(pow2_scale)), ptr(sc) if want_scale else None,
+                                       stream_of(xc)), "dmxq_dynamic_float_qdq")
+    return out, sc

@@ -55,7 +55,9 @@ _FAST_CALIBRATION_NAMES = {"hist_observe": "hist_observe", "hist_qparams": "hist
                            # the Hadamard rotation: its backward is an autograd Function of the front end (_front.py), above the raw op
                            "hadamard_qdq": "hadamard_qdq",
                            # the dynamic integer cast: straight-through above the raw op as well (cast.py)
-                           "dynamic_fixed_qdq": "dynamic_fixed_qdq"}
+                           "dynamic_fixed_qdq": "dynamic_fixed_qdq",
+                           # the dynamic scaled float cast: the same
+                           "dynamic_float_qdq": "dynamic_float_qdq"}
 FAST = None
 
 

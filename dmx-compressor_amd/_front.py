@@ -23,6 +23,8 @@ __all__ = [
     "rmsnorm", "histc", "gptq_fields", "gptq_block", "gptq_block_dynamic", "hist_observe", "hist_scratch_words", "hist_qparams", "error_stats", "cast_error",
     "error_scratch_bytes", "cast_error_entry", "hadamard", "hadamard_qdq", "hadamard_check_size", "HADAMARD_SIZES",
     "dynamic_fixed_qdq", "dynamic_check", "dynamic_class", "DYNAMIC_GRANULARITIES", "DYNAMIC_CHAIN_BY_DEFAULT",
+    "dynamic_float_qdq", "dynamic_float_check", "dynamic_float_class", "dynamic_float_fmax", "DYNAMIC_FLOAT_GRANULARITIES",
+    "DYNAMIC_FLOAT_CHAIN_BY_DEFAULT",
 ]
 
 _ops = None   # the raw namespace: set by bind()
@@ -1067,6 +1069,172 @@ def dynamic_fixed_qdq(x, fmt, granularity: str = "per_token", group_size: Option
             y, sc, zp = (torch.cat([p[k] for p in parts]) for k in range(3))
         y = y.reshape(xc.shape)
         return (y, sc, zp) if return_qparams else y
+
+    if x.requires_grad and torch.is_grad_enabled():
+        return _DynamicSTE.apply(x, run)
+    with torch.no_grad():
+        return run(x.detach())
+
+
+# ---------------------------------------------------------------------------------------------------- dynamic scaled float cast
+DYNAMIC_FLOAT_GRANULARITIES = ("per_token", "per_group", "per_tensor", "per_tile")
+DYNAMIC_FLOAT_TILES = (32, 64, 128)   # the tile sizes dmxq_dynamic_float_qdq keeps in registers
+# Launch geometries of dmxq_dynamic_float_qdq (dynamic_float_class) that fused=None sends to the chain although the kernel takes them:
+# DYNAMIC_CHAIN_BY_DEFAULT's rule -- a class goes to the kernel by default only where tools/bench_dynamic_float.py MEASURED it faster than
+# the chain on the same buffers; a class that is not gets listed here with its row.  profiles/r15_dynamic_float.txt (bf16 E4M3, us per
+# call, kernel against chain): wave_row per_token [8192,4096] 30.4 against 185.6; block_row per_token [8192,14336] 90.9 against 460.2;
+# group per_group 128 [8192,4096] 33.3 against 1672.9; group per_group 128 [8192,14336] 91.2 against 5831.5; tile per_tile 128
+# [4096,4096] 19.9 against 140.7; tile per_tile 128 [14336,4096] 45.8 against 378.9; wave_row per_token [2048,768] 5.3 against 56.8;
+# short_row per_token [60000,48] 24.3 against 332.9
+# -- every class is faster, none is listed.
+DYNAMIC_FLOAT_CHAIN_BY_DEFAULT = frozenset()
+# which route the calls of this front end took, counted on the host: private, for the tests (fused=True must have run the kernel)
+_dynamic_float_routes = {"fused": 0, "chain": 0}
+_DYNAMIC_FLOAT_CLASS_NAMES = dict(_DYNAMIC_CLASS_NAMES)
+_DYNAMIC_FLOAT_CLASS_NAMES[5] = "tile"
+_DYNF_GROUP, _DYNF_ROWS, _DYNF_TILE = 0, 1, 2   # dmxq_dynamic_float_mode (include/dmxq.h)
+
+
+def dynamic_float_fmax(fmt) -> float:
+    """the largest output of a FloatingPoint format, 2^(2^(e-1)) (2 - 2^-m): what a segment's absolute maximum is scaled to"""
+    return float(2.0 ** (2 ** (fmt.exponent - 1)) * (2.0 - 2.0 ** -fmt.mantissa))
+
+
+def dynamic_float_check(fmt, granularity, group_size=None, what: str = "dynamic_float_qdq"):
+    """-> (format, granularity, group_size) of a scaled float cast, or ValueError: a signed FloatingPoint format with fewer than 8 exponent
+    bits (8: fp32's range, no finite maximum to scale to), a known granularity, a positive group size with per_group / per_tile and none
+    otherwise.  No GPU involved."""
+    from .format import FloatingPoint, Format
+    fmt = Format.from_shorthand(fmt) if isinstance(fmt, str) else fmt
+    if not isinstance(fmt, FloatingPoint):
+        raise ValueError(f"{what}: a scaled cast scales to a float format's largest value, so it needs a FloatingPoint format "
+                         f"(FP[1|e|m,bias]), got {fmt!r}")
+    if fmt.unsigned:
+        raise ValueError(f"{what}: an unsigned format cannot be scaled by the absolute maximum, got {fmt!r}")
+    if fmt.exponent >= 8:
+        raise ValueError(f"{what}: a format with {fmt.exponent} exponent bits has fp32's range and no finite maximum to scale to, got {fmt!r}")
+    if granularity not in DYNAMIC_FLOAT_GRANULARITIES:
+        raise ValueError(f"{what}: granularity must be one of {DYNAMIC_FLOAT_GRANULARITIES}, got {granularity!r}")
+    if granularity in ("per_group", "per_tile"):
+        if isinstance(group_size, bool) or not isinstance(group_size, int) or group_size < 1:
+            raise ValueError(f"{what}: {granularity} needs a positive integer group_size, got {group_size!r}")
+    elif group_size is not None:
+        raise ValueError(f"{what}: group_size goes with granularity 'per_group' / 'per_tile', got {granularity!r} with group_size "
+                         f"{group_size!r}")
+    return fmt, granularity, group_size
+
+
+def dynamic_float_class(segment: int, dtype: torch.dtype, granularity: str = "per_token") -> Optional[str]:
+    """the launch geometry dmxq_dynamic_float_qdq picks for segments of `segment` elements of `dtype` (the tile size for "per_tile"),
+    asked of the library itself (dmxq_dynamic_float_class; no GPU involved), or None when it refuses them: dynamic_class's names --
+    "group", "short_row", "wave_row" (here up to 8 sixteen-bit vectors per lane), "block_row" -- and "tile" (32, 64, 128)"""
+    from ._lib import dtype_code, lib
+    mode = {"per_group": _DYNF_GROUP, "per_tile": _DYNF_TILE}.get(granularity, _DYNF_ROWS)
+    return _DYNAMIC_FLOAT_CLASS_NAMES.get(lib().dmxq_dynamic_float_class(dtype_code(dtype), mode, int(segment)))
+
+
+def _scale_from_amax(amax, fmax: float, pow2_scale: bool):
+    """the scale rule of the definition on a float32 tensor of absolute maxima, in torch: an IEEE division by fmax (through
+    scale_channels: torch divides by a Python scalar as a multiplication by its reciprocal), the round-up to a power of two on the bits,
+    and 1 where the scale is not finite or below 2^-126"""
+    n = amax.numel()
+    s = _ops.scale_channels(amax.reshape(n, 1), torch.full((1,), fmax, dtype=torch.float32, device=amax.device), 1, True, torch.float32).reshape(n)
+    if pow2_scale:
+        b = s.view(torch.int32)
+        b = (b & 0x7F800000) + torch.where((b & 0x007FFFFF) != 0, 0x00800000, 0).to(torch.int32)   # (a NaN: wraps to the bits of -0)
+        s = b.view(torch.float32)
+    ok = torch.isfinite(s) & (s >= 2.0 ** -126)
+    return torch.where(ok, s, torch.ones_like(s))
+
+
+def dynamic_float_qdq(x, fmt, granularity: str = "per_token", group_size: Optional[int] = None, pow2_scale: bool = False,
+                      out_dtype: Optional[torch.dtype] = None, return_scale: bool = False, fused: Optional[bool] = None,
+                      seed: Optional[int] = None):
+    """Low-bit float Q->DQ with a scale derived from the tensor itself on every call (not in the reference, whose float
+    casts are unscaled): the FP8 recipe's per-token / per-group activations and per-channel / per-tile weights.  `fmt` is a signed
+    FloatingPoint format with fewer than 8 exponent bits; fmax = 2^(2^(e-1)) (2 - 2^-m) is its largest output (480 for FP[1|4|3,7], 114688
+    for FP[1|5|2,15], 6 for FP[1|2|1,1]).  A segment of the contiguous tensor is the whole row of the last dim ("per_token"; per output
+    channel of an [out, in] weight), `group_size` consecutive elements of it ("per_group"; it must divide the last dim), the whole tensor
+    ("per_tensor"), or a group_size x group_size tile of the last two dims ("per_tile"; it must divide both, leading dims are batch:
+    x.reshape(B, R/g, g, C/g, g).permute(0, 1, 3, 2, 4).reshape(-1, g * g)).  Per segment, in fp32:
+        amax = max |x| (one NaN anywhere makes it NaN);  s = amax / fmax (IEEE division)
+        pow2_scale: s rounded UP to a power of two on its bits, b = (b & 0x7F800000) + ((b & 0x007FFFFF) ? 0x00800000 : 0)
+        s = 1 if s is not finite or below 2^-126 (an all-zero, a NaN, an Inf segment)
+        y = float_q(x / s) * s: IEEE quotient, the format's nearest cast (flush flag kept; NaN / Inf saturate as in float_qdq), one fp32
+        multiply, one rounding to out_dtype.
+    ONE launch (dmxq_dynamic_float_qdq) for a nearest-rounding format, out_dtype == x.dtype, a 16-byte aligned tensor and: a group that is
+    a power of two from 16 to 256; a row / tensor of any multiple of a 16-byte vector up to 16384 elements; a tile of 32, 64 or 128.
+    Otherwise the chain of existing launches, same bits: group_minmax -> max(|mn|, |mx|) -> the scale rule in torch -> scale_channels
+    (divide, float32) -> float_qdq -> scale_channels (multiply, out_dtype), on pieces of 32768 segments above 65535 segments (tiles are
+    gathered into rows first).  fused=None: the kernel where it applies and its geometry (dynamic_float_class) is not listed in
+    DYNAMIC_FLOAT_CHAIN_BY_DEFAULT; True: NotImplementedError instead of falling back; False: the chain.  seed: for a stochastic-rounding
+    format (the chain only), as ops.float_qdq takes it.  return_scale: (y, scale) with scale float32 [n_segments], or [..., R/g, C/g] for
+    tiles, on both routes.  ValueError (before any GPU use): a format that cannot be scaled, an unknown granularity, a group_size that does
+    not divide.  Autograd: a straight-through estimator.  Nothing is read back to the host."""
+    fmt, granularity, group_size = dynamic_float_check(fmt, granularity, group_size)
+    tile = granularity == "per_tile"
+    if x.dim() < (2 if tile else 1):
+        raise ValueError(f"dynamic_float_qdq: {granularity} expects a tensor with at least {2 if tile else 1} dimension(s)")
+    L = x.shape[-1]
+    if granularity == "per_group" and L % group_size:
+        raise ValueError(f"dynamic_float_qdq: the last dimension has {L} elements, not a multiple of the group size {group_size}")
+    if tile and (L % group_size or x.shape[-2] % group_size):
+        raise ValueError(f"dynamic_float_qdq: the last two dimensions are {tuple(x.shape[-2:])}, not multiples of the tile size {group_size}")
+    require_gpu(x, "dynamic_float_qdq")
+    out_dtype = out_dtype or x.dtype
+    fmax = dynamic_float_fmax(fmt)
+    S = {"per_token": L, "per_group": group_size, "per_tensor": x.numel(), "per_tile": group_size}[granularity]
+    mode = {"per_group": _DYNF_GROUP, "per_tile": _DYNF_TILE}.get(granularity, _DYNF_ROWS)
+    fields = (fmt.mantissa, fmt.exponent, fmt.bias, bool(fmt.flush_subnormal))
+
+    def run(xd):
+        xc = xd if xd.is_contiguous() else xd.contiguous()
+        sc_shape = (tuple(xc.shape[:-2]) + (xc.shape[-2] // S, L // S)) if tile else None
+        if xc.numel() == 0:
+            y = torch.empty(xc.shape, dtype=out_dtype, device=xc.device)
+            return (y, y.new_empty(sc_shape if tile else 0, dtype=torch.float32)) if return_scale else y
+        if fused is not False:
+            cls = dynamic_float_class(S, xc.dtype, granularity) if (fmt.rounding == "nearest" and out_dtype == xc.dtype and fmt.mantissa <= 22
+                                                                    and xc.data_ptr() % 16 == 0) else None
+            if cls is None and fused:
+                raise NotImplementedError(f"dynamic_float_qdq: no fused kernel for {granularity} segments of {S} {xc.dtype} elements -> "
+                                          f"{out_dtype} with {fmt!r} (base address {xc.data_ptr() % 16} mod 16)")
+            if cls is not None and fused is None and cls in DYNAMIC_FLOAT_CHAIN_BY_DEFAULT:
+                cls = None
+            if cls is not None:
+                try:
+                    y, sc = _ops.dynamic_float_qdq(xc, mode, S, *fields, ROUNDING_CODE[fmt.rounding], bool(pow2_scale), bool(return_scale),
+                                                   out_dtype)
+                    _dynamic_float_routes["fused"] += 1
+                    return (y, sc) if return_scale else y
+                except NotImplementedError:   # (DMXQ_ERR_UNSUPPORTED, nothing launched)
+                    if fused:
+                        raise
+        _dynamic_float_routes["chain"] += 1
+        if tile:
+            B = xc.numel() // (xc.shape[-2] * L)
+            x2 = xc.reshape(B, xc.shape[-2] // S, S, L // S, S).permute(0, 1, 3, 2, 4).reshape(-1, S * S)
+        else:
+            x2 = xc.reshape(-1, S)
+
+        def chain(part):
+            mn, mx = _ops.group_minmax(part, 0, 1)
+            sc = _scale_from_amax(torch.maximum(mn.abs(), mx.abs()), fmax, pow2_scale)
+            q = _ops.scale_channels(part, sc, 0, True, torch.float32)
+            q = float_qdq(q, *fields, False, fmt.rounding, torch.float32, seed)
+            return _ops.scale_channels(q, sc, 0, False, out_dtype), sc
+
+        if x2.shape[0] <= DYNAMIC_CHAIN_MAX_SEGMENTS:
+            y, sc = chain(x2)
+        else:   # (dmxq_group_minmax takes 65535 groups: segments are independent, so the chain runs on pieces and the results are joined)
+            parts = [chain(x2[i:i + DYNAMIC_CHAIN_PIECE]) for i in range(0, x2.shape[0], DYNAMIC_CHAIN_PIECE)]
+            y, sc = (torch.cat([p[k] for p in parts]) for k in range(2))
+        if tile:
+            y = y.reshape(B, xc.shape[-2] // S, L // S, S, S).permute(0, 1, 3, 2, 4).reshape(xc.shape)
+            sc = sc.reshape(sc_shape)
+        else:
+            y = y.reshape(xc.shape)
+        return (y, sc) if return_scale else y
 
     if x.requires_grad and torch.is_grad_enabled():
         return _DynamicSTE.apply(x, run)

@@ -79,6 +79,8 @@ SIGNATURES = {
     "dmxq_cast_error": [_vp, _i32, _i64, _i64, _vp, _i32, _vp, _vp, _i32, _vp, _vp, _i64, _vp],
     "dmxq_hadamard_qdq": [_vp, _vp, _i32, _i32, _i64, _i64, _i64, _i32, _vp, _vp, _vp, _vp],
     "dmxq_dynamic_class": [_i32, _i64, _i32],
+    "dmxq_dynamic_float_class": [_i32, _i32, _i64],
+    "dmxq_dynamic_float_qdq": [_vp, _vp, _i32, _i32, _i32, _i64, _i64, _i64, _i64, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp],
     "dmxq_dynamic_fixed_qdq": [_vp, _vp, _i32, _i32, _i64, _i64, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp],
 }
 

@@ -14,7 +14,7 @@ from torch.autograd import Function
 
 from . import ops
 from ._flags import HostFlags
-from .format import FixedPoint, Format, Same
+from .format import FixedPoint, FloatingPoint, Format, Same
 from .observer import _PER_CHANNEL, _SYMMETRIC, DummyObserver, HistogramObserver, MinMaxObserver, ObserverBase
 
 __all__ = ["CastToFormat", "CastTo", "CastToDict"]
@@ -98,6 +98,33 @@ def _parse_dynamic(granularity, group_size=None):
     return granularity, group_size
 
 
+def _parse_scaling(granularity, group_size=None, pow2_scale=False):
+    """set_scaling's arguments -> None or (granularity, group_size, pow2_scale).  granularity: None / False, "per_token", "per_tensor",
+    "per_group" or "per_tile" (these two with group_size as the second argument), the pair ("per_group" | "per_tile", g), or a dict
+    {"per_group": g} / {"per_tile": g} / {"granularity": name}, each optionally with "pow2_scale": bool (the spelling
+    DmxModule.configure takes)"""
+    if isinstance(granularity, (tuple, list)) and len(granularity) == 2 and group_size is None:
+        granularity, group_size = granularity
+    if isinstance(granularity, dict):
+        d = dict(granularity)
+        if "pow2_scale" in d:
+            if pow2_scale:
+                raise ValueError(f"set_scaling: pow2_scale given twice, got {granularity!r}")
+            pow2_scale = d.pop("pow2_scale")
+        if len(d) != 1 or group_size is not None or next(iter(d)) not in ("per_group", "per_tile", "granularity"):
+            raise ValueError(f"set_scaling: expected {{'per_group': int}}, {{'per_tile': int}} or {{'granularity': name}}, optionally with "
+                             f"'pow2_scale', got {granularity!r}")
+        (k, v), = d.items()
+        granularity, group_size = (v, None) if k == "granularity" else (k, v)
+    if not isinstance(pow2_scale, bool):
+        raise ValueError(f"set_scaling: pow2_scale must be a bool, got {pow2_scale!r}")
+    if granularity is None or granularity is False:
+        if group_size is not None or pow2_scale:
+            raise ValueError(f"set_scaling: group_size {group_size!r} / pow2_scale {pow2_scale!r} without a granularity")
+        return None
+    return granularity, group_size, pow2_scale
+
+
 class CastTo(HostFlags, torch.nn.Module):
     """Simulated numerical cast to a target format (cast.py:136-162).  Buffers and switches follow
     torch.ao's FakeQuantize, which the reference subclasses: scale, zero_point, fake_quant_enabled,
@@ -116,6 +143,9 @@ class CastTo(HostFlags, torch.nn.Module):
     #: None, or (granularity, group_size): scale and zero point are derived from every tensor itself (set_dynamic).  A plain
     #: attribute, not a buffer: the state_dict of a module does not change.
     _dynamic = None
+    #: None, or (granularity, group_size, pow2_scale): a float format is cast with a scale derived from every tensor itself (set_scaling;
+    #: DESIGN.md §8).  A plain attribute as well.
+    _scaling = None
 
     def __init__(self, format="SAME", observer=DummyObserver, group_size=None, block_dim=-1,
                  qscheme=torch.per_tensor_affine, ch_axis=-1, **observer_kwargs):
@@ -158,6 +188,8 @@ class CastTo(HostFlags, torch.nn.Module):
             format = Format.from_shorthand(format)
         if self._dynamic is not None and not isinstance(format, Same):
             ops.dynamic_check(format, *self._dynamic, what="CastTo.set_format on a dynamic cast")
+        if self._scaling is not None and not isinstance(format, Same):
+            ops.dynamic_float_check(format, *self._scaling[:2], what="CastTo.set_format on a scaled cast")
         self.format = format
         if hasattr(self, "activation_post_process"):
             self.activation_post_process.dtype = format
@@ -204,6 +236,39 @@ class CastTo(HostFlags, torch.nn.Module):
     def _dynamic_cast(self, x, out_dtype):
         g, gs = self._dynamic
         return ops.dynamic_fixed_qdq(x, self.format, g, gs, symmetric_qscheme=self.qscheme in _SYMMETRIC, out_dtype=out_dtype)
+
+    def set_scaling(self, granularity=None, group_size=None, pow2_scale: bool = False):
+        """Dynamic float scales (not in the reference): with fake-quant on and the observer off, a FloatingPoint format is
+        cast as float_q(x / s) * s with s = the segment's absolute maximum over the format's largest value, derived from the tensor
+        itself on every forward (ops.dynamic_float_qdq) -- one per row of the last dimension ("per_token"; per output channel of an
+        [out, in] weight), per `group_size` consecutive elements of it ("per_group", or {"per_group": g}), per group_size x group_size
+        tile of the last two dimensions ("per_tile", or {"per_tile": g}) or for the whole tensor ("per_tensor"); pow2_scale rounds s up
+        to a power of two.  A setting of its own beside set_dynamic (the integer formats'): a plain attribute, no buffer, no state_dict
+        key; None switches back to the unscaled cast.  ValueError for an unknown granularity and for a format that cannot be scaled (not
+        a FloatingPoint, unsigned, 8 exponent bits) -- here, or in set_format when the format comes later (a cast that is still SAME
+        accepts the setting)."""
+        sc = _parse_scaling(granularity, group_size, pow2_scale)
+        if sc is not None:
+            fmt = "FP[1|4|3,7](FN)" if isinstance(self.format, Same) else self.format   # (SAME: the granularity alone)
+            ops.dynamic_float_check(fmt, *sc[:2], what="CastTo.set_scaling")
+        self._scaling = sc
+
+    @property
+    def scaling(self):
+        """None, or the setting in configure's spelling: "per_token", "per_tensor", {"per_group": g} or {"per_tile": g}; as a dict with
+        "pow2_scale": True where that is set ({"granularity": "per_token", "pow2_scale": True})"""
+        sc = self._scaling
+        if sc is None:
+            return None
+        g, gs, pow2 = sc
+        out = {g: gs} if g in ("per_group", "per_tile") else g
+        if pow2:
+            out = dict(out, pow2_scale=True) if isinstance(out, dict) else {"granularity": g, "pow2_scale": True}
+        return out
+
+    def _scaled_cast(self, x, out_dtype):
+        g, gs, pow2 = self._scaling
+        return ops.dynamic_float_qdq(x, self.format, g, gs, pow2_scale=pow2, out_dtype=out_dtype)
 
     def enable_calibration(self, state: bool = True, observer_cls: ObserverBase = HistogramObserver,
                            qscheme_to_overload: Optional[torch.qscheme] = None, group_size: int = None,
@@ -287,6 +352,8 @@ class CastTo(HostFlags, torch.nn.Module):
         ste = torch.is_grad_enabled() and x.requires_grad
         if self._dynamic is not None and isinstance(fmt, FixedPoint) and not self.__dict__["_h_observer_enabled"]:
             return self._dynamic_cast(x, out_dtype)   # (a straight-through estimator under autograd by itself)
+        if self._scaling is not None and isinstance(fmt, FloatingPoint) and not self.__dict__["_h_observer_enabled"]:
+            return self._scaled_cast(x, out_dtype)    # (the same)
         if isinstance(fmt, FixedPoint):
             # per-tensor: one scale; per-channel: scale[c]; per-group: scale[c // group_size] (cast.py:279-293)
             if self.group_size:
@@ -363,7 +430,7 @@ class CastTo(HostFlags, torch.nn.Module):
             return self._quantize(x, x.dtype)
         had = pt.get("hadamard")
         if had is not None and len(pt) == 1 and d["_h_fake_quant_enabled"] and not d["_h_observer_enabled"] and isinstance(fmt, Format) \
-                and not isinstance(fmt, Same) and self._dynamic is None:   # (a dynamic cast: the step-by-step route below)
+                and not isinstance(fmt, Same) and self._dynamic is None and self._scaling is None:   # (a dynamic / scaled cast: the step-by-step route below)
             return self._hadamard_qdq(x, had, x.dtype)   # rotation, cast and inverse rotation: one call
         inverse_shaping = None
         shortcut = None
@@ -407,16 +474,18 @@ class CastTo(HostFlags, torch.nn.Module):
         if self.pre_transform and set(self.pre_transform) != {"hadamard"}:
             raise NotImplementedError("CastTo.measure_error: a cast with a pre_transform other than hadamard (shaping / shortcut / pre-format)")
         fmt, x = self.format, x.detach()
-        if self._dynamic is not None and isinstance(fmt, FixedPoint):
-            # a dynamic cast: the cast itself (between the two rotations of a "hadamard" pre_transform), then ops.error_stats
+        dyn_cast = self._dynamic_cast if self._dynamic is not None and isinstance(fmt, FixedPoint) else \
+            self._scaled_cast if self._scaling is not None and isinstance(fmt, FloatingPoint) else None
+        if dyn_cast is not None:
+            # a dynamic / scaled cast: the cast itself (between the two rotations of a "hadamard" pre_transform), then ops.error_stats
             with torch.no_grad():
                 had = self.pre_transform.get("hadamard")
                 if had is None:
-                    y = self._dynamic_cast(x, x.dtype)
+                    y = dyn_cast(x, x.dtype)
                 else:
                     r = ops.hadamard(x, had["size"], self.block_dim, out_dtype=torch.float32)
-                    y = (ops.hadamard(self._dynamic_cast(r, torch.float32), had["size"], self.block_dim, out_dtype=x.dtype)
-                         if had["inverse"] else self._dynamic_cast(r, x.dtype))
+                    y = (ops.hadamard(dyn_cast(r, torch.float32), had["size"], self.block_dim, out_dtype=x.dtype)
+                         if had["inverse"] else dyn_cast(r, x.dtype))
             return ops.error_stats(x, y)
         if self.pre_transform:
             had = self.pre_transform["hadamard"]
@@ -447,7 +516,8 @@ class CastTo(HostFlags, torch.nn.Module):
     def extra_repr(self):
         return f"format = dtype = {self.format!r}, qscheme = {self.qscheme}, ch_axis = {self.ch_axis}, " \
                f"group_size = {self.group_size}, block_dim = {self.block_dim}" \
-               + (f", dynamic = {self.dynamic!r}" if self._dynamic is not None else "")
+               + (f", dynamic = {self.dynamic!r}" if self._dynamic is not None else "") \
+               + (f", scaling = {self.scaling!r}" if self._scaling is not None else "")
 
 
 class CastToDict(torch.nn.ModuleDict):
@@ -505,6 +575,26 @@ class CastToDict(torch.nn.ModuleDict):
             if k not in self.keys():
                 raise RuntimeError(f"No CastTo with key {k}!")
             self[k].set_dynamic(t)
+
+    def set_scaling(self, scaling):
+        """one setting (None, "per_token", "per_tensor", {"per_group": g}, {"per_tile": g}, each dict optionally with "pow2_scale") for every
+        cast, or a list / dict of settings over the casts the way set_dynamic takes them"""
+        one = isinstance(scaling, dict) and set(scaling) <= {"per_group", "per_tile", "granularity", "pow2_scale"} \
+            and not set(scaling) & set(self.keys())
+        if scaling is None or isinstance(scaling, str) or one:
+            for c in self.values():
+                c.set_scaling(scaling)
+            return
+        if isinstance(scaling, (tuple, list)):
+            if len(scaling) != len(self):
+                raise ValueError(f"set_scaling: {len(scaling)} settings for {len(self)} casts")
+            scaling = dict(zip(self.keys(), scaling))
+        elif not isinstance(scaling, dict):
+            raise ValueError(f"set_scaling: expected a setting, or a list or dict of settings, got {scaling!r}")
+        for k, t in scaling.items():
+            if k not in self.keys():
+                raise RuntimeError(f"No CastTo with key {k}!")
+            self[k].set_scaling(t)
 
     def set_format(self, format):
         for k, f in self.pack_to_dict(format).items():

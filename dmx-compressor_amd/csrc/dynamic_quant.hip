@@ -27,14 +27,12 @@
 // Every segment is read completely before any of it is written.  No workspace, no synchronisation with the host: capturable.
 #include <math.h>
 
+#include "dynamic_geom.hpp"
 #include "fixedq.hpp"
 #include "reduce_common.hpp"
 
 namespace dmxq {
 namespace {
-
-constexpr int kDynThreads = 256;
-constexpr int kDynMaxRow = 16384;
 
 struct DynFmt {
   float t_min, t_max;
@@ -204,19 +202,6 @@ __global__ __launch_bounds__(kDynThreads) void dyn_rows_kernel(const void* __res
     dyn_cast_vec<V>(x, y, s, all_fast, all_zp0, f);
     if (v < nv && row_ok) store_vec<DT, V>(out, (v0 + v) * V, y);
   }
-}
-
-inline bool dyn_pow2(int64_t v) { return v >= 1 && (v & (v - 1)) == 0; }
-
-// The launch geometry of a segment length: THE rule, used by dyn_launch below and handed out through dmxq_dynamic_class (the front
-// end's ops.dynamic_class, by which the default route and the measurement table name a geometry).  V: elements per 16-byte vector.
-inline int dyn_class(int64_t S, int V, bool whole_rows) {
-  if (S < 1 || S % V != 0 || S > kDynMaxRow) return DMXQ_DYN_NONE;
-  if (dyn_pow2(S) && S >= 16 && S <= 256) return DMXQ_DYN_GROUP;
-  if (!whole_rows) return DMXQ_DYN_NONE;   // (a group that is no such power of two: a wave per short segment would idle most lanes)
-  const int64_t nv = S / V;
-  if (nv < kWave) return DMXQ_DYN_SHORT_ROW;               // a wave per row with idle lanes (measured apart)
-  return nv <= 16 * kWave ? DMXQ_DYN_WAVE_ROW : DMXQ_DYN_BLOCK_ROW;
 }
 
 template <int DT>

@@ -1036,6 +1036,45 @@ std::tuple<Tensor, Tensor, Tensor> dynamic_fixed_qdq_meta(const Tensor& x, int64
   return std::make_tuple(empty_like_shape(x, out_dtype), at::empty({n}, x.options().dtype(at::kFloat)), at::empty({n}, x.options().dtype(at::kLong)));
 }
 
+// ------------------------------------------------------------------------------------------------ dynamic scaled float cast
+// x: contiguous; mode: dmxq_dynamic_float_mode; -> (out, scale float32 [n_segments], or [..., R / g, C / g] for tiles; empty unless
+// want_scale).  DMXQ_ERR_UNSUPPORTED (NotImplementedError, nothing launched): the front end runs its chain of launches.
+std::vector<int64_t> dynamic_float_scale_shape(const Tensor& x, int64_t mode, int64_t segment, const char* what) {
+  TORCH_CHECK(segment >= 1, what, ": the segment must be positive");
+  if (mode == DMXQ_DYNF_TILE) {
+    TORCH_CHECK(x.dim() >= 2 && x.size(-2) % segment == 0 && x.size(-1) % segment == 0, what,
+                ": the tile size must divide the last two dimensions");
+    std::vector<int64_t> shape(x.sizes().begin(), x.sizes().end());
+    shape[shape.size() - 2] /= segment;
+    shape[shape.size() - 1] /= segment;
+    return shape;
+  }
+  TORCH_CHECK(x.numel() % segment == 0, what, ": the segment must divide the number of elements");
+  return {x.numel() / segment};
+}
+std::tuple<Tensor, Tensor> dynamic_float_qdq(const Tensor& x, int64_t mode, int64_t segment, int64_t man, int64_t exp, int64_t bias,
+                                             bool flush_subnormal, int64_t rounding, bool pow2_scale, bool want_scale, OptDtype out_dtype) {
+  const Tensor xc = prep(x, "dynamic_float_qdq");
+  const std::vector<int64_t> shape = dynamic_float_scale_shape(xc, mode, segment, "dynamic_float_qdq");
+  int64_t n = 1;
+  for (int64_t d : shape) n *= d;
+  const bool tile = mode == DMXQ_DYNF_TILE;
+  const int64_t cols = tile ? xc.size(-1) : 0, rows = tile && cols ? xc.numel() / cols : 0;
+  Tensor out = empty_like_shape(xc, out_dtype);
+  Tensor sc = want_scale ? at::empty(shape, xc.options().dtype(at::kFloat)) : at::empty({0}, xc.options().dtype(at::kFloat));
+  Launch l(xc);
+  check(dmxq_dynamic_float_qdq(xc.data_ptr(), out.data_ptr(), dt_code(xc.scalar_type()), dt_code(out.scalar_type()), (int)mode, n, segment, rows,
+                               cols, (int)man, (int)exp, (int)bias, flush_subnormal ? 1 : 0, (int)rounding, pow2_scale ? 1 : 0,
+                               want_scale ? (float*)sc.data_ptr() : nullptr, l.stream), "dmxq_dynamic_float_qdq");
+  return std::make_tuple(out, sc);
+}
+std::tuple<Tensor, Tensor> dynamic_float_qdq_meta(const Tensor& x, int64_t mode, int64_t segment, int64_t, int64_t, int64_t, bool, int64_t, bool,
+                                                  bool want_scale, OptDtype out_dtype) {
+  const std::vector<int64_t> shape = dynamic_float_scale_shape(x, mode, segment, "dynamic_float_qdq");
+  return std::make_tuple(empty_like_shape(x, out_dtype),
+                         want_scale ? at::empty(shape, x.options().dtype(at::kFloat)) : at::empty({0}, x.options().dtype(at::kFloat)));
+}
+
 }  // namespace
 
 TORCH_LIBRARY(dmxq, m) {
@@ -1089,6 +1128,7 @@ TORCH_LIBRARY(dmxq, m) {
   m.def("cast_error(Tensor x, int[] fmts, Tensor? scale, Tensor? zero_point, bool accumulate, Tensor(a!) stats, Tensor(b!) scratch) -> ()");
   m.def("hadamard_qdq(Tensor x, int size, bool inverse, int[] fmt, Tensor? scale, Tensor? zero_point, ScalarType? out_dtype=None) -> Tensor");
   m.def("dynamic_fixed_qdq(Tensor x, int segment, bool whole_rows, int precision, int fraction, bool clamp, bool symmetric, int rounding, int qmin, int qmax, bool symmetric_qscheme, bool want_qparams, ScalarType? out_dtype=None) -> (Tensor, Tensor, Tensor)");
+  m.def("dynamic_float_qdq(Tensor x, int mode, int segment, int man, int exp, int bias, bool flush_subnormal, int rounding, bool pow2_scale, bool want_scale, ScalarType? out_dtype=None) -> (Tensor, Tensor)");
 }
 
 #define DMXQ_IMPL(m, name) m.impl(#name, &name)
@@ -1098,7 +1138,7 @@ TORCH_LIBRARY(dmxq, m) {
   X(m, float_qdq); X(m, float_qdq_multi); X(m, fixed_qdq); X(m, fixed_qdq_multi); X(m, fixed_float_qdq_multi); X(m, nm_mask); X(m, topk_mask); X(m, bernoulli_mask); X(m, group_minmax); X(m, qparams); \
   X(m, histc); X(m, channel_maxabs); X(m, smoothquant_scale); X(m, scale_channels); X(m, unary); X(m, rope); X(m, rope_cast); X(m, softmax); X(m, norm); \
   X(m, unary_cast); X(m, unary_cast_table); X(m, lut16_apply); X(m, softmax_cast); X(m, norm_cast); X(m, group_minmax_accumulate); X(m, gptq_block); X(m, hist_observe); X(m, hist_qparams); \
-  X(m, error_stats); X(m, cast_error); X(m, hadamard_qdq); X(m, dynamic_fixed_qdq); X(m, gptq_block_dynamic)
+  X(m, error_stats); X(m, cast_error); X(m, hadamard_qdq); X(m, dynamic_fixed_qdq); X(m, gptq_block_dynamic); X(m, dynamic_float_qdq)
 
 // "CUDA" is the dispatch key of HIP tensors in a ROCm build of PyTorch
 TORCH_LIBRARY_IMPL(dmxq, CUDA, m) {
@@ -1157,4 +1197,6 @@ PYBIND11_MODULE(dmxq_fast, m) {
   m.def("dynamic_fixed_qdq", &dynamic_fixed_qdq, py::arg("x"), py::arg("segment"), py::arg("whole_rows"), py::arg("precision"), py::arg("fraction"),
         py::arg("clamp"), py::arg("symmetric"), py::arg("rounding"), py::arg("qmin"), py::arg("qmax"), py::arg("symmetric_qscheme"),
         py::arg("want_qparams"), py::arg("out_dtype") = py::none());
+  m.def("dynamic_float_qdq", &dynamic_float_qdq, py::arg("x"), py::arg("mode"), py::arg("segment"), py::arg("man"), py::arg("exp"), py::arg("bias"),
+        py::arg("flush_subnormal"), py::arg("rounding"), py::arg("pow2_scale"), py::arg("want_scale"), py::arg("out_dtype") = py::none());
 }

@@ -24,6 +24,15 @@ from ._lib import DmxqError
 __all__ = ["OptimalBrainCompressor"]
 
 
+def refuse_scaled_weight_cast(module):
+    """GPTQ on a module whose weight cast is a scaled float cast (CastTo.set_scaling) is not supported: NotImplementedError"""
+    wc = getattr(module, "weight_cast", None)
+    if wc is not None and wc._scaling is not None:
+        raise NotImplementedError(f"GPTQ with a scaled float weight cast (weight_scaling = {wc.scaling!r}) is not supported: a segment's "
+                                  "scale would move with every compensated column; clear the setting (set_scaling(None)) or use a "
+                                  "dynamic integer cast (weight_dynamic)")
+
+
 class OptimalBrainCompressor:
     H = None
 
@@ -128,7 +137,7 @@ class OptimalBrainCompressor:
         wc, st = m.weight_cast, m.weight_storage_cast
         if st is not None and not (isinstance(st.format, Same) and not st.pre_transform):
             return None
-        if wc.pre_transform or wc.dynamic is not None or not wc._flag("fake_quant_enabled") or wc._flag("observer_enabled"):
+        if wc.pre_transform or wc.dynamic is not None or wc._scaling is not None or not wc._flag("fake_quant_enabled") or wc._flag("observer_enabled"):
             return None   # (a dynamic cast: its scale buffers are not what it casts with)
         per_row = False
         if isinstance(wc.format, FixedPoint):
@@ -162,6 +171,7 @@ class OptimalBrainCompressor:
         per_token / per_tensor; a plain attribute, no state_dict key), and (2) switches the weight cast's fake_quant_enabled flag OFF, so
         that forwards use Q as written.  Static casts behave as before: nothing recorded, no switch touched."""
         self._check(microblock_size, block_size)
+        refuse_scaled_weight_cast(self.module)
         self._check_act_order(act_order)
         dyn = self._dynamic_plan(block_size)
         m = self.module

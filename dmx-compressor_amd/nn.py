@@ -165,6 +165,14 @@ class DmxModule(FastAttr, torch.nn.Module):
             self.output_casts.set_dynamic(config["output_dynamic"])
         if self.weight_cast is not None and "weight_dynamic" in config:
             self.weight_cast.set_dynamic(config["weight_dynamic"])   # (per_token: per output channel of the [out, in] view)
+        # dynamic scales for the float casts (CastTo.set_scaling): None, "per_token", "per_tensor", {"per_group": g} or {"per_tile": g},
+        # each dict optionally with "pow2_scale": True -- one setting for every cast of the dict, or a list / dict of settings
+        if "input_scaling" in config:
+            self.input_casts.set_scaling(config["input_scaling"])
+        if "output_scaling" in config:
+            self.output_casts.set_scaling(config["output_scaling"])
+        if self.weight_cast is not None and "weight_scaling" in config:
+            self.weight_cast.set_scaling(config["weight_scaling"])   # (per_token: per output channel; per_tile: tiles of the [out, in] view)
         if self.accum_cast is not None and "accum_format" in config:
             self.accum_cast.set_format(config["accum_format"])
         if self.weight_storage_cast is not None and "weight_storage_format" in config:
@@ -426,7 +434,8 @@ class DmxModule(FastAttr, torch.nn.Module):
         the unquantised inputs (fake quant off on the input casts and the weight cast); leaving switches both back on and runs GPTQ."""
         if isinstance(self, (torch.nn.Linear, torch.nn.Conv2d)):
             if state:
-                from .layer_reconstruction import OptimalBrainCompressor
+                from .layer_reconstruction import OptimalBrainCompressor, refuse_scaled_weight_cast
+                refuse_scaled_weight_cast(self)   # (before any switch is touched)
                 self.obc = OptimalBrainCompressor(self)
                 self.input_casts.disable_fake_quant()
                 self.weight_cast.disable_fake_quant()
@@ -494,7 +503,7 @@ class DmxModule(FastAttr, torch.nn.Module):
             return False
         oc = self.output_casts[next(iter(self.output_casts.keys()))]
         f = oc.format
-        if (not isinstance(f, FloatingPoint) or f.rounding != "nearest" or f.unsigned or oc.pre_transform
+        if (not isinstance(f, FloatingPoint) or f.rounding != "nearest" or f.unsigned or oc.pre_transform or oc._scaling is not None
                 or not oc._flag("fake_quant_enabled") or oc._flag("observer_enabled")):
             return False
         for c, idx in consumers:
@@ -503,7 +512,7 @@ class DmxModule(FastAttr, torch.nn.Module):
             if nc is None or (sq is not None and (sq._flag("enabled") or sq._flag("dynamic") or sq.calibrating)):
                 return False
             g = nc.format
-            if (not isinstance(g, FloatingPoint) or g.rounding != "nearest" or g.unsigned or nc.pre_transform
+            if (not isinstance(g, FloatingPoint) or g.rounding != "nearest" or g.unsigned or nc.pre_transform or nc._scaling is not None
                     or not nc._flag("fake_quant_enabled") or nc._flag("observer_enabled")
                     or (g.mantissa, g.exponent, g.bias, bool(g.flush_subnormal)) != (f.mantissa, f.exponent, f.bias, bool(f.flush_subnormal))):
                 return False
@@ -786,7 +795,8 @@ def _range_only_format(cast, dtype):
     fmt = cast.format
     if isinstance(fmt, Same):
         return (not cast.pre_transform), None
-    if (not isinstance(fmt, FloatingPoint) or cast.pre_transform or not cast._flag("fake_quant_enabled") or cast._flag("observer_enabled")):
+    if (not isinstance(fmt, FloatingPoint) or cast.pre_transform or cast._scaling is not None   # (a scaled cast is no pure range cast)
+            or not cast._flag("fake_quant_enabled") or cast._flag("observer_enabled")):
         return False, None
     # format.py:209-212: the dtype's own format passes the tensor through untouched (no flush, NaN stays NaN) -- SAME for the kernel
     if fmt.native_of() == dtype:
@@ -1495,7 +1505,7 @@ def _weight_batches(mods):
     with torch.no_grad():
         for m in mods:
             wc, st, sp, sq = m.weight_cast, m.weight_storage_cast, m.weight_sparsifier, m.smoothquant
-            if (wc is None or wc.pre_transform or wc.dynamic is not None or not wc._flag("fake_quant_enabled") or wc._flag("observer_enabled") or not m.weight.is_cuda
+            if (wc is None or wc.pre_transform or wc.dynamic is not None or wc._scaling is not None or not wc._flag("fake_quant_enabled") or wc._flag("observer_enabled") or not m.weight.is_cuda
                     or (sp is not None and not isinstance(sp.sparseness, Dense))
                     or (sq is not None and not sq._flag("fused_to_weight") and sq._flag("enabled"))
                     or (st is not None and not (isinstance(st.format, Same) and not st.pre_transform))):
@@ -1534,7 +1544,7 @@ def _bias_batches(mods):
     groups = {}
     for m in mods:
         bc, b = getattr(m, "bias_cast", None), getattr(m, "bias", None)
-        if bc is None or b is None or not b.is_cuda or bc.pre_transform or not bc._flag("fake_quant_enabled") or bc._flag("observer_enabled"):
+        if bc is None or b is None or not b.is_cuda or bc.pre_transform or bc._scaling is not None or not bc._flag("fake_quant_enabled") or bc._flag("observer_enabled"):
             continue
         fmt = bc.format
         if isinstance(fmt, FloatingPoint) and fmt.rounding == "nearest" and fmt.mantissa < 23 and fmt.native_of() != b.dtype:

@@ -54,7 +54,8 @@ typedef enum {
 
 const char* dmxq_status_string(int status);
 /* ABI version: bumped on any signature change.  Additions since 4 (dmxq_gptq_block, dmxq_hist_observe, dmxq_hist_qparams, dmxq_error_stats, dmxq_cast_error,
- * dmxq_error_scratch_bytes, dmxq_hadamard_qdq, dmxq_dynamic_fixed_qdq, dmxq_dynamic_class, dmxq_gptq_block_dynamic) leave it at 4: a caller built against 4 runs on
+ * dmxq_error_scratch_bytes, dmxq_hadamard_qdq, dmxq_dynamic_fixed_qdq, dmxq_dynamic_class, dmxq_gptq_block_dynamic,
+ * dmxq_dynamic_float_qdq, dmxq_dynamic_float_class) leave it at 4: a caller built against 4 runs on
  * this library unchanged.  4 = round 5: + dmxq_float_qdq_multi, dmxq_fixed_float_qdq_multi; 3 = round 4: + dmxq_weight_hypernet_multi,
  * dmxq_unary_cast_table, dmxq_lut16_apply.  Nothing was ever removed or changed: a caller built against version n runs on any library >= n. */
 int dmxq_abi_version(void);
@@ -547,12 +548,39 @@ int dmxq_hadamard_qdq(const void* in, void* out, int dtype_in, int dtype_out, in
 /* The launch geometry dmxq_dynamic_fixed_qdq picks for segments of `segment` elements of `dtype` (no GPU involved; the same function
  * makes the choice inside the entry): NONE = refused (DMXQ_ERR_UNSUPPORTED), GROUP = power-of-two segments of 16 .. 256 inside a wave,
  * SHORT_ROW = a wave per row of fewer than 64 vectors (lanes idle), WAVE_ROW = a wave per row of 64 .. 1024 vectors, BLOCK_ROW = a
- * 256-thread workgroup per row.  Returns the enum value, not a status. */
-typedef enum { DMXQ_DYN_NONE = 0, DMXQ_DYN_GROUP = 1, DMXQ_DYN_SHORT_ROW = 2, DMXQ_DYN_WAVE_ROW = 3, DMXQ_DYN_BLOCK_ROW = 4 } dmxq_dynamic_geometry;
+ * 256-thread workgroup per row; TILE (dmxq_dynamic_float_class only) = a g x g tile per wave or workgroup.  Returns the enum value, not
+ * a status. */
+typedef enum { DMXQ_DYN_NONE = 0, DMXQ_DYN_GROUP = 1, DMXQ_DYN_SHORT_ROW = 2, DMXQ_DYN_WAVE_ROW = 3, DMXQ_DYN_BLOCK_ROW = 4,
+               DMXQ_DYN_TILE = 5 } dmxq_dynamic_geometry;
 int dmxq_dynamic_class(int dtype, int64_t segment, int whole_rows);
 int dmxq_dynamic_fixed_qdq(const void* in, void* out, int dtype_in, int dtype_out, int64_t n_segments, int64_t segment, int whole_rows,
                            int precision, int fraction, int clamp, int symmetric, int rounding, int qmin, int qmax,
                            int symmetric_qscheme, float* scale_out, int64_t* zp_out, void* stream);
+
+/* Dynamic SCALED float cast (csrc/dynamic_float.hip): every segment of the contiguous tensor is scaled by its OWN absolute
+ * maximum, on every call, in ONE launch -- per token, per group, per 2-D tile (the FP8 recipe's activations and weights).  Not in the
+ * reference, whose float casts are unscaled; the per-element arithmetic is dmxq_float_qdq's.  The format is the SIGNED float
+ * (man_bits, exp_bits < 8, exp_bias, flush_subnormal) with largest output fmax = 2^(2^(exp_bits-1)) (2 - 2^-man_bits).  Per segment, in fp32:
+ *   amax = max |x| (one NaN anywhere makes it NaN);  s = amax / fmax (IEEE);
+ *   pow2_scale != 0: s rounded UP to a power of two on its bits, b = (b & 0x7F800000) + ((b & 0x007FFFFF) ? 0x00800000 : 0);
+ *   s = 1 when s is not finite or below 2^-126 (an all-zero, a NaN, an Inf segment);
+ *   out = float_q(x / s) * s: IEEE quotient, the format's nearest cast (flush flag kept, NaN / Inf saturate as in dmxq_float_qdq), one
+ *   fp32 multiply, one rounding to dtype_out.
+ * mode: DMXQ_DYNF_GROUP -- n_segments groups of `segment` consecutive elements, a power of two from 16 to 256; DMXQ_DYNF_ROWS --
+ * n_segments rows of `segment` elements, any multiple of a 16-byte vector (8 sixteen-bit or 4 fp32 elements) up to 16384 (rows, cols
+ * unused in both); DMXQ_DYNF_TILE -- the [rows, cols] matrix in segment x segment tiles, segment = 32, 64 or 128 dividing both (leading
+ * batch dims fold into rows), n_segments = (rows / segment) (cols / segment), tile t = (row tile) * (cols / segment) + (column tile).
+ * scale_out: NULL or a DEVICE array of n_segments floats, the s of every segment.
+ * DMXQ_ERR_UNSUPPORTED, nothing launched (the caller runs its chain of launches): dtype_in != dtype_out, rounding other than nearest, a
+ * base that is not 16-byte aligned, a segment outside the above, man_bits > 22.  DMXQ_ERR_BAD_ARG: null data pointers, negative sizes,
+ * invalid dtype / rounding / mode, exp_bits outside 1 .. 7 (8: fp32's exponent range has no finite maximum), a tile size that does not
+ * divide rows and cols or an n_segments that is not their tile count.  No workspace, no allocation, no host synchronisation: capturable.
+ * dmxq_dynamic_float_class: the geometry (dmxq_dynamic_geometry) the entry picks for `segment` under `mode`, no GPU involved. */
+typedef enum { DMXQ_DYNF_GROUP = 0, DMXQ_DYNF_ROWS = 1, DMXQ_DYNF_TILE = 2 } dmxq_dynamic_float_mode;
+int dmxq_dynamic_float_class(int dtype, int mode, int64_t segment);
+int dmxq_dynamic_float_qdq(const void* in, void* out, int dtype_in, int dtype_out, int mode, int64_t n_segments, int64_t segment,
+                           int64_t rows, int64_t cols, int man_bits, int exp_bits, int exp_bias, int flush_subnormal, int rounding,
+                           int pow2_scale, float* scale_out, void* stream);
 
 #ifdef __cplusplus
 }
