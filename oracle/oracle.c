@@ -352,7 +352,8 @@ int oracle_floor_log2f(float m) {
 /* numerical/format.py:545-564 MXFP.cast (intended layout: blocks along the last dim; the reference's
  * cat(dim=block_dim) slip is not reproduced).  Per block: scale = 2^floor(log2(max|x|)) / 2^(2^(e-1));
  * y = float_quantize(x / scale, man, exp, bias = 2^(e-1)-1, no flush) * scale.
- * An all-zero block gives log2(0) = -inf, scale 0 and NaN in the reference; here it stays zero (documented). */
+ * An all-zero block gives log2(0) = -inf, scale 0 and NaN in the reference; here it stays zero (documented).
+ * Total: every other maximum -- denormal, Inf, NaN -- gives what the reference's float32 tensor ops give. */
 int oracle_mxfp_qdq(const float* in, float* out, int64_t rows, int64_t L, int64_t B, int man, int exp_bits) {
   if (B < 1 || man < 0 || man > 22 || exp_bits < 1 || exp_bits > 8) return 1;
   const int bias = (1 << (exp_bits - 1)) - 1;
@@ -366,7 +367,9 @@ int oracle_mxfp_qdq(const float* in, float* out, int64_t rows, int64_t L, int64_
       float m = 0.0f;
       for (int64_t i = 0; i < len; i++) { float a = fabsf(x[i]); if (a > m || isnan(a)) m = a; }
       if (m == 0.0f) { for (int64_t i = 0; i < len; i++) y[i] = x[i] * 0.0f; continue; }
-      const float scale = powf(2.0f, (float)oracle_floor_log2f(m)) / big;
+      /* an Inf or NaN maximum has no integer floor(log2): the expression is evaluated in float, as the reference's tensor ops
+       * do -- 2^inf / big = inf (finite elements: 0 * inf = NaN, infinite ones: a saturated NaN times inf = +-Inf), NaN stays NaN */
+      const float scale = (isfinite(m) ? powf(2.0f, (float)oracle_floor_log2f(m)) : powf(2.0f, floorf(log2f(m)))) / big;
       for (int64_t i = 0; i < len; i++) y[i] = float_q1(x[i] / scale, man, exp_bits, bias, 0, R_NEAREST, 0u) * scale;
     }
   return 0;

@@ -88,7 +88,7 @@ def make(kind, shape, seed=0, dtype=torch.float32, block=16):
     else:
         raise ValueError(kind)
     t = torch.from_numpy(v.astype(np.float32)).reshape(shape)
-    if dtype == torch.float16:  # keep inputs finite: Inf/NaN blocks are covered by their own test
+    if dtype == torch.float16:  # keep inputs finite: Inf/NaN blocks are covered by their own tests (SBFP / MXFP: tests/_blockfmt_cases.py)
         t = t.clamp(-65504.0, 65504.0)
     return t.to(dtype)
 

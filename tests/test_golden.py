@@ -244,6 +244,38 @@ def test_boundaries_mxfp_maxima_just_below_powers_of_two(backend, dmx, oracle):
 
 
 @pytest.mark.parametrize("backend", backends(), indirect=True)
+def test_blockfmt_classes_of_block_maxima(backend, dmx, oracle):
+    """MXFP.cast and ScaledBlockFloatingPoint.cast of the reference itself (oracle/gen_golden_blockfmt.py) on the planted tables of
+    tests/_blockfmt_cases.py: a block of every class of block maximum -- zero, denormal, below the element format's range, from 2^105
+    up, Inf, NaN, just below a power of two; SBFP scales outside [2^-20, 2^20], saturating or flushing in the scaler format -- at every
+    block position of a wave of ordinary data, float32 and bfloat16.  The inputs are regenerated and checked by digest.  One
+    exemption: the elements of all-zero MXFP blocks, where the reference divides 0 by 0 and this project keeps the zeros with their
+    signs; their number is the number planted, so the exemption cannot grow."""
+    import _blockfmt_cases as C
+    from _data import sha256_bits
+    g = load("blockfmt_classes.npz")
+    hip = isinstance(backend, HipBackend)
+    assert [str(s) for s in g["sh"]] == [c[0] for c in C.GOLDEN_CASES]
+    for i, (sh, kind, f, B) in enumerate(C.GOLDEN_CASES):
+        for name in C.GOLDEN_DTYPES:
+            dt = C.DTYPES[name]
+            t = C.golden_table(kind, f, dt, B)
+            assert sha256_bits(t.x) == str(g[f"sha{i}_{name}"]), (sh, name)
+            if hip:
+                y = dmx.CastTo(format=sh)(t.x.to(backend.dev)).cpu()
+            else:
+                y = C.ref(kind, oracle, t.x, f, B).to(dt.torch)
+            want = tensor(g[f"y{i}_{name}"], dt.torch)
+            exempt = C.zero_block_mask(t.x, B) if kind == "mxfp" else torch.zeros(t.x.shape, dtype=torch.bool)
+            planted_zero = sum(B for _, _, c, _ in t.plan if c == "zero")
+            assert int(exempt.sum()) == (planted_zero if kind == "mxfp" else 0) and planted_zero == t.blocks_per_wave * B
+            both_nan = torch.isnan(y.float()) & torch.isnan(want.float())
+            bad = (y.view(T_BITS[dt.torch]) != want.view(T_BITS[dt.torch])) & ~both_nan & ~exempt
+            assert y.dtype == dt.torch and int(bad.sum()) == 0, (sh, name, int(bad.sum()))
+            assert bool((y.view(T_BITS[dt.torch])[exempt] == t.x.view(T_BITS[dt.torch])[exempt]).all()), (sh, name)   # zeros, signs kept
+
+
+@pytest.mark.parametrize("backend", backends(), indirect=True)
 def test_boundaries_asymmetric_bfp_with_planted_nonfinite_and_denormal_blocks(backend, dmx):
     """`BFP[p|8]{16}(_N)` (format.py:304-372) on tensors with planted Inf / NaN / denormal-maximum blocks, against the reference's
     own output.  The reference's post-pass rebuilds a whole [rows, 16] chunk from integers iff ANY row of the
