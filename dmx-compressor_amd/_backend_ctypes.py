@@ -884,3 +884,43 @@ def dynamic_float_qdq(x, mode, segment, man, exp, bias, flush_subnormal, roundin
                                        bias, int(bool(flush_subnormal)), rounding, int(bool(pow2_scale)), ptr(sc) if want_scale else None,
                                        stream_of(xc)), "dmxq_dynamic_float_qdq")
     return out, sc
+
+
+# ------------------------------------------------------------------------------------------------ Wanda
+@_guarded
+def channel_sumsq(x, acc, scratch):
+    """acc (float64 [C], C = x's last dim) += the sum of squares over every other dim; scratch: dmxq_channel_sumsq_workspace_bytes bytes of
+    any contiguous device tensor"""
+    xc = _prep(x, "channel_sumsq")
+    C = xc.shape[-1] if xc.dim() else 1
+    rows = xc.numel() // C if C else 0
+    if not (acc.is_cuda and acc.device == xc.device and acc.dtype == torch.float64 and acc.is_contiguous() and acc.numel() == C):
+        raise RuntimeError(f"channel_sumsq: acc must be a contiguous float64 tensor of {C} entries on the input's device")
+    need = lib().dmxq_channel_sumsq_workspace_bytes(rows, C)
+    if not (scratch.is_cuda and scratch.device == xc.device and scratch.is_contiguous() and scratch.numel() * scratch.element_size() >= need
+            and scratch.data_ptr() % 8 == 0):
+        raise RuntimeError(f"channel_sumsq: scratch must be a contiguous 8-byte aligned tensor of at least {need} bytes on the input's device")
+    check(lib().dmxq_channel_sumsq_accumulate(ptr(xc), dtype_code(xc.dtype), rows, C, ptr(acc), ptr(scratch), stream_of(xc)),
+          "dmxq_channel_sumsq_accumulate")
+
+
+def _wanda_shapes(w, act_norm):
+    if w.dim() != 2:
+        raise RuntimeError("wanda_nm: the weight must be a [rows, L] matrix")
+    if not (act_norm.is_cuda and act_norm.device == w.device and act_norm.dtype == torch.float32 and act_norm.is_contiguous()
+            and act_norm.numel() == w.shape[1]):
+        raise RuntimeError(f"wanda_nm: act_norm must be a contiguous float32 tensor of {w.shape[1]} entries on the weight's device")
+
+
+@_guarded
+def wanda_nm(w, act_norm, K, M, want_score, want_mask, want_y, mask_dtype=None, y_dtype=None):
+    """-> (score float32, mask, y): an output that was not requested comes back as an empty 1-d tensor"""
+    wc = _prep(w, "wanda_nm")
+    _wanda_shapes(wc, act_norm)
+    none = torch.empty(0, dtype=wc.dtype, device=wc.device)
+    score = torch.empty(wc.shape, dtype=torch.float32, device=wc.device) if want_score else None
+    mask = torch.empty(wc.shape, dtype=mask_dtype or torch.float32, device=wc.device) if want_mask else None
+    y = torch.empty(wc.shape, dtype=y_dtype or torch.promote_types(wc.dtype, torch.float32), device=wc.device) if want_y else None
+    check(lib().dmxq_wanda_nm(ptr(wc), dtype_code(wc.dtype), ptr(act_norm), ptr(score), ptr(mask), dtype_code(mask.dtype) if want_mask else 0,
+                              ptr(y), dtype_code(y.dtype) if want_y else 0, wc.shape[0], wc.shape[1], K, M, stream_of(wc)), "dmxq_wanda_nm")
+    return (score if want_score else none.float()), (mask if want_mask else none), (y if want_y else none)

@@ -25,6 +25,7 @@ __all__ = [
     "dynamic_fixed_qdq", "dynamic_check", "dynamic_class", "DYNAMIC_GRANULARITIES", "DYNAMIC_CHAIN_BY_DEFAULT",
     "dynamic_float_qdq", "dynamic_float_check", "dynamic_float_class", "dynamic_float_fmax", "DYNAMIC_FLOAT_GRANULARITIES",
     "DYNAMIC_FLOAT_CHAIN_BY_DEFAULT",
+    "channel_sumsq", "channel_sumsq_workspace_bytes", "wanda_score", "wanda_nm_sparsify", "wanda_class", "WANDA_CHAIN_BY_DEFAULT",
 ]
 
 _ops = None   # the raw namespace: set by bind()
@@ -1240,3 +1241,147 @@ def dynamic_float_qdq(x, fmt, granularity: str = "per_token", group_size: Option
         return _DynamicSTE.apply(x, run)
     with torch.no_grad():
         return run(x.detach())
+
+
+# ---------------------------------------------------------------------------------------------------- Wanda
+# Geometries of dmxq_wanda_nm -- the group size M: 0 (score only), 4, 8, 16 -- that fused=None sends to the chain although the kernel
+# takes them: DYNAMIC_FLOAT_CHAIN_BY_DEFAULT's rule, a class goes to the kernel by default only where tools/bench_wanda.py MEASURED it
+# faster than the chain (wanda_score, then nm_sparsify) on the same buffers.  profiles/r16_wanda.txt (bf16, us per call, kernel against
+# chain): y alone 2:4 [4096,4096] 18.6 against 46.6, 4:8 21.5 against 48.3, 2:4 [14336,4096] 51.2 against 151.5, 4:8 60.1 against 156.2;
+# score + mask 46.0 against 46.6, 45.0 against 47.3, 153.7 against 156.2, 155.3 against 156.2 -- no row is slower, none is listed.
+WANDA_CHAIN_BY_DEFAULT = frozenset()
+# which route the calls of this front end took, counted on the host: private, for the tests (fused=True must have run the kernel)
+_wanda_routes = {"fused": 0, "chain": 0}
+_sumsq_workspaces = {}   # (device, bytes) -> the workspace of channel_sumsq outside captures
+
+
+def channel_sumsq_workspace_bytes(rows: int, C: int) -> int:
+    """dmxq_channel_sumsq_workspace_bytes: what one channel_sumsq call over [rows, C] needs.  A host query of the library itself."""
+    from ._lib import lib
+    return int(lib().dmxq_channel_sumsq_workspace_bytes(int(rows), int(C)))
+
+
+def _sumsq_workspace(device, nbytes):
+    """The slabs' partial sums of one channel_sumsq call: kept per (device, size) between calls -- a calibration run calls with a handful
+    of shapes, once per forward of every observed module, on one stream -- except under a hipGraph capture, where the graph's own pool
+    has to own the memory its kernels write."""
+    n = max(nbytes, 8)
+    if torch.cuda.is_current_stream_capturing():
+        return torch.empty(n // 8 + 1, dtype=torch.float64, device=device)
+    key = (device, n)
+    ws = _sumsq_workspaces.get(key)
+    if ws is None:
+        ws = _sumsq_workspaces[key] = torch.empty(n // 8 + 1, dtype=torch.float64, device=device)
+    return ws
+
+
+def channel_sumsq(x, out=None):
+    """Per-channel sum of squares of x over every dimension but the last, in float64 (dmxq_channel_sumsq_accumulate; DESIGN.md §8
+    "Wanda"): a float64 [C] tensor on x's device, C = x.shape[-1]; with `out` the sums are ADDED into it (statistics over many batches)
+    and it is returned.  Every square is formed in double and the sum takes a fixed order without atomics: the same batches in the same
+    order give the same bits.  A non-contiguous x is made contiguous first.  Two launches, nothing read back: capturable."""
+    require_gpu(x, "channel_sumsq")
+    if x.dim() < 1:
+        raise ValueError("channel_sumsq: x needs a channel dimension")
+    C = x.shape[-1]
+    if out is None:
+        out = torch.zeros(C, dtype=torch.float64, device=x.device)
+    elif not (out.is_cuda and out.device == x.device and out.dtype == torch.float64 and out.is_contiguous() and out.shape == (C,)):
+        raise ValueError(f"channel_sumsq: out must be a contiguous float64 [{C}] tensor on the input's device")
+    if x.numel() == 0:
+        return out
+    xd = x.detach()
+    _ops.channel_sumsq(xd, out, _sumsq_workspace(x.device, channel_sumsq_workspace_bytes(x.numel() // C, C)))
+    return out
+
+
+def wanda_class(dtype: torch.dtype, L: int, M: int) -> bool:
+    """whether dmxq_wanda_nm takes rows of L elements of `dtype` with groups of M (0: score only) in its one-pass kernel, asked of the
+    library itself (dmxq_wanda_class; no GPU involved): M in {0, 4, 8, 16} and L a multiple of 16"""
+    from ._lib import dtype_code, lib
+    return bool(lib().dmxq_wanda_class(dtype_code(dtype), int(L), int(M)))
+
+
+def _wanda_check(w, act_norm, K, M, what):
+    """the argument errors of the Wanda ops, before any GPU use (ValueError / TypeError)"""
+    if not isinstance(w, torch.Tensor) or w.dim() != 2:
+        raise ValueError(f"{what}: the weight must be a [rows, L] matrix")
+    if w.dtype not in (torch.float32, torch.float16, torch.bfloat16):
+        raise TypeError(f"{what}: the weight must be float32, float16 or bfloat16, got {w.dtype}")
+    L = w.shape[1]
+    if not isinstance(act_norm, torch.Tensor) or act_norm.dtype != torch.float32:
+        raise TypeError(f"{what}: act_norm must be a float32 tensor, got {getattr(act_norm, 'dtype', type(act_norm))}")
+    if act_norm.shape != (L,):
+        raise ValueError(f"{what}: act_norm must hold one entry per input channel, [{L}], got {tuple(act_norm.shape)}")
+    if M or K:
+        if isinstance(K, bool) or isinstance(M, bool) or not isinstance(K, int) or not isinstance(M, int) or M < 1 or M > 64 or K < 1:
+            raise ValueError(f"{what}: K and M must be integers with 1 <= K <= M <= 64, got {K!r}:{M!r}")
+        if K > M:
+            raise ValueError(f"{what}: K = {K} non-zeros do not fit a group of M = {M}")
+        if L % M:
+            raise ValueError(f"{what}: the last dimension has {L} elements, not a multiple of the group size {M}")
+
+
+def _wanda(w, act_norm, K, M, want_score, want_mask, want_y, fused, out_dtype, what):
+    _wanda_check(w, act_norm, K, M, what)
+    if not (want_score or want_mask or want_y):
+        raise ValueError(f"{what}: nothing to compute: none of score, mask and y was asked for")
+    if not M and (want_mask or want_y):
+        raise ValueError(f"{what}: K = M = 0 asks for the score alone; a mask or y needs a K:M pattern")
+    require_gpu(w, what)
+    require_gpu(act_norm, what)
+    with torch.no_grad():
+        wc = w.detach()
+        wc = wc if wc.is_contiguous() else wc.contiguous()
+        an = act_norm.detach()
+        an = an if an.is_contiguous() else an.contiguous()
+        y_dtype = out_dtype or torch.promote_types(wc.dtype, torch.float32)
+        if wc.numel() == 0:
+            e = lambda dt: torch.empty(wc.shape, dtype=dt, device=wc.device)
+            return (e(torch.float32) if want_score else None, e(torch.float32) if want_mask else None, e(y_dtype) if want_y else None)
+        if fused is not False:
+            ok = wanda_class(wc.dtype, wc.shape[1], M) and wc.data_ptr() % 16 == 0 and an.data_ptr() % 16 == 0
+            if not ok and fused:
+                raise NotImplementedError(f"{what}: no one-pass kernel for groups of {M} in rows of {wc.shape[1]} {wc.dtype} elements "
+                                          f"(weight base address {wc.data_ptr() % 16} mod 16)")
+            if ok and fused is None and M in WANDA_CHAIN_BY_DEFAULT:
+                ok = False
+            if ok:
+                try:
+                    score, mask, y = _ops.wanda_nm(wc, an, int(K), int(M), bool(want_score), bool(want_mask), bool(want_y), None, y_dtype)
+                    _wanda_routes["fused"] += 1
+                    return (score if want_score else None), (mask if want_mask else None), (y if want_y else None)
+                except NotImplementedError:   # (DMXQ_ERR_UNSUPPORTED, nothing launched)
+                    if fused:
+                        raise
+        _wanda_routes["chain"] += 1
+        score = wc.float().abs() * an   # (the definition: one fp32 multiply per element)
+        mask = y = None
+        if want_mask or want_y:
+            mask, y = _nm(score, wc if want_y else None, K, M, -1, want_mask, want_y, None, y_dtype if want_y else None)
+        return (score if want_score else None), mask, y
+
+
+def wanda_score(w, act_norm, fused: Optional[bool] = None):
+    """The Wanda score of a [rows, L] weight (Sun et al., 2023): float32 |w| * act_norm, act_norm the float32 [L] vector of
+    the input channels' activation norms (channel_sumsq(...).sqrt().float()).  One launch (dmxq_wanda_nm with K = M = 0) where L is a
+    multiple of 16 and the tensors are 16-byte aligned, else the same multiply in torch; `fused` as in wanda_nm_sparsify."""
+    return _wanda(w, act_norm, 0, 0, True, False, False, fused, None, "wanda_score")[0]
+
+
+def wanda_nm_sparsify(w, act_norm, K: int, M: int, return_mask: bool = False, return_score: bool = False, fused: Optional[bool] = None,
+                      out_dtype: Optional[torch.dtype] = None, return_y: bool = True):
+    """N:M pruning of a [rows, L] weight by its Wanda score in ONE pass over the weight (dmxq_wanda_nm): by definition
+        score = w.float().abs() * act_norm;   y, mask = nm_sparsify(w, score, K, M, -1, return_mask=True)
+    bit for bit -- the K highest scores of every group of M along the last dim are kept (stable ascending rank, the lower index zeroed
+    first among ties, NaN highest, -0 == +0), y = w * mask is a real multiply (a masked negative weight gives -0.0) in torch's promotion
+    of (w.dtype, float32) unless out_dtype says otherwise, the mask is float32.  The score is formed in registers and only written when
+    return_score asks for it.  Returns y, or the tuple (y, mask, score) of what was asked for, in that order; return_y=False leaves y out
+    (mask and / or score alone).
+    fused=None: the kernel where it applies (M in {4, 8, 16}, L a multiple of 16, 16-byte aligned tensors) and M is not listed in
+    WANDA_CHAIN_BY_DEFAULT, else the chain above; True: NotImplementedError instead of falling back; False: the chain.
+    ValueError / TypeError before any GPU use: K > M, a last dim that M does not divide, an act_norm of the wrong length or dtype,
+    nothing asked for."""
+    score, mask, y = _wanda(w, act_norm, K, M, bool(return_score), bool(return_mask), bool(return_y), fused, out_dtype, "wanda_nm_sparsify")
+    out = tuple(t for t, want in ((y, return_y), (mask, return_mask), (score, return_score)) if want)
+    return out[0] if len(out) == 1 else out

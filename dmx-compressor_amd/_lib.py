@@ -82,6 +82,10 @@ SIGNATURES = {
     "dmxq_dynamic_float_class": [_i32, _i32, _i64],
     "dmxq_dynamic_float_qdq": [_vp, _vp, _i32, _i32, _i32, _i64, _i64, _i64, _i64, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp],
     "dmxq_dynamic_fixed_qdq": [_vp, _vp, _i32, _i32, _i64, _i64, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp],
+    "dmxq_channel_sumsq_workspace_bytes": [_i64, _i64],
+    "dmxq_channel_sumsq_accumulate": [_vp, _i32, _i64, _i64, _vp, _vp, _vp],
+    "dmxq_wanda_class": [_i32, _i64, _i32],
+    "dmxq_wanda_nm": [_vp, _i32, _vp, _vp, _vp, _i32, _vp, _i32, _i64, _i64, _i32, _i32, _vp],
 }
 
 
@@ -137,6 +141,7 @@ def lib():
             fn.restype = ctypes.c_int
         L.dmxq_topk_workspace_bytes.restype = ctypes.c_int64
         L.dmxq_error_scratch_bytes.restype = ctypes.c_int64
+        L.dmxq_channel_sumsq_workspace_bytes.restype = ctypes.c_int64
         L.dmxq_status_string.argtypes = [ctypes.c_int]
         L.dmxq_status_string.restype = ctypes.c_char_p
         L.dmxq_abi_version.restype = ctypes.c_int

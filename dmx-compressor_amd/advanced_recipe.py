@@ -6,7 +6,7 @@ from typing import Callable, Optional
 
 from .nn import DmxModule
 
-__all__ = ["DmxBaseRecipe", "DmxQuantizerCalibrationRecipe", "DmxSmoothQuantRecipe", "DmxGPTQRecipe"]
+__all__ = ["DmxBaseRecipe", "DmxQuantizerCalibrationRecipe", "DmxSmoothQuantRecipe", "DmxGPTQRecipe", "DmxWandaRecipe"]
 
 
 class DmxBaseRecipe:
@@ -50,3 +50,12 @@ class DmxGPTQRecipe(DmxBaseRecipe):
     def __init__(self, hp_gen, **kwargs):
         super().__init__(hp_gen, **kwargs)
         self.recipe_context_manager = DmxModule.optimal_brain_compressing
+
+
+class DmxWandaRecipe(DmxBaseRecipe):
+    """Wanda pruning (DmxModule.wanda_pruning): hp_gen maps the model to {module: DmxWandaHyperparams}; every Linear among them with a
+    weight sparseness gathers its own activation norms while the calibration batches run and is scored on exit"""
+
+    def __init__(self, hp_gen, **kwargs):
+        super().__init__(hp_gen, **kwargs)
+        self.recipe_context_manager = DmxModule.wanda_pruning

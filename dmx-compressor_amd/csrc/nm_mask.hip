@@ -9,18 +9,9 @@
 //   before(j, i) = s_j < s_i  or  (s_j == s_i or both NaN) and j < i   [NaN is "greater" than any number]
 //   rank_i = #{j : before(j, i)} ;  mask_i = (rank_i >= M - K) ? 1 : 0
 // y = x * mask is a real multiply (a masked negative gives -0.0, NaN*0 = NaN), as in the reference.
-#include "common.hpp"
+#include "nm_rank.hpp"   // the key, the rank rule and the unit I/O: shared with csrc/wanda.hip
 
 namespace dmxq {
-
-// key that orders like the reference's sort: monotone map of the float to a signed-comparable integer,
-// -0.0 == +0.0, every NaN maps to the same top key.
-__device__ __forceinline__ int32_t sort_key(float s) {
-  if (s != s) return 0x7FFFFFFF;
-  if (s == 0.0f) return 0;
-  const int32_t b = (int32_t)f2u(s);
-  return b >= 0 ? b : (int32_t)(0x80000000u - (uint32_t)b);
-}
 
 struct NmArgs {
   const void* score; const void* x; void* mask; void* y;
@@ -43,17 +34,7 @@ __global__ __launch_bounds__(kThreads) void nm_mask_kernel(NmArgs a) {
 #pragma unroll
     for (int i = 0; i < M; i++) key[i] = sort_key(load_rt(a.score, a.dts, e0 + i * a.inner));
     int rank[M];
-#pragma unroll
-    for (int i = 0; i < M; i++) rank[i] = 0;
-#pragma unroll
-    for (int i = 0; i < M; i++)
-#pragma unroll
-      for (int jj = 0; jj < i; jj++) {
-        // jj < i: on equal keys the lower index jj sorts first
-        const bool jj_first = key[jj] <= key[i];
-        rank[i] += jj_first ? 1 : 0;
-        rank[jj] += jj_first ? 0 : 1;
-      }
+    nm_rank<M>(key, rank);
 #pragma unroll
     for (int i = 0; i < M; i++) {
       const float mk = rank[i] >= M - a.K ? 1.0f : 0.0f;
@@ -68,49 +49,6 @@ __global__ __launch_bounds__(kThreads) void nm_mask_kernel(NmArgs a) {
 // Vectorised path: inner == 1 (groups along the contiguous dim), M in {2,4,8,16}, 16-byte aligned streams.
 // A lane owns U = 8 (M <= 8) or 16 consecutive elements = U/M whole groups, moved with 16-byte accesses
 // (one per 16-bit stream, two or four per fp32 stream); UNROLL units per lane are loaded before the ranking.
-template <int U>
-__device__ __forceinline__ void load_elems(const void* p, int dt, int64_t e0, float (&v)[U]) {
-  if (dt == DMXQ_F32) {
-#pragma unroll
-    for (int k = 0; k < U; k += 4) {
-      const f32x4 t = *(const f32x4*)((const float*)p + e0 + k);
-      v[k] = t.x; v[k + 1] = t.y; v[k + 2] = t.z; v[k + 3] = t.w;
-    }
-  } else {
-#pragma unroll
-    for (int k = 0; k < U; k += 8) {
-      const u32x4 t = *(const u32x4*)((const uint16_t*)p + e0 + k);
-#pragma unroll
-      for (int j = 0; j < 4; j++) {
-        if (dt == DMXQ_BF16) {
-          v[k + 2 * j] = u2f(t[j] << 16);
-          v[k + 2 * j + 1] = u2f(t[j] & 0xFFFF0000u);
-        } else {
-          v[k + 2 * j] = half_lo(t[j]);
-          v[k + 2 * j + 1] = half_hi(t[j]);
-        }
-      }
-    }
-  }
-}
-
-template <int U>
-__device__ __forceinline__ void store_elems(void* p, int dt, int64_t e0, const float (&v)[U]) {
-  if (dt == DMXQ_F32) {
-#pragma unroll
-    for (int k = 0; k < U; k += 4) *(f32x4*)((float*)p + e0 + k) = f32x4{v[k], v[k + 1], v[k + 2], v[k + 3]};
-  } else {
-#pragma unroll
-    for (int k = 0; k < U; k += 8) {
-      u32x4 t;
-#pragma unroll
-      for (int j = 0; j < 4; j++)
-        t[j] = dt == DMXQ_BF16 ? pack2<DMXQ_BF16>(v[k + 2 * j], v[k + 2 * j + 1]) : pack2<DMXQ_F16>(v[k + 2 * j], v[k + 2 * j + 1]);
-      *(u32x4*)((uint16_t*)p + e0 + k) = t;
-    }
-  }
-}
-
 template <int M, int UNROLL>
 __global__ __launch_bounds__(kThreads) void nm_mask_vec_kernel(NmArgs a, int64_t n_units) {
   constexpr int U = M <= 8 ? 8 : 16;
@@ -130,23 +68,7 @@ __global__ __launch_bounds__(kThreads) void nm_mask_vec_kernel(NmArgs a, int64_t
       const int64_t u = u0 + (int64_t)r * kThreads;
       if (u >= n_units) continue;
       float mk[U];
-#pragma unroll
-      for (int g = 0; g < U; g += M) {
-        int32_t key[M];
-        int rank[M];
-#pragma unroll
-        for (int i = 0; i < M; i++) { key[i] = sort_key(s[r][g + i]); rank[i] = 0; }
-#pragma unroll
-        for (int i = 0; i < M; i++)
-#pragma unroll
-          for (int jj = 0; jj < i; jj++) {
-            const bool jj_first = key[jj] <= key[i];  // equal keys: the lower index sorts first
-            rank[i] += jj_first ? 1 : 0;
-            rank[jj] += jj_first ? 0 : 1;
-          }
-#pragma unroll
-        for (int i = 0; i < M; i++) mk[g + i] = rank[i] >= M - a.K ? 1.0f : 0.0f;
-      }
+      nm_unit_mask<M, U>(s[r], a.K, mk);
       if (a.mask) store_elems<U>(a.mask, a.dtm, u * U, mk);
       if (a.y) {
         float y[U];
@@ -189,16 +111,7 @@ __global__ __launch_bounds__(kThreads) void nm_mask_f32_kernel(const float* __re
   const int thr = M - K;
   auto rank_bits = [&](const int32_t (&key)[M]) __attribute__((always_inline)) -> uint32_t {
     int rank[M];
-#pragma unroll
-    for (int i = 0; i < M; i++) rank[i] = 0;
-#pragma unroll
-    for (int i = 0; i < M; i++)
-#pragma unroll
-      for (int jj = 0; jj < i; jj++) {
-        const bool jj_first = key[jj] <= key[i];  // equal keys: the lower index sorts first
-        rank[i] += jj_first ? 1 : 0;
-        rank[jj] += jj_first ? 0 : 1;
-      }
+    nm_rank<M>(key, rank);
     uint32_t bits = 0u;
 #pragma unroll
     for (int i = 0; i < M; i++) bits |= rank[i] >= thr ? (1u << i) : 0u;

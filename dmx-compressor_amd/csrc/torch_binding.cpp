@@ -1075,6 +1075,48 @@ std::tuple<Tensor, Tensor> dynamic_float_qdq_meta(const Tensor& x, int64_t mode,
                          want_scale ? at::empty(shape, x.options().dtype(at::kFloat)) : at::empty({0}, x.options().dtype(at::kFloat)));
 }
 
+// ------------------------------------------------------------------------------------------------ Wanda
+// acc (float64 [C], C = x's last dim) += the sum of squares over every other dim; scratch: dmxq_channel_sumsq_workspace_bytes bytes of
+// any contiguous device tensor
+void channel_sumsq(const Tensor& x, Tensor acc, Tensor scratch) {
+  const Tensor xc = prep(x, "channel_sumsq");
+  const int64_t C = xc.dim() ? xc.size(-1) : 1, rows = C ? xc.numel() / C : 0;
+  TORCH_CHECK(acc.is_cuda() && acc.device() == xc.device() && acc.scalar_type() == at::kDouble && acc.is_contiguous() && acc.numel() == C,
+              "channel_sumsq: acc must be a contiguous float64 tensor of ", C, " entries on the input's device");
+  const int64_t need = dmxq_channel_sumsq_workspace_bytes(rows, C);
+  TORCH_CHECK(scratch.is_cuda() && scratch.device() == xc.device() && scratch.is_contiguous() &&
+              (int64_t)(scratch.numel() * scratch.element_size()) >= need && (uintptr_t)scratch.data_ptr() % 8 == 0,
+              "channel_sumsq: scratch must be a contiguous 8-byte aligned tensor of at least ", need, " bytes on the input's device");
+  Launch l(xc);
+  check(dmxq_channel_sumsq_accumulate(xc.data_ptr(), dt_code(xc.scalar_type()), rows, C, (double*)acc.data_ptr(), scratch.data_ptr(), l.stream),
+        "dmxq_channel_sumsq_accumulate");
+}
+void channel_sumsq_meta(const Tensor&, Tensor, Tensor) {}
+
+// -> (score float32, mask, y): an output that was not requested comes back as an empty 1-d tensor
+std::tuple<Tensor, Tensor, Tensor> wanda_nm(const Tensor& w, const Tensor& act_norm, int64_t K, int64_t M, bool want_score, bool want_mask,
+                                            bool want_y, OptDtype mask_dtype, OptDtype y_dtype) {
+  const Tensor wc = prep(w, "wanda_nm");
+  TORCH_CHECK(wc.dim() == 2, "wanda_nm: the weight must be a [rows, L] matrix");
+  TORCH_CHECK(act_norm.is_cuda() && act_norm.device() == wc.device() && act_norm.scalar_type() == at::kFloat && act_norm.is_contiguous() &&
+              act_norm.numel() == wc.size(1), "wanda_nm: act_norm must be a contiguous float32 tensor of ", wc.size(1),
+              " entries on the weight's device");
+  Tensor score = want_score ? empty_like_shape(wc, at::kFloat) : at::empty({0}, wc.options().dtype(at::kFloat));
+  Tensor mask = want_mask ? empty_like_shape(wc, mask_dtype.value_or(at::kFloat)) : none_like(wc);
+  Tensor y = want_y ? empty_like_shape(wc, y_dtype.value_or(at::promote_types(wc.scalar_type(), at::kFloat))) : none_like(wc);
+  Launch l(wc);
+  check(dmxq_wanda_nm(wc.data_ptr(), dt_code(wc.scalar_type()), (const float*)act_norm.data_ptr(), want_score ? (float*)score.data_ptr() : nullptr,
+                      want_mask ? mask.data_ptr() : nullptr, want_mask ? dt_code(mask.scalar_type()) : 0, want_y ? y.data_ptr() : nullptr,
+                      want_y ? dt_code(y.scalar_type()) : 0, wc.size(0), wc.size(1), (int)K, (int)M, l.stream), "dmxq_wanda_nm");
+  return std::make_tuple(score, mask, y);
+}
+std::tuple<Tensor, Tensor, Tensor> wanda_nm_meta(const Tensor& w, const Tensor&, int64_t, int64_t, bool want_score, bool want_mask, bool want_y,
+                                                 OptDtype mask_dtype, OptDtype y_dtype) {
+  return std::make_tuple(want_score ? empty_like_shape(w, at::kFloat) : at::empty({0}, w.options().dtype(at::kFloat)),
+                         want_mask ? empty_like_shape(w, mask_dtype.value_or(at::kFloat)) : none_like(w),
+                         want_y ? empty_like_shape(w, y_dtype.value_or(at::promote_types(w.scalar_type(), at::kFloat))) : none_like(w));
+}
+
 }  // namespace
 
 TORCH_LIBRARY(dmxq, m) {
@@ -1129,6 +1171,8 @@ TORCH_LIBRARY(dmxq, m) {
   m.def("hadamard_qdq(Tensor x, int size, bool inverse, int[] fmt, Tensor? scale, Tensor? zero_point, ScalarType? out_dtype=None) -> Tensor");
   m.def("dynamic_fixed_qdq(Tensor x, int segment, bool whole_rows, int precision, int fraction, bool clamp, bool symmetric, int rounding, int qmin, int qmax, bool symmetric_qscheme, bool want_qparams, ScalarType? out_dtype=None) -> (Tensor, Tensor, Tensor)");
   m.def("dynamic_float_qdq(Tensor x, int mode, int segment, int man, int exp, int bias, bool flush_subnormal, int rounding, bool pow2_scale, bool want_scale, ScalarType? out_dtype=None) -> (Tensor, Tensor)");
+  m.def("channel_sumsq(Tensor x, Tensor(a!) acc, Tensor(b!) scratch) -> ()");
+  m.def("wanda_nm(Tensor w, Tensor act_norm, int K, int M, bool want_score, bool want_mask, bool want_y, ScalarType? mask_dtype=None, ScalarType? y_dtype=None) -> (Tensor, Tensor, Tensor)");
 }
 
 #define DMXQ_IMPL(m, name) m.impl(#name, &name)
@@ -1138,7 +1182,8 @@ TORCH_LIBRARY(dmxq, m) {
   X(m, float_qdq); X(m, float_qdq_multi); X(m, fixed_qdq); X(m, fixed_qdq_multi); X(m, fixed_float_qdq_multi); X(m, nm_mask); X(m, topk_mask); X(m, bernoulli_mask); X(m, group_minmax); X(m, qparams); \
   X(m, histc); X(m, channel_maxabs); X(m, smoothquant_scale); X(m, scale_channels); X(m, unary); X(m, rope); X(m, rope_cast); X(m, softmax); X(m, norm); \
   X(m, unary_cast); X(m, unary_cast_table); X(m, lut16_apply); X(m, softmax_cast); X(m, norm_cast); X(m, group_minmax_accumulate); X(m, gptq_block); X(m, hist_observe); X(m, hist_qparams); \
-  X(m, error_stats); X(m, cast_error); X(m, hadamard_qdq); X(m, dynamic_fixed_qdq); X(m, gptq_block_dynamic); X(m, dynamic_float_qdq)
+  X(m, error_stats); X(m, cast_error); X(m, hadamard_qdq); X(m, dynamic_fixed_qdq); X(m, gptq_block_dynamic); X(m, dynamic_float_qdq); \
+  X(m, channel_sumsq); X(m, wanda_nm)
 
 // "CUDA" is the dispatch key of HIP tensors in a ROCm build of PyTorch
 TORCH_LIBRARY_IMPL(dmxq, CUDA, m) {

@@ -21,7 +21,7 @@ import torch.nn.functional as F
 
 from ._lib import DmxqError
 
-__all__ = ["OptimalBrainCompressor"]
+__all__ = ["OptimalBrainCompressor", "WandaCalibrator"]
 
 
 def refuse_scaled_weight_cast(module):
@@ -407,3 +407,74 @@ class OptimalBrainCompressor:
                     _W[:, j2:] -= acc
             if i2 < ncols:
                 W[:, i2:].addmm_(_E, Hinv[i1:i2, i2:], alpha=-1)
+
+
+# ---------------------------------------------------------------------------------------------------- Wanda
+def wanda_applies(module) -> bool:
+    """Wanda acts on a Linear with a 2-D weight and a weight sparseness other than DENSE; on anything else nothing happens"""
+    from .sparse import Dense
+    sp = getattr(module, "weight_sparsifier", None)
+    return (isinstance(module, torch.nn.Linear) and getattr(module, "weight", None) is not None and module.weight.dim() == 2
+            and sp is not None and not isinstance(sp.sparseness, Dense))
+
+
+def refuse_wanda(module):
+    """the configurations Wanda does not support, as a DmxqError before any state is touched"""
+    from .sparse import BlockTopK
+    sq = module.smoothquant
+    if sq is not None and sq._flag("enabled") and not sq._flag("fused_to_weight"):
+        raise DmxqError("Wanda with SmoothQuant enabled and not fused to the weight is not supported: the sparsifier sees W, but the GEMM "
+                        "sees W * s and x / s; fuse the scale to the weight first (fuse_to_weight) or disable SmoothQuant")
+    sp = module.weight_sparsifier.sparseness
+    if isinstance(sp, BlockTopK) and sp.block_dim not in (-1, module.weight.dim() - 1):
+        raise DmxqError(f"Wanda ranks the groups of {sp!r} along the input channels, the weight's last dimension; block_dim = "
+                        f"{sp.block_dim} is not supported")
+
+
+class WandaCalibrator:
+    """Wanda (Sun et al., 2023): while DmxModule.wanda_pruning is active, `observe` adds the per-input-channel sum of
+    squares of every forward's input into a float64 [in_features] device vector (one ops.channel_sumsq call, nothing read back) and
+    counts the tokens on the host; `apply` turns it into the fp32 norm vector, scores the weight with it and writes the score (and, for
+    an N:M sparseness, the mask) into the module's weight sparsifier.  The weight itself is never modified."""
+
+    def __init__(self, module, sumsq=None, n_tokens: int = 0):
+        self.module = module
+        self.sumsq = sumsq
+        self.n_tokens = int(n_tokens)
+
+    def observe(self, inp):
+        from . import ops
+        C = inp.shape[-1]
+        if self.sumsq is None or self.sumsq.device != inp.device:
+            prev = self.sumsq
+            self.sumsq = torch.zeros(C, dtype=torch.float64, device=inp.device)
+            if prev is not None:
+                self.sumsq += prev.to(inp.device)
+        ops.channel_sumsq(inp, out=self.sumsq)
+        self.n_tokens += inp.numel() // C if C else 0
+
+    def apply(self):
+        from . import ops
+        from .sparse import BlockTopK
+        m = self.module
+        if self.n_tokens == 0:
+            raise RuntimeError("Wanda: no calibration token was observed inside wanda_pruning (run at least one forward of the module); "
+                               "the score is left as it was")
+        sp = m.weight_sparsifier
+        w = m.weight.detach()
+        act_norm = self.sumsq.to(w.device).sqrt().to(torch.float32)
+        if isinstance(sp.sparseness, BlockTopK):
+            mask, score = ops.wanda_nm_sparsify(w, act_norm, sp.sparseness.K, sp.sparseness.block_size, return_mask=True, return_score=True,
+                                                return_y=False)
+        else:   # (global TopK, Bernoulli: the score only; the sparseness' own rule then compares per layer)
+            mask, score = None, ops.wanda_score(w, act_norm)
+        if sp.score.shape == score.shape and sp.score.device == score.device and sp.score.dtype == score.dtype:
+            sp.score.data = score
+        else:   # (the lazy sparsifier has not seen the weight yet: allocated as _LazySparsify.forward does)
+            sp.score = torch.nn.Parameter(score, requires_grad=True)
+        if mask is not None:
+            sp.mask = mask
+        else:
+            sp._mask, sp._mask_pending = None, True   # (read again from the new score)
+        m.__dict__.pop("_live_weight", None)   # (a LiveWeightBatch result computed with the old score)
+        m.wanda_act_norm, m.wanda_sumsq, m.wanda_n_tokens = act_norm, self.sumsq, self.n_tokens

@@ -27,7 +27,7 @@ from .smoothquant import ActivationWeightSmoothQuant
 from .sparse import Dense, Sparsify
 
 __all__ = ["DmxModule", "DmxQuantizerCalibrationHyperparams", "DmxModuleQuantizerCalibrationHyperparams",
-           "DmxModuleSmoothQuantHyperparams", "DmxModuleGPTQHyperparams", "Linear", "Conv1d", "Conv2d", "ResAdd", "ActActMatMul", "Softmax", "LayerNorm", "GELU", "ReLU", "SiLU", "QuickGELU", "Exp", "Mul", "RMSNorm", "ApplyRotaryPosEmb",
+           "DmxModuleSmoothQuantHyperparams", "DmxModuleGPTQHyperparams", "DmxWandaHyperparams", "Linear", "Conv1d", "Conv2d", "ResAdd", "ActActMatMul", "Softmax", "LayerNorm", "GELU", "ReLU", "SiLU", "QuickGELU", "Exp", "Mul", "RMSNorm", "ApplyRotaryPosEmb",
            "MaxPool2d", "AvgPool2d", "Embedding", "ReLU6", "Tanh", "Dropout", "NewGELU", "FastGELU", "BloomGELU", "ClippedGELU", "AdaptiveAvgPool2d",
            "BatchNorm2d", "GroupNorm", "ConvTranspose2d", "BAddBMM", "ScaledDotProductAttention", "DmxConfigRule", "configure_model",
            "fold_weights_and_biases", "GraphedForward", "LiveWeightBatch", "link_consumer", "link_consumers_from_fx", "DmxTracer"]
@@ -85,6 +85,17 @@ class DmxModuleGPTQHyperparams:
     act_order: bool = False
 
 
+@dataclass
+class DmxWandaHyperparams:
+    """Wanda pruning (DmxModule.wanda_pruning; not in the reference).  reset: entering the context zeroes the statistics of an earlier
+    context (False: the sums of squares and the token count continue from where the last context left them)"""
+    reset: bool = True
+
+    def __post_init__(self):
+        if not isinstance(self.reset, bool):
+            raise TypeError(f"DmxWandaHyperparams: reset must be a bool, got {self.reset!r}")
+
+
 def _shares_storage(a, b) -> bool:
     if not (isinstance(a, torch.Tensor) and isinstance(b, torch.Tensor)):
         return False
@@ -119,6 +130,11 @@ class DmxModule(FastAttr, torch.nn.Module):
     has_accum = False
     #: the OptimalBrainCompressor while `optimal_brain_compressing` is active (layer_reconstruction.py:24-27), else None
     obc = None
+    #: the WandaCalibrator while `wanda_pruning` is active (layer_reconstruction.py), else None; after a context the fp32 norm vector it
+    #: scored with, the float64 sums behind it and the token count stay as plain attributes (no buffer, no state_dict key)
+    wanda = None
+    wanda_act_norm = wanda_sumsq = None
+    wanda_n_tokens = 0
 
     def _dmx_init(self, n_inputs: int = 1, input_names=("input_cast",), sparsifiable: bool = False):
         pnames = [n for n, _ in self.named_parameters(recurse=False)]
@@ -451,6 +467,32 @@ class DmxModule(FastAttr, torch.nn.Module):
         yield self
         self.enable_optimal_brain_compression(False, hyperparams)
 
+    def enable_wanda(self, state: bool, hyperparams=None) -> None:
+        """Wanda: on a Linear with a 2-D weight and a weight sparseness other than DENSE (any other module: nothing
+        happens).  Entering starts observing the inputs as `_forward` receives them (after the input casts, whose switches stay as they
+        are); leaving scores the weight with the observed norms and writes the score -- for an N:M sparseness the mask as well -- into
+        `weight_sparsifier`.  The weight, `plastic` and `score_func` are not touched."""
+        from .layer_reconstruction import WandaCalibrator, refuse_wanda, wanda_applies
+        if hyperparams is None:
+            hyperparams = DmxWandaHyperparams()
+        if not isinstance(hyperparams, DmxWandaHyperparams):
+            raise TypeError(f"wanda_pruning takes a DmxWandaHyperparams, got {type(hyperparams).__name__}")
+        if not wanda_applies(self):
+            return
+        if state:
+            refuse_wanda(self)   # (before any state is touched)
+            keep = not hyperparams.reset and self.wanda_sumsq is not None
+            self.wanda = WandaCalibrator(self, self.wanda_sumsq.clone() if keep else None, self.wanda_n_tokens if keep else 0)
+        elif self.wanda is not None:
+            wanda, self.wanda = self.wanda, None
+            wanda.apply()
+
+    @contextmanager
+    def wanda_pruning(self, hyperparams=None):
+        self.enable_wanda(True, hyperparams)
+        yield self
+        self.enable_wanda(False, hyperparams)
+
     #: GPTQ's in-block column loop as one csrc/gptq.hip launch per column block when the weight format allows (False: the reference's
     #: per-microblock loop, for A/B comparisons)
     fuse_gptq = True
@@ -679,6 +721,8 @@ class DmxModule(FastAttr, torch.nn.Module):
             _input, args, kwargs = self.input_casts(input, *args, **kwargs)
         if self.obc is not None:
             self.obc.measure_hessian(_input)
+        if self.wanda is not None:
+            self.wanda.observe(_input)
         _output = self._forward(_input, *args, **kwargs)
         # (a GEMM-bearing module's output cast is a launch of its own; when the linked consumer applies the SAME cast to this value as
         #  its first input cast -- inside its fused kernel -- the cast here is redundant: FloatingPoint casts are projections)

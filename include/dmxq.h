@@ -55,7 +55,8 @@ typedef enum {
 const char* dmxq_status_string(int status);
 /* ABI version: bumped on any signature change.  Additions since 4 (dmxq_gptq_block, dmxq_hist_observe, dmxq_hist_qparams, dmxq_error_stats, dmxq_cast_error,
  * dmxq_error_scratch_bytes, dmxq_hadamard_qdq, dmxq_dynamic_fixed_qdq, dmxq_dynamic_class, dmxq_gptq_block_dynamic,
- * dmxq_dynamic_float_qdq, dmxq_dynamic_float_class) leave it at 4: a caller built against 4 runs on
+ * dmxq_dynamic_float_qdq, dmxq_dynamic_float_class, dmxq_channel_sumsq_accumulate, dmxq_channel_sumsq_workspace_bytes, dmxq_wanda_nm,
+ * dmxq_wanda_class) leave it at 4: a caller built against 4 runs on
  * this library unchanged.  4 = round 5: + dmxq_float_qdq_multi, dmxq_fixed_float_qdq_multi; 3 = round 4: + dmxq_weight_hypernet_multi,
  * dmxq_unary_cast_table, dmxq_lut16_apply.  Nothing was ever removed or changed: a caller built against version n runs on any library >= n. */
 int dmxq_abi_version(void);
@@ -581,6 +582,35 @@ int dmxq_dynamic_float_class(int dtype, int mode, int64_t segment);
 int dmxq_dynamic_float_qdq(const void* in, void* out, int dtype_in, int dtype_out, int mode, int64_t n_segments, int64_t segment,
                            int64_t rows, int64_t cols, int man_bits, int exp_bits, int exp_bias, int flush_subnormal, int rounding,
                            int pow2_scale, float* scale_out, void* stream);
+
+/* Wanda (Sun et al., 2023): activation-aware N:M pruning calibrated on the device (csrc/wanda.hip; DESIGN.md §8 "Wanda").  Not in the
+ * reference.  For a Linear weight W[rows, L] and calibration inputs X[n_tokens, L]:
+ *   sumsq[j] = sum_t (double)X[t, j]^2 in float64 over every observed batch;  act_norm = (float)sqrt(sumsq) (formed by the caller);
+ *   score = |(float)W| * act_norm, one fp32 multiply;  mask and y = W * mask by the rule of dmxq_nm_mask on that score.
+ *
+ * dmxq_channel_sumsq_accumulate: acc[c] += sum over the rows of the contiguous [rows, C] tensor of (double)x^2, c < C.  acc: DEVICE
+ * float64 [C], zeroed by the caller before the first batch.  Every product is formed in double (exact for fp32 and 16-bit inputs) and
+ * added by one fp64 fma; no floating-point atomics and a fixed order -- a channel's rows in index order inside a slab of rows, the
+ * slabs in slab order, then one addition into acc; the slab partition depends on (rows, C) alone -- so the same batches in the same
+ * order give the same bits, whatever the dtype or the alignment.  workspace: DEVICE memory of dmxq_channel_sumsq_workspace_bytes(rows, C)
+ * bytes (8-byte aligned; a host query, no GPU involved; 0 for an empty tensor), overwritten by every call.  Lanes move 16-byte vectors
+ * when C is a multiple of 8 (16-bit) or 4 (fp32) elements and `in` is 16-byte aligned, and single elements otherwise: same order, same
+ * bits.  No allocation, no host synchronisation: capturable.  DMXQ_ERR_BAD_ARG: invalid dtype, negative sizes, null pointers. */
+int64_t dmxq_channel_sumsq_workspace_bytes(int64_t rows, int64_t C);
+int dmxq_channel_sumsq_accumulate(const void* in, int dtype_in, int64_t rows, int64_t C, double* acc, void* workspace, void* stream);
+/* dmxq_wanda_nm: ONE pass over the contiguous weight w[rows, L]; act_norm: DEVICE float32 [L].  A lane forms the scores of 8 (M <= 8)
+ * or 16 (M = 16) consecutive elements in registers, ranks every group of M along L as dmxq_nm_mask does (ascending, stable, the lower
+ * index zeroed first among ties, NaN highest, -0 == +0; the K highest of a group are kept) and writes what is not NULL: score_out
+ * (float32 [rows, L]), mask_out (0 / 1 in dtype_mask), y_out (w * mask in dtype_y: a real multiply, a masked negative weight gives
+ * -0.0).  K = M = 0: the score only (score_out required, the other two NULL).  A zero norm scores 0 and an overflowing product Inf
+ * (both tie by index), a NaN norm makes its column rank highest: no special case anywhere.
+ * dmxq_wanda_class(dtype_w, L, M): 1 where the kernel takes the geometry -- M in {0, 4, 8, 16} and L a multiple of 16 -- else 0; a
+ * host function, no GPU involved.  DMXQ_ERR_UNSUPPORTED, nothing launched (the caller runs the chain |w| * act_norm -> dmxq_nm_mask,
+ * same bits): class 0, or a pointer that is not 16-byte aligned.  DMXQ_ERR_BAD_ARG: invalid dtypes, negative sizes, K > M, K < 1 with
+ * M > 0, M > 64, L % M != 0, all three outputs NULL, null w / act_norm.  No workspace, no allocation, no host synchronisation. */
+int dmxq_wanda_class(int dtype_w, int64_t L, int M);
+int dmxq_wanda_nm(const void* w, int dtype_w, const float* act_norm, float* score_out, void* mask_out, int dtype_mask, void* y_out,
+                  int dtype_y, int64_t rows, int64_t L, int K, int M, void* stream);
 
 #ifdef __cplusplus
 }
