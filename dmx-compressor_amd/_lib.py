@@ -86,7 +86,22 @@ SIGNATURES = {
     "dmxq_channel_sumsq_accumulate": [_vp, _i32, _i64, _i64, _vp, _vp, _vp],
     "dmxq_wanda_class": [_i32, _i64, _i32],
     "dmxq_wanda_nm": [_vp, _i32, _vp, _vp, _vp, _i32, _vp, _i32, _i64, _i64, _i32, _i32, _vp],
+    "dmxq_row_class_of": [_i32, _i32, _i32, _i32, _i64, _i64, _vp, _vp, _vp, _vp, _i32, _i64, _vp],
 }
+
+# dmxq_row_op / dmxq_row_cast_kind / dmxq_row_family / dmxq_row_grid (include/dmxq.h)
+ROW_SOFTMAX, ROW_LAYERNORM, ROW_RMSNORM = 0, 1, 2
+ROWCAST_NONE, ROWCAST_RANGE, ROWCAST_GENERAL, ROWCAST_MAN16 = 0, 1, 2, 3
+ROWK_UNSUPPORTED, ROWK_WAVE, ROWK_BLOCK, ROWK_LDS_ROWS, ROWK_GLOBAL_ROWS = 0, 1, 2, 3, 4
+ROWGRID_NONE, ROWGRID_PERSISTENT, ROWGRID_ONE_PASS, ROWGRID_MID_ONE_PASS, ROWGRID_MODULE_ONE_PASS, ROWGRID_MODULE_ROWS4, ROWGRID_CAPPED = range(7)
+
+
+class RowClass(ctypes.Structure):
+    """dmxq_row_class (include/dmxq.h)"""
+    _fields_ = [(n, _i32) for n in ("family", "epl", "vpl", "lpr", "rag", "half_vec", "fast32", "bfpout", "grid", "rows_per_iter")]
+
+    def key(self):
+        return tuple(getattr(self, n) for n, _ in self._fields_)
 
 
 class TensorDesc(ctypes.Structure):

@@ -23,10 +23,9 @@
 
 #include "floatq.hpp"
 #include "bfp_math.hpp"
+#include "row_class.hpp"
 
 namespace dmxq {
-
-constexpr int kRowLdsFloats = 16 * 1024;  // 64 KiB per workgroup -> 2 workgroups per CU
 
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
@@ -221,6 +220,17 @@ __device__ __forceinline__ RowVec<DT, EPL> row_load_tail(const void* p, int64_t 
 struct RowCast { Range16 ri, ro; CastG gi, go; int bfp_B = 0, bfp_wl = 0, bfp_lpb = 0; };  // bfp_*: the CONSUMER's BFP input cast, dmxq_softmax_cast_bfp
 struct NoRowCast {};
 template <bool CAST> using RowCastArg = std::conditional_t<CAST, RowCast, NoRowCast>;
+// what row_class_of (row_class.hpp) needs to know of the casts
+template <bool CAST>
+static inline int rowcast_kind(int dtype, const RowCastArg<CAST>& rc) {
+  if constexpr (!CAST) return DMXQ_ROWCAST_NONE;
+  else return dtype != DMXQ_F32 ? DMXQ_ROWCAST_RANGE : ((rc.go.active && rc.go.f.man <= 16) ? DMXQ_ROWCAST_MAN16 : DMXQ_ROWCAST_GENERAL);
+}
+template <bool CAST>
+static inline int64_t rowcast_bfp_block(const RowCastArg<CAST>& rc) {
+  if constexpr (CAST) return rc.bfp_B;
+  else return 0;
+}
 template <bool CAST, int DT, int EPL, class RC>
 __device__ __forceinline__ void rowcast_raw_in(RowVec<DT, EPL>& r, const RC& rc) {
   if constexpr (CAST && DT != DMXQ_F32) {
@@ -321,19 +331,12 @@ __device__ __forceinline__ float seg_max(float v) {
   if (LPR == 64) return fmaxf(lo, hi);
   return (threadIdx.x & 32) ? hi : lo;
 }
-// row slots per wave iteration: about 32 fp32 values per lane (occupancy beats bytes in flight per wave here: 64 was
-// 1-4 % slower on every shape of tools/bench_rows.py)
+// (row slots per wave iteration: rows_per_wave, row_class.hpp)
 #ifndef DMXQ_EXP_ROW_PACE
 #define DMXQ_EXP_ROW_PACE 0
 #endif
 constexpr int kRowPace = DMXQ_EXP_ROW_PACE;   // common.hpp pace_issue between a wave's row loads (experiment)
-#ifdef DMXQ_EXP_LN32
-constexpr int kLn32OnePass = DMXQ_EXP_LN32;
-#else
-constexpr int kLn32OnePass = 0;
-#endif
 constexpr bool kRowEarlyLoads = false;  // layernorm_wave_kernel: next rows requested before this iteration's stores (measured slower, see there)
-constexpr int rows_per_wave(int vpl, int epl) { return 32 / (vpl * epl) >= 4 ? 4 : (32 / (vpl * epl) >= 2 ? 2 : 1); }
 
 // 16-bit outputs: exp(x - m) as v_exp_f32(fma(x, log2 e, -m log2 e)) and one reciprocal per row -- relative error
 // ~2^-21, far inside the output format's 2^-9 / 2^-12 half-ulp (the rounding of m log2 e scales numerator and
@@ -659,7 +662,7 @@ template <int DT, int EPL, int VPL, bool RMS = false, bool CAST = false, int RPW
 __global__ __launch_bounds__(kThreads) void layernorm_block_kernel(const void* __restrict__ in, void* __restrict__ out,
                                                                   int64_t rows, int64_t cols, const void* __restrict__ w,
                                                                   const void* __restrict__ b, float eps, const RowCastArg<CAST> rc) {
-  constexpr int RPW = RPWO ? RPWO : (VPL * EPL <= 32 ? 2 : 1);
+  constexpr int RPW = RPWO ? RPWO : block_rows(VPL, EPL);
   constexpr int NW = kThreads / kWave;
   __shared__ float red[2][RPW][NW];
   const int t = threadIdx.x, lane = t & (kWave - 1), wv = t / kWave;
@@ -797,28 +800,7 @@ __global__ __launch_bounds__(kThreads) void layernorm_block_kernel(const void* _
   }
 }
 
-// lane-vector width for the wave kernels: 16 bytes when rows and bases allow it, else 8 bytes for 16-bit rows that are
-// a multiple of 4 elements; 0 = not applicable
-static inline int wave_epl(int dt, int64_t cols, const void* p0, const void* p1, const void* p2, const void* p3) {
-  const uintptr_t a = (uintptr_t)p0 | (uintptr_t)p1 | (uintptr_t)p2 | (uintptr_t)p3;
-  const int full = dt == DMXQ_F32 ? 4 : 8;
-  if (cols % full == 0 && (a & 15) == 0) return full;
-  if (dt != DMXQ_F32 && cols % 4 == 0 && (a & 7) == 0) return 4;
-  return 0;
-}
-
-// (lanes per row, vectors per lane) for a row of nv vectors: the instantiated shape with the fewest idle lane slots.
-// 64 lanes: VPL in {1,2,3,4,5,6,8,10,12,16}; 32 lanes: VPL in {1,3,5}.  vpl = 0: row too long for registers.
-static inline void wave_shape(int64_t nv, int* lpr, int* vpl) {
-  static const int v64[] = {1, 2, 3, 4, 5, 6, 8, 10, 12, 16}, v32[] = {1, 3, 5};
-  int64_t best = 0;
-  *lpr = 64; *vpl = 0;
-  for (int v : v64)
-    if ((int64_t)v * 64 >= nv) { best = (int64_t)v * 64; *vpl = v; break; }
-  for (int v : v32)
-    if ((int64_t)v * 32 >= nv) { if (best == 0 || (int64_t)v * 32 < best) { *lpr = 32; *vpl = v; } break; }
-}
-
+// (wave_epl, wave_shape and the class of a call: row_class.hpp)
 }  // namespace dmxq
 
 using namespace dmxq;
@@ -868,64 +850,49 @@ static int softmax_dispatch(const void* in, void* out, int dtype_in, int dtype_o
   if (rows * cols == 0) return DMXQ_OK;
   if (!in || !out) return DMXQ_ERR_BAD_ARG;
   hipStream_t s = (hipStream_t)stream;
-  // register-resident kernel: same dtype in and out, a row of 1 .. 1024 lane-vectors.  Rows that are whole aligned
-  // vectors take the aligned form; any other length / alignment the RAG form (unaligned 16-byte accesses + element tail)
-  const int full = dtype_in == DMXQ_F32 ? 4 : 8;
-  const uintptr_t eb = dtype_in == DMXQ_F32 ? 4 : 2;
-  const bool elem_aligned = ((reinterpret_cast<uintptr_t>(in) | reinterpret_cast<uintptr_t>(out)) & (eb - 1)) == 0;
-  if (dtype_in == dtype_out && elem_aligned && cols >= full && (cols + full - 1) / full <= 64 * 16) {
-    bool rag = !(cols % full == 0 && aligned16(in) && aligned16(out));
-    // 16-bit rows that are a multiple of 4 elements on 8-byte bases: aligned 8-byte lane-vectors (measured 5 % faster
-    // than the unaligned 16-byte form with an overlapped last vector on attention rows of 1500: 21.8 vs 22.9 us)
-    const bool half_vec = rag && full == 8 && cols % 4 == 0 && cols / 4 <= 64 * 16 &&
-                          ((reinterpret_cast<uintptr_t>(in) | reinterpret_cast<uintptr_t>(out)) & 7u) == 0;
-    if (half_vec) rag = false;
-    int lpr, vpl;
-    wave_shape(half_vec ? cols / 4 : (cols + full - 1) / full, &lpr, &vpl);
-    bool fast32 = false;
-    if constexpr (CAST) fast32 = !rag && rc.go.active && rc.go.f.man <= 16;
+  // the class of the call (row_class.hpp): register-resident rows -- same dtype in and out, 1 .. 1024 lane-vectors, aligned, half-vector
+  // or RAG form -- or the fallbacks below
+  const dmxq_row_class cls = row_class_of(DMXQ_ROW_SOFTMAX, dtype_in, dtype_out, dtype_in, rows, cols, in, out, nullptr, nullptr,
+                                          rowcast_kind<CAST>(dtype_in, rc), rowcast_bfp_block<CAST>(rc));
+  if (cls.family == DMXQ_ROWK_UNSUPPORTED) return DMXQ_ERR_UNSUPPORTED;
+  if (cls.family == DMXQ_ROWK_WAVE) {
+    const unsigned grid = one_pass_grid((rows + cls.rows_per_iter - 1) / cls.rows_per_iter);
 #define DMXQ_SM(D_, E_, V_, L_)                                                                                       \
   do {                                                                                                                \
-    constexpr int per_wg = 4 * rows_per_wave(V_, E_) * (64 / (L_));                                                   \
     if constexpr (CAST) {                                                                                             \
-      if (rc.bfp_B) { /* dmxq_softmax_cast_bfp: blocks of B elements = lpb adjacent lanes of one slot */               \
-        const int lpb = rc.bfp_B / (E_);                                                                              \
-        if (rag || rc.bfp_B % (E_) != 0 || lpb < 1 || (lpb & (lpb - 1)) != 0 || lpb > (L_)) return DMXQ_ERR_UNSUPPORTED; \
+      if (cls.bfpout) { /* dmxq_softmax_cast_bfp: blocks of B elements = lpb adjacent lanes of one slot */             \
         RowCast rb = rc;                                                                                              \
-        rb.bfp_lpb = lpb;                                                                                             \
-        if ((D_) == DMXQ_F32 && fast32)                                                                               \
+        rb.bfp_lpb = rc.bfp_B / (E_);                                                                                 \
+        if ((D_) == DMXQ_F32 && cls.fast32)                                                                           \
           DMXQ_LAUNCH((softmax_wave_kernel<D_, E_, V_, L_, false, CAST, (D_) == DMXQ_F32, 0, true>),                  \
-                      dim3(one_pass_grid((rows + per_wg - 1) / per_wg)), dim3(kThreads), 0, s, in, out, rows, cols, input_clamp_min, rb); \
+                      dim3(grid), dim3(kThreads), 0, s, in, out, rows, cols, input_clamp_min, rb);                    \
         else                                                                                                          \
           DMXQ_LAUNCH((softmax_wave_kernel<D_, E_, V_, L_, false, CAST, false, 0, true>),                             \
-                      dim3(one_pass_grid((rows + per_wg - 1) / per_wg)), dim3(kThreads), 0, s, in, out, rows, cols, input_clamp_min, rb); \
+                      dim3(grid), dim3(kThreads), 0, s, in, out, rows, cols, input_clamp_min, rb);                    \
         break;                                                                                                        \
       }                                                                                                               \
     }                                                                                                                 \
     if constexpr ((E_) * Elem<D_>::bytes == 16) {                                                                     \
-      if (rag) {                                                                                                      \
-        DMXQ_LAUNCH((softmax_wave_kernel<D_, E_, V_, L_, true, CAST>),                                         \
-                           dim3((unsigned)one_pass_grid((rows + per_wg - 1) / per_wg)), \
-                           dim3(kThreads), 0, s, in, out, rows, cols, input_clamp_min, rc);                           \
+      if (cls.rag) {                                                                                                  \
+        DMXQ_LAUNCH((softmax_wave_kernel<D_, E_, V_, L_, true, CAST>), dim3(grid), dim3(kThreads), 0, s, in, out, rows, cols,  \
+                    input_clamp_min, rc);                                                                             \
         break;                                                                                                        \
       }                                                                                                               \
     }                                                                                                                 \
     if constexpr (CAST && (D_) == DMXQ_F32) {                                                                         \
-      if (fast32) {                                                                                                   \
-        DMXQ_LAUNCH((softmax_wave_kernel<D_, E_, V_, L_, false, CAST, true>),                                  \
-                           dim3((unsigned)one_pass_grid((rows + per_wg - 1) / per_wg)), \
-                           dim3(kThreads), 0, s, in, out, rows, cols, input_clamp_min, rc);                           \
+      if (cls.fast32) {                                                                                               \
+        DMXQ_LAUNCH((softmax_wave_kernel<D_, E_, V_, L_, false, CAST, true>), dim3(grid), dim3(kThreads), 0, s, in, out, rows, cols, \
+                    input_clamp_min, rc);                                                                             \
         break;                                                                                                        \
       }                                                                                                               \
     }                                                                                                                 \
-      DMXQ_LAUNCH((softmax_wave_kernel<D_, E_, V_, L_, false, CAST>),                                          \
-                         dim3((unsigned)one_pass_grid((rows + per_wg - 1) / per_wg)), \
-                         dim3(kThreads), 0, s, in, out, rows, cols, input_clamp_min, rc);                             \
+    DMXQ_LAUNCH((softmax_wave_kernel<D_, E_, V_, L_, false, CAST>), dim3(grid), dim3(kThreads), 0, s, in, out, rows, cols,     \
+                input_clamp_min, rc);                                                                                 \
   } while (0)
 #define DMXQ_SM_V(D_, E_)                                                                            \
   do {                                                                                               \
-    if (lpr == 32) { if (vpl == 1) DMXQ_SM(D_, E_, 1, 32); else if (vpl == 3) DMXQ_SM(D_, E_, 3, 32); else DMXQ_SM(D_, E_, 5, 32); } \
-    else switch (vpl) {                                                                              \
+    if (cls.lpr == 32) { if (cls.vpl == 1) DMXQ_SM(D_, E_, 1, 32); else if (cls.vpl == 3) DMXQ_SM(D_, E_, 3, 32); else DMXQ_SM(D_, E_, 5, 32); } \
+    else switch (cls.vpl) {                                                                          \
       case 1: DMXQ_SM(D_, E_, 1, 64); break;   case 2: DMXQ_SM(D_, E_, 2, 64); break;                 \
       case 3: DMXQ_SM(D_, E_, 3, 64); break;   case 4: DMXQ_SM(D_, E_, 4, 64); break;                 \
       case 5: DMXQ_SM(D_, E_, 5, 64); break;   case 6: DMXQ_SM(D_, E_, 6, 64); break;                 \
@@ -934,15 +901,14 @@ static int softmax_dispatch(const void* in, void* out, int dtype_in, int dtype_o
     }                                                                                                \
   } while (0)
     if (dtype_in == DMXQ_F32) DMXQ_SM_V(DMXQ_F32, 4);
-    else if (dtype_in == DMXQ_BF16) { if (half_vec) DMXQ_SM_V(DMXQ_BF16, 4); else DMXQ_SM_V(DMXQ_BF16, 8); }
-    else { if (half_vec) DMXQ_SM_V(DMXQ_F16, 4); else DMXQ_SM_V(DMXQ_F16, 8); }
+    else if (dtype_in == DMXQ_BF16) { if (cls.epl == 4) DMXQ_SM_V(DMXQ_BF16, 4); else DMXQ_SM_V(DMXQ_BF16, 8); }
+    else { if (cls.epl == 4) DMXQ_SM_V(DMXQ_F16, 4); else DMXQ_SM_V(DMXQ_F16, 8); }
 #undef DMXQ_SM_V
 #undef DMXQ_SM
     return launch_status();
   }
-  if constexpr (CAST) return DMXQ_ERR_UNSUPPORTED;  // the fused-cast form exists for register-resident rows only
   const size_t scratch = (kThreads / kWave) * sizeof(float);
-  if (cols <= kRowLdsFloats)
+  if (cls.family == DMXQ_ROWK_LDS_ROWS)
     DMXQ_LAUNCH(softmax_rows_kernel<true>, dim3(row_grid(rows)), dim3(kThreads), scratch + cols * sizeof(float), s,
                        in, out, dtype_in, dtype_out, rows, cols, input_clamp_min);
   else
@@ -954,6 +920,21 @@ static int softmax_dispatch(const void* in, void* out, int dtype_in, int dtype_o
 extern "C" int dmxq_softmax(const void* in, void* out, int dtype_in, int dtype_out, int64_t rows, int64_t cols,
                             float input_clamp_min, void* stream) {
   return softmax_dispatch<false>(in, out, dtype_in, dtype_out, rows, cols, input_clamp_min, stream, NoRowCast{});
+}
+
+// the class of a row-function call, from the function the three dispatchers decide with (include/dmxq.h; host only)
+extern "C" int dmxq_row_class_of(int op, int dtype_in, int dtype_out, int dtype_wb, int64_t rows, int64_t cols, const void* in,
+                                 const void* out, const void* weight, const void* bias, int cast_kind, int64_t bfp_block,
+                                 dmxq_row_class* cls) {
+  if (!cls || op < DMXQ_ROW_SOFTMAX || op > DMXQ_ROW_RMSNORM || !valid_dtype(dtype_in) || !valid_dtype(dtype_out)) return DMXQ_ERR_BAD_ARG;
+  if (cast_kind < DMXQ_ROWCAST_NONE || cast_kind > DMXQ_ROWCAST_MAN16 || rows < 1 || cols < 1 || bfp_block < 0) return DMXQ_ERR_BAD_ARG;
+  if (bfp_block && cast_kind == DMXQ_ROWCAST_NONE) return DMXQ_ERR_BAD_ARG;
+  if ((weight || bias) && !valid_dtype(dtype_wb)) return DMXQ_ERR_BAD_ARG;
+  if (op == DMXQ_ROW_SOFTMAX) weight = bias = nullptr;
+  if (op == DMXQ_ROW_RMSNORM) bias = nullptr;
+  if (cast_kind != DMXQ_ROWCAST_NONE) dtype_out = dtype_wb = dtype_in;  // the fused entries take one dtype
+  *cls = row_class_of(op, dtype_in, dtype_out, dtype_wb, rows, cols, in, out, weight, bias, cast_kind, bfp_block);
+  return DMXQ_OK;
 }
 
 #endif  // part 1 (softmax)
@@ -988,8 +969,6 @@ extern "C" int dmxq_softmax_cast_bfp(const void* in, void* out, int dtype, int64
   if (!rowcast_of(dtype, cast_in, cast_out, &rc)) return DMXQ_ERR_UNSUPPORTED;
   rc.bfp_B = (int)block_size;
   rc.bfp_wl = precision;
-  const int full = dtype == DMXQ_F32 ? 4 : 8;
-  if (rows * cols != 0 && !(cols >= full && (cols + full - 1) / full <= 64 * 16)) return DMXQ_ERR_UNSUPPORTED;  // (register-resident rows only)
   return softmax_dispatch<true>(in, out, dtype, dtype, rows, cols, input_clamp_min, stream, rc);
 }
 
@@ -1004,32 +983,22 @@ static int norm_dispatch(const void* in, void* out, int dtype_in, int dtype_out,
   if (rows * cols == 0) return DMXQ_OK;
   if (!in || !out) return DMXQ_ERR_BAD_ARG;
   hipStream_t s = (hipStream_t)stream;
-  const bool same = dtype_in == dtype_out && ((!weight && !bias) || dtype_wb == dtype_in);
-  const int epl = same ? wave_epl(dtype_in, cols, in, out, weight, bias) : 0;
-  const int full_epl = dtype_in == DMXQ_F32 ? 4 : 8;
-  // (round 3: the wave kernel at 512 vectors per row -- one wave per 4096-element bf16 row, 8 vectors per lane -- measured 15.6 us against
-  // this kernel's 13.4 us on 4096 x 4096)
-  if (epl == full_epl && cols / epl > 256 && cols / epl <= 8 * kThreads) {  // long rows: workgroup per row
-    const int64_t nv = cols / epl;
-    const int vpl = (int)((nv + kThreads - 1) / kThreads);
-    // rows per workgroup iteration (round 3, tools/tune_rows -> profiles/r03_tune_rows.txt, RMSNorm / LayerNorm rows of 4096 bf16): 2, on a
-    // persistent grid (2560 / 3072 x 4096: 8.2 / 9.9 us against 9.3 / 10.8 us for one pass per workgroup) -- except tensors of 26-32 MiB,
-    // which fit the chip in ONE round of workgroups when each lane keeps ~16 vectors in flight: 8 rows per workgroup, one pass, 10.9 /
-    // 11.5 us against 11.9 / 13.2 us on 3584 / 4096 x 4096 (RMSNorm 63 -> 72 % of the roofline; LayerNorm 13.7 -> 12.3 us).  The fused
-    // module form (CAST) gains 2 % at most from it and keeps the one geometry.
-    const int64_t bytes = rows * cols * (dtype_in == DMXQ_F32 ? 4 : 2);
-    const bool mid = bytes > ((int64_t)26 << 20) && bytes <= ((int64_t)32 << 20);
+  // the class of the call (row_class.hpp): long rows of whole 16-byte vectors take a workgroup per row, shorter register-resident rows
+  // the wave kernel, everything else the fallbacks below
+  const dmxq_row_class cls = row_class_of(RMS ? DMXQ_ROW_RMSNORM : DMXQ_ROW_LAYERNORM, dtype_in, dtype_out, dtype_wb, rows, cols, in, out,
+                                          weight, bias, rowcast_kind<CAST>(dtype_in, rc), rowcast_bfp_block<CAST>(rc));
+  if (cls.family == DMXQ_ROWK_UNSUPPORTED) return DMXQ_ERR_UNSUPPORTED;
+  const int64_t wanted = (rows + cls.rows_per_iter - 1) / cls.rows_per_iter;
+  if (cls.family == DMXQ_ROWK_BLOCK) {
 #define DMXQ_LNB(D_, E_, V_)                                                                                          \
   do {                                                                                                                \
-    constexpr int rpw = (V_) * (E_) <= 32 ? 2 : 1, rpw_mid = 16 / (V_) >= 8 ? 8 : (16 / (V_) >= 4 ? 4 : 2);            \
+    constexpr int rpw = block_rows(V_, E_), rpw_mid = block_rows_mid(V_);                                              \
     if constexpr (CAST) {                                                                                             \
-      if (rc.bfp_B) { /* dmxq_*norm_cast_bfp: blocks of B elements = lpb adjacent lanes */                              \
-        const int lpb = rc.bfp_B / (E_);                                                                              \
-        if (rc.bfp_B % (E_) != 0 || lpb < 1 || (lpb & (lpb - 1)) != 0 || lpb > 64) return DMXQ_ERR_UNSUPPORTED;        \
+      if (cls.bfpout) { /* dmxq_*norm_cast_bfp: blocks of B elements = lpb adjacent lanes */                            \
         RowCast rb = rc;                                                                                              \
-        rb.bfp_lpb = lpb;                                                                                             \
+        rb.bfp_lpb = rc.bfp_B / (E_);                                                                                 \
         DMXQ_LAUNCH((layernorm_block_kernel<D_, E_, V_, RMS, CAST, 0, false, true>),                                \
-                    dim3((unsigned)resident_grid(layernorm_block_kernel<D_, E_, V_, RMS, CAST, 0, false, true>, (rows + rpw - 1) / rpw)), \
+                    dim3((unsigned)resident_grid(layernorm_block_kernel<D_, E_, V_, RMS, CAST, 0, false, true>, wanted)), \
                     dim3(kThreads), 0, s, in, out, rows, cols, weight, bias, eps, rb);                                \
         break;                                                                                                        \
       }                                                                                                               \
@@ -1038,27 +1007,27 @@ static int norm_dispatch(const void* in, void* out, int dtype_in, int dtype_out,
       /* the RMSNorm MODULE on 16-bit rows of 4096 (Llama's hidden size), 26-32 MiB: four rows per workgroup iteration on the persistent  */ \
       /* grid, 16 idle issue cycles between a lane's loads: 13.5-13.65 -> 12.66 us on 4096 x 4096 bf16 (profiles/r05_tune_rows_pace.txt; */ \
       /* four rows alone: 12.9-13.2)                                                                                                    */ \
-      if (mid && !rc.bfp_B) {                                                                                         \
+      if (cls.grid == DMXQ_ROWGRID_MODULE_ROWS4) {                                                                    \
         DMXQ_LAUNCH((layernorm_block_kernel<D_, E_, V_, RMS, CAST, 4>),                                               \
-                    dim3((unsigned)resident_grid(layernorm_block_kernel<D_, E_, V_, RMS, CAST, 4>, (rows + 3) / 4)), dim3(kThreads), 0, s, \
+                    dim3((unsigned)resident_grid(layernorm_block_kernel<D_, E_, V_, RMS, CAST, 4>, wanted)), dim3(kThreads), 0, s, \
                     in, out, rows, cols, weight, bias, eps, rc);                                                      \
         break;                                                                                                        \
       }                                                                                                               \
     }                                                                                                                 \
     if constexpr (!CAST && rpw_mid != rpw) {                                                                          \
-      if (mid) {                                                                                                      \
-        DMXQ_LAUNCH((layernorm_block_kernel<D_, E_, V_, RMS, CAST, rpw_mid, true>), dim3(one_pass_grid((rows + rpw_mid - 1) / rpw_mid)),   \
+      if (cls.grid == DMXQ_ROWGRID_MID_ONE_PASS) {                                                                    \
+        DMXQ_LAUNCH((layernorm_block_kernel<D_, E_, V_, RMS, CAST, rpw_mid, true>), dim3(one_pass_grid(wanted)),       \
                     dim3(kThreads), 0, s, in, out, rows, cols, weight, bias, eps, rc);                                \
         break;                                                                                                        \
       }                                                                                                               \
     }                                                                                                                 \
     DMXQ_LAUNCH((layernorm_block_kernel<D_, E_, V_, RMS, CAST>),                                                    \
-                       dim3((unsigned)resident_grid(layernorm_block_kernel<D_, E_, V_, RMS, CAST>, (rows + rpw - 1) / rpw)), \
+                       dim3((unsigned)resident_grid(layernorm_block_kernel<D_, E_, V_, RMS, CAST>, wanted)), \
                        dim3(kThreads), 0, s, in, out, rows, cols, weight, bias, eps, rc);                             \
   } while (0)
 #define DMXQ_LNB_V(D_, E_)                                                                                            \
   do {                                                                                                                \
-    switch (vpl) {                                                                                                    \
+    switch (cls.vpl) {                                                                                                \
       case 2: DMXQ_LNB(D_, E_, 2); break; case 3: DMXQ_LNB(D_, E_, 3); break; case 4: DMXQ_LNB(D_, E_, 4); break;      \
       case 5: DMXQ_LNB(D_, E_, 5); break; case 6: DMXQ_LNB(D_, E_, 6); break; default: DMXQ_LNB(D_, E_, 8); break;     \
     }                                                                                                                 \
@@ -1070,20 +1039,15 @@ static int norm_dispatch(const void* in, void* out, int dtype_in, int dtype_out,
 #undef DMXQ_LNB
     return launch_status();
   }
-  if (epl && cols <= (int64_t)64 * epl * 16) {
-    int lpr, vpl;
-    wave_shape(cols / epl, &lpr, &vpl);
+  if (cls.family == DMXQ_ROWK_WAVE) {
 #define DMXQ_LN(D_, E_, V_, L_)                                                                                       \
   do {                                                                                                                \
-    constexpr int per_wg = 4 * rows_per_wave(V_, E_) * (64 / (L_));                                                   \
     if constexpr (CAST) {                                                                                             \
-      if (rc.bfp_B) {                                                                                                 \
-        const int lpb = rc.bfp_B / (E_);                                                                              \
-        if (rc.bfp_B % (E_) != 0 || lpb < 1 || (lpb & (lpb - 1)) != 0 || lpb > (L_)) return DMXQ_ERR_UNSUPPORTED;      \
+      if (cls.bfpout) {                                                                                               \
         RowCast rb = rc;                                                                                              \
-        rb.bfp_lpb = lpb;                                                                                             \
+        rb.bfp_lpb = rc.bfp_B / (E_);                                                                                 \
         DMXQ_LAUNCH((layernorm_wave_kernel<D_, E_, V_, L_, RMS, CAST, 0, 0, -1, true>),                             \
-                    dim3((unsigned)resident_grid(layernorm_wave_kernel<D_, E_, V_, L_, RMS, CAST, 0, 0, -1, true>, (rows + per_wg - 1) / per_wg)), \
+                    dim3((unsigned)resident_grid(layernorm_wave_kernel<D_, E_, V_, L_, RMS, CAST, 0, 0, -1, true>, wanted)), \
                     dim3(kThreads), 0, s, in, out, rows, cols, weight, bias, eps, rb);                                \
         break;                                                                                                        \
       }                                                                                                               \
@@ -1093,18 +1057,20 @@ static int norm_dispatch(const void* in, void* out, int dtype_in, int dtype_out,
       /* grid, with 32 idle issue cycles between a wave's loads (layernorm_wave_kernel kLnModulePace).  Same-lease library A/B, 24000 x 768  */ \
       /* bf16: 15.26 -> 14.32 us (60.4 -> 64.4 %; pace 2: 14.55; four rows per wave on the persistent grid, pace 0 / 2: 15.50 / 15.53);       */ \
       /* 32768 / 48000 / 96000 rows: 19.9 -> 19.6, 28.3 -> 26.9, 53.4 -> 51.6 us (profiles/r05_tune_rows_pace.txt)                            */ \
-      DMXQ_LAUNCH((layernorm_wave_kernel<D_, E_, V_, L_, RMS, CAST>), dim3(one_pass_grid((rows + per_wg - 1) / per_wg)), dim3(kThreads), 0, s, \
-                  in, out, rows, cols, weight, bias, eps, rc);                                                        \
-      break;                                                                                                          \
+      if (cls.grid == DMXQ_ROWGRID_MODULE_ONE_PASS) {                                                                 \
+        DMXQ_LAUNCH((layernorm_wave_kernel<D_, E_, V_, L_, RMS, CAST>), dim3(one_pass_grid(wanted)), dim3(kThreads), 0, s,     \
+                    in, out, rows, cols, weight, bias, eps, rc);                                                      \
+        break;                                                                                                        \
+      }                                                                                                               \
     }                                                                                                                 \
     DMXQ_LAUNCH((layernorm_wave_kernel<D_, E_, V_, L_, RMS, CAST>),                                                 \
-                       dim3((unsigned)resident_grid(layernorm_wave_kernel<D_, E_, V_, L_, RMS, CAST>, (rows + per_wg - 1) / per_wg)), \
+                       dim3((unsigned)resident_grid(layernorm_wave_kernel<D_, E_, V_, L_, RMS, CAST>, wanted)), \
                        dim3(kThreads), 0, s, in, out, rows, cols, weight, bias, eps, rc);                             \
   } while (0)
 #define DMXQ_LN_V(D_, E_)                                                                            \
   do {                                                                                               \
-    if (lpr == 32) { if (vpl == 1) DMXQ_LN(D_, E_, 1, 32); else if (vpl == 3) DMXQ_LN(D_, E_, 3, 32); else DMXQ_LN(D_, E_, 5, 32); } \
-    else switch (vpl) {                                                                              \
+    if (cls.lpr == 32) { if (cls.vpl == 1) DMXQ_LN(D_, E_, 1, 32); else if (cls.vpl == 3) DMXQ_LN(D_, E_, 3, 32); else DMXQ_LN(D_, E_, 5, 32); } \
+    else switch (cls.vpl) {                                                                            \
       case 1: DMXQ_LN(D_, E_, 1, 64); break;   case 2: DMXQ_LN(D_, E_, 2, 64); break;                 \
       case 3: DMXQ_LN(D_, E_, 3, 64); break;   case 4: DMXQ_LN(D_, E_, 4, 64); break;                 \
       case 5: DMXQ_LN(D_, E_, 5, 64); break;   case 6: DMXQ_LN(D_, E_, 6, 64); break;                 \
@@ -1113,15 +1079,14 @@ static int norm_dispatch(const void* in, void* out, int dtype_in, int dtype_out,
     }                                                                                                \
   } while (0)
     if (dtype_in == DMXQ_F32) DMXQ_LN_V(DMXQ_F32, 4);
-    else if (dtype_in == DMXQ_BF16) { if (epl == 8) DMXQ_LN_V(DMXQ_BF16, 8); else DMXQ_LN_V(DMXQ_BF16, 4); }
-    else { if (epl == 8) DMXQ_LN_V(DMXQ_F16, 8); else DMXQ_LN_V(DMXQ_F16, 4); }
+    else if (dtype_in == DMXQ_BF16) { if (cls.epl == 8) DMXQ_LN_V(DMXQ_BF16, 8); else DMXQ_LN_V(DMXQ_BF16, 4); }
+    else { if (cls.epl == 8) DMXQ_LN_V(DMXQ_F16, 8); else DMXQ_LN_V(DMXQ_F16, 4); }
 #undef DMXQ_LN_V
 #undef DMXQ_LN
     return launch_status();
   }
-  if constexpr (CAST) return DMXQ_ERR_UNSUPPORTED;  // the fused-cast form exists for register-resident rows only
   const size_t scratch = (kThreads / kWave) * sizeof(float);
-  if (cols <= kRowLdsFloats)
+  if (cls.family == DMXQ_ROWK_LDS_ROWS)
     DMXQ_LAUNCH((layernorm_rows_kernel<true, RMS>), dim3(row_grid(rows)), dim3(kThreads), scratch + cols * sizeof(float),
                        s, in, out, dtype_in, dtype_out, rows, cols, weight, bias, dtype_wb, eps);
   else

@@ -56,7 +56,7 @@ const char* dmxq_status_string(int status);
 /* ABI version: bumped on any signature change.  Additions since 4 (dmxq_gptq_block, dmxq_hist_observe, dmxq_hist_qparams, dmxq_error_stats, dmxq_cast_error,
  * dmxq_error_scratch_bytes, dmxq_hadamard_qdq, dmxq_dynamic_fixed_qdq, dmxq_dynamic_class, dmxq_gptq_block_dynamic,
  * dmxq_dynamic_float_qdq, dmxq_dynamic_float_class, dmxq_channel_sumsq_accumulate, dmxq_channel_sumsq_workspace_bytes, dmxq_wanda_nm,
- * dmxq_wanda_class) leave it at 4: a caller built against 4 runs on
+ * dmxq_wanda_class, dmxq_row_class_of) leave it at 4: a caller built against 4 runs on
  * this library unchanged.  4 = round 5: + dmxq_float_qdq_multi, dmxq_fixed_float_qdq_multi; 3 = round 4: + dmxq_weight_hypernet_multi,
  * dmxq_unary_cast_table, dmxq_lut16_apply.  Nothing was ever removed or changed: a caller built against version n runs on any library >= n. */
 int dmxq_abi_version(void);
@@ -611,6 +611,39 @@ int dmxq_channel_sumsq_accumulate(const void* in, int dtype_in, int64_t rows, in
 int dmxq_wanda_class(int dtype_w, int64_t L, int M);
 int dmxq_wanda_nm(const void* w, int dtype_w, const float* act_norm, float* score_out, void* mask_out, int dtype_mask, void* y_out,
                   int dtype_y, int64_t rows, int64_t L, int K, int M, void* stream);
+
+/* Which kernel a row function launches (csrc/row_class.hpp): what dmxq_softmax* / dmxq_layernorm* / dmxq_rmsnorm* will do for one call,
+ * answered by the function their dispatch itself decides with.  A host function: no GPU involved, no HIP call, the pointers are not
+ * dereferenced -- only their alignment matters (in == out, an in-place call, takes the same class as the out-of-place one).
+ *   op            dmxq_row_op;  dtype_wb is read only where weight or bias is not NULL (RMSNorm: bias = NULL);
+ *   cast_kind     dmxq_row_cast_kind: NONE = the plain entries (dmxq_softmax, dmxq_layernorm, dmxq_rmsnorm), anything else = the *_cast
+ *                 entries (one dtype throughout).  16-bit rows take range-only casts, so every other kind is the same class there; on
+ *                 float32 rows MAN16 = the output cast is active and keeps <= 16 mantissa bits (softmax then takes its FAST32 form),
+ *                 GENERAL = any other pair of casts;
+ *   bfp_block     0, or the block size of the *_cast_bfp entries.
+ * Answer (dmxq_row_class):
+ *   family        dmxq_row_family: UNSUPPORTED = the entry refuses the call (DMXQ_ERR_UNSUPPORTED: a fused form outside the
+ *                 register-resident rows, a block size that is not a power-of-two number of lane-vectors of one slot); WAVE = a row per
+ *                 `lpr` = 64 or 32 lanes; BLOCK = a row per 256-thread workgroup (lpr = 256); LDS_ROWS / GLOBAL_ROWS = the fallbacks, a
+ *                 workgroup per row staged in LDS / read three times (epl = vpl = lpr = 0);
+ *   epl, vpl, lpr elements per lane-vector, lane-vectors per lane (the kernel's template argument: 7 needed = 8), lanes per row;
+ *   rag           rows of any length / alignment: unaligned 16-byte vectors with an overlapped last one (softmax);
+ *   half_vec      8-byte lane-vectors (16-bit rows that are a multiple of 4 elements on 8-byte bases);
+ *   fast32        float32 softmax behind a MAN16 output cast;  bfpout: the fused BFP epilogue;
+ *   grid          dmxq_row_grid: PERSISTENT = as many workgroups as are resident, each looping; ONE_PASS = a workgroup per rows_per_iter
+ *                 rows; MID_ONE_PASS = the BLOCK kernel's one-pass form for tensors of 26-32 MiB; MODULE_ONE_PASS = the LayerNorm module
+ *                 on 16-bit rows of 768; MODULE_ROWS4 = the RMSNorm module on 16-bit rows of 4096 at 26-32 MiB (persistent, 4 rows);
+ *                 CAPPED = the fallbacks' min(rows, 4096) workgroups;
+ *   rows_per_iter rows one workgroup takes per iteration.
+ * Returns DMXQ_OK, or DMXQ_ERR_BAD_ARG (invalid op / dtype / cast_kind, rows or cols < 1, bfp_block < 0, bfp_block without a cast, cls NULL). */
+typedef enum { DMXQ_ROW_SOFTMAX = 0, DMXQ_ROW_LAYERNORM = 1, DMXQ_ROW_RMSNORM = 2 } dmxq_row_op;
+typedef enum { DMXQ_ROWCAST_NONE = 0, DMXQ_ROWCAST_RANGE = 1, DMXQ_ROWCAST_GENERAL = 2, DMXQ_ROWCAST_MAN16 = 3 } dmxq_row_cast_kind;
+typedef enum { DMXQ_ROWK_UNSUPPORTED = 0, DMXQ_ROWK_WAVE = 1, DMXQ_ROWK_BLOCK = 2, DMXQ_ROWK_LDS_ROWS = 3, DMXQ_ROWK_GLOBAL_ROWS = 4 } dmxq_row_family;
+typedef enum { DMXQ_ROWGRID_NONE = 0, DMXQ_ROWGRID_PERSISTENT = 1, DMXQ_ROWGRID_ONE_PASS = 2, DMXQ_ROWGRID_MID_ONE_PASS = 3,
+               DMXQ_ROWGRID_MODULE_ONE_PASS = 4, DMXQ_ROWGRID_MODULE_ROWS4 = 5, DMXQ_ROWGRID_CAPPED = 6 } dmxq_row_grid;
+typedef struct { int family, epl, vpl, lpr, rag, half_vec, fast32, bfpout, grid, rows_per_iter; } dmxq_row_class;
+int dmxq_row_class_of(int op, int dtype_in, int dtype_out, int dtype_wb, int64_t rows, int64_t cols, const void* in, const void* out,
+                      const void* weight, const void* bias, int cast_kind, int64_t bfp_block, dmxq_row_class* cls);
 
 #ifdef __cplusplus
 }

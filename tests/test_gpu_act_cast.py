@@ -21,6 +21,8 @@ import torch
 
 from _approx_cases import inputs_with_specials as _inputs   # (shared with the module-forward fixtures: tests/_approx_cases.py)
 from _data import make, outside_cast_bracket
+# (tolerances and float64 truths of the row functions, shared with tests/test_gpu_row_classes.py)
+from _row_truth import cpu_cast as _cpu_cast, ln_truth as _ln_truth, n_ulp as _n_ulp, rms_truth as _rms_truth, row_n_ulp as _row_n_ulp
 
 pytestmark = pytest.mark.gpu
 F = torch.nn.functional
@@ -30,13 +32,6 @@ FMT = {"SAME": None, "FLOAT16": "FP[1|5|10,15](FN)", "BFLOAT16": "FP[1|8|7,127](
 
 def _fmt(dmx, name):
     return None if FMT[name] is None else dmx.Format.from_shorthand(FMT[name])
-
-
-def _cpu_cast(oracle, f):
-    """CastTo.forward on the CPU through the oracle: dtype -> same dtype"""
-    if f is None:
-        return lambda x: x.clone()
-    return lambda x: oracle.floating_point_cast(x, f.mantissa, f.exponent, f.bias, f.flush_subnormal).to(x.dtype)
 
 
 def _quick_gelu64(c, dtype):
@@ -52,13 +47,6 @@ UNARY = {
     "exp": (lambda c, dt: torch.exp(c.double()), None, {torch.float32: 3}),
     "quick_gelu": (_quick_gelu64, None, {torch.float32: 3, torch.bfloat16: 2, torch.float16: 2}),
 }
-
-
-def _n_ulp(table, dtype, fo):
-    n = table.get(dtype, 1)
-    if dtype == torch.float32 and fo is not None and fo.mantissa <= 16:
-        n = 64  # v_exp / v_rcp forms behind an output cast of <= 16 mantissa bits (csrc/act_cast.hip)
-    return n
 
 
 @pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float16, torch.float32])
@@ -91,29 +79,6 @@ def test_unary_cast_every_16_bit_pattern(dmx, cuda, oracle, dtype):
         got = dmx.ops.unary_cast(x.to(cuda), func, fi, fo)
         bad = outside_cast_bracket(got, f64(cin, dtype), _cpu_cast(oracle, fo), dtype, _n_ulp(tol, dtype, fo), None if floor_fn is None else floor_fn(cin))
         assert bad == 0, (func, dtype, bad)
-
-
-# softmax / layer_norm / rms_norm: the float32 tolerances of the unfused functions (tests/test_gpu_sparse_calib_approx.py TOL); only
-# softmax uses the v_exp / v_rcp forms, so only softmax is granted the 64 fp32 ulps behind a narrow output cast
-ROW_TOL = {"softmax": {torch.float32: 8}, "layernorm": {torch.float32: 3}, "rmsnorm": {torch.float32: 4}}
-
-
-def _row_n_ulp(kind, dtype, fo):
-    return _n_ulp(ROW_TOL[kind], dtype, fo if kind == "softmax" else None)
-
-
-def _ln_truth(c, cols, w, b, eps):
-    xd = c.double()
-    truth = F.layer_norm(xd, (cols,), None if w is None else w.double(), None if b is None else b.double(), eps)
-    mu, rstd = xd.mean(-1, keepdim=True), (xd.var(-1, unbiased=False, keepdim=True) + eps).rsqrt()
-    floor = (xd.abs().amax(-1, keepdim=True) + mu.abs()) * rstd * (1.0 if w is None else w.double().abs()) + (0.0 if b is None else b.double().abs())
-    return truth, floor
-
-
-def _rms_truth(c, cols, w, eps):
-    xd = c.double()
-    y = xd * (xd.pow(2).mean(-1, keepdim=True) + eps).rsqrt()
-    return y if w is None else y * w.double()
 
 
 @pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float16, torch.float32])

@@ -6,6 +6,7 @@ import pytest
 import torch
 
 from _data import bits_equal, make, mismatches_nan_aware
+from _row_truth import ln_truth as _ln_truth, tol as _tol
 
 pytestmark = pytest.mark.gpu
 
@@ -166,31 +167,8 @@ def test_channel_maxabs_and_smoothquant_scale(dmx, cuda, oracle):
     assert torch.all(z == 1e-5)                                              # clamp at scale_min
 
 
-# Tolerances of the exact-function ops, in ulps of the OUTPUT format against the float64 truth rounded once
-# (tests/_data.py err_in_ulps; measured maxima for the kernels AND for torch's own CPU result, which is what the reference
-# evaluates, are in profiles/r02_accuracy_table.txt):
-#   16-bit outputs: 1 ulp everywhere ("within 1 ULP of the stated format");
-#   fp32 outputs: gelu 2 (erf / tanh + 3 products), softmax 8 (expf <= 1, a row sum of up to 16k fp32 terms, one division;
-#   the argument x - max is compensated -- torch's CPU softmax measures 7-24 on the same inputs), layer_norm 3 (two row
-#   reductions, rsqrt, fma).  gelu and layer_norm are counted against the magnitude of their CANCELLING terms.
-TOL = {"gelu": {torch.float32: 2.0}, "softmax": {torch.float32: 8.0}, "layernorm": {torch.float32: 3.0}}
-
-
-def _tol(op, dtype):
-    return TOL[op].get(dtype, 1.0)
-
-
-def _ln_truth(x, cols, w, b, eps=1e-5):
-    F = torch.nn.functional
-    xd = x.double()
-    truth = F.layer_norm(xd, (cols,), None if w is None else w.double(), None if b is None else b.double(), eps)
-    # cancelling terms of y = (x - mean) rstd w + b: the row mean is a sum of terms of the row's magnitude, so its rounding
-    # error -- and with it the error of every (x - mean) -- is relative to max|x| of the ROW, not to the element
-    mu, rstd = xd.mean(-1, keepdim=True), (xd.var(-1, unbiased=False, keepdim=True) + eps).rsqrt()
-    floor = (xd.abs().amax(-1, keepdim=True) + mu.abs()) * rstd * (1.0 if w is None else w.double().abs()) + (0.0 if b is None else b.double().abs())
-    return truth, floor
-
-
+# Tolerances of the exact-function ops, in ulps of the OUTPUT format against the float64 truth rounded once:
+# stated in tests/_row_truth.py (TOL, tol, ln_truth), shared with the other row-function tests
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16, torch.float16])
 def test_gelu_softmax_layernorm_exact_function_parity(dmx, cuda, dtype):
     """Approximator slot = the exact torch.nn.functional function (vsimd absent).  Ground truth: float64, rounded once."""
