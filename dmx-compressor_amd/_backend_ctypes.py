@@ -887,21 +887,30 @@ def dynamic_float_qdq(x, mode, segment, man, exp, bias, flush_subnormal, roundin
 
 
 # ------------------------------------------------------------------------------------------------ Wanda
+def _channel_sum(x, acc, scratch, entry, what):
+    xc = _prep(x, what)
+    C = xc.shape[-1] if xc.dim() else 1
+    rows = xc.numel() // C if C else 0
+    if not (acc.is_cuda and acc.device == xc.device and acc.dtype == torch.float64 and acc.is_contiguous() and acc.numel() == C):
+        raise RuntimeError(f"{what}: acc must be a contiguous float64 tensor of {C} entries on the input's device")
+    need = lib().dmxq_channel_sumsq_workspace_bytes(rows, C)
+    if not (scratch.is_cuda and scratch.device == xc.device and scratch.is_contiguous() and scratch.numel() * scratch.element_size() >= need
+            and scratch.data_ptr() % 8 == 0):
+        raise RuntimeError(f"{what}: scratch must be a contiguous 8-byte aligned tensor of at least {need} bytes on the input's device")
+    check(getattr(lib(), entry)(ptr(xc), dtype_code(xc.dtype), rows, C, ptr(acc), ptr(scratch), stream_of(xc)), entry)
+
+
 @_guarded
 def channel_sumsq(x, acc, scratch):
     """acc (float64 [C], C = x's last dim) += the sum of squares over every other dim; scratch: dmxq_channel_sumsq_workspace_bytes bytes of
     any contiguous device tensor"""
-    xc = _prep(x, "channel_sumsq")
-    C = xc.shape[-1] if xc.dim() else 1
-    rows = xc.numel() // C if C else 0
-    if not (acc.is_cuda and acc.device == xc.device and acc.dtype == torch.float64 and acc.is_contiguous() and acc.numel() == C):
-        raise RuntimeError(f"channel_sumsq: acc must be a contiguous float64 tensor of {C} entries on the input's device")
-    need = lib().dmxq_channel_sumsq_workspace_bytes(rows, C)
-    if not (scratch.is_cuda and scratch.device == xc.device and scratch.is_contiguous() and scratch.numel() * scratch.element_size() >= need
-            and scratch.data_ptr() % 8 == 0):
-        raise RuntimeError(f"channel_sumsq: scratch must be a contiguous 8-byte aligned tensor of at least {need} bytes on the input's device")
-    check(lib().dmxq_channel_sumsq_accumulate(ptr(xc), dtype_code(xc.dtype), rows, C, ptr(acc), ptr(scratch), stream_of(xc)),
-          "dmxq_channel_sumsq_accumulate")
+    _channel_sum(x, acc, scratch, "dmxq_channel_sumsq_accumulate", "channel_sumsq")
+
+
+@_guarded
+def channel_sumabs(x, acc, scratch):
+    """the |x| twin of channel_sumsq (AWQ): same checks, same scratch"""
+    _channel_sum(x, acc, scratch, "dmxq_channel_sumabs_accumulate", "channel_sumabs")
 
 
 def _wanda_shapes(w, act_norm):
@@ -924,3 +933,20 @@ def wanda_nm(w, act_norm, K, M, want_score, want_mask, want_y, mask_dtype=None, 
     check(lib().dmxq_wanda_nm(ptr(wc), dtype_code(wc.dtype), ptr(act_norm), ptr(score), ptr(mask), dtype_code(mask.dtype) if want_mask else 0,
                               ptr(y), dtype_code(y.dtype) if want_y else 0, wc.shape[0], wc.shape[1], K, M, stream_of(wc)), "dmxq_wanda_nm")
     return (score if want_score else none.float()), (mask if want_mask else none), (y if want_y else none)
+
+
+# ------------------------------------------------------------------------------------------------ AWQ
+@_guarded
+def awq_group_error(w, s, group, precision, fraction, clamp, symmetric, qmin, qmax, symmetric_qscheme, want_wq):
+    """-> (d float32, wq in w's dtype): wq comes back as an empty 1-d tensor when it was not requested"""
+    wc = _prep(w, "awq_group_error")
+    if wc.dim() != 2:
+        raise RuntimeError("awq_group_error: the weight must be a [rows, L] matrix")
+    if not (s.is_cuda and s.device == wc.device and s.dtype == torch.float32 and s.is_contiguous() and s.numel() == wc.shape[1]):
+        raise RuntimeError(f"awq_group_error: s must be a contiguous float32 tensor of {wc.shape[1]} entries on the weight's device")
+    d = torch.empty(wc.shape, dtype=torch.float32, device=wc.device)
+    wq = torch.empty(wc.shape if want_wq else 0, dtype=wc.dtype, device=wc.device)
+    check(lib().dmxq_awq_group_error(ptr(wc), dtype_code(wc.dtype), ptr(s), ptr(d), ptr(wq) if want_wq else None, wc.shape[0], wc.shape[1], group,
+                                     precision, fraction, int(bool(clamp)), int(bool(symmetric)), qmin, qmax, int(bool(symmetric_qscheme)),
+                                     stream_of(wc)), "dmxq_awq_group_error")
+    return d, wq

@@ -26,6 +26,7 @@ __all__ = [
     "dynamic_float_qdq", "dynamic_float_check", "dynamic_float_class", "dynamic_float_fmax", "DYNAMIC_FLOAT_GRANULARITIES",
     "DYNAMIC_FLOAT_CHAIN_BY_DEFAULT",
     "channel_sumsq", "channel_sumsq_workspace_bytes", "wanda_score", "wanda_nm_sparsify", "wanda_class", "WANDA_CHAIN_BY_DEFAULT",
+    "channel_sumabs", "awq_candidate_scales", "awq_scaled_error", "awq_class", "awq_search", "AWQ_CHAIN_BY_DEFAULT",
 ]
 
 _ops = None   # the raw namespace: set by bind()
@@ -1385,3 +1386,174 @@ def wanda_nm_sparsify(w, act_norm, K: int, M: int, return_mask: bool = False, re
     score, mask, y = _wanda(w, act_norm, K, M, bool(return_score), bool(return_mask), bool(return_y), fused, out_dtype, "wanda_nm_sparsify")
     out = tuple(t for t, want in ((y, return_y), (mask, return_mask), (score, return_score)) if want)
     return out[0] if len(out) == 1 else out
+
+
+# ---------------------------------------------------------------------------------------------------- AWQ
+# Group sizes of dmxq_awq_group_error that fused=None sends to the four-launch chain although the kernel takes them: WANDA_CHAIN_BY_DEFAULT's
+# rule, a class goes to the kernel by default only where tools/bench_awq.py MEASURED it faster than the chain (scale_channels ->
+# dynamic_fixed_qdq -> scale_channels to float32 -> the subtraction) on the same buffers.  profiles/r17_awq.txt (bf16 XP[4,0] g128, us per
+# candidate, kernel against chain): [4096,4096] 32.0 against 93.5, [14336,4096] 95.3 against 327.2, [4096,14336] 90.4 against 325.3 -- no
+# row is slower, none is listed.
+AWQ_CHAIN_BY_DEFAULT = frozenset()
+# which route the calls of this front end took, counted on the host: private, for the tests (fused=True must have run the kernel)
+_awq_routes = {"fused": 0, "chain": 0}
+AWQ_SCALE_MIN = 1e-4   # the floor of a candidate scale before it is normalised
+
+
+def channel_sumabs(x, out=None):
+    """Per-channel sum of |x| over every dimension but the last, in float64 (dmxq_channel_sumabs_accumulate; DESIGN.md §8 "AWQ"): the
+    twin of channel_sumsq -- the same kernel body with |x| as the term, the same workspace, slab partition and fixed order without
+    atomics (the same batches in the same order give the same bits), `out` ADDED into and returned.  Two launches, nothing read back:
+    capturable."""
+    require_gpu(x, "channel_sumabs")
+    if x.dim() < 1:
+        raise ValueError("channel_sumabs: x needs a channel dimension")
+    C = x.shape[-1]
+    if out is None:
+        out = torch.zeros(C, dtype=torch.float64, device=x.device)
+    elif not (out.is_cuda and out.device == x.device and out.dtype == torch.float64 and out.is_contiguous() and out.shape == (C,)):
+        raise ValueError(f"channel_sumabs: out must be a contiguous float64 [{C}] tensor on the input's device")
+    if x.numel() == 0:
+        return out
+    _ops.channel_sumabs(x.detach(), out, _sumsq_workspace(x.device, channel_sumsq_workspace_bytes(x.numel() // C, C)))
+    return out
+
+
+def awq_class(dtype: torch.dtype, L: int, group: int) -> bool:
+    """whether dmxq_awq_group_error takes rows of L elements of `dtype` with groups of `group` in its one-launch kernel, asked of the
+    library itself (dmxq_awq_class; no GPU involved): group a power of two from 16 to 256 that divides L"""
+    from ._lib import dtype_code, lib
+    return bool(lib().dmxq_awq_class(dtype_code(dtype), int(L), int(group)))
+
+
+def awq_candidate_scales(x_mean, n_grid: int, scale_cast=None):
+    """The candidate scale vectors of an AWQ search (Lin et al., 2023): float32 [n_grid, in] on x_mean's device.  x_mean is
+    the float32 [in] vector of the input channels' mean magnitudes; for k = 0 .. n_grid - 1 and r = k / n_grid
+        s_k = clamp(x_mean ** r, min=1e-4);   s_k /= sqrt(max(s_k) * min(s_k));   s_k = scale_cast(s_k)
+    in float32 torch arithmetic on the device (scale_cast: SmoothQuant's cast of its scale, or None).  Row 0 is exactly all ones: plain
+    round-to-nearest.  Nothing is read back."""
+    if isinstance(n_grid, bool) or not isinstance(n_grid, int) or n_grid < 1:
+        raise ValueError(f"awq_candidate_scales: n_grid must be a positive integer, got {n_grid!r}")
+    if not isinstance(x_mean, torch.Tensor) or x_mean.dim() != 1 or x_mean.dtype != torch.float32:
+        raise ValueError("awq_candidate_scales: x_mean must be a float32 [in] vector")
+    with torch.no_grad():
+        rows = []
+        for k in range(n_grid):
+            s = x_mean.pow(k / n_grid).clamp(min=AWQ_SCALE_MIN)
+            s = s / (s.max() * s.min()).sqrt()
+            rows.append(scale_cast(s) if scale_cast is not None else s)
+        return torch.stack(rows).to(torch.float32).contiguous()
+
+
+def _awq_check(w, s, fmt, group_size, what):
+    """the argument errors of the AWQ ops, before any GPU use (ValueError / TypeError)"""
+    fmt, _, group_size = dynamic_check(fmt, "per_group", group_size, what=what)
+    if not isinstance(w, torch.Tensor) or w.dim() != 2:
+        raise ValueError(f"{what}: the weight must be an [out, in] matrix")
+    if w.dtype not in (torch.float32, torch.float16, torch.bfloat16):
+        raise TypeError(f"{what}: the weight must be float32, float16 or bfloat16, got {w.dtype}")
+    L = w.shape[1]
+    if not isinstance(s, torch.Tensor) or s.dtype != torch.float32:
+        raise TypeError(f"{what}: s must be a float32 tensor, got {getattr(s, 'dtype', type(s))}")
+    if s.shape != (L,):
+        raise ValueError(f"{what}: s must hold one entry per input channel, [{L}], got {tuple(s.shape)}")
+    if L % group_size:
+        raise ValueError(f"{what}: the last dimension has {L} elements, not a multiple of the group size {group_size}")
+    return fmt, group_size
+
+
+def awq_scaled_error(w, s, fmt, group_size: int, symmetric_qscheme: bool = False, return_wq: bool = False, fused: Optional[bool] = None):
+    """The error of ONE AWQ candidate on an [out, in] weight: with the float32 [in] scale vector s, by definition
+        ws = scale_channels(w, s, -1, divide=False, out_dtype=w.dtype)
+        wq = dynamic_fixed_qdq(ws, fmt, "per_group", group_size, symmetric_qscheme)
+        d  = scale_channels(wq, s, -1, divide=True, out_dtype=torch.float32) - w.float()
+    -- the weight as the layer would hold it under SmoothQuant's scale s, cast by a per-group dynamic integer cast, brought back and
+    compared: d = Q(w s) / s - w in float32.  Returns d, or (d, wq) with return_wq.
+    ONE launch (dmxq_awq_group_error: 6 B per bf16 element, 8 with wq, against the chain's four launches and ~22 B) for a
+    nearest-rounding format, group_size a power of two from 16 to 256 and 16-byte aligned tensors; the chain otherwise, same bits.
+    fused=None: the kernel where it applies and group_size is not listed in AWQ_CHAIN_BY_DEFAULT; True: NotImplementedError instead of
+    falling back; False: the chain.
+    ValueError / TypeError before any GPU use: a format without an integer range, a group_size that does not divide the last dim, an s
+    of the wrong length or dtype, a weight that is no matrix."""
+    from .observer import get_qmin_qmax
+    fmt, group_size = _awq_check(w, s, fmt, group_size, "awq_scaled_error")
+    require_gpu(w, "awq_scaled_error")
+    require_gpu(s, "awq_scaled_error")
+    qmin, qmax = get_qmin_qmax(fmt)
+    sym = bool(symmetric_qscheme)
+    with torch.no_grad():
+        wc = w.detach()
+        wc = wc if wc.is_contiguous() else wc.contiguous()
+        sc = s.detach()
+        sc = sc if sc.is_contiguous() else sc.contiguous()
+        if wc.numel() == 0:
+            d = torch.empty(wc.shape, dtype=torch.float32, device=wc.device)
+            return (d, torch.empty_like(wc)) if return_wq else d
+        if fused is not False:
+            ok = (fmt.rounding == "nearest" and fmt.precision <= 22 and awq_class(wc.dtype, wc.shape[1], group_size)
+                  and wc.data_ptr() % 16 == 0 and sc.data_ptr() % 16 == 0)
+            if not ok and fused:
+                raise NotImplementedError(f"awq_scaled_error: no one-launch kernel for groups of {group_size} in rows of {wc.shape[1]} {wc.dtype} "
+                                          f"elements with {fmt!r} (weight base address {wc.data_ptr() % 16} mod 16)")
+            if ok and fused is None and group_size in AWQ_CHAIN_BY_DEFAULT:
+                ok = False
+            if ok:
+                try:
+                    d, wq = _ops.awq_group_error(wc, sc, int(group_size), fmt.precision, fmt.fraction, bool(fmt.clamp), bool(fmt.symmetric),
+                                                 qmin, qmax, sym, bool(return_wq))
+                    _awq_routes["fused"] += 1
+                    return (d, wq) if return_wq else d
+                except NotImplementedError:   # (DMXQ_ERR_UNSUPPORTED, nothing launched)
+                    if fused:
+                        raise
+        _awq_routes["chain"] += 1
+        ws = _ops.scale_channels(wc, sc, -1, False, wc.dtype)
+        wq = dynamic_fixed_qdq(ws, fmt, "per_group", group_size, symmetric_qscheme=sym)
+        d = _ops.scale_channels(wq, sc, -1, True, torch.float32) - wc.float()
+        return (d, wq) if return_wq else d
+
+
+class _full_fp32_matmul:
+    """float32 GEMMs in full precision inside the block (no TF32 or other reduced-precision mode), the setting restored on exit"""
+
+    def __enter__(self):
+        self.prev = torch.backends.cuda.matmul.allow_tf32
+        torch.backends.cuda.matmul.allow_tf32 = False
+
+    def __exit__(self, *exc):
+        torch.backends.cuda.matmul.allow_tf32 = self.prev
+
+
+def awq_search(w, gram, scales, error_fn):
+    """The AWQ search over candidate scales: for every row s_k of `scales` (float32 [n_grid, in]) the error
+    D_k = error_fn(k, s_k) (float32 [out, in]: Q(w s_k) / s_k - w, e.g. awq_scaled_error) is weighed by the calibration inputs' second
+    moment `gram` (float32 [in, in], the mean of x^T x over the tokens):
+        loss_k = sum((D_k @ gram) * D_k) / out        -- the mean squared output error over the calibration tokens
+    with the GEMM in full float32 and the final sum in float64.  Returns (losses float64 [n_grid], best 0-d int64), both on the device:
+    best is the argmin over the finite losses, 0 when none is finite.  Nothing is read back to the host.
+    ValueError before any GPU use: shapes of w, gram and scales that do not belong together."""
+    if not isinstance(w, torch.Tensor) or w.dim() != 2:
+        raise ValueError("awq_search: the weight must be an [out, in] matrix")
+    out_f, in_f = w.shape
+    if not isinstance(gram, torch.Tensor) or gram.shape != (in_f, in_f) or gram.dtype != torch.float32:
+        raise ValueError(f"awq_search: gram must be a float32 [{in_f}, {in_f}] matrix, got "
+                         f"{getattr(gram, 'dtype', type(gram))} {tuple(getattr(gram, 'shape', ()))}")
+    if not isinstance(scales, torch.Tensor) or scales.dim() != 2 or scales.shape[1] != in_f or scales.shape[0] < 1 or scales.dtype != torch.float32:
+        raise ValueError(f"awq_search: scales must be a float32 [n_grid, {in_f}] matrix with at least one row, got "
+                         f"{getattr(scales, 'dtype', type(scales))} {tuple(getattr(scales, 'shape', ()))}")
+    if out_f < 1:
+        raise ValueError("awq_search: the weight has no rows")
+    require_gpu(w, "awq_search")
+    require_gpu(gram, "awq_search")
+    require_gpu(scales, "awq_search")
+    with torch.no_grad(), _full_fp32_matmul():
+        losses = torch.empty(scales.shape[0], dtype=torch.float64, device=w.device)
+        for k in range(scales.shape[0]):
+            d = error_fn(k, scales[k])
+            if d.shape != w.shape or d.dtype != torch.float32:
+                raise ValueError(f"awq_search: error_fn must return a float32 {tuple(w.shape)} tensor, got {d.dtype} {tuple(d.shape)}")
+            losses[k] = ((d @ gram) * d).sum(dtype=torch.float64) / out_f
+        finite = torch.isfinite(losses)
+        best = torch.where(finite, losses, torch.full_like(losses, float("inf"))).argmin()
+        best = torch.where(finite.any(), best, torch.zeros_like(best))
+        return losses, best

@@ -86,6 +86,9 @@ SIGNATURES = {
     "dmxq_channel_sumsq_accumulate": [_vp, _i32, _i64, _i64, _vp, _vp, _vp],
     "dmxq_wanda_class": [_i32, _i64, _i32],
     "dmxq_wanda_nm": [_vp, _i32, _vp, _vp, _vp, _i32, _vp, _i32, _i64, _i64, _i32, _i32, _vp],
+    "dmxq_channel_sumabs_accumulate": [_vp, _i32, _i64, _i64, _vp, _vp, _vp],
+    "dmxq_awq_class": [_i32, _i64, _i64],
+    "dmxq_awq_group_error": [_vp, _i32, _vp, _vp, _vp, _i64, _i64, _i64, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp],
     "dmxq_row_class_of": [_i32, _i32, _i32, _i32, _i64, _i64, _vp, _vp, _vp, _vp, _i32, _i64, _vp],
 }
 

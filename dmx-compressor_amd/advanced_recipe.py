@@ -6,7 +6,7 @@ from typing import Callable, Optional
 
 from .nn import DmxModule
 
-__all__ = ["DmxBaseRecipe", "DmxQuantizerCalibrationRecipe", "DmxSmoothQuantRecipe", "DmxGPTQRecipe", "DmxWandaRecipe"]
+__all__ = ["DmxBaseRecipe", "DmxQuantizerCalibrationRecipe", "DmxSmoothQuantRecipe", "DmxGPTQRecipe", "DmxWandaRecipe", "DmxAWQRecipe"]
 
 
 class DmxBaseRecipe:
@@ -59,3 +59,13 @@ class DmxWandaRecipe(DmxBaseRecipe):
     def __init__(self, hp_gen, **kwargs):
         super().__init__(hp_gen, **kwargs)
         self.recipe_context_manager = DmxModule.wanda_pruning
+
+
+class DmxAWQRecipe(DmxBaseRecipe):
+    """AWQ scaling (DmxModule.awq_scaling): hp_gen maps the model to {module: DmxAWQHyperparams}; every Linear among them with a
+    smoothquant member and a weight cast gathers its own input statistics while the calibration batches run; on exit it searches its
+    per-input-channel scale and hands it to its SmoothQuant"""
+
+    def __init__(self, hp_gen, **kwargs):
+        super().__init__(hp_gen, **kwargs)
+        self.recipe_context_manager = DmxModule.awq_scaling

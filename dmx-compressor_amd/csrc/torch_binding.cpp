@@ -1078,20 +1078,25 @@ std::tuple<Tensor, Tensor> dynamic_float_qdq_meta(const Tensor& x, int64_t mode,
 // ------------------------------------------------------------------------------------------------ Wanda
 // acc (float64 [C], C = x's last dim) += the sum of squares over every other dim; scratch: dmxq_channel_sumsq_workspace_bytes bytes of
 // any contiguous device tensor
-void channel_sumsq(const Tensor& x, Tensor acc, Tensor scratch) {
-  const Tensor xc = prep(x, "channel_sumsq");
+typedef int (*channel_sum_fn)(const void*, int, int64_t, int64_t, double*, void*, void*);
+void channel_sum(const Tensor& x, Tensor acc, Tensor scratch, channel_sum_fn fn, const char* what);
+void channel_sumsq(const Tensor& x, Tensor acc, Tensor scratch) { channel_sum(x, acc, scratch, dmxq_channel_sumsq_accumulate, "channel_sumsq"); }
+// the |x| twin (AWQ): same checks, same scratch
+void channel_sumabs(const Tensor& x, Tensor acc, Tensor scratch) { channel_sum(x, acc, scratch, dmxq_channel_sumabs_accumulate, "channel_sumabs"); }
+void channel_sum(const Tensor& x, Tensor acc, Tensor scratch, channel_sum_fn fn, const char* what) {
+  const Tensor xc = prep(x, what);
   const int64_t C = xc.dim() ? xc.size(-1) : 1, rows = C ? xc.numel() / C : 0;
   TORCH_CHECK(acc.is_cuda() && acc.device() == xc.device() && acc.scalar_type() == at::kDouble && acc.is_contiguous() && acc.numel() == C,
-              "channel_sumsq: acc must be a contiguous float64 tensor of ", C, " entries on the input's device");
+              what, ": acc must be a contiguous float64 tensor of ", C, " entries on the input's device");
   const int64_t need = dmxq_channel_sumsq_workspace_bytes(rows, C);
   TORCH_CHECK(scratch.is_cuda() && scratch.device() == xc.device() && scratch.is_contiguous() &&
               (int64_t)(scratch.numel() * scratch.element_size()) >= need && (uintptr_t)scratch.data_ptr() % 8 == 0,
-              "channel_sumsq: scratch must be a contiguous 8-byte aligned tensor of at least ", need, " bytes on the input's device");
+              what, ": scratch must be a contiguous 8-byte aligned tensor of at least ", need, " bytes on the input's device");
   Launch l(xc);
-  check(dmxq_channel_sumsq_accumulate(xc.data_ptr(), dt_code(xc.scalar_type()), rows, C, (double*)acc.data_ptr(), scratch.data_ptr(), l.stream),
-        "dmxq_channel_sumsq_accumulate");
+  check(fn(xc.data_ptr(), dt_code(xc.scalar_type()), rows, C, (double*)acc.data_ptr(), scratch.data_ptr(), l.stream), what);
 }
 void channel_sumsq_meta(const Tensor&, Tensor, Tensor) {}
+void channel_sumabs_meta(const Tensor&, Tensor, Tensor) {}
 
 // -> (score float32, mask, y): an output that was not requested comes back as an empty 1-d tensor
 std::tuple<Tensor, Tensor, Tensor> wanda_nm(const Tensor& w, const Tensor& act_norm, int64_t K, int64_t M, bool want_score, bool want_mask,
@@ -1115,6 +1120,27 @@ std::tuple<Tensor, Tensor, Tensor> wanda_nm_meta(const Tensor& w, const Tensor&,
   return std::make_tuple(want_score ? empty_like_shape(w, at::kFloat) : at::empty({0}, w.options().dtype(at::kFloat)),
                          want_mask ? empty_like_shape(w, mask_dtype.value_or(at::kFloat)) : none_like(w),
                          want_y ? empty_like_shape(w, y_dtype.value_or(at::promote_types(w.scalar_type(), at::kFloat))) : none_like(w));
+}
+
+// ------------------------------------------------------------------------------------------------ AWQ
+// -> (d float32, wq in w's dtype): wq comes back as an empty 1-d tensor when it was not requested
+std::tuple<Tensor, Tensor> awq_group_error(const Tensor& w, const Tensor& s, int64_t group, int64_t precision, int64_t fraction, bool clamp,
+                                           bool symmetric, int64_t qmin, int64_t qmax, bool symmetric_qscheme, bool want_wq) {
+  const Tensor wc = prep(w, "awq_group_error");
+  TORCH_CHECK(wc.dim() == 2, "awq_group_error: the weight must be a [rows, L] matrix");
+  TORCH_CHECK(s.is_cuda() && s.device() == wc.device() && s.scalar_type() == at::kFloat && s.is_contiguous() && s.numel() == wc.size(1),
+              "awq_group_error: s must be a contiguous float32 tensor of ", wc.size(1), " entries on the weight's device");
+  Tensor d = empty_like_shape(wc, at::kFloat);
+  Tensor wq = want_wq ? empty_like_shape(wc, wc.scalar_type()) : none_like(wc);
+  Launch l(wc);
+  check(dmxq_awq_group_error(wc.data_ptr(), dt_code(wc.scalar_type()), (const float*)s.data_ptr(), (float*)d.data_ptr(),
+                             want_wq ? wq.data_ptr() : nullptr, wc.size(0), wc.size(1), group, (int)precision, (int)fraction, clamp, symmetric,
+                             (int)qmin, (int)qmax, symmetric_qscheme, l.stream), "dmxq_awq_group_error");
+  return std::make_tuple(d, wq);
+}
+std::tuple<Tensor, Tensor> awq_group_error_meta(const Tensor& w, const Tensor&, int64_t, int64_t, int64_t, bool, bool, int64_t, int64_t, bool,
+                                                bool want_wq) {
+  return std::make_tuple(empty_like_shape(w, at::kFloat), want_wq ? empty_like_shape(w, w.scalar_type()) : none_like(w));
 }
 
 }  // namespace
@@ -1173,6 +1199,8 @@ TORCH_LIBRARY(dmxq, m) {
   m.def("dynamic_float_qdq(Tensor x, int mode, int segment, int man, int exp, int bias, bool flush_subnormal, int rounding, bool pow2_scale, bool want_scale, ScalarType? out_dtype=None) -> (Tensor, Tensor)");
   m.def("channel_sumsq(Tensor x, Tensor(a!) acc, Tensor(b!) scratch) -> ()");
   m.def("wanda_nm(Tensor w, Tensor act_norm, int K, int M, bool want_score, bool want_mask, bool want_y, ScalarType? mask_dtype=None, ScalarType? y_dtype=None) -> (Tensor, Tensor, Tensor)");
+  m.def("channel_sumabs(Tensor x, Tensor(a!) acc, Tensor(b!) scratch) -> ()");
+  m.def("awq_group_error(Tensor w, Tensor s, int group, int precision, int fraction, bool clamp, bool symmetric, int qmin, int qmax, bool symmetric_qscheme, bool want_wq) -> (Tensor, Tensor)");
 }
 
 #define DMXQ_IMPL(m, name) m.impl(#name, &name)
@@ -1183,7 +1211,7 @@ TORCH_LIBRARY(dmxq, m) {
   X(m, histc); X(m, channel_maxabs); X(m, smoothquant_scale); X(m, scale_channels); X(m, unary); X(m, rope); X(m, rope_cast); X(m, softmax); X(m, norm); \
   X(m, unary_cast); X(m, unary_cast_table); X(m, lut16_apply); X(m, softmax_cast); X(m, norm_cast); X(m, group_minmax_accumulate); X(m, gptq_block); X(m, hist_observe); X(m, hist_qparams); \
   X(m, error_stats); X(m, cast_error); X(m, hadamard_qdq); X(m, dynamic_fixed_qdq); X(m, gptq_block_dynamic); X(m, dynamic_float_qdq); \
-  X(m, channel_sumsq); X(m, wanda_nm)
+  X(m, channel_sumsq); X(m, wanda_nm); X(m, channel_sumabs); X(m, awq_group_error)
 
 // "CUDA" is the dispatch key of HIP tensors in a ROCm build of PyTorch
 TORCH_LIBRARY_IMPL(dmxq, CUDA, m) {

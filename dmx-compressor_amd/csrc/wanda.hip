@@ -42,7 +42,18 @@ constexpr int kSumsqRowsInFlight = 16;
 // one rounding, which is what x.double().pow(2) summed row by row does.  16 rows are loaded before the first is used (raw vectors:
 // four registers a row; widened when they are added).  Consecutive waves take neighbouring column tiles of the same slab, so a
 // workgroup reads four contiguous kilobytes of every row.
-template <int DT, int VEC>
+//
+// TERM: what a row adds to its channel -- the one kernel body serves dmxq_channel_sumsq_accumulate (the square: Wanda) and
+// dmxq_channel_sumabs_accumulate (|x|, exact in a double as well: AWQ, csrc/awq.hip), with the same partition, order and lane forms.
+constexpr int kTermSquare = 0, kTermAbs = 1;
+template <int TERM>
+__device__ __forceinline__ double channel_term_add(float x, double acc) {
+  const double d = (double)x;
+  if constexpr (TERM == kTermAbs) return acc + __builtin_fabs(d);
+  else return __builtin_fma(d, d, acc);
+}
+
+template <int DT, int VEC, int TERM>
 __global__ __launch_bounds__(kThreads) void channel_sumsq_slab_kernel(const void* __restrict__ in, int64_t rows, int64_t C, int64_t n_cols /* lane-columns */,
                                                                       int64_t n_tiles, int64_t rows_per_slab, int64_t n_slabs,
                                                                       double* __restrict__ partial) {
@@ -65,10 +76,7 @@ __global__ __launch_bounds__(kThreads) void channel_sumsq_slab_kernel(const void
         if (r + u < r1) x[u] = load1<DT>(in, (r + u) * C + c0);   // (wave-uniform condition)
 #pragma unroll
       for (int u = 0; u < kSumsqRowsInFlight; u++)
-        if (r + u < r1) {
-          const double d = (double)x[u];
-          acc[0] = __builtin_fma(d, d, acc[0]);
-        }
+        if (r + u < r1) acc[0] = channel_term_add<TERM>(x[u], acc[0]);
     } else {
       u32x4 raw[kSumsqRowsInFlight];
 #pragma unroll
@@ -80,10 +88,7 @@ __global__ __launch_bounds__(kThreads) void channel_sumsq_slab_kernel(const void
           float x[VEC];
           widen<DT, VEC>(raw[u], x);
 #pragma unroll
-          for (int k = 0; k < VEC; k++) {
-            const double d = (double)x[k];
-            acc[k] = __builtin_fma(d, d, acc[k]);
-          }
+          for (int k = 0; k < VEC; k++) acc[k] = channel_term_add<TERM>(x[k], acc[k]);
         }
     }
   }
@@ -199,7 +204,8 @@ extern "C" int64_t dmxq_channel_sumsq_workspace_bytes(int64_t rows, int64_t C) {
   return sumsq_plan(rows, C).n_slabs * C * (int64_t)sizeof(double);
 }
 
-extern "C" int dmxq_channel_sumsq_accumulate(const void* in, int dtype_in, int64_t rows, int64_t C, double* acc, void* workspace, void* stream) {
+template <int TERM>
+static int channel_sum_accumulate(const void* in, int dtype_in, int64_t rows, int64_t C, double* acc, void* workspace, void* stream) {
   if (!valid_dtype(dtype_in) || rows < 0 || C < 0) return DMXQ_ERR_BAD_ARG;
   if (rows == 0 || C == 0) return DMXQ_OK;
   if (!in || !acc || !workspace) return DMXQ_ERR_BAD_ARG;
@@ -213,7 +219,7 @@ extern "C" int dmxq_channel_sumsq_accumulate(const void* in, int dtype_in, int64
   const int64_t blocks = (n_tiles * p.n_slabs + kThreads / kWave - 1) / (kThreads / kWave);
   const int64_t fold_blocks = (C + kFoldChannels - 1) / kFoldChannels;
   if (blocks > 0x7FFFFFFF || fold_blocks > 0x7FFFFFFF) return DMXQ_ERR_UNSUPPORTED;
-#define DMXQ_SUMSQ(D_, V_) DMXQ_LAUNCH((channel_sumsq_slab_kernel<D_, V_>), dim3((unsigned)blocks), dim3(kThreads), 0, s, in, rows, C, n_cols, n_tiles, p.rows_per_slab, p.n_slabs, partial)
+#define DMXQ_SUMSQ(D_, V_) DMXQ_LAUNCH((channel_sumsq_slab_kernel<D_, V_, TERM>), dim3((unsigned)blocks), dim3(kThreads), 0, s, in, rows, C, n_cols, n_tiles, p.rows_per_slab, p.n_slabs, partial)
   if (vec_ok) {
     if (dtype_in == DMXQ_F32) DMXQ_SUMSQ(DMXQ_F32, 4);
     else if (dtype_in == DMXQ_F16) DMXQ_SUMSQ(DMXQ_F16, 8);
@@ -226,6 +232,15 @@ extern "C" int dmxq_channel_sumsq_accumulate(const void* in, int dtype_in, int64
 #undef DMXQ_SUMSQ
   DMXQ_LAUNCH(channel_sumsq_fold_kernel, dim3((unsigned)fold_blocks), dim3(kThreads), 0, s, partial, C, p.n_slabs, acc);
   return launch_status();
+}
+
+extern "C" int dmxq_channel_sumsq_accumulate(const void* in, int dtype_in, int64_t rows, int64_t C, double* acc, void* workspace, void* stream) {
+  return channel_sum_accumulate<kTermSquare>(in, dtype_in, rows, C, acc, workspace, stream);
+}
+
+// the |x| twin (AWQ's per-channel mean magnitude): dmxq_channel_sumsq_workspace_bytes(rows, C) is its workspace query too
+extern "C" int dmxq_channel_sumabs_accumulate(const void* in, int dtype_in, int64_t rows, int64_t C, double* acc, void* workspace, void* stream) {
+  return channel_sum_accumulate<kTermAbs>(in, dtype_in, rows, C, acc, workspace, stream);
 }
 
 // 1: dmxq_wanda_nm takes (dtype_w, L, M) in its one-pass kernel (given 16-byte aligned pointers), 0: it refuses them.  One rule

@@ -21,7 +21,7 @@ import torch.nn.functional as F
 
 from ._lib import DmxqError
 
-__all__ = ["OptimalBrainCompressor", "WandaCalibrator"]
+__all__ = ["OptimalBrainCompressor", "WandaCalibrator", "AWQCalibrator"]
 
 
 def refuse_scaled_weight_cast(module):
@@ -478,3 +478,122 @@ class WandaCalibrator:
             sp._mask, sp._mask_pending = None, True   # (read again from the new score)
         m.__dict__.pop("_live_weight", None)   # (a LiveWeightBatch result computed with the old score)
         m.wanda_act_norm, m.wanda_sumsq, m.wanda_n_tokens = act_norm, self.sumsq, self.n_tokens
+
+
+# ---------------------------------------------------------------------------------------------------- AWQ
+def awq_applies(module) -> bool:
+    """AWQ acts on a Linear with a 2-D weight, a smoothquant member and a weight cast other than SAME; on anything else nothing happens"""
+    from .format import Same
+    wc = getattr(module, "weight_cast", None)
+    return (isinstance(module, torch.nn.Linear) and getattr(module, "weight", None) is not None and module.weight.dim() == 2
+            and getattr(module, "smoothquant", None) is not None and wc is not None and not isinstance(wc.format, Same))
+
+
+def refuse_awq(module):
+    """the configurations AWQ does not support, as a DmxqError before any state is touched"""
+    sq = module.smoothquant
+    if sq._flag("fused_to_weight"):
+        raise DmxqError("AWQ on a module whose SmoothQuant scale has been fused to the weight already is not supported: the search would "
+                        "scale an already scaled weight; start from the unfused weight (a fresh module or its original state_dict)")
+    if sq._flag("enabled"):
+        raise DmxqError("AWQ with SmoothQuant enabled is not supported: the search writes the scale SmoothQuant already holds; disable it "
+                        "first (smoothquant.disable()), AWQ enables it again with its own scale")
+    if sq._flag("dynamic"):
+        raise DmxqError("AWQ with a dynamic SmoothQuant is not supported: every forward would overwrite the searched scale; switch it off "
+                        "first (smoothquant.set_dynamic(False))")
+    if sq.calibrating:
+        raise DmxqError("AWQ inside a SmoothQuant calibration is not supported: both write smoothquant.scale; leave calibrating_smoothquant "
+                        "first")
+    if sq.process_group is not None:
+        raise DmxqError("AWQ on a sharded module (smoothquant.set_process_group) is not supported: the candidates' losses would need an "
+                        "all-reduce; run the search on the whole weight, or clear the group (set_process_group(None))")
+
+
+class AWQCalibrator:
+    """AWQ (Lin et al., 2023): while DmxModule.awq_scaling is active, `observe` adds every forward's per-input-channel
+    sum of |x| into a float64 [in] device vector (one ops.channel_sumabs call) and folds x^T x into a float32 [in, in] running mean over
+    the tokens (one addmm_), counting the tokens on the host -- nothing is read back; `apply` forms the candidate scales from the mean
+    magnitudes, measures each candidate's output error with the module's own weight cast (ops.awq_search), and hands the best one to
+    the module's SmoothQuant, which carries it from there on.  The weight itself is not modified (unless fuse_to_weight asks for it)."""
+
+    def __init__(self, module, hyperparams, sumabs=None, gram=None, n_tokens: int = 0):
+        self.module = module
+        self.hyperparams = hyperparams
+        self.sumabs, self.gram = sumabs, gram
+        self.n_tokens = int(n_tokens)
+
+    def observe(self, inp):
+        from . import ops
+        C = inp.shape[-1]
+        t = inp.numel() // C if C else 0
+        if t == 0:
+            return
+        if self.sumabs is None or self.sumabs.device != inp.device:
+            prev, prev_g = self.sumabs, self.gram
+            self.sumabs = torch.zeros(C, dtype=torch.float64, device=inp.device)
+            self.gram = torch.zeros(C, C, dtype=torch.float32, device=inp.device)
+            if prev is not None:
+                self.sumabs += prev.to(inp.device)
+                self.gram += prev_g.to(inp.device)
+        with torch.no_grad():
+            x = inp.detach()
+            ops.channel_sumabs(x, out=self.sumabs)
+            n = self.n_tokens
+            x = x.reshape(-1, C).float() * (1.0 / math.sqrt(n + t))
+            self.gram *= n / (n + t)
+            with ops._front._full_fp32_matmul():
+                self.gram.addmm_(x.t(), x)
+        self.n_tokens = n + t
+
+    def _kernel_plan(self):
+        """(format, group size, symmetric_qscheme) when a candidate's error is ops.awq_scaled_error by definition of the module's stages --
+        a nearest-rounding dynamic per_group integer weight cast that runs as such, without pre_transform, behind a SAME storage cast --
+        else None: the stages themselves run"""
+        from .cast import _SYMMETRIC
+        from .format import FixedPoint, Same
+        m = self.module
+        wc, st = m.weight_cast, m.weight_storage_cast
+        if wc._dynamic is None or wc._dynamic[0] != "per_group" or not isinstance(wc.format, FixedPoint) or wc.format.rounding != "nearest":
+            return None
+        if not wc._flag("fake_quant_enabled") or wc._flag("observer_enabled") or wc.pre_transform:
+            return None
+        if st is not None and not (isinstance(st.format, Same) and not st.pre_transform):
+            return None
+        return wc.format, wc._dynamic[1], wc.qscheme in _SYMMETRIC
+
+    def apply(self):
+        from . import ops
+        m = self.module
+        sq = m.smoothquant
+        if self.n_tokens == 0:
+            raise RuntimeError("AWQ: no calibration token was observed inside awq_scaling (run at least one forward of the module); "
+                               "the scale is left as it was")
+        with torch.no_grad():
+            E = m.effective_weight.detach()
+            E = E if E.is_contiguous() else E.contiguous()
+            x_mean = (self.sumabs.to(E.device) / self.n_tokens).to(torch.float32)
+            scales = ops.awq_candidate_scales(x_mean, self.hyperparams.n_grid, sq.scale_cast)
+            plan = self._kernel_plan()
+            if plan is not None and (E.dtype not in (torch.float32, torch.float16, torch.bfloat16) or E.shape[1] % plan[1]):
+                plan = None
+            if plan is not None:
+                fmt, g, sym = plan
+                error_fn = lambda k, s: ops.awq_scaled_error(E, s, fmt, g, symmetric_qscheme=sym)
+            else:
+                E32 = E.float()
+
+                def error_fn(k, s):   # the module's own stages, as weight_hypernet runs them behind the sparsifier
+                    wq = ops.scale_channels(E, s, sq.win_ch_axis, False, E.dtype)
+                    if m.weight_storage_cast is not None:
+                        wq = m.weight_storage_cast(wq)
+                    wq = m.weight_cast(wq)
+                    return ops.scale_channels(wq, s, sq.win_ch_axis, True, torch.float32) - E32
+
+            losses, best = ops.awq_search(E, self.gram.to(E.device), scales, error_fn)
+            sq.scale = scales.index_select(0, best.reshape(1))[0].clone()
+        sq.enable(True)
+        if self.hyperparams.fuse_to_weight:
+            sq.fuse_to_weight(m.weight)
+        m.__dict__.pop("_live_weight", None)   # (a LiveWeightBatch result computed without the scale)
+        m.awq_losses, m.awq_best, m.awq_x_mean, m.awq_n_tokens = losses, best, x_mean, self.n_tokens
+        m.awq_sumabs, m.awq_gram = self.sumabs, self.gram

@@ -27,7 +27,7 @@ from .smoothquant import ActivationWeightSmoothQuant
 from .sparse import Dense, Sparsify
 
 __all__ = ["DmxModule", "DmxQuantizerCalibrationHyperparams", "DmxModuleQuantizerCalibrationHyperparams",
-           "DmxModuleSmoothQuantHyperparams", "DmxModuleGPTQHyperparams", "DmxWandaHyperparams", "Linear", "Conv1d", "Conv2d", "ResAdd", "ActActMatMul", "Softmax", "LayerNorm", "GELU", "ReLU", "SiLU", "QuickGELU", "Exp", "Mul", "RMSNorm", "ApplyRotaryPosEmb",
+           "DmxModuleSmoothQuantHyperparams", "DmxModuleGPTQHyperparams", "DmxWandaHyperparams", "DmxAWQHyperparams", "Linear", "Conv1d", "Conv2d", "ResAdd", "ActActMatMul", "Softmax", "LayerNorm", "GELU", "ReLU", "SiLU", "QuickGELU", "Exp", "Mul", "RMSNorm", "ApplyRotaryPosEmb",
            "MaxPool2d", "AvgPool2d", "Embedding", "ReLU6", "Tanh", "Dropout", "NewGELU", "FastGELU", "BloomGELU", "ClippedGELU", "AdaptiveAvgPool2d",
            "BatchNorm2d", "GroupNorm", "ConvTranspose2d", "BAddBMM", "ScaledDotProductAttention", "DmxConfigRule", "configure_model",
            "fold_weights_and_biases", "GraphedForward", "LiveWeightBatch", "link_consumer", "link_consumers_from_fx", "DmxTracer"]
@@ -96,6 +96,27 @@ class DmxWandaHyperparams:
             raise TypeError(f"DmxWandaHyperparams: reset must be a bool, got {self.reset!r}")
 
 
+@dataclass
+class DmxAWQHyperparams:
+    """AWQ scaling (DmxModule.awq_scaling; not in the reference).  n_grid: the number of candidate scale vectors, x_mean ** (k / n_grid)
+    for k = 0 .. n_grid - 1 (candidate 0 is plain round-to-nearest); fuse_to_weight: fold the chosen scale into the weight on leaving
+    the context (SmoothQuant's fuse_to_weight); reset: entering the context zeroes the statistics of an earlier context (False: the
+    sums, the second moment and the token count continue from where the last context left them)"""
+    n_grid: int = 20
+    fuse_to_weight: bool = False
+    reset: bool = True
+
+    def __post_init__(self):
+        if isinstance(self.n_grid, bool) or not isinstance(self.n_grid, int):
+            raise TypeError(f"DmxAWQHyperparams: n_grid must be an int, got {self.n_grid!r}")
+        if not 1 <= self.n_grid <= 1024:
+            raise ValueError(f"DmxAWQHyperparams: n_grid must lie in 1 .. 1024, got {self.n_grid}")
+        if not isinstance(self.fuse_to_weight, bool):
+            raise TypeError(f"DmxAWQHyperparams: fuse_to_weight must be a bool, got {self.fuse_to_weight!r}")
+        if not isinstance(self.reset, bool):
+            raise TypeError(f"DmxAWQHyperparams: reset must be a bool, got {self.reset!r}")
+
+
 def _shares_storage(a, b) -> bool:
     if not (isinstance(a, torch.Tensor) and isinstance(b, torch.Tensor)):
         return False
@@ -135,6 +156,12 @@ class DmxModule(FastAttr, torch.nn.Module):
     wanda = None
     wanda_act_norm = wanda_sumsq = None
     wanda_n_tokens = 0
+    #: the AWQCalibrator while `awq_scaling` is active (layer_reconstruction.py), else None; after a context the candidates' losses
+    #: (float64 [n_grid]) and the chosen index (0-d int64), both on the device, the fp32 mean magnitudes, the token count and the
+    #: statistics behind them stay as plain attributes (no buffer, no state_dict key)
+    awq = None
+    awq_losses = awq_best = awq_x_mean = awq_sumabs = awq_gram = None
+    awq_n_tokens = 0
 
     def _dmx_init(self, n_inputs: int = 1, input_names=("input_cast",), sparsifiable: bool = False):
         pnames = [n for n, _ in self.named_parameters(recurse=False)]
@@ -493,6 +520,34 @@ class DmxModule(FastAttr, torch.nn.Module):
         yield self
         self.enable_wanda(False, hyperparams)
 
+    def enable_awq(self, state: bool, hyperparams=None) -> None:
+        """AWQ: on a Linear with a 2-D weight, a smoothquant member and a weight cast other than SAME (any other module:
+        nothing happens).  Entering starts observing the inputs as `_forward` receives them (after the input casts, whose switches
+        stay as they are); leaving searches the per-input-channel scale that minimises the weight cast's output error on those inputs
+        and hands it to `smoothquant` (scale set, enabled; fused to the weight if the hyper-parameters ask for it).  Neither the weight
+        nor `migration_strength` is touched."""
+        from .layer_reconstruction import AWQCalibrator, awq_applies, refuse_awq
+        if hyperparams is None:
+            hyperparams = DmxAWQHyperparams()
+        if not isinstance(hyperparams, DmxAWQHyperparams):
+            raise TypeError(f"awq_scaling takes a DmxAWQHyperparams, got {type(hyperparams).__name__}")
+        if state:
+            if not awq_applies(self):
+                return
+            refuse_awq(self)   # (before any state is touched)
+            keep = not hyperparams.reset and self.awq_sumabs is not None
+            self.awq = AWQCalibrator(self, hyperparams, self.awq_sumabs.clone() if keep else None, self.awq_gram.clone() if keep else None,
+                                     self.awq_n_tokens if keep else 0)
+        elif self.awq is not None:
+            awq, self.awq = self.awq, None
+            awq.apply()
+
+    @contextmanager
+    def awq_scaling(self, hyperparams=None):
+        self.enable_awq(True, hyperparams)
+        yield self
+        self.enable_awq(False, hyperparams)
+
     #: GPTQ's in-block column loop as one csrc/gptq.hip launch per column block when the weight format allows (False: the reference's
     #: per-microblock loop, for A/B comparisons)
     fuse_gptq = True
@@ -723,6 +778,8 @@ class DmxModule(FastAttr, torch.nn.Module):
             self.obc.measure_hessian(_input)
         if self.wanda is not None:
             self.wanda.observe(_input)
+        if self.awq is not None:
+            self.awq.observe(_input)
         _output = self._forward(_input, *args, **kwargs)
         # (a GEMM-bearing module's output cast is a launch of its own; when the linked consumer applies the SAME cast to this value as
         #  its first input cast -- inside its fused kernel -- the cast here is redundant: FloatingPoint casts are projections)

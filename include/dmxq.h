@@ -56,7 +56,7 @@ const char* dmxq_status_string(int status);
 /* ABI version: bumped on any signature change.  Additions since 4 (dmxq_gptq_block, dmxq_hist_observe, dmxq_hist_qparams, dmxq_error_stats, dmxq_cast_error,
  * dmxq_error_scratch_bytes, dmxq_hadamard_qdq, dmxq_dynamic_fixed_qdq, dmxq_dynamic_class, dmxq_gptq_block_dynamic,
  * dmxq_dynamic_float_qdq, dmxq_dynamic_float_class, dmxq_channel_sumsq_accumulate, dmxq_channel_sumsq_workspace_bytes, dmxq_wanda_nm,
- * dmxq_wanda_class, dmxq_row_class_of) leave it at 4: a caller built against 4 runs on
+ * dmxq_wanda_class, dmxq_row_class_of, dmxq_channel_sumabs_accumulate, dmxq_awq_group_error, dmxq_awq_class) leave it at 4: a caller built against 4 runs on
  * this library unchanged.  4 = round 5: + dmxq_float_qdq_multi, dmxq_fixed_float_qdq_multi; 3 = round 4: + dmxq_weight_hypernet_multi,
  * dmxq_unary_cast_table, dmxq_lut16_apply.  Nothing was ever removed or changed: a caller built against version n runs on any library >= n. */
 int dmxq_abi_version(void);
@@ -611,6 +611,31 @@ int dmxq_channel_sumsq_accumulate(const void* in, int dtype_in, int64_t rows, in
 int dmxq_wanda_class(int dtype_w, int64_t L, int M);
 int dmxq_wanda_nm(const void* w, int dtype_w, const float* act_norm, float* score_out, void* mask_out, int dtype_mask, void* y_out,
                   int dtype_y, int64_t rows, int64_t L, int K, int M, void* stream);
+
+/* AWQ (Lin et al., 2023): activation-aware weight scaling searched on the device (csrc/awq.hip, csrc/wanda.hip; DESIGN.md §8 "AWQ").
+ * Not in the reference.  The search evaluates, for candidate per-input-channel scale vectors s, the error D = Q(W s) / s - W of the
+ * module's own weight cast against the calibration inputs' second moment.
+ *
+ * dmxq_channel_sumabs_accumulate: the |x| twin of dmxq_channel_sumsq_accumulate -- acc[c] += sum over the rows of (double)|x|, one
+ * kernel body with the per-element term as a template argument: the same workspace query (dmxq_channel_sumsq_workspace_bytes), slab
+ * partition, summation order, vector / scalar lane forms and status codes.  Capturable.
+ *
+ * dmxq_awq_group_error: ONE candidate in ONE launch over the contiguous weight w[rows, L] of dtype_w; s: DEVICE float32 [L].  Per
+ * element, with column = element index mod L:
+ *   ws = dtype_w(fp32(w) * s[column])  ->  wq = the per-group dynamic integer cast of dmxq_dynamic_fixed_qdq on ws (groups of `group`
+ *   consecutive elements, nearest rounding, (qmin, qmax, symmetric_qscheme) as there; the same device code), one rounding to dtype_w
+ *   ->  d = fp32(wq) / s[column] - fp32(w), one IEEE division and one subtraction in fp32.
+ * d_out: float32 [rows, L], required; wq_out: dtype_w [rows, L] or NULL.  Bit for bit the four-launch chain dmxq_scale_channels
+ * (multiply, dtype_w) -> dmxq_dynamic_fixed_qdq -> dmxq_scale_channels (divide, float32) -> the subtraction.  A lane owns four
+ * consecutive elements (the float32 side moves as 16 bytes per lane); a group is group / 4 adjacent lanes.
+ * dmxq_awq_class(dtype_w, L, group): 1 where the kernel takes the geometry -- group a power of two from 16 to 256 that divides L --
+ * else 0; a host function, no GPU involved.  DMXQ_ERR_UNSUPPORTED, nothing launched (the caller runs the chain, same bits): class 0,
+ * fraction != 0, no clamp, precision > 22, a pointer that is not 16-byte aligned.  DMXQ_ERR_BAD_ARG: invalid dtype, negative sizes,
+ * qmax <= qmin, null w / s / d_out.  No workspace, no allocation, no host synchronisation. */
+int dmxq_channel_sumabs_accumulate(const void* in, int dtype_in, int64_t rows, int64_t C, double* acc, void* workspace, void* stream);
+int dmxq_awq_class(int dtype_w, int64_t L, int64_t group);
+int dmxq_awq_group_error(const void* w, int dtype_w, const float* s, float* d_out, void* wq_out, int64_t rows, int64_t L, int64_t group,
+                         int precision, int fraction, int clamp, int symmetric, int qmin, int qmax, int symmetric_qscheme, void* stream);
 
 /* Which kernel a row function launches (csrc/row_class.hpp): what dmxq_softmax* / dmxq_layernorm* / dmxq_rmsnorm* will do for one call,
  * answered by the function their dispatch itself decides with.  A host function: no GPU involved, no HIP call, the pointers are not
