@@ -950,3 +950,37 @@ def awq_group_error(w, s, group, precision, fraction, clamp, symmetric, qmin, qm
                                      precision, fraction, int(bool(clamp)), int(bool(symmetric)), qmin, qmax, int(bool(symmetric_qscheme)),
                                      stream_of(wc)), "dmxq_awq_group_error")
     return d, wq
+
+
+# ------------------------------------------------------------------------------------------------ block-scaled float cast
+@_guarded
+def block_scaled_float_qdq(x, group, fmt, scale_fmt, scale_max, tensor_scale, want_scale, want_code, out_dtype=None):
+    """-> (out, scale, scale_code_value): float32 [n_groups] each, empty unless wanted; fmt / scale_fmt: (man, exp, bias, flush, rounding);
+    tensor_scale: None or ONE float32 on x's device (read by the kernel only)"""
+    xc = _prep(x, "block_scaled_float_qdq")
+    if len(fmt) != 5 or len(scale_fmt) != 5:
+        raise RuntimeError("block_scaled_float_qdq: a format is (man, exp, bias, flush, rounding)")
+    if group < 1 or xc.numel() % group != 0:
+        raise RuntimeError("block_scaled_float_qdq: the group must divide the number of elements")
+    if tensor_scale is not None and not (tensor_scale.is_cuda and tensor_scale.device == xc.device and tensor_scale.dtype == torch.float32
+                                         and tensor_scale.numel() == 1):
+        raise RuntimeError("block_scaled_float_qdq: tensor_scale must be ONE float32 on the input's device")
+    n = xc.numel() // group
+    out = torch.empty(xc.shape, dtype=out_dtype or xc.dtype, device=xc.device)
+    sc = torch.empty(n if want_scale else 0, dtype=torch.float32, device=xc.device)
+    sq = torch.empty(n if want_code else 0, dtype=torch.float32, device=xc.device)
+    check(lib().dmxq_block_scaled_float_qdq(ptr(xc), ptr(out), dtype_code(xc.dtype), dtype_code(out.dtype), n, group, *[int(v) for v in fmt],
+                                            *[int(v) for v in scale_fmt], float(scale_max), ptr(tensor_scale) if tensor_scale is not None else None,
+                                            ptr(sc) if want_scale else None, ptr(sq) if want_code else None, stream_of(xc)),
+          "dmxq_block_scaled_float_qdq")
+    return out, sc, sq
+
+
+@_guarded
+def block_scaled_tensor_scale(x, fmax, scale_max):
+    """-> float32 [1]: (max |x| / fmax) / scale_max over the whole contiguous tensor, 1 where not finite or below 2^-126"""
+    xc = _prep(x, "block_scaled_tensor_scale")
+    t = torch.empty(1, dtype=torch.float32, device=xc.device)
+    check(lib().dmxq_block_scaled_tensor_scale(ptr(xc), dtype_code(xc.dtype), xc.numel(), float(fmax), float(scale_max), ptr(t), stream_of(xc)),
+          "dmxq_block_scaled_tensor_scale")
+    return t

@@ -57,7 +57,9 @@ _FAST_CALIBRATION_NAMES = {"hist_observe": "hist_observe", "hist_qparams": "hist
                            # the dynamic integer cast: straight-through above the raw op as well (cast.py)
                            "dynamic_fixed_qdq": "dynamic_fixed_qdq",
                            # the dynamic scaled float cast: the same
-                           "dynamic_float_qdq": "dynamic_float_qdq"}
+                           "dynamic_float_qdq": "dynamic_float_qdq",
+                           # the block-scaled float cast: the same
+                           "block_scaled_float_qdq": "block_scaled_float_qdq", "block_scaled_tensor_scale": "block_scaled_tensor_scale"}
 FAST = None
 
 

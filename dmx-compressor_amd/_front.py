@@ -25,6 +25,8 @@ __all__ = [
     "dynamic_fixed_qdq", "dynamic_check", "dynamic_class", "DYNAMIC_GRANULARITIES", "DYNAMIC_CHAIN_BY_DEFAULT",
     "dynamic_float_qdq", "dynamic_float_check", "dynamic_float_class", "dynamic_float_fmax", "DYNAMIC_FLOAT_GRANULARITIES",
     "DYNAMIC_FLOAT_CHAIN_BY_DEFAULT",
+    "block_scaled_float_qdq", "block_scaled_tensor_scale", "block_scaled_float_class", "block_scaled_check", "NVFP4",
+    "BLOCK_SCALED_CHAIN_BY_DEFAULT",
     "channel_sumsq", "channel_sumsq_workspace_bytes", "wanda_score", "wanda_nm_sparsify", "wanda_class", "WANDA_CHAIN_BY_DEFAULT",
     "channel_sumabs", "awq_candidate_scales", "awq_scaled_error", "awq_class", "awq_search", "AWQ_CHAIN_BY_DEFAULT",
 ]
@@ -1237,6 +1239,217 @@ def dynamic_float_qdq(x, fmt, granularity: str = "per_token", group_size: Option
         else:
             y = y.reshape(xc.shape)
         return (y, sc) if return_scale else y
+
+    if x.requires_grad and torch.is_grad_enabled():
+        return _DynamicSTE.apply(x, run)
+    with torch.no_grad():
+        return run(x.detach())
+
+
+# ---------------------------------------------------------------------------------------------------- block-scaled float cast
+# Group classes of dmxq_block_scaled_float_qdq (block_scaled_float_class) that fused=None sends to the chain although the kernel takes
+# them: DYNAMIC_FLOAT_CHAIN_BY_DEFAULT's rule -- a class goes to the kernel by default only where tools/bench_block_scaled.py MEASURED it
+# faster than the chain on the same buffers; a class that is not gets listed here with its row.  profiles/r18_block_scaled.txt:
+# (bf16, E4M3 scale capped at 448, us per call, kernel against chain; a dynamic t is reduction plus cast): E2M1 g16 dynamic t [8192,4096]
+# 82.3 against 14165.7; E2M1 g16 static t [8192,4096] 49.6 against 14127.0; E4M3 g128 dynamic t [8192,4096] 66.5 against 2129.7; E4M3 g128
+# static t [8192,4096] 34.1 against 2104.1; E2M1 g16 dynamic t [8192,14336] 194.2 against 49487.9; E2M1 g16 static t [8192,14336] 101.5
+# against 49406.3; E4M3 g128 dynamic t [8192,14336] 179.3 against 7376.7; E4M3 g128 static t [8192,14336] 100.6 against 7360.4; E2M1 g16
+# dynamic t [2048,768] 11.4 against 712.2; E2M1 g16 static t [2048,768] 4.0 against 696.1; E4M3 g128 dynamic t [2048,768] 11.6 against
+# 177.0; E4M3 g128 static t [2048,768] 4.0 against 159.0 -- every row is faster, the class is not listed.
+BLOCK_SCALED_CHAIN_BY_DEFAULT = frozenset()
+# which route the calls of this front end took, counted on the host: private, for the tests (fused=True must have run the kernel)
+_block_scaled_routes = {"fused": 0, "chain": 0}
+#: the ready setting of CastTo.set_scaling / ops.block_scaled_float_qdq for format FP[1|2|1,1](_N): E2M1 elements in groups of 16, an E4M3
+#: group scale capped at 448 (the OCP E4M3FN code range; the library's FP[1|4|3,7] reaches 480), one float32 scale per tensor
+NVFP4 = {"per_group": 16, "scale_format": "FP[1|4|3,7](_N)", "scale_max": 448.0, "tensor_scale": "dynamic"}
+
+
+def block_scaled_check(fmt, group_size, scale_format, scale_max=None, tensor_scale="dynamic", what: str = "block_scaled_float_qdq"):
+    """-> (format, scale format, scale_max) of a block-scaled cast, or ValueError: an element format dynamic_float_check accepts per group;
+    a FloatingPoint scale format with fewer than 8 exponent bits and nearest rounding; 0 < scale_max <= the scale format's largest value
+    (the default); tensor_scale "dynamic", None, a float or a one-element tensor.  No GPU involved."""
+    from .format import FloatingPoint, Format
+    fmt, _, _ = dynamic_float_check(fmt, "per_group", group_size, what=what)
+    sf = Format.from_shorthand(scale_format) if isinstance(scale_format, str) else scale_format
+    if not isinstance(sf, FloatingPoint):
+        raise ValueError(f"{what}: the group scales are quantised to a float format, so scale_format must be a FloatingPoint format "
+                         f"(FP[1|e|m,bias]), got {scale_format!r}")
+    if sf.exponent >= 8:
+        raise ValueError(f"{what}: a scale format with {sf.exponent} exponent bits has fp32's range and no largest value to cap the scale "
+                         f"codes at, got {sf!r}; use ops.dynamic_float_qdq for float32 scales")
+    if sf.rounding != "nearest":
+        raise ValueError(f"{what}: the scale format must round to nearest, got {sf!r}")
+    sfmax = dynamic_float_fmax(sf)
+    if scale_max is None:
+        scale_max = sfmax
+    if isinstance(scale_max, bool) or not isinstance(scale_max, (int, float)) or not (0.0 < float(scale_max) <= sfmax):
+        raise ValueError(f"{what}: scale_max must be a number in (0, {sfmax:g}] (the largest value of {sf!r}), got {scale_max!r}")
+    if not (tensor_scale is None or (isinstance(tensor_scale, str) and tensor_scale == "dynamic")
+            or (isinstance(tensor_scale, (int, float)) and not isinstance(tensor_scale, bool))
+            or (isinstance(tensor_scale, torch.Tensor) and tensor_scale.numel() == 1)):
+        raise ValueError(f"{what}: tensor_scale must be 'dynamic', None, a float or a one-element tensor, got {tensor_scale!r}")
+    return fmt, sf, float(scale_max)
+
+
+def block_scaled_float_class(group_size: int, dtype: torch.dtype) -> Optional[str]:
+    """"group" where dmxq_block_scaled_float_qdq takes groups of `group_size` elements of `dtype` (a power of two from 16 to 256, in
+    adjacent lanes of a wave), None where it refuses them; asked of the library itself (dmxq_block_scaled_float_class; no GPU involved)"""
+    from ._lib import dtype_code, lib
+    return _DYNAMIC_CLASS_NAMES.get(lib().dmxq_block_scaled_float_class(dtype_code(dtype), int(group_size)))
+
+
+def _div_ieee(v, d):
+    """v / d as an IEEE division of a float32 vector by ONE float32 on the device (through scale_channels: torch divides by a Python
+    scalar as a multiplication by its reciprocal)"""
+    n = v.numel()
+    return _ops.scale_channels(v.reshape(n, 1), d.reshape(1), 1, True, torch.float32).reshape(n)
+
+
+def _one(value, device):
+    return torch.full((1,), float(value), dtype=torch.float32, device=device)
+
+
+def _usable_scale(s):
+    return torch.isfinite(s) & (s >= 2.0 ** -126)
+
+
+def _bs_tensor_scale(xc, tensor_scale, fmax, scale_max, native=True):
+    """step 1 of the definition -> float32 [1] on xc's device, already 1 where it is not finite or below 2^-126.  The dynamic t: the
+    library's own small reduction (dmxq_block_scaled_tensor_scale: three launches) where `native` and it takes the tensor (whole aligned
+    16-byte vectors); else -- the chain -- dmxq_group_minmax's whole-tensor reduction (one group over everything: one NaN makes it NaN)
+    and the two divisions as scale_channels launches.  A maximum is exact in any order: the same bits on both routes."""
+    dev = xc.device
+    if tensor_scale is None:
+        return _one(1.0, dev)
+    if isinstance(tensor_scale, str):
+        if native:
+            try:
+                return _ops.block_scaled_tensor_scale(xc, fmax, scale_max)
+            except NotImplementedError:   # (DMXQ_ERR_UNSUPPORTED, nothing launched)
+                pass
+        mn, mx = _ops.group_minmax(xc.reshape(1, -1), 0, 1)
+        t = _div_ieee(_div_ieee(torch.maximum(mn.abs(), mx.abs()), _one(fmax, dev)), _one(scale_max, dev))
+    elif isinstance(tensor_scale, torch.Tensor):
+        t = tensor_scale.detach().reshape(1)
+    else:
+        t = _one(tensor_scale, dev)
+    return torch.where(_usable_scale(t), t, torch.ones_like(t))
+
+
+def block_scaled_tensor_scale(x, fmt, scale_format, scale_max=None):
+    """Step 1 of ops.block_scaled_float_qdq alone, for calibrating a static tensor scale: t = (max |x| / fmax) / scale_max (two IEEE
+    divisions; 1 where that is not finite -- a NaN or Inf anywhere -- or below 2^-126), float32 [1] on x's device, never read back."""
+    fmt, sf, scale_max = block_scaled_check(fmt, 16, scale_format, scale_max, what="block_scaled_tensor_scale")
+    require_gpu(x, "block_scaled_tensor_scale")
+    with torch.no_grad():
+        xc = x.detach()
+        xc = xc if xc.is_contiguous() else xc.contiguous()
+        if xc.numel() == 0:
+            return _one(1.0, xc.device)
+        return _bs_tensor_scale(xc, "dynamic", dynamic_float_fmax(fmt), scale_max)
+
+
+def block_scaled_float_qdq(x, fmt, group_size: int, scale_format, scale_max: Optional[float] = None, tensor_scale="dynamic",
+                           out_dtype: Optional[torch.dtype] = None, return_scale: bool = False, fused: Optional[bool] = None,
+                           seed: Optional[int] = None):
+    """Low-bit float Q->DQ with a QUANTISED scale per group under one float32 scale per tensor (not in the reference): the
+    numerics of a stored block-scaled format -- E2M1 in groups of 16 with an E4M3 scale ("NVFP4": ops.NVFP4), E4M3 with quantised group
+    scales -- where ops.dynamic_float_qdq keeps every scale as a full float32 number.  `fmt`: the element format E, a signed
+    FloatingPoint with fewer than 8 exponent bits and largest output fmax; `scale_format`: the scale format Sf, a FloatingPoint with fewer
+    than 8 exponent bits, nearest rounding and largest output sfmax; 0 < scale_max <= sfmax (default sfmax) caps the scale code (448: an
+    FP[1|4|3,7] scale stays inside the OCP E4M3FN codes); a group is `group_size` consecutive elements of the last dim, which it must
+    divide.  In fp32:
+        t  = the tensor scale: "dynamic" -- (max |x| / fmax) / scale_max over the whole tensor, two IEEE divisions, one NaN anywhere makes
+             the maximum NaN; None -- 1; a float, or a one-element float32 tensor on x's device (never read back); in every case 1 where it
+             is not finite or below 2^-126
+        a  = max |x| over the group (one NaN makes it NaN);  c = (a / fmax) / t, two IEEE divisions
+        sq = min(float_q_Sf(c), scale_max): the scale format's nearest cast, NaN / Inf saturating to sfmax -- never NaN
+        s  = sq * t, one multiply;  usable when finite and >= 2^-126
+        usable: y = float_q_E(x / s) * s -- IEEE quotient, the format's nearest cast (NaN / Inf saturate as in float_qdq), one multiply,
+                one rounding to out_dtype;  else: y = a zero with the sign bit of float_q_E(x) and the reported s is 0 (an all-zero
+                group, or one so far below the tensor's maximum that its scale code is 0: a stored format holds zeros there)
+    The output holds no NaN.  ONE launch for the groups (dmxq_block_scaled_float_qdq) for nearest-rounding formats, out_dtype == x.dtype,
+    a 16-byte aligned tensor and a group that is a power of two from 16 to 256; the dynamic t is the library's own small reduction in
+    front (dmxq_block_scaled_tensor_scale: three launches; in the chain group_minmax over the whole tensor).  Otherwise the chain of existing launches, same bits: group_minmax ->
+    max(|mn|, |mx|) -> scale_channels divisions by fmax and t -> float_qdq with Sf -> minimum, multiply, where -> scale_channels (divide,
+    float32) -> float_qdq with E -> scale_channels (multiply, out_dtype), on pieces of 32768 groups above 65535.  fused=None: the kernel
+    where it applies and its class is not listed in BLOCK_SCALED_CHAIN_BY_DEFAULT; True: NotImplementedError instead of falling back;
+    False: the chain.  seed: for a stochastic-rounding element format (the chain only).  return_scale: (y, scale, scale_code_value,
+    tensor_scale) -- float32 [n_groups] s and sq, float32 [1] t -- on both routes.  ValueError (before any GPU use): a format that cannot be
+    used, a scale_max out of range, a group_size that does not divide.  Autograd: a straight-through estimator.  Nothing is read back to
+    the host."""
+    fmt, sf, scale_max = block_scaled_check(fmt, group_size, scale_format, scale_max, tensor_scale)
+    if x.dim() < 1:
+        raise ValueError("block_scaled_float_qdq expects a tensor with at least 1 dimension")
+    L, g = x.shape[-1], group_size
+    if L % g:
+        raise ValueError(f"block_scaled_float_qdq: the last dimension has {L} elements, not a multiple of the group size {g}")
+    require_gpu(x, "block_scaled_float_qdq")
+    if isinstance(tensor_scale, torch.Tensor) and (tensor_scale.device != x.device or tensor_scale.dtype != torch.float32):
+        raise ValueError(f"block_scaled_float_qdq: a tensor_scale tensor must be float32 on the input's device, got {tensor_scale.dtype} on "
+                         f"{tensor_scale.device}")
+    out_dtype = out_dtype or x.dtype
+    fmax = dynamic_float_fmax(fmt)
+    fields = (fmt.mantissa, fmt.exponent, fmt.bias, bool(fmt.flush_subnormal))
+    sfields = (sf.mantissa, sf.exponent, sf.bias, bool(sf.flush_subnormal))
+
+    def run(xd):
+        xc = xd if xd.is_contiguous() else xd.contiguous()
+        dev = xc.device
+        if xc.numel() == 0:
+            y = torch.empty(xc.shape, dtype=out_dtype, device=dev)
+            e = y.new_empty(0, dtype=torch.float32)
+            return (y, e, e.clone(), _one(1.0, dev)) if return_scale else y
+        cls = None
+        if fused is not False:
+            cls = block_scaled_float_class(g, xc.dtype) if (fmt.rounding == "nearest" and out_dtype == xc.dtype and fmt.mantissa <= 22
+                                                            and sf.mantissa <= 22 and xc.data_ptr() % 16 == 0) else None
+            if cls is None and fused:
+                raise NotImplementedError(f"block_scaled_float_qdq: no fused kernel for groups of {g} {xc.dtype} elements -> {out_dtype} "
+                                          f"with {fmt!r} under {sf!r} scales (base address {xc.data_ptr() % 16} mod 16)")
+            if cls is not None and fused is None and cls in BLOCK_SCALED_CHAIN_BY_DEFAULT:
+                cls = None
+        if cls is not None:
+            # an absent and a given t go to the kernel as they are (it applies the t = 1 rule itself) unless the caller wants to see t
+            if not return_scale and (tensor_scale is None or isinstance(tensor_scale, torch.Tensor)):
+                t = None if tensor_scale is None else tensor_scale.detach().reshape(1)
+            else:
+                t = _bs_tensor_scale(xc, tensor_scale, fmax, scale_max, True)
+            try:
+                y, sc, sq = _ops.block_scaled_float_qdq(xc, g, [*fields, ROUNDING_CODE[fmt.rounding]], [*sfields, ROUNDING_CODE["nearest"]],
+                                                        scale_max, t, bool(return_scale), bool(return_scale), out_dtype)
+                _block_scaled_routes["fused"] += 1
+                return (y, sc, sq, t) if return_scale else y
+            except NotImplementedError:   # (DMXQ_ERR_UNSUPPORTED, nothing launched)
+                if fused:
+                    raise
+        _block_scaled_routes["chain"] += 1
+        t = _bs_tensor_scale(xc, tensor_scale, fmax, scale_max, False)
+        x2 = xc.reshape(-1, g)
+        fmax_t, smax_t = _one(fmax, dev), _one(scale_max, dev)
+
+        def chain(part):
+            mn, mx = _ops.group_minmax(part, 0, 1)
+            c = _div_ieee(_div_ieee(torch.maximum(mn.abs(), mx.abs()), fmax_t), t)
+            sq = torch.minimum(float_qdq(c, *sfields, False, "nearest", torch.float32), smax_t.expand_as(c))
+            s = sq * t.expand_as(sq)
+            ok = _usable_scale(s)
+            s1 = torch.where(ok, s, torch.ones_like(s))
+            q = _ops.scale_channels(part, s1, 0, True, torch.float32)
+            q = float_qdq(q, *fields, False, fmt.rounding, torch.float32, seed)
+            y = _ops.scale_channels(q, s1, 0, False, out_dtype)
+            # an unusable group: zeros carrying the sign bit of float_q_E(x)
+            z = float_qdq(part, *fields, False, fmt.rounding, torch.float32, seed)
+            y = torch.where(ok[:, None], y, torch.copysign(torch.zeros_like(z), z).to(out_dtype))
+            return y, torch.where(ok, s, torch.zeros_like(s)), sq
+
+        if x2.shape[0] <= DYNAMIC_CHAIN_MAX_SEGMENTS:
+            y, sc, sq = chain(x2)
+        else:   # (dmxq_group_minmax takes 65535 groups: groups are independent once t is known, so the chain runs on pieces)
+            parts = [chain(x2[i:i + DYNAMIC_CHAIN_PIECE]) for i in range(0, x2.shape[0], DYNAMIC_CHAIN_PIECE)]
+            y, sc, sq = (torch.cat([p[k] for p in parts]) for k in range(3))
+        y = y.reshape(xc.shape)
+        return (y, sc, sq, t) if return_scale else y
 
     if x.requires_grad and torch.is_grad_enabled():
         return _DynamicSTE.apply(x, run)

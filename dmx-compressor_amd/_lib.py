@@ -89,6 +89,9 @@ SIGNATURES = {
     "dmxq_channel_sumabs_accumulate": [_vp, _i32, _i64, _i64, _vp, _vp, _vp],
     "dmxq_awq_class": [_i32, _i64, _i64],
     "dmxq_awq_group_error": [_vp, _i32, _vp, _vp, _vp, _i64, _i64, _i64, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp],
+    "dmxq_block_scaled_float_class": [_i32, _i64],
+    "dmxq_block_scaled_tensor_scale": [_vp, _i32, _i64, _f32, _f32, _vp, _vp],
+    "dmxq_block_scaled_float_qdq": [_vp, _vp, _i32, _i32, _i64, _i64, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _f32, _vp, _vp, _vp, _vp],
     "dmxq_row_class_of": [_i32, _i32, _i32, _i32, _i64, _i64, _vp, _vp, _vp, _vp, _i32, _i64, _vp],
 }
 

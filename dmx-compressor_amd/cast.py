@@ -125,6 +125,22 @@ def _parse_scaling(granularity, group_size=None, pow2_scale=False):
     return granularity, group_size, pow2_scale
 
 
+_BLOCK_SCALE_KEYS = ("scale_format", "scale_max", "tensor_scale")
+
+
+def _split_block_scale(setting):
+    """set_scaling's dict form -> (the setting without the block-scale keys, None or {those keys}): "scale_format" (the format the
+    group scales are quantised to), optionally "scale_max" and "tensor_scale" (ops.block_scaled_float_qdq; ops.NVFP4 is such a dict)"""
+    if not isinstance(setting, dict) or not any(k in setting for k in _BLOCK_SCALE_KEYS):
+        return setting, None
+    d = dict(setting)
+    b = {k: d.pop(k) for k in _BLOCK_SCALE_KEYS if k in d}
+    if "scale_format" not in b:
+        raise ValueError(f"set_scaling: {sorted(b)} only mean something for quantised group scales: add 'scale_format' (the format of "
+                         f"the scales, e.g. 'FP[1|4|3,7](_N)') or drop them, got {setting!r}")
+    return d, b
+
+
 class CastTo(HostFlags, torch.nn.Module):
     """Simulated numerical cast to a target format (cast.py:136-162).  Buffers and switches follow
     torch.ao's FakeQuantize, which the reference subclasses: scale, zero_point, fake_quant_enabled,
@@ -146,6 +162,9 @@ class CastTo(HostFlags, torch.nn.Module):
     #: None, or (granularity, group_size, pow2_scale): a float format is cast with a scale derived from every tensor itself (set_scaling;
     #: DESIGN.md §8).  A plain attribute as well.
     _scaling = None
+    #: None, or (scale_format, scale_max, tensor_scale) beside a per_group _scaling: the group scales are quantised to scale_format under
+    #: one float32 scale per tensor (ops.block_scaled_float_qdq).  A plain attribute as well.
+    _block_scale = None
 
     def __init__(self, format="SAME", observer=DummyObserver, group_size=None, block_dim=-1,
                  qscheme=torch.per_tensor_affine, ch_axis=-1, **observer_kwargs):
@@ -190,6 +209,8 @@ class CastTo(HostFlags, torch.nn.Module):
             ops.dynamic_check(format, *self._dynamic, what="CastTo.set_format on a dynamic cast")
         if self._scaling is not None and not isinstance(format, Same):
             ops.dynamic_float_check(format, *self._scaling[:2], what="CastTo.set_format on a scaled cast")
+            if self._block_scale is not None:
+                ops.block_scaled_check(format, self._scaling[1], *self._block_scale, what="CastTo.set_format on a scaled cast")
         self.format = format
         if hasattr(self, "activation_post_process"):
             self.activation_post_process.dtype = format
@@ -246,12 +267,28 @@ class CastTo(HostFlags, torch.nn.Module):
         to a power of two.  A setting of its own beside set_dynamic (the integer formats'): a plain attribute, no buffer, no state_dict
         key; None switches back to the unscaled cast.  ValueError for an unknown granularity and for a format that cannot be scaled (not
         a FloatingPoint, unsigned, 8 exponent bits) -- here, or in set_format when the format comes later (a cast that is still SAME
-        accepts the setting)."""
+        accepts the setting).
+        Quantised group scales (ops.block_scaled_float_qdq): the dict form {"per_group": g, "scale_format": Sf} with, optionally,
+        "scale_max" and "tensor_scale" ("dynamic" -- the default --, None, a float or a one-element tensor) casts every group's scale to
+        the float format Sf under one float32 scale per tensor -- ops.NVFP4 is the ready setting for FP[1|2|1,1](_N).  These keys go with
+        per_group only and not with pow2_scale: ValueError otherwise."""
+        granularity, block = _split_block_scale(granularity)
         sc = _parse_scaling(granularity, group_size, pow2_scale)
+        if block is not None:
+            if sc is None or sc[0] != "per_group":
+                raise ValueError(f"set_scaling: scale_format / scale_max / tensor_scale quantise the scales of GROUPS: give "
+                                 f"{{'per_group': g}} with them (got granularity {None if sc is None else sc[0]!r}), or drop them")
+            if sc[2]:
+                raise ValueError("set_scaling: pow2_scale and scale_format are two different scale rules: drop pow2_scale (a power-of-two "
+                                 "scale format is FP[1|e|0,bias]) or drop scale_format")
         if sc is not None:
             fmt = "FP[1|4|3,7](FN)" if isinstance(self.format, Same) else self.format   # (SAME: the granularity alone)
             ops.dynamic_float_check(fmt, *sc[:2], what="CastTo.set_scaling")
-        self._scaling = sc
+            if block is not None:
+                _, _, smax = ops.block_scaled_check(fmt, sc[1], block["scale_format"], block.get("scale_max"),
+                                                    block.get("tensor_scale", "dynamic"), what="CastTo.set_scaling")
+                block = (block["scale_format"], smax, block.get("tensor_scale", "dynamic"))
+        self._scaling, self._block_scale = sc, block
 
     @property
     def scaling(self):
@@ -261,6 +298,9 @@ class CastTo(HostFlags, torch.nn.Module):
         if sc is None:
             return None
         g, gs, pow2 = sc
+        if self._block_scale is not None:
+            sf, smax, ts = self._block_scale
+            return {"per_group": gs, "scale_format": sf if isinstance(sf, str) else repr(sf), "scale_max": smax, "tensor_scale": ts}
         out = {g: gs} if g in ("per_group", "per_tile") else g
         if pow2:
             out = dict(out, pow2_scale=True) if isinstance(out, dict) else {"granularity": g, "pow2_scale": True}
@@ -268,6 +308,9 @@ class CastTo(HostFlags, torch.nn.Module):
 
     def _scaled_cast(self, x, out_dtype):
         g, gs, pow2 = self._scaling
+        if self._block_scale is not None:
+            sf, smax, ts = self._block_scale
+            return ops.block_scaled_float_qdq(x, self.format, gs, sf, smax, ts, out_dtype=out_dtype)
         return ops.dynamic_float_qdq(x, self.format, g, gs, pow2_scale=pow2, out_dtype=out_dtype)
 
     def enable_calibration(self, state: bool = True, observer_cls: ObserverBase = HistogramObserver,
@@ -577,9 +620,9 @@ class CastToDict(torch.nn.ModuleDict):
             self[k].set_dynamic(t)
 
     def set_scaling(self, scaling):
-        """one setting (None, "per_token", "per_tensor", {"per_group": g}, {"per_tile": g}, each dict optionally with "pow2_scale") for every
-        cast, or a list / dict of settings over the casts the way set_dynamic takes them"""
-        one = isinstance(scaling, dict) and set(scaling) <= {"per_group", "per_tile", "granularity", "pow2_scale"} \
+        """one setting (None, "per_token", "per_tensor", {"per_group": g}, {"per_tile": g}, each dict optionally with "pow2_scale"; a
+        per_group dict also with "scale_format" / "scale_max" / "tensor_scale", such as ops.NVFP4) for every cast, or a list / dict of settings over the casts the way set_dynamic takes them"""
+        one = isinstance(scaling, dict) and set(scaling) <= {"per_group", "per_tile", "granularity", "pow2_scale", *_BLOCK_SCALE_KEYS} \
             and not set(scaling) & set(self.keys())
         if scaling is None or isinstance(scaling, str) or one:
             for c in self.values():

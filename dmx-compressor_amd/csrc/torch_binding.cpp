@@ -1143,6 +1143,52 @@ std::tuple<Tensor, Tensor> awq_group_error_meta(const Tensor& w, const Tensor&, 
   return std::make_tuple(empty_like_shape(w, at::kFloat), want_wq ? empty_like_shape(w, w.scalar_type()) : none_like(w));
 }
 
+// ------------------------------------------------------------------------------------------------ block-scaled float cast
+// x: contiguous; groups of `group` consecutive elements; fmt / scale_fmt: (man, exp, bias, flush, rounding); tensor_scale: None (t = 1) or
+// ONE float32 on x's device, read by the kernel only -> (out, scale, scale_code_value: float32 [n_groups], empty unless wanted).
+// DMXQ_ERR_UNSUPPORTED (NotImplementedError, nothing launched): the front end runs its chain of launches.
+std::tuple<Tensor, Tensor, Tensor> block_scaled_float_qdq(const Tensor& x, int64_t group, at::IntArrayRef fmt, at::IntArrayRef scale_fmt,
+                                                          double scale_max, const OptTensor& tensor_scale, bool want_scale, bool want_code,
+                                                          OptDtype out_dtype) {
+  const Tensor xc = prep(x, "block_scaled_float_qdq");
+  TORCH_CHECK(fmt.size() == 5 && scale_fmt.size() == 5, "block_scaled_float_qdq: a format is (man, exp, bias, flush, rounding)");
+  TORCH_CHECK(group >= 1 && xc.numel() % group == 0, "block_scaled_float_qdq: the group must divide the number of elements");
+  const float* tp = nullptr;
+  if (tensor_scale.has_value() && tensor_scale->defined()) {
+    const Tensor& t = *tensor_scale;
+    TORCH_CHECK(t.is_cuda() && t.device() == xc.device() && t.scalar_type() == at::kFloat && t.numel() == 1,
+                "block_scaled_float_qdq: tensor_scale must be ONE float32 on the input's device");
+    tp = (const float*)t.data_ptr();
+  }
+  const int64_t n = xc.numel() / group;
+  Tensor out = empty_like_shape(xc, out_dtype);
+  Tensor sc = at::empty({want_scale ? n : 0}, xc.options().dtype(at::kFloat));
+  Tensor sq = at::empty({want_code ? n : 0}, xc.options().dtype(at::kFloat));
+  Launch l(xc);
+  check(dmxq_block_scaled_float_qdq(xc.data_ptr(), out.data_ptr(), dt_code(xc.scalar_type()), dt_code(out.scalar_type()), n, group, (int)fmt[0],
+                                    (int)fmt[1], (int)fmt[2], (int)fmt[3], (int)fmt[4], (int)scale_fmt[0], (int)scale_fmt[1], (int)scale_fmt[2],
+                                    (int)scale_fmt[3], (int)scale_fmt[4], (float)scale_max, tp, want_scale ? (float*)sc.data_ptr() : nullptr,
+                                    want_code ? (float*)sq.data_ptr() : nullptr, l.stream), "dmxq_block_scaled_float_qdq");
+  return std::make_tuple(out, sc, sq);
+}
+// the dynamic tensor scale of a contiguous tensor -> float32 [1] on its device (DMXQ_ERR_UNSUPPORTED: the front end's group_minmax route)
+Tensor block_scaled_tensor_scale(const Tensor& x, double fmax, double scale_max) {
+  const Tensor xc = prep(x, "block_scaled_tensor_scale");
+  Tensor t = at::empty({1}, xc.options().dtype(at::kFloat));
+  Launch l(xc);
+  check(dmxq_block_scaled_tensor_scale(xc.data_ptr(), dt_code(xc.scalar_type()), xc.numel(), (float)fmax, (float)scale_max, (float*)t.data_ptr(),
+                                       l.stream), "dmxq_block_scaled_tensor_scale");
+  return t;
+}
+Tensor block_scaled_tensor_scale_meta(const Tensor& x, double, double) { return at::empty({1}, x.options().dtype(at::kFloat)); }
+std::tuple<Tensor, Tensor, Tensor> block_scaled_float_qdq_meta(const Tensor& x, int64_t group, at::IntArrayRef, at::IntArrayRef, double,
+                                                               const OptTensor&, bool want_scale, bool want_code, OptDtype out_dtype) {
+  TORCH_CHECK(group >= 1 && x.numel() % group == 0, "block_scaled_float_qdq: the group must divide the number of elements");
+  const int64_t n = x.numel() / group;
+  return std::make_tuple(empty_like_shape(x, out_dtype), at::empty({want_scale ? n : 0}, x.options().dtype(at::kFloat)),
+                         at::empty({want_code ? n : 0}, x.options().dtype(at::kFloat)));
+}
+
 }  // namespace
 
 TORCH_LIBRARY(dmxq, m) {
@@ -1201,6 +1247,8 @@ TORCH_LIBRARY(dmxq, m) {
   m.def("wanda_nm(Tensor w, Tensor act_norm, int K, int M, bool want_score, bool want_mask, bool want_y, ScalarType? mask_dtype=None, ScalarType? y_dtype=None) -> (Tensor, Tensor, Tensor)");
   m.def("channel_sumabs(Tensor x, Tensor(a!) acc, Tensor(b!) scratch) -> ()");
   m.def("awq_group_error(Tensor w, Tensor s, int group, int precision, int fraction, bool clamp, bool symmetric, int qmin, int qmax, bool symmetric_qscheme, bool want_wq) -> (Tensor, Tensor)");
+  m.def("block_scaled_float_qdq(Tensor x, int group, int[] fmt, int[] scale_fmt, float scale_max, Tensor? tensor_scale, bool want_scale, bool want_code, ScalarType? out_dtype=None) -> (Tensor, Tensor, Tensor)");
+  m.def("block_scaled_tensor_scale(Tensor x, float fmax, float scale_max) -> Tensor");
 }
 
 #define DMXQ_IMPL(m, name) m.impl(#name, &name)
@@ -1211,7 +1259,7 @@ TORCH_LIBRARY(dmxq, m) {
   X(m, histc); X(m, channel_maxabs); X(m, smoothquant_scale); X(m, scale_channels); X(m, unary); X(m, rope); X(m, rope_cast); X(m, softmax); X(m, norm); \
   X(m, unary_cast); X(m, unary_cast_table); X(m, lut16_apply); X(m, softmax_cast); X(m, norm_cast); X(m, group_minmax_accumulate); X(m, gptq_block); X(m, hist_observe); X(m, hist_qparams); \
   X(m, error_stats); X(m, cast_error); X(m, hadamard_qdq); X(m, dynamic_fixed_qdq); X(m, gptq_block_dynamic); X(m, dynamic_float_qdq); \
-  X(m, channel_sumsq); X(m, wanda_nm); X(m, channel_sumabs); X(m, awq_group_error)
+  X(m, channel_sumsq); X(m, wanda_nm); X(m, channel_sumabs); X(m, awq_group_error); X(m, block_scaled_float_qdq); X(m, block_scaled_tensor_scale)
 
 // "CUDA" is the dispatch key of HIP tensors in a ROCm build of PyTorch
 TORCH_LIBRARY_IMPL(dmxq, CUDA, m) {
@@ -1272,4 +1320,7 @@ PYBIND11_MODULE(dmxq_fast, m) {
         py::arg("want_qparams"), py::arg("out_dtype") = py::none());
   m.def("dynamic_float_qdq", &dynamic_float_qdq, py::arg("x"), py::arg("mode"), py::arg("segment"), py::arg("man"), py::arg("exp"), py::arg("bias"),
         py::arg("flush_subnormal"), py::arg("rounding"), py::arg("pow2_scale"), py::arg("want_scale"), py::arg("out_dtype") = py::none());
+  m.def("block_scaled_float_qdq", &block_scaled_float_qdq, py::arg("x"), py::arg("group"), py::arg("fmt"), py::arg("scale_fmt"), py::arg("scale_max"),
+        py::arg("tensor_scale"), py::arg("want_scale"), py::arg("want_code"), py::arg("out_dtype") = py::none());
+  m.def("block_scaled_tensor_scale", &block_scaled_tensor_scale);
 }

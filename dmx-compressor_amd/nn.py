@@ -209,7 +209,8 @@ class DmxModule(FastAttr, torch.nn.Module):
         if self.weight_cast is not None and "weight_dynamic" in config:
             self.weight_cast.set_dynamic(config["weight_dynamic"])   # (per_token: per output channel of the [out, in] view)
         # dynamic scales for the float casts (CastTo.set_scaling): None, "per_token", "per_tensor", {"per_group": g} or {"per_tile": g},
-        # each dict optionally with "pow2_scale": True -- one setting for every cast of the dict, or a list / dict of settings
+        # each dict optionally with "pow2_scale": True; a per_group dict also with "scale_format" / "scale_max" / "tensor_scale" (quantised
+        # group scales under a tensor scale: ops.NVFP4) -- one setting for every cast of the dict, or a list / dict of settings
         if "input_scaling" in config:
             self.input_casts.set_scaling(config["input_scaling"])
         if "output_scaling" in config:

@@ -56,7 +56,8 @@ const char* dmxq_status_string(int status);
 /* ABI version: bumped on any signature change.  Additions since 4 (dmxq_gptq_block, dmxq_hist_observe, dmxq_hist_qparams, dmxq_error_stats, dmxq_cast_error,
  * dmxq_error_scratch_bytes, dmxq_hadamard_qdq, dmxq_dynamic_fixed_qdq, dmxq_dynamic_class, dmxq_gptq_block_dynamic,
  * dmxq_dynamic_float_qdq, dmxq_dynamic_float_class, dmxq_channel_sumsq_accumulate, dmxq_channel_sumsq_workspace_bytes, dmxq_wanda_nm,
- * dmxq_wanda_class, dmxq_row_class_of, dmxq_channel_sumabs_accumulate, dmxq_awq_group_error, dmxq_awq_class) leave it at 4: a caller built against 4 runs on
+ * dmxq_wanda_class, dmxq_row_class_of, dmxq_channel_sumabs_accumulate, dmxq_awq_group_error, dmxq_awq_class,
+ * dmxq_block_scaled_float_qdq, dmxq_block_scaled_float_class, dmxq_block_scaled_tensor_scale) leave it at 4: a caller built against 4 runs on
  * this library unchanged.  4 = round 5: + dmxq_float_qdq_multi, dmxq_fixed_float_qdq_multi; 3 = round 4: + dmxq_weight_hypernet_multi,
  * dmxq_unary_cast_table, dmxq_lut16_apply.  Nothing was ever removed or changed: a caller built against version n runs on any library >= n. */
 int dmxq_abi_version(void);
@@ -636,6 +637,41 @@ int dmxq_channel_sumabs_accumulate(const void* in, int dtype_in, int64_t rows, i
 int dmxq_awq_class(int dtype_w, int64_t L, int64_t group);
 int dmxq_awq_group_error(const void* w, int dtype_w, const float* s, float* d_out, void* wq_out, int64_t rows, int64_t L, int64_t group,
                          int precision, int fraction, int clamp, int symmetric, int qmin, int qmax, int symmetric_qscheme, void* stream);
+
+/* Two-level BLOCK-SCALED float cast (csrc/block_scaled_float.hip; DESIGN.md §8 "Block-scaled float cast"): the group scale of
+ * dmxq_dynamic_float_qdq QUANTISED to a low-bit float format, under one float32 scale per tensor -- the numerics of a stored block-scaled
+ * format (E2M1 elements in groups of 16 with an E4M3 group scale: "NVFP4"; E4M3 elements with quantised group scales).  Not in the
+ * reference.  E = the signed element format (man_bits, exp_bits < 8, exp_bias, flush_subnormal) with largest output fmax; Sf = the scale
+ * format (scale_man_bits, scale_exp_bits < 8, scale_exp_bias, scale_flush_subnormal) with largest output sfmax (scales are never
+ * negative: no sign field); 0 < scale_max <= sfmax caps the scale code (448 keeps an FP[1|4|3,7] scale inside the OCP E4M3FN codes).
+ * tensor_scale: NULL (t = 1) or ONE float on the DEVICE, read by the kernel (never by the host); t = 1 where it is not finite or below
+ * 2^-126.  Per group of `group` consecutive elements of the contiguous tensor, in fp32:
+ *   a  = max |x| (one NaN anywhere makes it NaN);  c = (a / fmax) / t, two IEEE divisions;
+ *   sq = min(float_q_Sf(c), scale_max): the scale format's nearest cast, NaN / Inf saturating to sfmax -- sq is never NaN;
+ *   s  = sq * t, one fp32 multiply; usable when finite and >= 2^-126;
+ *   usable:  out = float_q_E(x / s) * s: IEEE quotient, the element format's nearest cast (flush flag kept, NaN / Inf saturate as in
+ *            dmxq_float_qdq), one fp32 multiply, one rounding to dtype_out;
+ *   else:    out = a zero with the sign bit of float_q_E(x), and the reported s is 0 (an all-zero group, or one whose scale code is 0).
+ * The output holds no NaN.  scale_out / scale_q_out: NULL or DEVICE arrays of n_groups floats, s and sq of every group.
+ * The kernel takes dtype_in == dtype_out (bf16 / f16 / f32), group a power of two from 16 to 256, nearest rounding in both formats and
+ * 16-byte aligned bases: dmxq_dynamic_float_qdq's flat group geometry, ONE launch.  dmxq_block_scaled_float_class(dtype, group):
+ * DMXQ_DYN_GROUP where it does, DMXQ_DYN_NONE otherwise; a host function, no GPU involved.
+ * DMXQ_ERR_UNSUPPORTED, nothing launched (the caller runs its chain of launches, same bits): other dtype pairs, other group sizes,
+ * unaligned bases, a rounding other than nearest in either format, man_bits > 22 in either format.  DMXQ_ERR_BAD_ARG: null data
+ * pointers, negative sizes, invalid dtype / rounding, exp_bits outside 1 .. 7 or negative man_bits in either format, scale_max outside
+ * (0, sfmax].  No workspace, no allocation, no host synchronisation: capturable.
+ * dmxq_block_scaled_tensor_scale: the DYNAMIC tensor scale of the contiguous tensor in[n] into the one DEVICE float t_out --
+ * t = (max |x| / fmax) / scale_max, two IEEE divisions, one NaN anywhere makes the maximum NaN, t = 1 where it is not finite or below
+ * 2^-126 (n = 0: 1) -- in three small launches (the word is zeroed, one integer atomic per workgroup on the magnitude bits, one thread
+ * finishes in place): exact in any order, capturable, no workspace.  DMXQ_ERR_UNSUPPORTED, nothing launched (the caller uses
+ * dmxq_group_minmax over the whole tensor): n not whole 16-byte vectors, an unaligned base.  DMXQ_ERR_BAD_ARG: invalid dtype, n < 0, null
+ * pointers, fmax or scale_max not positive and finite. */
+int dmxq_block_scaled_float_class(int dtype, int64_t group);
+int dmxq_block_scaled_tensor_scale(const void* in, int dtype_in, int64_t n, float fmax, float scale_max, float* t_out, void* stream);
+int dmxq_block_scaled_float_qdq(const void* in, void* out, int dtype_in, int dtype_out, int64_t n_groups, int64_t group, int man_bits,
+                                int exp_bits, int exp_bias, int flush_subnormal, int rounding, int scale_man_bits, int scale_exp_bits,
+                                int scale_exp_bias, int scale_flush_subnormal, int scale_rounding, float scale_max,
+                                const float* tensor_scale, float* scale_out, float* scale_q_out, void* stream);
 
 /* Which kernel a row function launches (csrc/row_class.hpp): what dmxq_softmax* / dmxq_layernorm* / dmxq_rmsnorm* will do for one call,
  * answered by the function their dispatch itself decides with.  A host function: no GPU involved, no HIP call, the pointers are not
