@@ -18,7 +18,7 @@ import torch
 from ._lib import DmxqError, ROUNDING_CODE, require_gpu
 
 __all__ = [
-    "bfp_qdq", "block_quantize", "bfp_qdq_multi", "bfp_pack", "bfp_unpack", "weight_hypernet", "weight_hypernet_multi", "input_hypernet", "binary_cast", "rope_cast", "relu_cast", "unary_cast", "unary_cast_table", "lut16_apply", "softmax_cast", "layernorm_cast", "rmsnorm_cast", "sbfp_qdq", "mxfp_qdq", "float_qdq", "float_qdq_multi", "fixed_qdq", "fixed_qdq_multi", "fixed_float_qdq_multi", "nm_mask", "nm_sparsify", "topk_mask", "topk_sparsify", "bernoulli_mask", "group_minmax", "group_minmax_accumulate", "qparams", "channel_maxabs",
+    "bfp_qdq", "block_quantize", "bfp_qdq_multi", "bfp_pack", "bfp_unpack", "weight_hypernet", "weight_hypernet_multi", "input_hypernet", "binary_cast", "rope_cast", "relu_cast", "unary_cast", "unary_cast_table", "lut16_apply", "softmax_cast", "layernorm_cast", "rmsnorm_cast", "sbfp_qdq", "mxfp_qdq", "float_qdq", "float_qdq_multi", "fixed_qdq", "fixed_qdq_multi", "fixed_float_qdq_multi", "nm_mask", "nm_sparsify", "nm_mask_class", "topk_mask", "topk_sparsify", "bernoulli_mask", "group_minmax", "group_minmax_accumulate", "qparams", "channel_maxabs",
     "smoothquant_scale", "scale_channels", "gelu", "silu", "quick_gelu", "exp", "silu_experimental", "rope", "softmax", "layernorm",
     "rmsnorm", "histc", "gptq_fields", "gptq_block", "gptq_block_dynamic", "hist_observe", "hist_scratch_words", "hist_qparams", "error_stats", "cast_error",
     "error_scratch_bytes", "cast_error_entry", "hadamard", "hadamard_qdq", "hadamard_check_size", "HADAMARD_SIZES",
@@ -277,6 +277,33 @@ def nm_sparsify(x, score, K: int, M: int, block_dim: int = -1, out_dtype: Option
     require_gpu(x, "nm_sparsify")
     mask, y = _nm(score, x, K, M, block_dim, return_mask, True, None, out_dtype)
     return (y, mask) if return_mask else y
+
+
+def nm_mask_class(score, K: int, M: int, block_dim: int = -1, x=None, mask_dtype: Optional[torch.dtype] = None,
+                  out_dtype: Optional[torch.dtype] = None, return_mask: Optional[bool] = None) -> str:
+    """The kernel `nm_mask(score, K, M, block_dim, mask_dtype)` -- or, with `x`, `nm_sparsify(x, score, K, M, block_dim, out_dtype,
+    return_mask)` -- launches: "typed", "f32_mask", "vector", "group_m", "any_m", or "none" for an empty tensor; asked of the library
+    itself (dmxq_nm_mask_class, the function dmxq_nm_mask decides with; no GPU involved, tensors on any device: only dtypes, sizes and the
+    alignment of the bases count).  The outputs are fresh allocations, so their bases are taken as 16-byte aligned, and so is the
+    contiguous copy of an input that is not contiguous."""
+    import ctypes
+
+    from ._lib import NM_ROUTE_NAMES, check, dtype_code, lib, split3
+    want_y = x is not None
+    want_mask = (not want_y) if return_mask is None else bool(return_mask)
+    outer, L, inner = split3(score.shape, block_dim) if score.dim() else (1, 1, 1)
+    fresh = 0x100000    # (any 16-byte aligned address: never dereferenced)
+
+    def base(t):
+        return t.data_ptr() if t.is_contiguous() and t.numel() else fresh
+
+    y_dtype = (out_dtype or torch.promote_types(x.dtype, score.dtype)) if want_y else score.dtype
+    route = ctypes.c_int(0)
+    check(lib().dmxq_nm_mask_class(dtype_code(score.dtype), dtype_code(x.dtype) if want_y else 0, dtype_code(mask_dtype or score.dtype),
+                                   dtype_code(y_dtype), outer, L, inner, int(K), int(M), base(score),
+                                   (base(x) if x.shape == score.shape else fresh) if want_y else None, fresh if want_mask else None,
+                                   fresh if want_y else None, ctypes.byref(route)), "dmxq_nm_mask_class")
+    return NM_ROUTE_NAMES[route.value]
 
 
 def _topk(score, x, density, want_mask, want_y, mask_dtype, y_dtype):

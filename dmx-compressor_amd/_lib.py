@@ -52,6 +52,7 @@ SIGNATURES = {
     "dmxq_float_qdq_multi": [_vp, _i64, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _u64, _vp],
     "dmxq_fixed_float_qdq_multi": [_vp, _i64, _i32, _i32, _i32, _i32, _i32, _i64, _vp, _i64, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _u64, _vp],
     "dmxq_nm_mask": [_vp, _i32, _vp, _i32, _vp, _i32, _vp, _i32, _i64, _i64, _i64, _i32, _i32, _vp],
+    "dmxq_nm_mask_class": [_i32, _i32, _i32, _i32, _i64, _i64, _i64, _i32, _i32, _vp, _vp, _vp, _vp, _vp],
     "dmxq_topk_workspace_bytes": [_i64],
     "dmxq_topk_mask": [_vp, _i32, _vp, _i32, _vp, _i32, _vp, _i32, _i64, _i64, _vp, _vp],
     "dmxq_bernoulli_mask": [_vp, _vp, _i32, _i32, _i64, _u64, _vp],
@@ -100,6 +101,11 @@ ROW_SOFTMAX, ROW_LAYERNORM, ROW_RMSNORM = 0, 1, 2
 ROWCAST_NONE, ROWCAST_RANGE, ROWCAST_GENERAL, ROWCAST_MAN16 = 0, 1, 2, 3
 ROWK_UNSUPPORTED, ROWK_WAVE, ROWK_BLOCK, ROWK_LDS_ROWS, ROWK_GLOBAL_ROWS = 0, 1, 2, 3, 4
 ROWGRID_NONE, ROWGRID_PERSISTENT, ROWGRID_ONE_PASS, ROWGRID_MID_ONE_PASS, ROWGRID_MODULE_ONE_PASS, ROWGRID_MODULE_ROWS4, ROWGRID_CAPPED = range(7)
+
+# dmxq_nm_route (include/dmxq.h) and the grid cap of the grid-stride kernels (DMXQ_GRID_CAP)
+NM_NONE, NM_TYPED, NM_F32_MASK, NM_VECTOR, NM_GROUP_M, NM_ANY_M = range(6)
+NM_ROUTE_NAMES = {NM_NONE: "none", NM_TYPED: "typed", NM_F32_MASK: "f32_mask", NM_VECTOR: "vector", NM_GROUP_M: "group_m", NM_ANY_M: "any_m"}
+GRID_CAP = 2048
 
 
 class RowClass(ctypes.Structure):

@@ -363,9 +363,21 @@ using namespace dmxq;
 
 // Typed N:M mask-and-multiply over a flat [n] stream of whole M-groups (inner == 1), y = x * mask(score); called by
 // dmxq_nm_mask (nm_mask.hip) before its generic kernels.  DMXQ_ERR_UNSUPPORTED: not one of the instantiated dtype triples.
+// dmxq_internal_nm_typed_ok: the applicability test on its own -- a host predicate, nothing launched, no pointer dereferenced --, asked by
+// the launcher below and by dmxq_nm_mask_class (nm_mask.hip): groups of 2, 4 or 8, whole 8-element units, 16-byte bases and one of the six
+// (x, score -> y) triples instantiated below.
+extern "C" int dmxq_internal_nm_typed_ok(const void* score, int dtype_score, const void* x, int dtype_x, const void* y, int dtype_y,
+                                         int64_t n, int M) {
+  if (!(M == 2 || M == 4 || M == 8) || n % 8 != 0 || !aligned16(score) || !aligned16(x) || !aligned16(y)) return 0;
+  const bool same = dtype_x == dtype_score && dtype_y == dtype_x && valid_dtype(dtype_x);                        // bf16, f16 or f32 throughout
+  const bool wide = dtype_score == DMXQ_F32 && dtype_y == DMXQ_F32 && (dtype_x == DMXQ_BF16 || dtype_x == DMXQ_F16);  // torch's promotion
+  const bool back = dtype_score == DMXQ_F32 && dtype_x == DMXQ_BF16 && dtype_y == DMXQ_BF16;                     // ... cast back to the weight's dtype
+  return (same || wide || back) ? 1 : 0;
+}
+
 extern "C" int dmxq_internal_nm_sparsify_typed(const void* score, int dtype_score, const void* x, int dtype_x, void* y, int dtype_y,
                                                int64_t n, int K, int M, void* stream) {
-  if (!(M == 2 || M == 4 || M == 8) || n % 8 != 0 || !aligned16(score) || !aligned16(x) || !aligned16(y)) return DMXQ_ERR_UNSUPPORTED;
+  if (!dmxq_internal_nm_typed_ok(score, dtype_score, x, dtype_x, y, dtype_y, n, M)) return DMXQ_ERR_UNSUPPORTED;
   const HnArgs a{x, score, nullptr, y, n / 8, n, K, 1, 8, 0, n < ((int64_t)1 << 31) ? 1 : 0, make_fastdiv31(n)};
   hipStream_t s = (hipStream_t)stream;
   const int64_t tiles = (a.n_units + (int64_t)kThreads * kHnUnits - 1) / ((int64_t)kThreads * kHnUnits);

@@ -189,13 +189,21 @@ __global__ __launch_bounds__(kThreads) void nm_mask_anyM_kernel(NmArgs a, int M)
 
 using namespace dmxq;
 
-// hypernet.hip: compile-time typed mask-and-multiply (no mask output); DMXQ_ERR_UNSUPPORTED = not applicable
+// hypernet.hip: compile-time typed mask-and-multiply (no mask output) and its applicability test (a host predicate)
+extern "C" int dmxq_internal_nm_typed_ok(const void* score, int dtype_score, const void* x, int dtype_x, const void* y, int dtype_y,
+                                         int64_t n, int M);
 extern "C" int dmxq_internal_nm_sparsify_typed(const void* score, int dtype_score, const void* x, int dtype_x, void* y, int dtype_y,
                                                int64_t n, int K, int M, void* stream);
 
-extern "C" int dmxq_nm_mask(const void* score, int dtype_score, const void* x, int dtype_x, void* mask_out,
-                            int dtype_mask, void* y_out, int dtype_y, int64_t outer, int64_t L, int64_t inner, int K,
-                            int M, void* stream) {
+static_assert(kMaxBlocks == DMXQ_GRID_CAP, "include/dmxq.h states the grid cap");
+constexpr int kNmF32Units = 4;   // 16-byte vectors per lane of nm_mask_f32_kernel
+
+// The route of one dmxq_nm_mask call (include/dmxq.h): every decision of the entry below is taken here; a host function, nothing is
+// launched and no address is dereferenced.
+extern "C" int dmxq_nm_mask_class(int dtype_score, int dtype_x, int dtype_mask, int dtype_y, int64_t outer, int64_t L, int64_t inner,
+                                  int K, int M, const void* score, const void* x, const void* mask_out, const void* y_out, int* route) {
+  if (!route) return DMXQ_ERR_BAD_ARG;
+  *route = DMXQ_NM_NONE;
   if (!valid_dtype(dtype_score) || outer < 0 || L < 0 || inner < 0) return DMXQ_ERR_BAD_ARG;
   if (M < 1 || M > 64 || K < 1 || K > M || L % M != 0) return DMXQ_ERR_BAD_ARG;  // sparse.py:158,166-168
   if (mask_out && !valid_dtype(dtype_mask)) return DMXQ_ERR_BAD_ARG;
@@ -204,28 +212,43 @@ extern "C" int dmxq_nm_mask(const void* score, int dtype_score, const void* x, i
   const int64_t n = outer * L * inner;
   if (n == 0) return DMXQ_OK;
   if (!score) return DMXQ_ERR_BAD_ARG;
-  NmArgs a{score, x, mask_out, y_out, dtype_score, dtype_x, dtype_mask, dtype_y, outer, L, inner, K};
-  hipStream_t s = (hipStream_t)stream;
   const bool vec_ok = inner == 1 && (M == 2 || M == 4 || M == 8 || M == 16) && n % 16 == 0 && aligned16(score) &&
                       (!x || aligned16(x)) && (!mask_out || aligned16(mask_out)) && (!y_out || aligned16(y_out));
-  if (vec_ok && y_out && !mask_out) {
-    const int rc = dmxq_internal_nm_sparsify_typed(score, dtype_score, x, dtype_x, y_out, dtype_y, n, K, M, stream);
-    if (rc != DMXQ_ERR_UNSUPPORTED) return rc;
+  if (vec_ok && y_out && !mask_out && dmxq_internal_nm_typed_ok(score, dtype_score, x, dtype_x, y_out, dtype_y, n, M)) {
+    *route = DMXQ_NM_TYPED;
+  } else if (vec_ok && mask_out && !y_out && dtype_score == DMXQ_F32 && dtype_mask == DMXQ_F32 && M <= 8 &&
+             (n / 4 + kThreads * kNmF32Units - 1) / (kThreads * kNmF32Units) <= 0x7FFFFFFF) {
+    *route = DMXQ_NM_F32_MASK;
+  } else if (vec_ok) {
+    *route = DMXQ_NM_VECTOR;
+  } else {
+    *route = (M == 2 || M == 4 || M == 8 || M == 16) ? DMXQ_NM_GROUP_M : DMXQ_NM_ANY_M;
   }
-  if (vec_ok && mask_out && !y_out && dtype_score == DMXQ_F32 && dtype_mask == DMXQ_F32 && M <= 8) {
-    constexpr int UN = 4;
+  return DMXQ_OK;
+}
+
+extern "C" int dmxq_nm_mask(const void* score, int dtype_score, const void* x, int dtype_x, void* mask_out,
+                            int dtype_mask, void* y_out, int dtype_y, int64_t outer, int64_t L, int64_t inner, int K,
+                            int M, void* stream) {
+  int route = DMXQ_NM_NONE;
+  const int rc = dmxq_nm_mask_class(dtype_score, dtype_x, dtype_mask, dtype_y, outer, L, inner, K, M, score, x, mask_out, y_out, &route);
+  if (rc != DMXQ_OK || route == DMXQ_NM_NONE) return rc;   // an argument error, or an empty tensor
+  const int64_t n = outer * L * inner;
+  NmArgs a{score, x, mask_out, y_out, dtype_score, dtype_x, dtype_mask, dtype_y, outer, L, inner, K};
+  hipStream_t s = (hipStream_t)stream;
+  if (route == DMXQ_NM_TYPED) return dmxq_internal_nm_sparsify_typed(score, dtype_score, x, dtype_x, y_out, dtype_y, n, K, M, stream);
+  if (route == DMXQ_NM_F32_MASK) {
+    constexpr int UN = kNmF32Units;
     const int64_t n_vec = n / 4;
     const int64_t tiles = (n_vec + kThreads * UN - 1) / (kThreads * UN);
-    if (tiles <= 0x7FFFFFFF) {
-      switch (M) {
-        case 2: DMXQ_LAUNCH((nm_mask_f32_kernel<2, UN>), dim3((unsigned)tiles), dim3(kThreads), 0, s, (const float*)score, (float*)mask_out, n_vec, K); break;
-        case 4: DMXQ_LAUNCH((nm_mask_f32_kernel<4, UN>), dim3((unsigned)tiles), dim3(kThreads), 0, s, (const float*)score, (float*)mask_out, n_vec, K); break;
-        default: DMXQ_LAUNCH((nm_mask_f32_kernel<8, UN>), dim3((unsigned)tiles), dim3(kThreads), 0, s, (const float*)score, (float*)mask_out, n_vec, K); break;
-      }
-      return launch_status();
+    switch (M) {
+      case 2: DMXQ_LAUNCH((nm_mask_f32_kernel<2, UN>), dim3((unsigned)tiles), dim3(kThreads), 0, s, (const float*)score, (float*)mask_out, n_vec, K); break;
+      case 4: DMXQ_LAUNCH((nm_mask_f32_kernel<4, UN>), dim3((unsigned)tiles), dim3(kThreads), 0, s, (const float*)score, (float*)mask_out, n_vec, K); break;
+      default: DMXQ_LAUNCH((nm_mask_f32_kernel<8, UN>), dim3((unsigned)tiles), dim3(kThreads), 0, s, (const float*)score, (float*)mask_out, n_vec, K); break;
     }
+    return launch_status();
   }
-  if (vec_ok) {
+  if (route == DMXQ_NM_VECTOR) {
     switch (M) {
       case 2: launch_nm_vec<2>(a, n, s); break;
       case 4: launch_nm_vec<4>(a, n, s); break;

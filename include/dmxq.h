@@ -57,7 +57,7 @@ const char* dmxq_status_string(int status);
  * dmxq_error_scratch_bytes, dmxq_hadamard_qdq, dmxq_dynamic_fixed_qdq, dmxq_dynamic_class, dmxq_gptq_block_dynamic,
  * dmxq_dynamic_float_qdq, dmxq_dynamic_float_class, dmxq_channel_sumsq_accumulate, dmxq_channel_sumsq_workspace_bytes, dmxq_wanda_nm,
  * dmxq_wanda_class, dmxq_row_class_of, dmxq_channel_sumabs_accumulate, dmxq_awq_group_error, dmxq_awq_class,
- * dmxq_block_scaled_float_qdq, dmxq_block_scaled_float_class, dmxq_block_scaled_tensor_scale) leave it at 4: a caller built against 4 runs on
+ * dmxq_block_scaled_float_qdq, dmxq_block_scaled_float_class, dmxq_block_scaled_tensor_scale, dmxq_nm_mask_class) leave it at 4: a caller built against 4 runs on
  * this library unchanged.  4 = round 5: + dmxq_float_qdq_multi, dmxq_fixed_float_qdq_multi; 3 = round 4: + dmxq_weight_hypernet_multi,
  * dmxq_unary_cast_table, dmxq_lut16_apply.  Nothing was ever removed or changed: a caller built against version n runs on any library >= n. */
 int dmxq_abi_version(void);
@@ -174,6 +174,24 @@ int dmxq_fixed_float_qdq_multi(const dmxq_affine_desc* fixed, int64_t n_fixed, i
  * mask_out (dtype_mask, float mask of 0/1) and/or y_out = x * mask (dtype_y) may be NULL.  M <= 64. */
 int dmxq_nm_mask(const void* score, int dtype_score, const void* x, int dtype_x, void* mask_out, int dtype_mask,
                  void* y_out, int dtype_y, int64_t outer, int64_t L, int64_t inner, int K, int M, void* stream);
+
+/* Which kernel dmxq_nm_mask launches for one call (csrc/nm_mask.hip), answered by the function the entry itself decides with.  A host
+ * function: no GPU involved, no HIP call, the four addresses are never dereferenced -- only whether they are NULL (mask_out / y_out: that
+ * output is not wanted) and their 16-byte alignment matter.  *route (dmxq_nm_route):
+ *   NONE      an empty tensor: nothing is launched;
+ *   TYPED     y only, compile-time dtypes (csrc/hypernet.hip): inner == 1, M in {2, 4, 8}, n % 16 == 0, 16-byte bases and (x, score -> y)
+ *             one of (bf16, bf16 -> bf16), (f16, f16 -> f16), (f32, f32 -> f32), (bf16, f32 -> f32), (f16, f32 -> f32), (bf16, f32 -> bf16);
+ *   F32_MASK  mask only, float32 score and mask, M in {2, 4, 8}, the same geometry: a lane per 16-byte vector;
+ *   VECTOR    any other call of that geometry, M = 16 included: a lane per 8 (M = 16: 16) consecutive elements, run-time dtypes;
+ *   GROUP_M   M in {2, 4, 8, 16} otherwise (inner != 1, n % 16 != 0 or a base off the 16-byte grid): a lane per group, scalar accesses;
+ *   ANY_M     every other M up to 64: the same with run-time loops.
+ * Returns DMXQ_OK, or DMXQ_ERR_BAD_ARG exactly where dmxq_nm_mask does (and for route == NULL).
+ * DMXQ_GRID_CAP: the most workgroups a grid-stride kernel of the library is launched with (VECTOR, GROUP_M, ANY_M, and the chunk loops
+ * of dmxq_topk_mask); larger tensors take further rounds of the same grid. */
+#define DMXQ_GRID_CAP 2048
+typedef enum { DMXQ_NM_NONE = 0, DMXQ_NM_TYPED = 1, DMXQ_NM_F32_MASK = 2, DMXQ_NM_VECTOR = 3, DMXQ_NM_GROUP_M = 4, DMXQ_NM_ANY_M = 5 } dmxq_nm_route;
+int dmxq_nm_mask_class(int dtype_score, int dtype_x, int dtype_mask, int dtype_y, int64_t outer, int64_t L, int64_t inner, int K, int M,
+                       const void* score, const void* x, const void* mask_out, const void* y_out, int* route);
 
 /* Unstructured top-k mask ("TOPK{density}") and its application: the n_zero lowest scores of the flattened tensor are
  * zeroed.  Replaces: sparse.py:109-123 TopK.forward (argsort + scatter; n_zero = int(n * (1 - density))) and
