@@ -855,6 +855,31 @@ def dynamic_fixed_qdq(x, segment, whole_rows, precision, fraction, clamp, symmet
     return out, sc, zp
 
 
+# ------------------------------------------------------------------------------------------------ learned step size (backward)
+@_guarded
+def lsq_backward(x, g, scale, zero_point, segment, whole_rows, precision, rounding, qmin, qmax, grad_factor, want_dz, want_dx):
+    """-> (dx, empty unless want_dx; ds float32 [n_segments]; dz float32 [n_segments], empty unless want_dz)"""
+    xc, gc = _prep(x, "lsq_backward"), _prep(g, "lsq_backward")
+    if gc.device != xc.device or gc.numel() != xc.numel():
+        raise RuntimeError("lsq_backward: x and g must hold the same number of elements on one device")
+    if segment < 1 or xc.numel() % segment != 0:
+        raise RuntimeError("lsq_backward: the segment must divide the number of elements")
+    n = xc.numel() // segment
+    for t in (scale, zero_point):
+        if not (t.is_cuda and t.device == xc.device and t.dtype == torch.float32 and t.is_contiguous() and t.numel() == n):
+            raise RuntimeError(f"lsq_backward: scale and zero_point must be contiguous float32 tensors of {n} entries on x's GPU")
+    dx = torch.empty(xc.shape if want_dx else 0, dtype=xc.dtype, device=xc.device)
+    ds = torch.empty(n, dtype=torch.float32, device=xc.device)
+    dz = torch.empty(n if want_dz else 0, dtype=torch.float32, device=xc.device)
+    sb = int(lib().dmxq_lsq_scratch_bytes(segment)) if whole_rows == 2 else 0
+    scratch = torch.empty(sb // 8, dtype=torch.float64, device=xc.device)
+    check(lib().dmxq_lsq_backward(ptr(xc), ptr(gc), ptr(dx) if want_dx else None, dtype_code(xc.dtype), dtype_code(gc.dtype), dtype_code(dx.dtype), n, segment,
+                                  int(whole_rows), precision, rounding, qmin, qmax, ptr(scale), ptr(zero_point), float(grad_factor),
+                                  int(bool(want_dz)), ptr(ds), ptr(dz) if want_dz else None, ptr(scratch) if sb else None, sb, stream_of(xc)),
+          "dmxq_lsq_backward")
+    return dx, ds, dz
+
+
 # ------------------------------------------------------------------------------------------------ dynamic scaled float cast
 DYNF_GROUP, DYNF_ROWS, DYNF_TILE = 0, 1, 2   # dmxq_dynamic_float_mode (include/dmxq.h)
 

@@ -59,7 +59,9 @@ _FAST_CALIBRATION_NAMES = {"hist_observe": "hist_observe", "hist_qparams": "hist
                            # the dynamic scaled float cast: the same
                            "dynamic_float_qdq": "dynamic_float_qdq",
                            # the block-scaled float cast: the same
-                           "block_scaled_float_qdq": "block_scaled_float_qdq", "block_scaled_tensor_scale": "block_scaled_tensor_scale"}
+                           "block_scaled_float_qdq": "block_scaled_float_qdq", "block_scaled_tensor_scale": "block_scaled_tensor_scale",
+                           # the learned step size backward: called from inside an autograd Function of the front end (_front.py)
+                           "lsq_backward": "lsq_backward"}
 FAST = None
 
 

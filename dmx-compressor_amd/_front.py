@@ -25,6 +25,7 @@ __all__ = [
     "dynamic_fixed_qdq", "dynamic_check", "dynamic_class", "DYNAMIC_GRANULARITIES", "DYNAMIC_CHAIN_BY_DEFAULT",
     "dynamic_float_qdq", "dynamic_float_check", "dynamic_float_class", "dynamic_float_fmax", "DYNAMIC_FLOAT_GRANULARITIES",
     "DYNAMIC_FLOAT_CHAIN_BY_DEFAULT",
+    "lsq_backward", "lsq_fixed_qdq", "lsq_class", "lsq_scratch_bytes", "lsq_grad_factor", "LSQ_CHAIN_BY_DEFAULT",
     "block_scaled_float_qdq", "block_scaled_tensor_scale", "block_scaled_float_class", "block_scaled_check", "NVFP4",
     "BLOCK_SCALED_CHAIN_BY_DEFAULT",
     "channel_sumsq", "channel_sumsq_workspace_bytes", "wanda_score", "wanda_nm_sparsify", "wanda_class", "WANDA_CHAIN_BY_DEFAULT",
@@ -1105,6 +1106,192 @@ def dynamic_fixed_qdq(x, fmt, granularity: str = "per_token", group_size: Option
         return _DynamicSTE.apply(x, run)
     with torch.no_grad():
         return run(x.detach())
+
+
+# ---------------------------------------------------------------------------------------------------- learned step size (LSQ / LSQ+)
+# Launch geometries of dmxq_lsq_backward (lsq_class) that fused=None sends to the chain of torch operations although the kernel takes
+# them: DYNAMIC_CHAIN_BY_DEFAULT's rule -- a class goes to the kernel by default only where tools/bench_lsq.py MEASURED it faster than the
+# chain on the same buffers; a class that is not gets listed here with its row.  profiles/r19_lsq.txt (bf16 XP[4,0] affine, us per call,
+# kernel against chain): group (128) [8192,4096] 50.2 against 1676.9, [8192,14336] 147.9 against 5703.5, [2048,768] 6.0 against 160.4;
+# wave_row [8192,4096] 50.3 against 1648.0, [2048,768] 6.8 against 158.7; block_row [8192,14336] 135.6 against 5665.7; tensor [8192,4096]
+# 57.9 against 1663.5, [8192,14336] 148.3 against 5669.8, [2048,768] 8.4 against 163.5, [60000,48] 11.4 against 215.1; short_row [60000,48]
+# 39.6 against 218.1 (5 % of 8 TB/s: most lanes idle, still 5.5 x the chain) -- every class is faster, none is listed.
+LSQ_CHAIN_BY_DEFAULT = frozenset()
+# which route the calls of this front end took, counted on the host: private, for the tests (fused=True must have run the kernel)
+_lsq_routes = {"fused": 0, "chain": 0}
+_LSQ_CLASS_NAMES = dict(_DYNAMIC_CLASS_NAMES)
+_LSQ_CLASS_NAMES[6] = "tensor"   # DMXQ_LSQ_TENSOR (include/dmxq.h)
+_LSQ_MODE = {"per_group": 0, "per_token": 1, "per_tensor": 2}   # dmxq_lsq_backward's whole_rows
+
+
+def lsq_class(segment: int, dtype: torch.dtype, granularity: str) -> Optional[str]:
+    """the launch geometry dmxq_lsq_backward picks for segments of `segment` elements of `dtype` under `granularity`, asked of the library
+    itself (dmxq_lsq_class; no GPU involved), or None when it refuses them: dynamic_class's names for per_group / per_token, "tensor"
+    (one segment over the grid, partial rows folded by a second launch) for per_tensor"""
+    from ._lib import dtype_code, lib
+    if granularity not in _LSQ_MODE:
+        raise ValueError(f"lsq_class: granularity must be one of {DYNAMIC_GRANULARITIES}, got {granularity!r}")
+    return _LSQ_CLASS_NAMES.get(lib().dmxq_lsq_class(dtype_code(dtype), int(segment), _LSQ_MODE[granularity]))
+
+
+def lsq_scratch_bytes(n: int) -> int:
+    """dmxq_lsq_scratch_bytes: the scratch a per_tensor dmxq_lsq_backward over n elements needs (16 bytes per workgroup).  A host
+    function: no GPU involved."""
+    from ._lib import lib
+    return int(lib().dmxq_lsq_scratch_bytes(int(n)))
+
+
+def lsq_grad_factor(grad_scale, segment: int, qmax: int) -> float:
+    """grad_scale's three spellings -> the factor k of the definition: "lsq" 1 / sqrt(segment * qmax) (Esser et al., 2020), None 1, a
+    float as given"""
+    if grad_scale is None:
+        return 1.0
+    if isinstance(grad_scale, str):
+        if grad_scale != "lsq":
+            raise ValueError(f"lsq: grad_scale must be 'lsq', None or a float, got {grad_scale!r}")
+        return 1.0 / math.sqrt(float(segment) * float(qmax)) if segment > 0 else 1.0
+    if isinstance(grad_scale, bool) or not isinstance(grad_scale, (int, float)):
+        raise ValueError(f"lsq: grad_scale must be 'lsq', None or a float, got {grad_scale!r}")
+    return float(grad_scale)
+
+
+def _lsq_segment(x, fmt, granularity, group_size, what):
+    """-> (format, S): dynamic_check plus the shape rules, ValueError before any GPU use"""
+    fmt, granularity, group_size = dynamic_check(fmt, granularity, group_size, what=what)
+    if fmt.rounding != "nearest":
+        raise ValueError(f"{what}: a learned step size is defined for nearest rounding, got {fmt!r}")
+    if x.dim() < 1:
+        raise ValueError(f"{what}: expects a tensor with at least one dimension")
+    L = x.shape[-1]
+    if granularity == "per_group" and L % group_size:
+        raise ValueError(f"{what}: the last dimension has {L} elements, not a multiple of the group size {group_size}")
+    return fmt, {"per_token": L, "per_group": group_size, "per_tensor": x.numel()}[granularity]
+
+
+def _lsq_params(scale, zero_point, n_seg, what):
+    for name, t in (("scale", scale), ("zero_point", zero_point)):
+        if not isinstance(t, torch.Tensor) or not t.is_floating_point() or t.numel() != n_seg:
+            raise ValueError(f"{what}: {name} must be a floating point tensor of {n_seg} entries (one per segment), got "
+                             f"{tuple(t.shape) if isinstance(t, torch.Tensor) else t!r}")
+
+
+def _lsq_zq(zero_point, qmin, qmax):
+    return torch.clamp(torch.round(zero_point.detach().float().reshape(-1)), qmin, qmax)
+
+
+def lsq_backward(x, g, scale, zero_point, fmt, granularity: str = "per_token", group_size: Optional[int] = None, grad_factor: float = 1.0,
+                 want_dz: bool = True, fused: Optional[bool] = None, want_dx: bool = True):
+    """The backward pass of a learned step size integer cast (LSQ / LSQ+; DESIGN.md §8 "Learned step size") -> (dx, ds, dz): dx in x's
+    dtype and shape (None without want_dx: nothing is stored), ds / dz float32 [n_segments] (dz None without want_dz).  Segments as in dynamic_fixed_qdq; scale / zero_point:
+    float tensors of n_segments entries; (qmin, qmax) = observer.get_qmin_qmax(fmt); zq = clamp(rint(z), qmin, qmax).  Per element,
+    every operation float32 in this order:
+        v = x / s + zq;  r = the forward's nearest rounding of v;  in = qmin <= r <= qmax;  q = clamp(r, qmin, qmax)
+        dx = in ? g : 0;  e = in ? q - v : q - zq;  ts = g * e;  tz = in ? 0 : -(g * s)
+    and per segment ds = float(grad_factor * sum float64(ts)), dz = float(grad_factor * sum float64(tz)).
+    ONE launch (dmxq_lsq_backward: one read of x and g, one write of dx) where x and g share one dtype and are 16-byte aligned and the
+    segment is one of lsq_class's geometries; else the chain: the same definition in torch operations on the device, same dx bit for
+    bit, ds / dz up to the order of a float64 sum.  fused=None: the kernel where it applies and its geometry is not listed in
+    LSQ_CHAIN_BY_DEFAULT; True: NotImplementedError instead of falling back; False: the chain.  ValueError before any GPU use."""
+    from .observer import get_qmin_qmax
+    fmt, S = _lsq_segment(x, fmt, granularity, group_size, "lsq_backward")
+    if g.shape != x.shape:
+        raise ValueError(f"lsq_backward: g has shape {tuple(g.shape)}, x has {tuple(x.shape)}")
+    n_seg = x.numel() // S if S else 0
+    _lsq_params(scale, zero_point, n_seg, "lsq_backward")
+    require_gpu(x, "lsq_backward")
+    require_gpu(g, "lsq_backward")
+    qmin, qmax = get_qmin_qmax(fmt)
+    with torch.no_grad():
+        xc, gc = x.detach(), g.detach()
+        xc = xc if xc.is_contiguous() else xc.contiguous()
+        gc = gc if gc.is_contiguous() else gc.contiguous()
+        s = scale.detach().float().reshape(-1).contiguous()
+        z = zero_point.detach().float().reshape(-1).contiguous()
+        if xc.numel() == 0:
+            return (torch.empty_like(xc) if want_dx else None), s.new_zeros(n_seg), (s.new_zeros(n_seg) if want_dz else None)
+        if fused is not False:
+            cls = lsq_class(S, xc.dtype, granularity) if (gc.dtype == xc.dtype and fmt.precision <= 22 and xc.data_ptr() % 16 == 0
+                                                           and gc.data_ptr() % 16 == 0) else None
+            if cls is None and fused:
+                raise NotImplementedError(f"lsq_backward: no fused kernel for segments of {S} {xc.dtype} elements ({granularity}) with a "
+                                          f"{gc.dtype} gradient and {fmt!r} (base addresses {xc.data_ptr() % 16} / {gc.data_ptr() % 16} mod 16)")
+            if cls is not None and fused is None and cls in LSQ_CHAIN_BY_DEFAULT:
+                cls = None
+            if cls is not None:
+                try:
+                    dx, ds, dz = _ops.lsq_backward(xc, gc, s, z, S, _LSQ_MODE[granularity], fmt.precision, ROUNDING_CODE[fmt.rounding], qmin, qmax,
+                                                   float(grad_factor), bool(want_dz), bool(want_dx))
+                    _lsq_routes["fused"] += 1
+                    return (dx if want_dx else None), ds, (dz if want_dz else None)
+                except NotImplementedError:   # (DMXQ_ERR_UNSUPPORTED, nothing launched)
+                    if fused:
+                        raise
+        _lsq_routes["chain"] += 1
+        # the definition, spelled in torch on the device
+        x2, g2 = xc.reshape(-1, S).float(), gc.reshape(-1, S).float()
+        sc, zq = s[:, None], _lsq_zq(z, qmin, qmax)[:, None]
+        v = x2 / sc + zq
+        r = torch.round((v + 0.5).double() - 0.5).float()
+        inside = (r >= qmin) & (r <= qmax)
+        q = torch.clamp(r, qmin, qmax)
+        dx = torch.where(inside, g2, torch.zeros_like(g2)).to(xc.dtype).reshape(xc.shape) if want_dx else None
+        ts = g2 * torch.where(inside, q - v, q - zq)
+        ds = (ts.sum(dim=1, dtype=torch.float64) * float(grad_factor)).float()
+        dz = None
+        if want_dz:
+            tz = torch.where(inside, torch.zeros_like(g2), -(g2 * sc))
+            dz = (tz.sum(dim=1, dtype=torch.float64) * float(grad_factor)).float()
+        return dx, ds, dz
+
+
+class _LsqCast(torch.autograd.Function):
+    """forward: the static affine cast (ops.fixed_qdq, one scale per segment); backward: lsq_backward, only the gradients that are needed"""
+
+    @staticmethod
+    def forward(ctx, x, scale, zero_point, fmt, granularity, group_size, S, k, out_dtype, fused):
+        from .observer import get_qmin_qmax
+        qmin, qmax = get_qmin_qmax(fmt)
+        xd = x.detach()
+        xc = xd if xd.is_contiguous() else xd.contiguous()
+        zq = _lsq_zq(zero_point, qmin, qmax).to(torch.int64)
+        s = scale.detach().float().reshape(-1).contiguous()
+        if xc.numel() == 0:
+            y = torch.empty(xc.shape, dtype=out_dtype, device=xc.device)
+        else:
+            y = fixed_qdq(xc.reshape(-1, S), fmt.precision, fmt.fraction, fmt.clamp, fmt.symmetric, fmt.rounding, scale=s, zero_point=zq, ch_axis=0,
+                          out_dtype=out_dtype).reshape(xc.shape)
+        ctx.save_for_backward(xc, scale, zero_point)
+        ctx.args = (fmt, granularity, group_size, k, fused, x.dtype)
+        return y
+
+    @staticmethod
+    def backward(ctx, g):
+        xc, scale, zero_point = ctx.saved_tensors
+        fmt, granularity, group_size, k, fused, in_dtype = ctx.args
+        need_x, need_s, need_z = ctx.needs_input_grad[:3]
+        if g.dtype != in_dtype:
+            g = g.to(in_dtype)
+        dx, ds, dz = lsq_backward(xc, g, scale, zero_point, fmt, granularity, group_size, grad_factor=k, want_dz=bool(need_z), fused=fused,
+                                  want_dx=bool(need_x))
+        return (dx, ds.reshape(scale.shape).to(scale.dtype) if need_s else None,
+                dz.reshape(zero_point.shape).to(zero_point.dtype) if need_z else None, None, None, None, None, None, None, None)
+
+
+def lsq_fixed_qdq(x, scale, zero_point, fmt, granularity: str = "per_token", group_size: Optional[int] = None, grad_scale="lsq",
+                  out_dtype: Optional[torch.dtype] = None, fused: Optional[bool] = None):
+    """Integer Q->DQ with a LEARNED scale and zero point per segment (LSQ / LSQ+; DESIGN.md §8 "Learned step size"; segments as in
+    dynamic_fixed_qdq).  Forward, bit for bit the static affine cast:
+        y = fixed_qdq(x.reshape(-1, S), fmt..., scale=s, zero_point=clamp(rint(z), qmin, qmax).to(int64), ch_axis=0).reshape(x.shape)
+    Backward: lsq_backward with grad_factor from grad_scale ("lsq": 1 / sqrt(S * qmax); None: 1; a float as given) -- x.grad is the
+    clipped straight-through estimator, scale.grad / zero_point.grad come in the parameters' shapes, and only the gradients autograd
+    asks for are formed.  fused: lsq_backward's.  ValueError before any GPU use: dynamic_check's cases, a format without nearest
+    rounding, parameters that are not one entry per segment."""
+    from .observer import get_qmin_qmax
+    fmt, S = _lsq_segment(x, fmt, granularity, group_size, "lsq_fixed_qdq")
+    _lsq_params(scale, zero_point, x.numel() // S if S else 0, "lsq_fixed_qdq")
+    k = lsq_grad_factor(grad_scale, S, get_qmin_qmax(fmt)[1])
+    require_gpu(x, "lsq_fixed_qdq")
+    return _LsqCast.apply(x, scale, zero_point, fmt, granularity, group_size, S, k, out_dtype or x.dtype, fused)
 
 
 # ---------------------------------------------------------------------------------------------------- dynamic scaled float cast

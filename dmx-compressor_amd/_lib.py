@@ -93,6 +93,10 @@ SIGNATURES = {
     "dmxq_block_scaled_float_class": [_i32, _i64],
     "dmxq_block_scaled_tensor_scale": [_vp, _i32, _i64, _f32, _f32, _vp, _vp],
     "dmxq_block_scaled_float_qdq": [_vp, _vp, _i32, _i32, _i64, _i64, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _f32, _vp, _vp, _vp, _vp],
+    "dmxq_lsq_class": [_i32, _i64, _i32],
+    "dmxq_lsq_scratch_bytes": [_i64],
+    "dmxq_lsq_backward": [_vp, _vp, _vp, _i32, _i32, _i32, _i64, _i64, _i32, _i32, _i32, _i32, _i32, _vp, _vp, ctypes.c_double, _i32, _vp, _vp, _vp, _i64,
+                          _vp],
     "dmxq_row_class_of": [_i32, _i32, _i32, _i32, _i64, _i64, _vp, _vp, _vp, _vp, _i32, _i64, _vp],
 }
 
@@ -169,6 +173,7 @@ def lib():
         L.dmxq_topk_workspace_bytes.restype = ctypes.c_int64
         L.dmxq_error_scratch_bytes.restype = ctypes.c_int64
         L.dmxq_channel_sumsq_workspace_bytes.restype = ctypes.c_int64
+        L.dmxq_lsq_scratch_bytes.restype = ctypes.c_int64
         L.dmxq_status_string.argtypes = [ctypes.c_int]
         L.dmxq_status_string.restype = ctypes.c_char_p
         L.dmxq_abi_version.restype = ctypes.c_int

@@ -19,6 +19,11 @@ from .observer import _PER_CHANNEL, _SYMMETRIC, DummyObserver, HistogramObserver
 
 __all__ = ["CastToFormat", "CastTo", "CastToDict"]
 
+_LEARNED_SCALE_MIN = float(torch.finfo(torch.float32).eps)   # learned_scale is clamped from below to this before every forward
+_LEARNABLE_HADAMARD = ("CastTo: learned scales (set_learnable) under a 'hadamard' pre_transform are not supported: the fused rotated cast "
+                       "reads the stored scale / zero_point buffers, and the rotated straight-through estimator would give the learned "
+                       "parameters no gradient; drop one of the two settings")
+
 
 class CastToFormat(Function):
     """Numerical cast with a straight-through-estimator backward (cast.py:20-32)."""
@@ -165,6 +170,11 @@ class CastTo(HostFlags, torch.nn.Module):
     #: None, or (scale_format, scale_max, tensor_scale) beside a per_group _scaling: the group scales are quantised to scale_format under
     #: one float32 scale per tensor (ops.block_scaled_float_qdq).  A plain attribute as well.
     _block_scale = None
+    #: None, or {"granularity", "group_size", "learn_zero_point", "grad_scale", "init"}: an integer format is cast with a LEARNED scale and
+    #: zero point per segment (set_learnable; DESIGN.md §8 "Learned step size").  The two nn.Parameters exist only while this is set.
+    _learnable = None
+    #: the learned parameters still wait for their data-dependent initial values (filled in place by the first forward): a host flag
+    _learnable_pending = False
 
     def __init__(self, format="SAME", observer=DummyObserver, group_size=None, block_dim=-1,
                  qscheme=torch.per_tensor_affine, ch_axis=-1, **observer_kwargs):
@@ -211,6 +221,10 @@ class CastTo(HostFlags, torch.nn.Module):
             ops.dynamic_float_check(format, *self._scaling[:2], what="CastTo.set_format on a scaled cast")
             if self._block_scale is not None:
                 ops.block_scaled_check(format, self._scaling[1], *self._block_scale, what="CastTo.set_format on a scaled cast")
+        if self._learnable is not None and not isinstance(format, Same):
+            f_ = ops.dynamic_check(format, self._learnable["granularity"], self._learnable["group_size"], what="CastTo.set_format on a learnable cast")[0]
+            if f_.rounding != "nearest":
+                raise ValueError(f"CastTo.set_format on a learnable cast: a learned step size is defined for nearest rounding, got {f_!r}")
         self.format = format
         if hasattr(self, "activation_post_process"):
             self.activation_post_process.dtype = format
@@ -229,6 +243,9 @@ class CastTo(HostFlags, torch.nn.Module):
             # an orthonormal block-Hadamard rotation along block_dim around the cast (ops.hadamard_qdq): 64, or
             # {"size": 64, "inverse": False} to leave the result in the rotated basis; a bad size raises ValueError here
             self.pre_transform["hadamard"] = _parse_hadamard(self.pre_transform["hadamard"])
+            if self._learnable is not None:
+                self.pre_transform.pop("hadamard")
+                raise ValueError(_LEARNABLE_HADAMARD)
 
     def set_dynamic(self, granularity=None, group_size=None):
         """Dynamic scales (not in the reference): with fake-quant on and the observer off, an integer format is cast with a
@@ -239,6 +256,8 @@ class CastTo(HostFlags, torch.nn.Module):
         calibration path runs as ever.  ValueError for an unknown granularity and for a format without an integer range -- here, or in
         set_format when the format comes later (a cast that is still SAME accepts the setting)."""
         dyn = _parse_dynamic(granularity, group_size)
+        if dyn is not None and self._learnable is not None:
+            raise ValueError("CastTo.set_dynamic: this cast has learned scales (set_learnable), an exclusive source: set_learnable(None) first")
         if dyn is not None:
             if isinstance(self.format, Same):
                 ops.dynamic_check("XP[8,0](CSN)", *dyn, what="CastTo.set_dynamic")   # (the granularity alone)
@@ -258,6 +277,112 @@ class CastTo(HostFlags, torch.nn.Module):
         g, gs = self._dynamic
         return ops.dynamic_fixed_qdq(x, self.format, g, gs, symmetric_qscheme=self.qscheme in _SYMMETRIC, out_dtype=out_dtype)
 
+    # ------------------------------------------------------------------ learned step size (LSQ / LSQ+)
+    def set_learnable(self, granularity=None, group_size=None, learn_zero_point: bool = False, grad_scale="lsq", init: str = "minmax",
+                      like: Optional[torch.Tensor] = None):
+        """Learned step size (LSQ, Esser et al. 2020; LSQ+, Bhalgat et al. 2020; not in the reference): with fake-quant on
+        and the observer off, an integer format is cast with a scale and a zero point that are nn.Parameters of this cast --
+        `learned_scale` and `learned_zero_point`, float32 [n_segments], the second trained only with learn_zero_point -- through
+        ops.lsq_fixed_qdq: the forward is the static affine cast with those values, the backward clips the gradient of x to the
+        integer range and gives the parameters theirs (grad_scale: "lsq" = 1 / sqrt(segment * qmax), None, or a float).  Segments as in
+        set_dynamic: "per_token" (per output channel of an [out, in] weight), "per_group" with group_size (or {"per_group": g}),
+        "per_tensor".  The parameters are registered HERE and nowhere else: an untouched cast keeps its four buffers.
+        like: the tensor this cast will see (DmxModule passes its weight): it fixes n_segments.  Without it only "per_tensor" is
+        possible -- an activation's per-token or per-group scales have no fixed shape to register: ValueError.
+        init: "minmax" -- the (scale, zero point) ops.dynamic_fixed_qdq derives for the tensor, so the first forward equals the dynamic
+        cast of the same granularity bit for bit; "lsq" -- s = 2 mean|x| / sqrt(qmax), z = 0.  From `like` at once where it lives on the
+        GPU, else from the first tensor the cast sees (in place, under no_grad; a host flag guards it, which loading a state_dict that
+        carries the parameters clears).
+        Exclusive with set_dynamic and set_scaling, and with a "hadamard" pre_transform, whose fused rotated cast reads the stored
+        scale buffers (ValueError in either order).  None removes the parameters and returns to the
+        stored scales.  While the observer is enabled the calibration path runs as ever."""
+        lrn = _parse_dynamic(granularity, group_size)
+        if lrn is None:
+            for n in ("learned_scale", "learned_zero_point"):
+                if n in self._parameters:
+                    del self._parameters[n]
+            self._learnable, self._learnable_pending = None, False
+            return
+        if "hadamard" in self.pre_transform:
+            raise ValueError(_LEARNABLE_HADAMARD)
+        if self._dynamic is not None or self._scaling is not None:
+            raise ValueError("CastTo.set_learnable: this cast derives its scales from every tensor (set_dynamic / set_scaling); a learned "
+                             "scale is a third, exclusive source: switch that off first")
+        fmt = "XP[8,0](CSN)" if isinstance(self.format, Same) else self.format   # (SAME: the granularity alone)
+        fmt, g, gs = ops.dynamic_check(fmt, *lrn, what="CastTo.set_learnable")
+        if fmt.rounding != "nearest":
+            raise ValueError(f"CastTo.set_learnable: a learned step size is defined for nearest rounding, got {fmt!r}")
+        if init not in ("minmax", "lsq"):
+            raise ValueError(f"CastTo.set_learnable: init must be 'minmax' or 'lsq', got {init!r}")
+        if not isinstance(learn_zero_point, bool):
+            raise ValueError(f"CastTo.set_learnable: learn_zero_point must be a bool, got {learn_zero_point!r}")
+        ops.lsq_grad_factor(grad_scale, 1, 1)   # (ValueError for a bad spelling)
+        if like is None:
+            if g != "per_tensor":
+                raise ValueError(f"CastTo.set_learnable: {g!r} needs like= (the tensor this cast will see, e.g. a weight): the learned scales "
+                                 "are parameters of a fixed shape, and a per-token or per-group scale of an activation has none -- "
+                                 "activation casts take 'per_tensor' only")
+            n_seg, dev = 1, self.scale.device
+        else:
+            if like.dim() < 1 or like.numel() == 0:
+                raise ValueError("CastTo.set_learnable: like must be a non-empty tensor with at least one dimension")
+            if g == "per_group" and like.shape[-1] % gs:
+                raise ValueError(f"CastTo.set_learnable: the last dimension of like has {like.shape[-1]} elements, not a multiple of the "
+                                 f"group size {gs}")
+            n_seg = {"per_token": like.numel() // like.shape[-1], "per_group": like.numel() // (gs or 1), "per_tensor": 1}[g]
+            dev = like.device
+        self._learnable = {"granularity": g, "group_size": gs, "learn_zero_point": learn_zero_point, "grad_scale": grad_scale, "init": init}
+        self.register_parameter("learned_scale", torch.nn.Parameter(torch.ones(n_seg, dtype=torch.float32, device=dev)))
+        self.register_parameter("learned_zero_point", torch.nn.Parameter(torch.zeros(n_seg, dtype=torch.float32, device=dev),
+                                                                         requires_grad=learn_zero_point))
+        self._learnable_pending = True
+        if like is not None and like.is_cuda and not isinstance(self.format, Same):
+            self._learnable_init(like)
+
+    @property
+    def learnable(self):
+        """None, or the setting: {"granularity": "per_token" | "per_tensor" | {"per_group": g}, "learn_zero_point", "grad_scale", "init"}"""
+        lrn = self._learnable
+        if lrn is None:
+            return None
+        g = {"per_group": lrn["group_size"]} if lrn["granularity"] == "per_group" else lrn["granularity"]
+        return {"granularity": g, "learn_zero_point": lrn["learn_zero_point"], "grad_scale": lrn["grad_scale"], "init": lrn["init"]}
+
+    def _learnable_init(self, x):
+        """fills learned_scale / learned_zero_point in place from the tensor x (set_learnable's init rules); nothing is read back"""
+        from .observer import get_qmin_qmax
+        lrn = self._learnable
+        g, gs = lrn["granularity"], lrn["group_size"]
+        with torch.no_grad():
+            xd = x.detach()
+            if lrn["init"] == "minmax":
+                _, sc, zp = ops.dynamic_fixed_qdq(xd, self.format, g, gs, symmetric_qscheme=self.qscheme in _SYMMETRIC, return_qparams=True)
+                zp = zp.float()
+            else:
+                S = {"per_token": xd.shape[-1], "per_group": gs, "per_tensor": xd.numel()}[g]
+                sc = xd.reshape(-1, S).float().abs().mean(dim=1) * (2.0 / float(get_qmin_qmax(self.format)[1]) ** 0.5)
+                zp = torch.zeros_like(sc)
+            if sc.numel() != self.learned_scale.numel():
+                raise ValueError(f"CastTo: the learned scales were registered for {self.learned_scale.numel()} segments, this tensor has "
+                                 f"{sc.numel()} ({g}, shape {tuple(x.shape)})")
+            self.learned_scale.data.copy_(sc.reshape(self.learned_scale.shape))
+            self.learned_zero_point.data.copy_(zp.reshape(self.learned_zero_point.shape))
+        self._learnable_pending = False
+
+    def _learnable_cast(self, x, out_dtype):
+        lrn = self._learnable
+        if self._learnable_pending:
+            self._learnable_init(x)
+        with torch.no_grad():
+            self.learned_scale.data.clamp_(min=_LEARNED_SCALE_MIN)
+        return ops.lsq_fixed_qdq(x, self.learned_scale, self.learned_zero_point, self.format, lrn["granularity"], lrn["group_size"],
+                                 grad_scale=lrn["grad_scale"], out_dtype=out_dtype)
+
+    def _load_from_state_dict(self, state_dict, prefix, *args, **kwargs):
+        if self._learnable is not None and prefix + "learned_scale" in state_dict:
+            self._learnable_pending = False   # (the loaded values are the initial values)
+        super()._load_from_state_dict(state_dict, prefix, *args, **kwargs)
+
     def set_scaling(self, granularity=None, group_size=None, pow2_scale: bool = False):
         """Dynamic float scales (not in the reference): with fake-quant on and the observer off, a FloatingPoint format is
         cast as float_q(x / s) * s with s = the segment's absolute maximum over the format's largest value, derived from the tensor
@@ -274,6 +399,8 @@ class CastTo(HostFlags, torch.nn.Module):
         per_group only and not with pow2_scale: ValueError otherwise."""
         granularity, block = _split_block_scale(granularity)
         sc = _parse_scaling(granularity, group_size, pow2_scale)
+        if sc is not None and self._learnable is not None:
+            raise ValueError("CastTo.set_scaling: this cast has learned scales (set_learnable), an exclusive source: set_learnable(None) first")
         if block is not None:
             if sc is None or sc[0] != "per_group":
                 raise ValueError(f"set_scaling: scale_format / scale_max / tensor_scale quantise the scales of GROUPS: give "
@@ -397,6 +524,8 @@ class CastTo(HostFlags, torch.nn.Module):
             return self._dynamic_cast(x, out_dtype)   # (a straight-through estimator under autograd by itself)
         if self._scaling is not None and isinstance(fmt, FloatingPoint) and not self.__dict__["_h_observer_enabled"]:
             return self._scaled_cast(x, out_dtype)    # (the same)
+        if self._learnable is not None and isinstance(fmt, FixedPoint) and not self.__dict__["_h_observer_enabled"]:
+            return self._learnable_cast(x, out_dtype)   # (ops.lsq_fixed_qdq: an autograd Function with the LSQ backward)
         if isinstance(fmt, FixedPoint):
             # per-tensor: one scale; per-channel: scale[c]; per-group: scale[c // group_size] (cast.py:279-293)
             if self.group_size:
@@ -518,9 +647,10 @@ class CastTo(HostFlags, torch.nn.Module):
             raise NotImplementedError("CastTo.measure_error: a cast with a pre_transform other than hadamard (shaping / shortcut / pre-format)")
         fmt, x = self.format, x.detach()
         dyn_cast = self._dynamic_cast if self._dynamic is not None and isinstance(fmt, FixedPoint) else \
-            self._scaled_cast if self._scaling is not None and isinstance(fmt, FloatingPoint) else None
+            self._scaled_cast if self._scaling is not None and isinstance(fmt, FloatingPoint) else \
+            self._learnable_cast if self._learnable is not None and isinstance(fmt, FixedPoint) else None
         if dyn_cast is not None:
-            # a dynamic / scaled cast: the cast itself (between the two rotations of a "hadamard" pre_transform), then ops.error_stats
+            # a dynamic / scaled / learnable cast: the cast itself (between the two rotations of a "hadamard" pre_transform), then ops.error_stats
             with torch.no_grad():
                 had = self.pre_transform.get("hadamard")
                 if had is None:
@@ -560,7 +690,8 @@ class CastTo(HostFlags, torch.nn.Module):
         return f"format = dtype = {self.format!r}, qscheme = {self.qscheme}, ch_axis = {self.ch_axis}, " \
                f"group_size = {self.group_size}, block_dim = {self.block_dim}" \
                + (f", dynamic = {self.dynamic!r}" if self._dynamic is not None else "") \
-               + (f", scaling = {self.scaling!r}" if self._scaling is not None else "")
+               + (f", scaling = {self.scaling!r}" if self._scaling is not None else "") \
+               + (f", learnable = {self.learnable!r}" if self._learnable is not None else "")
 
 
 class CastToDict(torch.nn.ModuleDict):

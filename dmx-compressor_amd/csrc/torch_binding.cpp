@@ -1036,6 +1036,41 @@ std::tuple<Tensor, Tensor, Tensor> dynamic_fixed_qdq_meta(const Tensor& x, int64
   return std::make_tuple(empty_like_shape(x, out_dtype), at::empty({n}, x.options().dtype(at::kFloat)), at::empty({n}, x.options().dtype(at::kLong)));
 }
 
+// ------------------------------------------------------------------------------------------------ learned step size (backward)
+// x, g: contiguous, one shape, numel % segment == 0; scale, zero_point: float32 [n_segments]; whole_rows: 0 groups, 1 rows, 2 the whole
+// tensor (the partial rows' scratch is allocated here) -> (dx, empty unless want_dx: then nothing is stored; ds float32 [n_segments];
+// dz float32 [n_segments], empty unless want_dz).
+// DMXQ_ERR_UNSUPPORTED (NotImplementedError, nothing launched): the front end runs its chain of torch operations.
+std::tuple<Tensor, Tensor, Tensor> lsq_backward(const Tensor& x, const Tensor& g, const Tensor& scale, const Tensor& zero_point, int64_t segment,
+                                                int64_t whole_rows, int64_t precision, int64_t rounding, int64_t qmin, int64_t qmax,
+                                                double grad_factor, bool want_dz, bool want_dx) {
+  const Tensor xc = prep(x, "lsq_backward"), gc = prep(g, "lsq_backward");
+  TORCH_CHECK(gc.device() == xc.device() && gc.numel() == xc.numel(), "lsq_backward: x and g must hold the same number of elements on one device");
+  TORCH_CHECK(segment >= 1 && xc.numel() % segment == 0, "lsq_backward: the segment must divide the number of elements");
+  const int64_t n = xc.numel() / segment;
+  TORCH_CHECK(scale.is_cuda() && scale.device() == xc.device() && scale.scalar_type() == at::kFloat && scale.is_contiguous() && scale.numel() == n &&
+              zero_point.is_cuda() && zero_point.device() == xc.device() && zero_point.scalar_type() == at::kFloat && zero_point.is_contiguous() &&
+              zero_point.numel() == n, "lsq_backward: scale and zero_point must be contiguous float32 tensors of ", n, " entries on x's GPU");
+  Tensor dx = want_dx ? empty_like_shape(xc, c10::nullopt) : at::empty({0}, xc.options());
+  Tensor ds = at::empty({n}, xc.options().dtype(at::kFloat));
+  Tensor dz = at::empty({want_dz ? n : 0}, xc.options().dtype(at::kFloat));
+  const int64_t sb = whole_rows == 2 ? dmxq_lsq_scratch_bytes(segment) : 0;
+  Tensor scratch = at::empty({sb / 8}, xc.options().dtype(at::kDouble));
+  Launch l(xc);
+  check(dmxq_lsq_backward(xc.data_ptr(), gc.data_ptr(), want_dx ? dx.data_ptr() : nullptr, dt_code(xc.scalar_type()), dt_code(gc.scalar_type()),
+                          dt_code(dx.scalar_type()), n, segment, (int)whole_rows, (int)precision, (int)rounding, (int)qmin, (int)qmax,
+                          (const float*)scale.data_ptr(), (const float*)zero_point.data_ptr(), grad_factor, want_dz ? 1 : 0,
+                          (float*)ds.data_ptr(), want_dz ? (float*)dz.data_ptr() : nullptr, sb ? scratch.data_ptr() : nullptr, sb, l.stream),
+        "dmxq_lsq_backward");
+  return std::make_tuple(dx, ds, dz);
+}
+std::tuple<Tensor, Tensor, Tensor> lsq_backward_meta(const Tensor& x, const Tensor&, const Tensor&, const Tensor&, int64_t segment, int64_t, int64_t,
+                                                     int64_t, int64_t, int64_t, double, bool want_dz, bool want_dx) {
+  const int64_t n = segment >= 1 ? x.numel() / segment : 0;
+  return std::make_tuple(want_dx ? empty_like_shape(x, c10::nullopt) : at::empty({0}, x.options()), at::empty({n}, x.options().dtype(at::kFloat)),
+                         at::empty({want_dz ? n : 0}, x.options().dtype(at::kFloat)));
+}
+
 // ------------------------------------------------------------------------------------------------ dynamic scaled float cast
 // x: contiguous; mode: dmxq_dynamic_float_mode; -> (out, scale float32 [n_segments], or [..., R / g, C / g] for tiles; empty unless
 // want_scale).  DMXQ_ERR_UNSUPPORTED (NotImplementedError, nothing launched): the front end runs its chain of launches.
@@ -1249,6 +1284,7 @@ TORCH_LIBRARY(dmxq, m) {
   m.def("awq_group_error(Tensor w, Tensor s, int group, int precision, int fraction, bool clamp, bool symmetric, int qmin, int qmax, bool symmetric_qscheme, bool want_wq) -> (Tensor, Tensor)");
   m.def("block_scaled_float_qdq(Tensor x, int group, int[] fmt, int[] scale_fmt, float scale_max, Tensor? tensor_scale, bool want_scale, bool want_code, ScalarType? out_dtype=None) -> (Tensor, Tensor, Tensor)");
   m.def("block_scaled_tensor_scale(Tensor x, float fmax, float scale_max) -> Tensor");
+  m.def("lsq_backward(Tensor x, Tensor g, Tensor scale, Tensor zero_point, int segment, int whole_rows, int precision, int rounding, int qmin, int qmax, float grad_factor, bool want_dz, bool want_dx) -> (Tensor, Tensor, Tensor)");
 }
 
 #define DMXQ_IMPL(m, name) m.impl(#name, &name)
@@ -1259,7 +1295,8 @@ TORCH_LIBRARY(dmxq, m) {
   X(m, histc); X(m, channel_maxabs); X(m, smoothquant_scale); X(m, scale_channels); X(m, unary); X(m, rope); X(m, rope_cast); X(m, softmax); X(m, norm); \
   X(m, unary_cast); X(m, unary_cast_table); X(m, lut16_apply); X(m, softmax_cast); X(m, norm_cast); X(m, group_minmax_accumulate); X(m, gptq_block); X(m, hist_observe); X(m, hist_qparams); \
   X(m, error_stats); X(m, cast_error); X(m, hadamard_qdq); X(m, dynamic_fixed_qdq); X(m, gptq_block_dynamic); X(m, dynamic_float_qdq); \
-  X(m, channel_sumsq); X(m, wanda_nm); X(m, channel_sumabs); X(m, awq_group_error); X(m, block_scaled_float_qdq); X(m, block_scaled_tensor_scale)
+  X(m, channel_sumsq); X(m, wanda_nm); X(m, channel_sumabs); X(m, awq_group_error); X(m, block_scaled_float_qdq); X(m, block_scaled_tensor_scale); \
+  X(m, lsq_backward)
 
 // "CUDA" is the dispatch key of HIP tensors in a ROCm build of PyTorch
 TORCH_LIBRARY_IMPL(dmxq, CUDA, m) {
@@ -1323,4 +1360,5 @@ PYBIND11_MODULE(dmxq_fast, m) {
   m.def("block_scaled_float_qdq", &block_scaled_float_qdq, py::arg("x"), py::arg("group"), py::arg("fmt"), py::arg("scale_fmt"), py::arg("scale_max"),
         py::arg("tensor_scale"), py::arg("want_scale"), py::arg("want_code"), py::arg("out_dtype") = py::none());
   m.def("block_scaled_tensor_scale", &block_scaled_tensor_scale);
+  m.def("lsq_backward", &lsq_backward);
 }

@@ -33,10 +33,20 @@ def refuse_scaled_weight_cast(module):
                                   "dynamic integer cast (weight_dynamic)")
 
 
+def refuse_learnable_weight_cast(module, what):
+    """GPTQ, AWQ, Wanda and folding on a module whose weight cast has learned scales (CastTo.set_learnable): NotImplementedError"""
+    wc = getattr(module, "weight_cast", None)
+    if wc is not None and wc._learnable is not None:
+        raise NotImplementedError(f"{what} with a learnable weight cast (weight_learnable = {wc.learnable!r}) is not supported: the scales "
+                                  "are parameters that training moves, not values a calibration may assume; clear the setting "
+                                  "(set_learnable(None)) first")
+
+
 class OptimalBrainCompressor:
     H = None
 
     def __init__(self, module):
+        refuse_learnable_weight_cast(module, "GPTQ")
         self.module = module
         self.example_counter = 0
 
@@ -137,7 +147,7 @@ class OptimalBrainCompressor:
         wc, st = m.weight_cast, m.weight_storage_cast
         if st is not None and not (isinstance(st.format, Same) and not st.pre_transform):
             return None
-        if wc.pre_transform or wc.dynamic is not None or wc._scaling is not None or not wc._flag("fake_quant_enabled") or wc._flag("observer_enabled"):
+        if wc.pre_transform or wc.dynamic is not None or wc._scaling is not None or wc._learnable is not None or not wc._flag("fake_quant_enabled") or wc._flag("observer_enabled"):
             return None   # (a dynamic cast: its scale buffers are not what it casts with)
         per_row = False
         if isinstance(wc.format, FixedPoint):
@@ -438,6 +448,7 @@ class WandaCalibrator:
     an N:M sparseness, the mask) into the module's weight sparsifier.  The weight itself is never modified."""
 
     def __init__(self, module, sumsq=None, n_tokens: int = 0):
+        refuse_learnable_weight_cast(module, "Wanda")
         self.module = module
         self.sumsq = sumsq
         self.n_tokens = int(n_tokens)
@@ -517,6 +528,7 @@ class AWQCalibrator:
     the module's SmoothQuant, which carries it from there on.  The weight itself is not modified (unless fuse_to_weight asks for it)."""
 
     def __init__(self, module, hyperparams, sumabs=None, gram=None, n_tokens: int = 0):
+        refuse_learnable_weight_cast(module, "AWQ")
         self.module = module
         self.hyperparams = hyperparams
         self.sumabs, self.gram = sumabs, gram

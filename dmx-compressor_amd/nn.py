@@ -117,6 +117,18 @@ class DmxAWQHyperparams:
             raise TypeError(f"DmxAWQHyperparams: reset must be a bool, got {self.reset!r}")
 
 
+def _learnable_args(setting) -> dict:
+    """configure's *_learnable value -> CastTo.set_learnable's keyword arguments: None, "per_token", "per_tensor", {"per_group": g}, or
+    {"granularity": one of those, "learn_zero_point": bool, "grad_scale": "lsq" | None | float, "init": "minmax" | "lsq"}"""
+    if isinstance(setting, dict) and set(setting) != {"per_group"}:
+        extra = set(setting) - {"granularity", "learn_zero_point", "grad_scale", "init"}
+        if extra or "granularity" not in setting:
+            raise ValueError(f"*_learnable: expected a granularity, or a dict with 'granularity' and optionally 'learn_zero_point', "
+                             f"'grad_scale', 'init', got {setting!r}")
+        return dict(setting)
+    return {"granularity": setting}
+
+
 def _shares_storage(a, b) -> bool:
     if not (isinstance(a, torch.Tensor) and isinstance(b, torch.Tensor)):
         return False
@@ -217,12 +229,23 @@ class DmxModule(FastAttr, torch.nn.Module):
             self.output_casts.set_scaling(config["output_scaling"])
         if self.weight_cast is not None and "weight_scaling" in config:
             self.weight_cast.set_scaling(config["weight_scaling"])   # (per_token: per output channel; per_tile: tiles of the [out, in] view)
+        # learned scales for the integer casts (CastTo.set_learnable; LSQ / LSQ+): *_dynamic's spellings, or a dict {"granularity": one of
+        # them, "learn_zero_point", "grad_scale", "init"}.  Activation casts take "per_tensor" only; the weight cast sizes its parameters
+        # from the weight (further down, after the weight_format of this config, so that a weight on the GPU initialises them at once)
+        if "input_learnable" in config:
+            for c in self.input_casts.values():
+                c.set_learnable(**_learnable_args(config["input_learnable"]))
+        if "output_learnable" in config:
+            for c in self.output_casts.values():
+                c.set_learnable(**_learnable_args(config["output_learnable"]))
         if self.accum_cast is not None and "accum_format" in config:
             self.accum_cast.set_format(config["accum_format"])
         if self.weight_storage_cast is not None and "weight_storage_format" in config:
             self.weight_storage_cast.set_format(config["weight_storage_format"])
         if self.weight_cast is not None and "weight_format" in config:
             self.weight_cast.set_format(config["weight_format"])
+        if self.weight_cast is not None and "weight_learnable" in config:
+            self.weight_cast.set_learnable(**_learnable_args(config["weight_learnable"]), like=getattr(self, "weight", None))
         if self.weight_cast is not None and "pre_weight_transform" in config:
             self.weight_cast.set_pre_transform(config["pre_weight_transform"])
         if self.bias_cast is not None and "bias_format" in config:
@@ -397,6 +420,8 @@ class DmxModule(FastAttr, torch.nn.Module):
         return self.weight_sparsifier(self.weight) if self.weight_sparsifier is not None else self.weight
 
     def fold_weight_and_bias(self) -> None:
+        from .layer_reconstruction import refuse_learnable_weight_cast
+        refuse_learnable_weight_cast(self, "folding the weight")
         with torch.no_grad():
             if self.bias_cast is not None and not isinstance(self.bias_format, Same) and self.bias is not None:
                 self.bias.data = self.bias_cast(self.bias.data)
@@ -1607,7 +1632,7 @@ def _weight_batches(mods):
     with torch.no_grad():
         for m in mods:
             wc, st, sp, sq = m.weight_cast, m.weight_storage_cast, m.weight_sparsifier, m.smoothquant
-            if (wc is None or wc.pre_transform or wc.dynamic is not None or wc._scaling is not None or not wc._flag("fake_quant_enabled") or wc._flag("observer_enabled") or not m.weight.is_cuda
+            if (wc is None or wc.pre_transform or wc.dynamic is not None or wc._scaling is not None or wc._learnable is not None or not wc._flag("fake_quant_enabled") or wc._flag("observer_enabled") or not m.weight.is_cuda
                     or (sp is not None and not isinstance(sp.sparseness, Dense))
                     or (sq is not None and not sq._flag("fused_to_weight") and sq._flag("enabled"))
                     or (st is not None and not (isinstance(st.format, Same) and not st.pre_transform))):

@@ -57,7 +57,7 @@ const char* dmxq_status_string(int status);
  * dmxq_error_scratch_bytes, dmxq_hadamard_qdq, dmxq_dynamic_fixed_qdq, dmxq_dynamic_class, dmxq_gptq_block_dynamic,
  * dmxq_dynamic_float_qdq, dmxq_dynamic_float_class, dmxq_channel_sumsq_accumulate, dmxq_channel_sumsq_workspace_bytes, dmxq_wanda_nm,
  * dmxq_wanda_class, dmxq_row_class_of, dmxq_channel_sumabs_accumulate, dmxq_awq_group_error, dmxq_awq_class,
- * dmxq_block_scaled_float_qdq, dmxq_block_scaled_float_class, dmxq_block_scaled_tensor_scale, dmxq_nm_mask_class) leave it at 4: a caller built against 4 runs on
+ * dmxq_block_scaled_float_qdq, dmxq_block_scaled_float_class, dmxq_block_scaled_tensor_scale, dmxq_nm_mask_class, dmxq_lsq_backward, dmxq_lsq_class, dmxq_lsq_scratch_bytes) leave it at 4: a caller built against 4 runs on
  * this library unchanged.  4 = round 5: + dmxq_float_qdq_multi, dmxq_fixed_float_qdq_multi; 3 = round 4: + dmxq_weight_hypernet_multi,
  * dmxq_unary_cast_table, dmxq_lut16_apply.  Nothing was ever removed or changed: a caller built against version n runs on any library >= n. */
 int dmxq_abi_version(void);
@@ -576,6 +576,34 @@ int dmxq_dynamic_class(int dtype, int64_t segment, int whole_rows);
 int dmxq_dynamic_fixed_qdq(const void* in, void* out, int dtype_in, int dtype_out, int64_t n_segments, int64_t segment, int whole_rows,
                            int precision, int fraction, int clamp, int symmetric, int rounding, int qmin, int qmax,
                            int symmetric_qscheme, float* scale_out, int64_t* zp_out, void* stream);
+
+/* Learned step size (LSQ, Esser et al. 2020; LSQ+, Bhalgat et al. 2020): the BACKWARD pass of an integer cast whose scale s and float zero
+ * point z are trained (csrc/lsq.hip; DESIGN.md §8 "Learned step size").  Not in the reference, whose casts are identity straight-through
+ * estimators.  The forward is dmxq_fixed_qdq with one (s, zq) per segment, zq = clamp(rint(z), qmin, qmax).  x, g, dx: the contiguous
+ * [n_segments, segment] tensor, the incoming gradient and the gradient of x, one dtype; scale, zero_point: DEVICE float32 [n_segments];
+ * ds, dz: DEVICE float32 [n_segments] outputs.  Per element, every operation fp32 in this order:
+ *   v = x / s + zq (IEEE division);  r = the forward's nearest rounding of v;  in = qmin <= r <= qmax;  q = clamp(r, qmin, qmax);
+ *   dx = in ? g : 0;  e = in ? q - v : q - zq;  ts = g * e;  tz = in ? 0 : -(g * s)
+ * and per segment ds = (float)(grad_factor * sum (double)ts), dz = (float)(grad_factor * sum (double)tz): float64 sums without
+ * floating-point atomics, in an order that depends on the shape alone (the same call twice gives the same bits).  A NaN x gives
+ * dx = 0 there and a NaN ds for its segment; a NaN g gives a NaN ds and is passed on as dx where the element is `in`.
+ * want_dz == 0: tz is not formed and dz not written (may be NULL).  dx == NULL: dx is not stored.
+ * whole_rows: 0 -- groups inside rows, a power of two from 16 to 256; 1 -- rows, any multiple of a 16-byte vector (8 sixteen-bit or
+ * 4 fp32 elements) up to 16384; 2 -- the whole tensor as ONE segment (n_segments <= 1) of any whole number of vectors: workgroups write
+ * float64 partial rows into `scratch` (dmxq_lsq_scratch_bytes(segment) bytes of device memory, 8-byte aligned, contents free; unused
+ * and may be NULL otherwise) and a second small launch folds them in a fixed order.
+ * dmxq_lsq_class: the geometry the entry picks (dmxq_dynamic_geometry, or DMXQ_LSQ_TENSOR under whole_rows == 2), DMXQ_DYN_NONE where
+ * it refuses; dmxq_lsq_scratch_bytes: both host functions, no GPU involved.
+ * DMXQ_ERR_UNSUPPORTED, nothing launched (the caller runs its chain of torch operations): dtypes that differ, a segment outside the
+ * above or not whole vectors, x / g / dx not 16-byte aligned, rounding other than nearest, precision > 22, no scratch for the
+ * tensor class.  DMXQ_ERR_BAD_ARG: null pointers, negative sizes, invalid dtype / rounding / whole_rows, qmax <= qmin, more than one
+ * segment under whole_rows == 2, a scratch smaller than the query says.  No allocation, no host synchronisation: capturable. */
+typedef enum { DMXQ_LSQ_TENSOR = 6 } dmxq_lsq_geometry;
+int dmxq_lsq_class(int dtype, int64_t segment, int whole_rows);
+int64_t dmxq_lsq_scratch_bytes(int64_t n);
+int dmxq_lsq_backward(const void* x, const void* g, void* dx, int dtype_x, int dtype_g, int dtype_dx, int64_t n_segments, int64_t segment,
+                      int whole_rows, int precision, int rounding, int qmin, int qmax, const float* scale, const float* zero_point,
+                      double grad_factor, int want_dz, float* ds, float* dz, void* scratch, int64_t scratch_bytes, void* stream);
 
 /* Dynamic SCALED float cast (csrc/dynamic_float.hip): every segment of the contiguous tensor is scaled by its OWN absolute
  * maximum, on every call, in ONE launch -- per token, per group, per 2-D tile (the FP8 recipe's activations and weights).  Not in the
