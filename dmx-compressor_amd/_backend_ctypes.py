@@ -911,6 +911,43 @@ def dynamic_float_qdq(x, mode, segment, man, exp, bias, flush_subnormal, roundin
     return out, sc
 
 
+# ------------------------------------------------------------------------------------------------ codebook casts
+def _codebook_args(xc, segment, levels, what):
+    if segment < 1 or xc.numel() % segment != 0:
+        raise RuntimeError(f"{what}: the segment must divide the number of elements")
+    if not (levels.is_cuda and levels.device == xc.device and levels.dtype == torch.float32 and levels.is_contiguous() and levels.dim() == 1):
+        raise RuntimeError(f"{what}: the levels must be a contiguous 1-d float32 tensor on x's GPU")
+
+
+@_guarded
+def codebook_qdq(x, mode, segment, levels, norm, want_scale, want_index, out_dtype=None):
+    """-> (out, scale float32 [n_segments], index uint8 in x's shape): the last two empty unless wanted"""
+    xc = _prep(x, "codebook_qdq")
+    _codebook_args(xc, segment, levels, "codebook_qdq")
+    n = xc.numel() // segment
+    out = torch.empty(xc.shape, dtype=out_dtype or xc.dtype, device=xc.device)
+    sc = torch.empty(n if want_scale else 0, dtype=torch.float32, device=xc.device)
+    idx = torch.empty(xc.shape if want_index else 0, dtype=torch.uint8, device=xc.device)
+    check(lib().dmxq_codebook_qdq(ptr(xc), ptr(out), dtype_code(xc.dtype), dtype_code(out.dtype), mode, n, segment, ptr(levels), levels.numel(),
+                                  float(norm), ptr(sc) if want_scale else None, ptr(idx) if want_index else None, stream_of(xc)),
+          "dmxq_codebook_qdq")
+    return out, sc, idx
+
+
+@_guarded
+def codebook_accumulate(x, mode, segment, levels, norm, acc, accumulate):
+    """acc (float64 [K, 3]) (+)= the Lloyd statistics of x under the table; the partial rows' workspace is allocated here"""
+    xc = _prep(x, "codebook_accumulate")
+    _codebook_args(xc, segment, levels, "codebook_accumulate")
+    if not (acc.is_cuda and acc.device == xc.device and acc.dtype == torch.float64 and acc.is_contiguous() and acc.numel() == levels.numel() * 3):
+        raise RuntimeError("codebook_accumulate: acc must be a contiguous float64 [K, 3] tensor on x's GPU")
+    n = xc.numel() // segment
+    wb = int(lib().dmxq_codebook_workspace_bytes(dtype_code(xc.dtype), mode, n, segment))
+    ws = torch.empty(wb // 8 + 1, dtype=torch.float64, device=xc.device)
+    check(lib().dmxq_codebook_accumulate(ptr(xc), dtype_code(xc.dtype), mode, n, segment, ptr(levels), levels.numel(), float(norm), ptr(acc),
+                                         int(bool(accumulate)), ptr(ws), stream_of(xc)), "dmxq_codebook_accumulate")
+
+
 # ------------------------------------------------------------------------------------------------ Wanda
 def _channel_sum(x, acc, scratch, entry, what):
     xc = _prep(x, what)

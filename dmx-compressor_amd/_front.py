@@ -25,6 +25,8 @@ __all__ = [
     "dynamic_fixed_qdq", "dynamic_check", "dynamic_class", "DYNAMIC_GRANULARITIES", "DYNAMIC_CHAIN_BY_DEFAULT",
     "dynamic_float_qdq", "dynamic_float_check", "dynamic_float_class", "dynamic_float_fmax", "DYNAMIC_FLOAT_GRANULARITIES",
     "DYNAMIC_FLOAT_CHAIN_BY_DEFAULT",
+    "codebook_qdq", "codebook_check", "codebook_class", "codebook_accumulate", "codebook_fit", "CODEBOOKS", "NF4", "CODEBOOK_GRANULARITIES",
+    "CODEBOOK_KERNEL_LEVELS", "CODEBOOK_CHAIN_BY_DEFAULT",
     "lsq_backward", "lsq_fixed_qdq", "lsq_class", "lsq_scratch_bytes", "lsq_grad_factor", "LSQ_CHAIN_BY_DEFAULT",
     "block_scaled_float_qdq", "block_scaled_tensor_scale", "block_scaled_float_class", "block_scaled_check", "NVFP4",
     "BLOCK_SCALED_CHAIN_BY_DEFAULT",
@@ -1356,7 +1358,8 @@ def _scale_from_amax(amax, fmax: float, pow2_scale: bool):
     scale_channels: torch divides by a Python scalar as a multiplication by its reciprocal), the round-up to a power of two on the bits,
     and 1 where the scale is not finite or below 2^-126"""
     n = amax.numel()
-    s = _ops.scale_channels(amax.reshape(n, 1), torch.full((1,), fmax, dtype=torch.float32, device=amax.device), 1, True, torch.float32).reshape(n)
+    f = fmax if isinstance(fmax, torch.Tensor) else torch.full((1,), fmax, dtype=torch.float32, device=amax.device)   # (a [1] device tensor: as is)
+    s = _ops.scale_channels(amax.reshape(n, 1), f, 1, True, torch.float32).reshape(n)
     if pow2_scale:
         b = s.view(torch.int32)
         b = (b & 0x7F800000) + torch.where((b & 0x007FFFFF) != 0, 0x00800000, 0).to(torch.int32)   # (a NaN: wraps to the bits of -0)
@@ -1458,6 +1461,353 @@ def dynamic_float_qdq(x, fmt, granularity: str = "per_token", group_size: Option
         return _DynamicSTE.apply(x, run)
     with torch.no_grad():
         return run(x.detach())
+
+
+# ---------------------------------------------------------------------------------------------------- codebook casts
+CODEBOOK_GRANULARITIES = ("per_token", "per_group", "per_tensor")
+CODEBOOK_KERNEL_LEVELS = 16   # the largest table dmxq_codebook_qdq / dmxq_codebook_accumulate hold in registers (the chain: up to 256)
+# Launch geometries of dmxq_codebook_qdq (codebook_class) that fused=None sends to the chain although the kernel takes them:
+# DYNAMIC_FLOAT_CHAIN_BY_DEFAULT's rule -- a class goes to the kernel by default only where tools/bench_codebook.py MEASURED it faster than
+# the chain on the same buffers; a class that is not gets listed here with its row.  profiles/r20_codebook.txt (bf16 NF4, us per call,
+# kernel against chain): group per_group 64 [8192,4096] 55.6 against 3858.5; wave_row per_token [8192,4096] 52.9 against 581.3; group
+# per_group 64 [8192,14336] 176.7 against 13431.2; block_row per_token [8192,14336] 165.3 against 1827.6; group per_group 64 [2048,768]
+# 5.7 against 197.5; wave_row per_token [2048,768] 6.3 against 96.9 -- every measured class is faster, none is listed (short_row was
+# not measured: it runs wave_row's kernel body with idle lanes).
+CODEBOOK_CHAIN_BY_DEFAULT = frozenset()
+# which route the calls of this front end took, counted on the host: private, for the tests (fused=True must have run the kernel)
+_codebook_routes = {"fused": 0, "chain": 0}
+_codebook_accumulate_routes = {"fused": 0, "chain": 0}
+_CODEBOOK_ACC_REPLICAS = 4096   # copies of the [K, 3] rows that codebook_accumulate's torch form spreads its index_add_ over
+
+
+def _uniform_codebook(K: int):
+    """linspace(-1, 1, K) in float32, as a tuple of Python floats"""
+    if isinstance(K, bool) or not isinstance(K, int) or not 2 <= K <= 256:
+        raise ValueError(f"CODEBOOKS['uniform']: K must be an integer from 2 to 256, got {K!r}")
+    return tuple(torch.linspace(-1.0, 1.0, K, dtype=torch.float32).tolist())
+
+
+#: named tables: "nf4" -- the 16 levels of bitsandbytes' NormalFloat4 (QLoRA, Dettmers et al. 2023), each exactly representable in
+#: float32; "fp4_e2m1" -- the values of FP[1|2|1,1] with -0 and +0 merged, 15 levels; "uniform" -- a function, K -> linspace(-1, 1, K)
+#: (as a codebook name: "uniform<K>", e.g. "uniform8")
+CODEBOOKS = {
+    "nf4": (-1.0, -0.6961928009986877, -0.5250730514526367, -0.39491748809814453, -0.28444138169288635, -0.18477343022823334,
+            -0.09105003625154495, 0.0, 0.07958029955625534, 0.16093020141124725, 0.24611230194568634, 0.33791524171829224,
+            0.44070982933044434, 0.5626170039176941, 0.7229568362236023, 1.0),
+    "fp4_e2m1": (-6.0, -4.0, -3.0, -2.0, -1.5, -1.0, -0.5, 0.0, 0.5, 1.0, 1.5, 2.0, 3.0, 4.0, 6.0),
+    "uniform": _uniform_codebook,
+}
+#: the ready setting of CastTo.set_codebook / ops.codebook_qdq: NormalFloat4 under one absolute-maximum scale per 64 elements
+NF4 = {"codebook": "nf4", "per_group": 64}
+_codebook_device_cache = {}   # (levels, device) -> float32 [K] tensor: a named / host table is uploaded once per device
+
+
+def _codebook_host_levels(codebook, what):
+    """a name, list, tuple or CPU tensor -> the checked tuple of float32 values (ValueError); a device tensor -> None"""
+    if isinstance(codebook, torch.Tensor) and codebook.is_cuda:
+        return None
+    if isinstance(codebook, str):
+        if codebook.startswith("uniform") and codebook[7:].isdigit():
+            return _uniform_codebook(int(codebook[7:]))
+        lv = CODEBOOKS.get(codebook)
+        if lv is None or callable(lv):
+            raise ValueError(f"{what}: unknown codebook {codebook!r}; known: {sorted(k for k, v in CODEBOOKS.items() if not callable(v))} and "
+                             f"'uniform<K>', or give the levels as a list or tensor")
+        return tuple(lv)
+    if isinstance(codebook, torch.Tensor):
+        if codebook.dim() != 1 or not codebook.is_floating_point():
+            raise ValueError(f"{what}: a codebook tensor must be a 1-d float tensor of levels, got shape {tuple(codebook.shape)} {codebook.dtype}")
+        vals = codebook.detach().to(torch.float32).tolist()
+    elif isinstance(codebook, (list, tuple)):
+        try:
+            vals = torch.tensor([float(v) for v in codebook], dtype=torch.float32).tolist()   # (rounded to float32 once, here)
+        except (TypeError, ValueError):
+            raise ValueError(f"{what}: the levels of a codebook must be numbers, got {codebook!r}") from None
+    else:
+        raise ValueError(f"{what}: a codebook is a name, a list of levels or a 1-d tensor, got {type(codebook).__name__}")
+    if not 2 <= len(vals) <= 256:
+        raise ValueError(f"{what}: a codebook has 2 to 256 levels, got {len(vals)}")
+    if not all(math.isfinite(v) for v in vals):
+        raise ValueError(f"{what}: the levels of a codebook must be finite, got {vals}")
+    if any(b < a for a, b in zip(vals, vals[1:])):
+        raise ValueError(f"{what}: the levels of a codebook must be non-decreasing, got {vals}")
+    return tuple(vals)
+
+
+def codebook_check(codebook, granularity="per_group", group_size=64, norm=None, what: str = "codebook_qdq"):
+    """-> (levels, granularity, group_size, norm) of a codebook cast, or ValueError before any GPU use: `levels` is the checked tuple of
+    float32 values of a name ("nf4", "fp4_e2m1", "uniform<K>"), list or CPU tensor -- 2 to 256 finite, non-decreasing levels -- or a
+    device tensor as it is (1-d, 2 to 256 entries by its shape; never read back); a known granularity, a positive integer group_size
+    with per_group and none otherwise (that it divides the last dimension is checked against the tensor); norm None or a positive finite
+    number."""
+    levels = _codebook_host_levels(codebook, what)
+    if levels is None:
+        if codebook.dim() != 1 or not codebook.is_floating_point() or not 2 <= codebook.shape[0] <= 256:
+            raise ValueError(f"{what}: a codebook tensor must be a 1-d float tensor of 2 to 256 levels, got shape {tuple(codebook.shape)} "
+                             f"{codebook.dtype}")
+        levels = codebook
+    if granularity not in CODEBOOK_GRANULARITIES:
+        raise ValueError(f"{what}: granularity must be one of {CODEBOOK_GRANULARITIES}, got {granularity!r}")
+    if granularity == "per_group":
+        if isinstance(group_size, bool) or not isinstance(group_size, int) or group_size < 1:
+            raise ValueError(f"{what}: per_group needs a positive integer group_size, got {group_size!r}")
+    else:
+        group_size = None   # (the default group_size of the signature means nothing without per_group)
+    if norm is not None:
+        if isinstance(norm, bool) or not isinstance(norm, (int, float)) or not (0.0 < float(norm) < math.inf):
+            raise ValueError(f"{what}: norm must be None (the table's own largest magnitude) or a positive finite number, got {norm!r}")
+        norm = float(torch.tensor(float(norm), dtype=torch.float32))   # (the float32 value the kernel receives)
+        if not (0.0 < norm < math.inf):
+            raise ValueError(f"{what}: norm is not a positive finite float32 number")
+    return levels, granularity, group_size, norm
+
+
+def _codebook_tensor(levels, device):
+    """the float32 [K] device tensor of a checked table: a device tensor as it is (converted on the device if need be), a host tuple
+    uploaded once per device and kept (a later call, also inside a graph capture, copies nothing)"""
+    if isinstance(levels, torch.Tensor):
+        t = levels.detach()
+        t = t if t.dtype == torch.float32 else t.float()
+        t = t if t.device == device else t.to(device)
+        return t if t.is_contiguous() else t.contiguous()
+    key = (levels, str(device))
+    t = _codebook_device_cache.get(key)
+    if t is None:
+        t = _codebook_device_cache[key] = torch.tensor(levels, dtype=torch.float32, device=device)
+    return t
+
+
+def codebook_class(segment: int, dtype: torch.dtype, whole_rows: bool = False) -> Optional[str]:
+    """the launch geometry dmxq_codebook_qdq / dmxq_codebook_accumulate pick for segments of `segment` elements of `dtype` (whole_rows:
+    per_token / per_tensor), asked of the library itself (no GPU involved), or None when they refuse them: dynamic_float_class's names
+    without "tile" """
+    from ._lib import dtype_code, lib
+    return _DYNAMIC_CLASS_NAMES.get(lib().dmxq_codebook_class(dtype_code(dtype), _DYNF_ROWS if whole_rows else _DYNF_GROUP, int(segment)))
+
+
+def _codebook_per_group(granularity, group_size, per_group, what):
+    """the per_group=g spelling of (granularity, group_size)"""
+    if per_group is None:
+        return granularity, group_size
+    if granularity != "per_group":
+        raise ValueError(f"{what}: per_group={per_group!r} names the granularity itself, got granularity {granularity!r} beside it")
+    return "per_group", per_group
+
+
+def _codebook_segment(x, granularity, group_size, what):
+    if x.dim() < 1:
+        raise ValueError(f"{what}: {granularity} expects a tensor with at least 1 dimension")
+    L = x.shape[-1]
+    if granularity == "per_group" and L % group_size:
+        raise ValueError(f"{what}: the last dimension has {L} elements, not a multiple of the group size {group_size}")
+    return {"per_token": L, "per_group": group_size, "per_tensor": x.numel()}[granularity]
+
+
+def _codebook_chain(x2, c, norm_t, want_lookup=True, out_dtype=None):
+    """the definition on the rows of x2 [n, S] as a chain of launches -> (y or None, scale [n], u [n, S] float32, idx int64 [n, S])"""
+    K = c.shape[0]
+    t = (c[:-1] + c[1:]) * 0.5
+    z = torch.argmin(c.abs())   # (the first of equal minima: the lowest index)
+
+    def chain(part):
+        mn, mx = _ops.group_minmax(part, 0, 1)
+        sc = _scale_from_amax(torch.maximum(mn.abs(), mx.abs()), norm_t, False)
+        u = _ops.scale_channels(part, sc, 0, True, torch.float32)
+        idx = torch.bucketize(u, t, right=False)
+        idx = torch.where(torch.isnan(u), z, idx)
+        y = _ops.scale_channels(c[idx], sc, 0, False, out_dtype) if want_lookup else sc
+        return y, sc, u, idx
+
+    if x2.shape[0] <= DYNAMIC_CHAIN_MAX_SEGMENTS:
+        y, sc, u, idx = chain(x2)
+    else:   # (dmxq_group_minmax takes 65535 groups: segments are independent, so the chain runs on pieces and the results are joined)
+        parts = [chain(x2[i:i + DYNAMIC_CHAIN_PIECE]) for i in range(0, x2.shape[0], DYNAMIC_CHAIN_PIECE)]
+        y, sc, u, idx = (torch.cat([p[k] for p in parts]) for k in range(4))
+    return (y if want_lookup else None), sc, u, idx
+
+
+def _codebook_norm_tensor(c, norm):
+    """the [1] float32 device tensor the chain divides the maxima by: the given norm, or max(|c_0|, |c_{K-1}|) formed on the device"""
+    if norm is not None:
+        return torch.full((1,), norm, dtype=torch.float32, device=c.device)
+    return torch.maximum(c[:1].abs(), c[-1:].abs())
+
+
+def codebook_qdq(x, codebook, granularity: str = "per_group", group_size: Optional[int] = 64, norm: Optional[float] = None,
+                 out_dtype: Optional[torch.dtype] = None, return_scale: bool = False, return_index: bool = False,
+                 fused: Optional[bool] = None, per_group: Optional[int] = None):
+    """Q->DQ onto a small table of ARBITRARY levels under a per-segment absolute-maximum scale (DESIGN.md §8 "Codebook casts"; not in
+    the reference): NF4 (ops.NF4), Lloyd-Max / k-means tables (ops.codebook_fit).  `codebook`: a name of ops.CODEBOOKS, a list / CPU tensor
+    of K non-decreasing finite levels (checked: ValueError), or a device tensor (taken as is, never read back), 2 <= K <= 256.  In fp32:
+    thresholds t_j = (c_j + c_{j+1}) * 0.5; z = the lowest index of the level with the smallest |c|; and per segment of the contiguous
+    tensor (the row of the last dim with "per_token", `group_size` elements of it with "per_group", the whole tensor with "per_tensor"):
+        amax = max |x| (one NaN anywhere makes it NaN);  s = amax / norm (IEEE; norm=None: max(|c_0|, |c_{K-1}|), formed on the device);
+        s = 1 if s is not finite or below 2^-126;  u = x / s (IEEE);  idx = #{j : u > t_j} = bucketize(u, t, right=False), a tie goes
+        to the lower level, a NaN u takes idx = z;  y = c[idx] * s: one fp32 multiply, one rounding to out_dtype.
+    ONE launch (dmxq_codebook_qdq) for K <= 16, out_dtype == x.dtype, a 16-byte aligned tensor and: a group that is a power of two from
+    16 to 256; a row / tensor of any multiple of a 16-byte vector up to 16384 elements.  Otherwise the chain, same bits: group_minmax ->
+    the scale rule in torch -> scale_channels (divide, float32) -> torch.bucketize with the NaN override -> gather -> scale_channels
+    (multiply, out_dtype), on pieces of 32768 segments above 65535 segments.  fused=None: the kernel where it applies and its geometry
+    (codebook_class) is not listed in CODEBOOK_CHAIN_BY_DEFAULT; True: NotImplementedError instead of falling back; False: the chain.
+    per_group=g spells granularity="per_group", group_size=g, so that a setting such as ops.NF4 unpacks into the call:
+    codebook_qdq(x, **ops.NF4).
+    Returns y, followed by scale (float32 [n_segments]) with return_scale and index (uint8, x's shape) with return_index.  Autograd: a
+    straight-through estimator.  Nothing is read back to the host on either route."""
+    granularity, group_size = _codebook_per_group(granularity, group_size, per_group, "codebook_qdq")
+    levels, granularity, group_size, norm = codebook_check(codebook, granularity, group_size, norm)
+    S = _codebook_segment(x, granularity, group_size, "codebook_qdq")
+    require_gpu(x, "codebook_qdq")
+    out_dtype = out_dtype or x.dtype
+    mode = _DYNF_GROUP if granularity == "per_group" else _DYNF_ROWS
+    K = len(levels) if not isinstance(levels, torch.Tensor) else levels.shape[0]
+
+    def pick(y, sc, idx):
+        out = (y,) + ((sc,) if return_scale else ()) + ((idx,) if return_index else ())
+        return out if len(out) > 1 else y
+
+    def run(xd):
+        xc = xd if xd.is_contiguous() else xd.contiguous()
+        if xc.numel() == 0:
+            return pick(torch.empty(xc.shape, dtype=out_dtype, device=xc.device), torch.empty(0, dtype=torch.float32, device=xc.device),
+                        torch.empty(xc.shape, dtype=torch.uint8, device=xc.device))
+        c = _codebook_tensor(levels, xc.device)
+        if fused is not False:
+            cls = codebook_class(S, xc.dtype, mode == _DYNF_ROWS) if (K <= CODEBOOK_KERNEL_LEVELS and out_dtype == xc.dtype
+                                                                       and xc.data_ptr() % 16 == 0) else None
+            if cls is None and fused:
+                raise NotImplementedError(f"codebook_qdq: no fused kernel for {granularity} segments of {S} {xc.dtype} elements -> {out_dtype} "
+                                          f"with {K} levels (base address {xc.data_ptr() % 16} mod 16)")
+            if cls is not None and fused is None and cls in CODEBOOK_CHAIN_BY_DEFAULT:
+                cls = None
+            if cls is not None:
+                try:
+                    y, sc, idx = _ops.codebook_qdq(xc, mode, S, c, 0.0 if norm is None else norm, bool(return_scale), bool(return_index), out_dtype)
+                    _codebook_routes["fused"] += 1
+                    return pick(y, sc, idx)
+                except NotImplementedError:   # (DMXQ_ERR_UNSUPPORTED, nothing launched)
+                    if fused:
+                        raise
+        _codebook_routes["chain"] += 1
+        y, sc, _, idx = _codebook_chain(xc.reshape(-1, S), c, _codebook_norm_tensor(c, norm), True, out_dtype)
+        return pick(y.reshape(xc.shape), sc, idx.to(torch.uint8).reshape(xc.shape) if return_index else None)
+
+    if x.requires_grad and torch.is_grad_enabled():
+        return _DynamicSTE.apply(x, run)
+    with torch.no_grad():
+        return run(x.detach())
+
+
+def codebook_accumulate(x, codebook, granularity: str = "per_group", group_size: Optional[int] = 64, norm: Optional[float] = None, acc=None,
+                        accumulate: bool = False, fused: Optional[bool] = None, per_group: Optional[int] = None):
+    """The weighted Lloyd statistics of x under a table (DESIGN.md §8 "Codebook casts"), float64 [K, 3] on the device: with scale s,
+    quotient u and index idx formed exactly as codebook_qdq forms them, over the elements whose u is finite,
+        A[idx, 0] += w u;  A[idx, 1] += w;  A[idx, 2] += 1,   w = (double)s * (double)s
+    -- the true-MSE form: an element's error is s^2 (u - c)^2, so the best level of a cell is A[k, 0] / A[k, 1].  accumulate=True adds
+    into `acc` (several tensors or batches under one table), else `acc` (or a fresh tensor) is overwritten.  ONE pass over x plus a fold
+    launch (dmxq_codebook_accumulate: no floating-point atomics, the same input gives the same bits) where codebook_qdq's kernel applies;
+    otherwise the chain's (s, u, idx) and torch index_add_.  fused: as codebook_qdq.  Nothing is read back to the host."""
+    granularity, group_size = _codebook_per_group(granularity, group_size, per_group, "codebook_accumulate")
+    levels, granularity, group_size, norm = codebook_check(codebook, granularity, group_size, norm, what="codebook_accumulate")
+    S = _codebook_segment(x, granularity, group_size, "codebook_accumulate")
+    require_gpu(x, "codebook_accumulate")
+    K = len(levels) if not isinstance(levels, torch.Tensor) else levels.shape[0]
+    if acc is not None and (acc.dtype != torch.float64 or tuple(acc.shape) != (K, 3) or acc.device != x.device or not acc.is_contiguous()):
+        raise ValueError(f"codebook_accumulate: acc must be a contiguous float64 [{K}, 3] tensor on x's device")
+    if accumulate and acc is None:
+        raise ValueError("codebook_accumulate: accumulate=True needs acc")
+    mode = _DYNF_GROUP if granularity == "per_group" else _DYNF_ROWS
+    with torch.no_grad():
+        xd = x.detach()
+        xc = xd if xd.is_contiguous() else xd.contiguous()
+        if acc is None:
+            acc = torch.zeros(K, 3, dtype=torch.float64, device=xc.device)
+        elif not accumulate and xc.numel() == 0:
+            acc.zero_()
+        if xc.numel() == 0:
+            return acc
+        c = _codebook_tensor(levels, xc.device)
+        if fused is not False:
+            cls = codebook_class(S, xc.dtype, mode == _DYNF_ROWS) if (K <= CODEBOOK_KERNEL_LEVELS and xc.data_ptr() % 16 == 0) else None
+            if cls is None and fused:
+                raise NotImplementedError(f"codebook_accumulate: no fused kernel for {granularity} segments of {S} {xc.dtype} elements with {K} "
+                                          f"levels (base address {xc.data_ptr() % 16} mod 16)")
+            if cls is not None:
+                try:
+                    _ops.codebook_accumulate(xc, mode, S, c, 0.0 if norm is None else norm, acc, bool(accumulate))
+                    _codebook_accumulate_routes["fused"] += 1
+                    return acc
+                except NotImplementedError:   # (DMXQ_ERR_UNSUPPORTED, nothing launched)
+                    if fused:
+                        raise
+        _codebook_accumulate_routes["chain"] += 1
+        _, sc, u, idx = _codebook_chain(xc.reshape(-1, S), c, _codebook_norm_tensor(c, norm), False)
+        fin = torch.isfinite(u)
+        w = (sc.double() * sc.double())[:, None].expand_as(u)
+        zero = torch.zeros((), dtype=torch.float64, device=xc.device)
+        terms = torch.stack([torch.where(fin, w * u.double(), zero), torch.where(fin, w, zero), fin.double()], dim=-1).reshape(-1, 3)
+        # index_add_ adds with atomics: onto K rows alone every element of the tensor meets every other one (measured: seconds for 8 M
+        # elements), so the rows are kept in _CODEBOOK_ACC_REPLICAS copies, element i adding to copy i mod R, and the copies are summed
+        n = idx.numel()
+        R = min(_CODEBOOK_ACC_REPLICAS, n)
+        rows = idx.reshape(-1) + K * (torch.arange(n, device=xc.device) % R)
+        A = torch.zeros(R * K, 3, dtype=torch.float64, device=xc.device).index_add_(0, rows, terms).reshape(R, K, 3).sum(dim=0)
+        if accumulate:
+            acc += A
+        else:
+            acc.copy_(A)
+        return acc
+
+
+def codebook_fit(x, codebook="nf4", granularity: str = "per_group", group_size: Optional[int] = 64, norm: Optional[float] = None, iters: int = 8,
+                 return_history: bool = False, fused: Optional[bool] = None, per_group: Optional[int] = None):
+    """Fits a table to a tensor (or a list of tensors sharing it) by weighted Lloyd iterations on the device (DESIGN.md §8 "Codebook
+    casts") -> (levels float32 [K] on the device, norm) or (levels, norm, history).  Every iteration: A = codebook_accumulate over the
+    tensors, then c_k <- float(A[k, 0] / A[k, 1]) where A[k, 2] > 0 (an empty level keeps its value) -- the minimiser of the true
+    squared error sum s^2 (u - c)^2 over every cell, so the error never rises; cells are intervals, so the levels stay ordered.  The update
+    is torch on the K-vector on the device: no host synchronisation inside the loop, an iteration is capturable.  `norm` stays FIXED across
+    the iterations: None is resolved ONCE from the initial table, max(|c_0|, |c_{K-1}|) (the one read of a device table; a name or list
+    needs none), and returned -- pass the same norm when casting with the fitted table.  return_history: the relative L2 error
+    sqrt(sum_sq_err / sum_sq_ref) (ops.error_stats rows) before every iteration and after the last, float64 [iters + 1] on the device."""
+    xs = list(x) if isinstance(x, (list, tuple)) else [x]
+    if not xs:
+        raise ValueError("codebook_fit: no tensor to fit the table to")
+    if isinstance(iters, bool) or not isinstance(iters, int) or iters < 0:
+        raise ValueError(f"codebook_fit: iters must be a non-negative integer, got {iters!r}")
+    granularity, group_size = _codebook_per_group(granularity, group_size, per_group, "codebook_fit")
+    levels, granularity, group_size, norm = codebook_check(codebook, granularity, group_size, norm, what="codebook_fit")
+    for t in xs:
+        _codebook_segment(t, granularity, group_size, "codebook_fit")
+        require_gpu(t, "codebook_fit")
+    if norm is None:
+        if isinstance(levels, torch.Tensor):
+            norm = float(torch.maximum(levels[0].abs(), levels[-1].abs()).float())   # (the ONE read of a device table, before the loop)
+        else:
+            norm = max(abs(levels[0]), abs(levels[-1]))
+        if not (0.0 < norm < math.inf):
+            raise ValueError(f"codebook_fit: the initial table gives norm {norm!r}; pass a positive finite norm")
+    with torch.no_grad():
+        c = _codebook_tensor(levels, xs[0].device).clone()
+        K = c.shape[0]
+
+        def rel_error():
+            row = None
+            for t in xs:
+                y = codebook_qdq(t.detach(), c, granularity, group_size, norm, fused=fused)
+                row = error_stats(t.detach(), y, out=row, accumulate=row is not None)
+            return torch.sqrt(row[0] / row[1])
+
+        history = []
+        for _ in range(iters):
+            if return_history:
+                history.append(rel_error())
+            A = torch.zeros(K, 3, dtype=torch.float64, device=c.device)
+            for t in xs:
+                codebook_accumulate(t, c, granularity, group_size, norm, acc=A, accumulate=True, fused=fused)
+            c = torch.where(A[:, 2] > 0, (A[:, 0] / A[:, 1]).float(), c)
+        if return_history:
+            history.append(rel_error())
+            return c, norm, torch.stack(history)
+        return c, norm
 
 
 # ---------------------------------------------------------------------------------------------------- block-scaled float cast

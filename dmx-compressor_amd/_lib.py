@@ -97,6 +97,10 @@ SIGNATURES = {
     "dmxq_lsq_scratch_bytes": [_i64],
     "dmxq_lsq_backward": [_vp, _vp, _vp, _i32, _i32, _i32, _i64, _i64, _i32, _i32, _i32, _i32, _i32, _vp, _vp, ctypes.c_double, _i32, _vp, _vp, _vp, _i64,
                           _vp],
+    "dmxq_codebook_class": [_i32, _i32, _i64],
+    "dmxq_codebook_qdq": [_vp, _vp, _i32, _i32, _i32, _i64, _i64, _vp, _i32, _f32, _vp, _vp, _vp],
+    "dmxq_codebook_workspace_bytes": [_i32, _i32, _i64, _i64],
+    "dmxq_codebook_accumulate": [_vp, _i32, _i32, _i64, _i64, _vp, _i32, _f32, _vp, _i32, _vp, _vp],
     "dmxq_row_class_of": [_i32, _i32, _i32, _i32, _i64, _i64, _vp, _vp, _vp, _vp, _i32, _i64, _vp],
 }
 
@@ -174,6 +178,7 @@ def lib():
         L.dmxq_error_scratch_bytes.restype = ctypes.c_int64
         L.dmxq_channel_sumsq_workspace_bytes.restype = ctypes.c_int64
         L.dmxq_lsq_scratch_bytes.restype = ctypes.c_int64
+        L.dmxq_codebook_workspace_bytes.restype = ctypes.c_int64
         L.dmxq_status_string.argtypes = [ctypes.c_int]
         L.dmxq_status_string.restype = ctypes.c_char_p
         L.dmxq_abi_version.restype = ctypes.c_int

@@ -20,6 +20,10 @@ from .observer import _PER_CHANNEL, _SYMMETRIC, DummyObserver, HistogramObserver
 __all__ = ["CastToFormat", "CastTo", "CastToDict"]
 
 _LEARNED_SCALE_MIN = float(torch.finfo(torch.float32).eps)   # learned_scale is clamped from below to this before every forward
+_CODEBOOK_HADAMARD = ("CastTo: a codebook (set_codebook) under a 'hadamard' pre_transform is not supported: the fused rotated cast runs the "
+                      "format's arithmetic, not a table's")
+_CODEBOOK_EXCLUSIVE = ("this cast has a codebook (set_codebook), which replaces the format's arithmetic and its scales: "
+                       "set_codebook(None) first")
 _LEARNABLE_HADAMARD = ("CastTo: learned scales (set_learnable) under a 'hadamard' pre_transform are not supported: the fused rotated cast "
                        "reads the stored scale / zero_point buffers, and the rotated straight-through estimator would give the learned "
                        "parameters no gradient; drop one of the two settings")
@@ -175,6 +179,9 @@ class CastTo(HostFlags, torch.nn.Module):
     _learnable = None
     #: the learned parameters still wait for their data-dependent initial values (filled in place by the first forward): a host flag
     _learnable_pending = False
+    #: None, or {"granularity", "group_size", "norm", "name"}: the cast runs ops.codebook_qdq with the float32 buffer `codebook` in place of
+    #: the format's arithmetic (set_codebook; DESIGN.md §8 "Codebook casts").  The buffer exists only while this is set.
+    _codebook = None
 
     def __init__(self, format="SAME", observer=DummyObserver, group_size=None, block_dim=-1,
                  qscheme=torch.per_tensor_affine, ch_axis=-1, **observer_kwargs):
@@ -246,6 +253,9 @@ class CastTo(HostFlags, torch.nn.Module):
             if self._learnable is not None:
                 self.pre_transform.pop("hadamard")
                 raise ValueError(_LEARNABLE_HADAMARD)
+            if self._codebook is not None:
+                self.pre_transform.pop("hadamard")
+                raise ValueError(_CODEBOOK_HADAMARD)
 
     def set_dynamic(self, granularity=None, group_size=None):
         """Dynamic scales (not in the reference): with fake-quant on and the observer off, an integer format is cast with a
@@ -256,6 +266,8 @@ class CastTo(HostFlags, torch.nn.Module):
         calibration path runs as ever.  ValueError for an unknown granularity and for a format without an integer range -- here, or in
         set_format when the format comes later (a cast that is still SAME accepts the setting)."""
         dyn = _parse_dynamic(granularity, group_size)
+        if dyn is not None and self._codebook is not None:
+            raise ValueError("CastTo.set_dynamic: " + _CODEBOOK_EXCLUSIVE)
         if dyn is not None and self._learnable is not None:
             raise ValueError("CastTo.set_dynamic: this cast has learned scales (set_learnable), an exclusive source: set_learnable(None) first")
         if dyn is not None:
@@ -305,6 +317,8 @@ class CastTo(HostFlags, torch.nn.Module):
             return
         if "hadamard" in self.pre_transform:
             raise ValueError(_LEARNABLE_HADAMARD)
+        if self._codebook is not None:
+            raise ValueError("CastTo.set_learnable: " + _CODEBOOK_EXCLUSIVE)
         if self._dynamic is not None or self._scaling is not None:
             raise ValueError("CastTo.set_learnable: this cast derives its scales from every tensor (set_dynamic / set_scaling); a learned "
                              "scale is a third, exclusive source: switch that off first")
@@ -379,6 +393,14 @@ class CastTo(HostFlags, torch.nn.Module):
                                  grad_scale=lrn["grad_scale"], out_dtype=out_dtype)
 
     def _load_from_state_dict(self, state_dict, prefix, *args, **kwargs):
+        cb = self._codebook
+        if cb is not None and prefix + "codebook" in state_dict:   # (load time: the host copy of the setting follows the loaded values)
+            lv = state_dict[prefix + "codebook"].detach().float().cpu()
+            if cb["name"] is not None and lv.tolist() != list(ops.codebook_check(cb["name"])[0]):
+                cb["name"] = None
+            if prefix + "codebook_norm" in state_dict:
+                v = float(state_dict[prefix + "codebook_norm"].detach().float().cpu().reshape(-1)[0])
+                cb["norm"] = v if v > 0.0 else None
         if self._learnable is not None and prefix + "learned_scale" in state_dict:
             self._learnable_pending = False   # (the loaded values are the initial values)
         super()._load_from_state_dict(state_dict, prefix, *args, **kwargs)
@@ -399,6 +421,8 @@ class CastTo(HostFlags, torch.nn.Module):
         per_group only and not with pow2_scale: ValueError otherwise."""
         granularity, block = _split_block_scale(granularity)
         sc = _parse_scaling(granularity, group_size, pow2_scale)
+        if sc is not None and self._codebook is not None:
+            raise ValueError("CastTo.set_scaling: " + _CODEBOOK_EXCLUSIVE)
         if sc is not None and self._learnable is not None:
             raise ValueError("CastTo.set_scaling: this cast has learned scales (set_learnable), an exclusive source: set_learnable(None) first")
         if block is not None:
@@ -439,6 +463,83 @@ class CastTo(HostFlags, torch.nn.Module):
             sf, smax, ts = self._block_scale
             return ops.block_scaled_float_qdq(x, self.format, gs, sf, smax, ts, out_dtype=out_dtype)
         return ops.dynamic_float_qdq(x, self.format, g, gs, pow2_scale=pow2, out_dtype=out_dtype)
+
+    # ------------------------------------------------------------------ codebook casts
+    def set_codebook(self, setting=None):
+        """Codebook cast (not in the reference; DESIGN.md §8 "Codebook casts"): with fake-quant on and the observer off, the tensor is cast
+        onto a small table of levels under a per-segment absolute-maximum scale (ops.codebook_qdq) IN PLACE of the format's arithmetic; a
+        SAME cast stays the identity.  setting: None, or a dict {"codebook": a name of ops.CODEBOOKS | a list / tensor of levels,
+        "per_group": g | "granularity": "per_token" / "per_tensor" / "per_group" (with "group_size"), "norm": None or a positive number} such
+        as ops.NF4.  The table is registered HERE as the float32 buffer `codebook` [K], beside `codebook_norm` [1] (the pinned norm, 0 for
+        none), so that a fitted table (fit_codebook) is saved and loaded with the module -- into a cast that was given a table of the same
+        size; None removes both, and an untouched cast keeps its four buffers.  Exclusive with set_dynamic, set_scaling,
+        set_learnable and a "hadamard" pre_transform (ValueError in either order).  ValueError for everything ops.codebook_check refuses."""
+        if setting is None:
+            for n in ("codebook", "codebook_norm"):
+                if n in self._buffers:
+                    del self._buffers[n]
+            self._codebook = None
+            return
+        if not isinstance(setting, dict) or "codebook" not in setting or not set(setting) <= {"codebook", "per_group", "granularity", "group_size", "norm"}:
+            raise ValueError(f"set_codebook: expected None or a dict with 'codebook' and optionally 'per_group' / 'granularity' / 'group_size' / "
+                             f"'norm' (such as ops.NF4), got {setting!r}")
+        if "per_group" in setting:
+            if setting.get("granularity", "per_group") != "per_group" or "group_size" in setting:
+                raise ValueError(f"set_codebook: 'per_group' names the granularity and its group size by itself, got {setting!r}")
+            g, gs = "per_group", setting["per_group"]
+        else:
+            g, gs = setting.get("granularity", "per_group"), setting.get("group_size", 64 if setting.get("granularity", "per_group") == "per_group" else None)
+            if g != "per_group" and gs is not None:
+                raise ValueError(f"set_codebook: group_size goes with granularity 'per_group', got {setting!r}")
+        levels, g, gs, norm = ops.codebook_check(setting["codebook"], g, gs, setting.get("norm"), what="CastTo.set_codebook")
+        if self._dynamic is not None or self._scaling is not None or self._learnable is not None:
+            raise ValueError("CastTo.set_codebook: this cast already takes its scales from set_dynamic / set_scaling / set_learnable; a codebook "
+                             "replaces the format's arithmetic and is exclusive with them: switch that off first")
+        if "hadamard" in self.pre_transform:
+            raise ValueError(_CODEBOOK_HADAMARD)
+        t = levels.detach().to(torch.float32).clone() if isinstance(levels, torch.Tensor) else torch.tensor(levels, dtype=torch.float32)
+        for n in ("codebook", "codebook_norm"):
+            if n in self._buffers:
+                del self._buffers[n]
+        self.register_buffer("codebook", t.to(t.device if t.is_cuda else self.scale.device))
+        # the pinned norm travels with the table (0: none pinned, the table's own largest magnitude); the cast itself reads the host copy
+        self.register_buffer("codebook_norm", torch.tensor([0.0 if norm is None else norm], dtype=torch.float32, device=self.codebook.device))
+        self._codebook = {"granularity": g, "group_size": gs, "norm": norm,
+                          "name": setting["codebook"] if isinstance(setting["codebook"], str) else None}
+
+    @property
+    def codebook_setting(self):
+        """None, or the setting in the spelling set_codebook accepts: {"codebook": the name it was set by, or the buffer's levels as a
+        list, "per_group": g | "granularity": ..., and "norm" where one is pinned}.  A fitted table reads back as its levels."""
+        cb = self._codebook
+        if cb is None:
+            return None
+        out = {"codebook": cb["name"] if cb["name"] is not None else self.codebook.detach().cpu().tolist()}
+        out.update({"per_group": cb["group_size"]} if cb["granularity"] == "per_group" else {"granularity": cb["granularity"]})
+        if cb["norm"] is not None:
+            out["norm"] = cb["norm"]
+        return out
+
+    def fit_codebook(self, x, iters: int = 8):
+        """replaces the table IN PLACE by ops.codebook_fit's result for the tensor x (or list of tensors), started from the current table,
+        and pins the norm the fit used: the cast then reproduces the fitted error.  -> the buffer"""
+        if self._codebook is None:
+            raise ValueError("CastTo.fit_codebook: no codebook is set (set_codebook first)")
+        cb = self._codebook
+        first = x[0] if isinstance(x, (list, tuple)) else x
+        if self.codebook.device != first.device:
+            self.codebook = self.codebook.to(first.device)
+        c, norm = ops.codebook_fit(x, self.codebook, cb["granularity"], cb["group_size"], cb["norm"], iters=iters)
+        with torch.no_grad():
+            self.codebook.copy_(c)
+            self.codebook_norm.fill_(norm)
+        cb["norm"], cb["name"] = norm, None
+        return self.codebook
+
+    def _codebook_cast(self, x, out_dtype):
+        cb = self._codebook
+        c = self.codebook if self.codebook.device == x.device else self.codebook.to(x.device)
+        return ops.codebook_qdq(x, c, cb["granularity"], cb["group_size"], cb["norm"], out_dtype=out_dtype)
 
     def enable_calibration(self, state: bool = True, observer_cls: ObserverBase = HistogramObserver,
                            qscheme_to_overload: Optional[torch.qscheme] = None, group_size: int = None,
@@ -520,6 +621,8 @@ class CastTo(HostFlags, torch.nn.Module):
         fmt = self.format
         # the autograd wrappers only matter when a gradient will flow (straight-through estimator); inference skips them
         ste = torch.is_grad_enabled() and x.requires_grad
+        if self._codebook is not None and not self.__dict__["_h_observer_enabled"]:
+            return self._codebook_cast(x, out_dtype)  # (a straight-through estimator under autograd by itself)
         if self._dynamic is not None and isinstance(fmt, FixedPoint) and not self.__dict__["_h_observer_enabled"]:
             return self._dynamic_cast(x, out_dtype)   # (a straight-through estimator under autograd by itself)
         if self._scaling is not None and isinstance(fmt, FloatingPoint) and not self.__dict__["_h_observer_enabled"]:
@@ -646,7 +749,8 @@ class CastTo(HostFlags, torch.nn.Module):
         if self.pre_transform and set(self.pre_transform) != {"hadamard"}:
             raise NotImplementedError("CastTo.measure_error: a cast with a pre_transform other than hadamard (shaping / shortcut / pre-format)")
         fmt, x = self.format, x.detach()
-        dyn_cast = self._dynamic_cast if self._dynamic is not None and isinstance(fmt, FixedPoint) else \
+        dyn_cast = self._codebook_cast if self._codebook is not None and isinstance(fmt, Format) and not isinstance(fmt, Same) else \
+            self._dynamic_cast if self._dynamic is not None and isinstance(fmt, FixedPoint) else \
             self._scaled_cast if self._scaling is not None and isinstance(fmt, FloatingPoint) else \
             self._learnable_cast if self._learnable is not None and isinstance(fmt, FixedPoint) else None
         if dyn_cast is not None:
@@ -691,7 +795,16 @@ class CastTo(HostFlags, torch.nn.Module):
                f"group_size = {self.group_size}, block_dim = {self.block_dim}" \
                + (f", dynamic = {self.dynamic!r}" if self._dynamic is not None else "") \
                + (f", scaling = {self.scaling!r}" if self._scaling is not None else "") \
-               + (f", learnable = {self.learnable!r}" if self._learnable is not None else "")
+               + (f", learnable = {self.learnable!r}" if self._learnable is not None else "") \
+               + (f", codebook = {self._codebook_repr()}" if self._codebook is not None else "")
+
+    def _codebook_repr(self):
+        cb = self._codebook   # (no device read: a table without a name shows its size)
+        out = {"codebook": cb["name"] if cb["name"] is not None else f"<{self.codebook.shape[0]} levels>"}
+        out.update({"per_group": cb["group_size"]} if cb["granularity"] == "per_group" else {"granularity": cb["granularity"]})
+        if cb["norm"] is not None:
+            out["norm"] = cb["norm"]
+        return repr(out)
 
 
 class CastToDict(torch.nn.ModuleDict):
@@ -769,6 +882,25 @@ class CastToDict(torch.nn.ModuleDict):
             if k not in self.keys():
                 raise RuntimeError(f"No CastTo with key {k}!")
             self[k].set_scaling(t)
+
+    def set_codebook(self, codebook):
+        """one setting (None, or a dict with "codebook" such as ops.NF4) for every cast, or a list / dict of settings over the casts the
+        way set_scaling takes them"""
+        one = isinstance(codebook, dict) and "codebook" in codebook and not set(codebook) & set(self.keys())
+        if codebook is None or one:
+            for c in self.values():
+                c.set_codebook(codebook)
+            return
+        if isinstance(codebook, (tuple, list)):
+            if len(codebook) != len(self):
+                raise ValueError(f"set_codebook: {len(codebook)} settings for {len(self)} casts")
+            codebook = dict(zip(self.keys(), codebook))
+        elif not isinstance(codebook, dict):
+            raise ValueError(f"set_codebook: expected a setting, or a list or dict of settings, got {codebook!r}")
+        for k, t in codebook.items():
+            if k not in self.keys():
+                raise RuntimeError(f"No CastTo with key {k}!")
+            self[k].set_codebook(t)
 
     def set_format(self, format):
         for k, f in self.pack_to_dict(format).items():

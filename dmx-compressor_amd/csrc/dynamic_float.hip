@@ -30,7 +30,7 @@
 // no synchronisation with the host: capturable.  The scales go out as plain stores from one lane per segment.
 #include <math.h>
 
-#include "dynamic_geom.hpp"
+#include "dynamic_float.hpp"   // DfSeg, df_quotient_vec, df_block_max, dynf_class: shared with csrc/codebook.hip
 #include "floatq.hpp"
 
 namespace dmxq {
@@ -42,33 +42,11 @@ struct DfFmt {
   int pow2;
 };
 
-// a segment's scale and its reciprocal, from the bits of its absolute maximum
-struct DfSeg {
-  float s, rs;
-  __device__ __forceinline__ void setup(uint32_t amax_bits, const DfFmt& f) {
-    float t = u2f(amax_bits) / f.fmax;
-    if (f.pow2) {
-      const uint32_t b = f2u(t);
-      t = u2f((b & 0x7F800000u) + ((b & 0x007FFFFFu) ? 0x00800000u : 0u));
-    }
-    s = (t >= 0x1p-126f && t < INFINITY) ? t : 1.0f;
-    rs = 1.0f / s;
-  }
-};
-
 // called by whole waves; `fast`: every scale of the wave lies inside the reciprocal's range (wave-uniform)
 template <int V>
 __device__ __forceinline__ void df_cast_vec(const float (&x)[V], float (&y)[V], const DfSeg& sg, bool fast, const DfFmt& f) {
   float q[V];
-  bool ok = fast;
-#pragma unroll
-  for (int k = 0; k < V; k++) { q[k] = div_by_recip(x[k], sg.s, sg.rs); ok = ok && div_by_recip_ok(x[k]); }
-  if (__builtin_expect(__builtin_amdgcn_ballot_w64(!ok) != 0ull, 0)) {
-    if (!ok) {
-#pragma unroll
-      for (int k = 0; k < V; k++) q[k] = x[k] / sg.s;
-    }
-  }
+  df_quotient_vec<V>(x, q, sg, fast);
   castg_vec<DMXQ_F32, V>(q, f.c);
 #pragma unroll
   for (int k = 0; k < V; k++) y[k] = q[k] * sg.s;
@@ -92,7 +70,7 @@ __global__ __launch_bounds__(kDynThreads) void dynf_group_kernel(const void* __r
   for (int u = 0; u < U; u++) {
     const int64_t i = base + (int64_t)u * kWave;
     DfSeg sg;
-    sg.setup(group_max_u32(absmax_bits<DT>(raw[u]), lanes), f);
+    sg.setup(group_max_u32(absmax_bits<DT>(raw[u]), lanes), f.fmax, f.pow2);
     const bool fast = __builtin_amdgcn_ballot_w64(!recip_ok(sg.s)) == 0ull;
     float x[V], y[V];
     widen<DT, V>(raw[u], x);
@@ -102,19 +80,6 @@ __global__ __launch_bounds__(kDynThreads) void dynf_group_kernel(const void* __r
       if (scale_out && (lane & (lanes - 1)) == 0) scale_out[i >> lanes_log2] = sg.s;
     }
   }
-}
-
-// the maximum of a workgroup's waves (WAVES > 1): through LDS
-template <int WAVES>
-__device__ __forceinline__ uint32_t df_block_max(uint32_t m) {
-  if constexpr (WAVES > 1) {
-    __shared__ uint32_t s_max[WAVES];
-    if ((threadIdx.x & (kWave - 1)) == 0) s_max[threadIdx.x / kWave] = m;
-    __syncthreads();
-#pragma unroll
-    for (int i = 0; i < WAVES; i++) m = max(m, s_max[i]);
-  }
-  return m;
 }
 
 // rows of nv vectors; WAVES = 1: a wave per row, four rows per workgroup; WAVES = 4: the workgroup's row.  U x 64 x WAVES >= nv.
@@ -140,7 +105,7 @@ __global__ __launch_bounds__(kDynThreads) void dynf_rows_kernel(const void* __re
   for (int u = 0; u < U; u++) m = max(m, absmax_bits<DT>(raw[u]));
   m = df_block_max<WAVES>(group_max_u32(m, kWave));
   DfSeg sg;
-  sg.setup(m, f);
+  sg.setup(m, f.fmax, f.pow2);
   const bool fast = __builtin_amdgcn_ballot_w64(!recip_ok(sg.s)) == 0ull;   // (one segment per wave)
   if (t == 0 && row_ok && scale_out) scale_out[row] = sg.s;
 #pragma unroll
@@ -179,7 +144,7 @@ __global__ __launch_bounds__(kDynThreads) void dynf_tile_kernel(const void* __re
   for (int u = 0; u < U; u++) m = max(m, absmax_bits<DT>(raw[u]));
   m = df_block_max<WAVES>(group_max_u32(m, kWave));
   DfSeg sg;
-  sg.setup(m, f);
+  sg.setup(m, f.fmax, f.pow2);
   const bool fast = __builtin_amdgcn_ballot_w64(!recip_ok(sg.s)) == 0ull;   // (one segment per wave)
   if (t == 0 && tile_ok && scale_out) scale_out[tile] = sg.s;
 #pragma unroll
@@ -190,14 +155,6 @@ __global__ __launch_bounds__(kDynThreads) void dynf_tile_kernel(const void* __re
     df_cast_vec<V>(x, y, sg, fast, f);
     if (tile_ok) store_vec<DT, V>(out, (v0 + (int64_t)(j >> gv_log2) * cv + (j & gv_mask)) * V, y);
   }
-}
-
-// dynamic_geom.hpp's rule, except that a wave keeps a row only up to 8 sixteen-bit vectors per lane (16 for fp32): 16 sixteen-bit
-// vectors with their 128 widened elements and this cast's fallbacks no longer unroll (the raw vectors would go to scratch), and a
-// workgroup holds such a row with 8 per lane
-inline int dynf_class(int64_t S, int V, bool whole_rows) {
-  const int cls = dyn_class(S, V, whole_rows);
-  return (cls == DMXQ_DYN_WAVE_ROW && V == 8 && S / V > 8 * kWave) ? DMXQ_DYN_BLOCK_ROW : cls;
 }
 
 template <int DT>

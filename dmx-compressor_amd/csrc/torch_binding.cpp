@@ -1110,6 +1110,51 @@ std::tuple<Tensor, Tensor> dynamic_float_qdq_meta(const Tensor& x, int64_t mode,
                          want_scale ? at::empty(shape, x.options().dtype(at::kFloat)) : at::empty({0}, x.options().dtype(at::kFloat)));
 }
 
+// ------------------------------------------------------------------------------------------------ codebook casts
+// x: contiguous; mode: DMXQ_DYNF_GROUP / DMXQ_DYNF_ROWS; levels: contiguous float32 [K] on x's GPU; norm <= 0: the table's own maximum
+// -> (out, scale float32 [n_segments], index uint8 in x's shape; the last two empty unless wanted).
+// DMXQ_ERR_UNSUPPORTED (NotImplementedError, nothing launched): the front end runs its chain of launches.
+void codebook_args(const Tensor& xc, int64_t segment, const Tensor& levels, const char* what) {
+  TORCH_CHECK(segment >= 1 && xc.numel() % segment == 0, what, ": the segment must divide the number of elements");
+  TORCH_CHECK(levels.is_cuda() && levels.device() == xc.device() && levels.scalar_type() == at::kFloat && levels.is_contiguous() &&
+              levels.dim() == 1, what, ": the levels must be a contiguous 1-d float32 tensor on x's GPU");
+}
+std::tuple<Tensor, Tensor, Tensor> codebook_qdq(const Tensor& x, int64_t mode, int64_t segment, const Tensor& levels, double norm, bool want_scale,
+                                                bool want_index, OptDtype out_dtype) {
+  const Tensor xc = prep(x, "codebook_qdq");
+  codebook_args(xc, segment, levels, "codebook_qdq");
+  const int64_t n = xc.numel() / segment;
+  Tensor out = empty_like_shape(xc, out_dtype);
+  Tensor sc = at::empty({want_scale ? n : 0}, xc.options().dtype(at::kFloat));
+  Tensor idx = want_index ? empty_like_shape(xc, at::kByte) : at::empty({0}, xc.options().dtype(at::kByte));
+  Launch l(xc);
+  check(dmxq_codebook_qdq(xc.data_ptr(), out.data_ptr(), dt_code(xc.scalar_type()), dt_code(out.scalar_type()), (int)mode, n, segment,
+                          (const float*)levels.data_ptr(), (int)levels.numel(), (float)norm, want_scale ? (float*)sc.data_ptr() : nullptr,
+                          want_index ? (uint8_t*)idx.data_ptr() : nullptr, l.stream), "dmxq_codebook_qdq");
+  return std::make_tuple(out, sc, idx);
+}
+std::tuple<Tensor, Tensor, Tensor> codebook_qdq_meta(const Tensor& x, int64_t, int64_t segment, const Tensor&, double, bool want_scale,
+                                                     bool want_index, OptDtype out_dtype) {
+  const int64_t n = (want_scale && segment >= 1) ? x.numel() / segment : 0;
+  return std::make_tuple(empty_like_shape(x, out_dtype), at::empty({n}, x.options().dtype(at::kFloat)),
+                         want_index ? empty_like_shape(x, at::kByte) : at::empty({0}, x.options().dtype(at::kByte)));
+}
+// acc (float64 [K, 3]) (+)= the Lloyd statistics of x under the table; the partial rows' workspace is allocated here
+void codebook_accumulate(const Tensor& x, int64_t mode, int64_t segment, const Tensor& levels, double norm, Tensor acc, bool accumulate) {
+  const Tensor xc = prep(x, "codebook_accumulate");
+  codebook_args(xc, segment, levels, "codebook_accumulate");
+  TORCH_CHECK(acc.is_cuda() && acc.device() == xc.device() && acc.scalar_type() == at::kDouble && acc.is_contiguous() &&
+              acc.numel() == levels.numel() * 3, "codebook_accumulate: acc must be a contiguous float64 [K, 3] tensor on x's GPU");
+  const int64_t n = xc.numel() / segment;
+  const int64_t wb = dmxq_codebook_workspace_bytes(dt_code(xc.scalar_type()), (int)mode, n, segment);
+  Tensor ws = at::empty({wb / 8 + 1}, xc.options().dtype(at::kDouble));
+  Launch l(xc);
+  check(dmxq_codebook_accumulate(xc.data_ptr(), dt_code(xc.scalar_type()), (int)mode, n, segment, (const float*)levels.data_ptr(),
+                                 (int)levels.numel(), (float)norm, (double*)acc.data_ptr(), accumulate ? 1 : 0, ws.data_ptr(), l.stream),
+        "dmxq_codebook_accumulate");
+}
+void codebook_accumulate_meta(const Tensor&, int64_t, int64_t, const Tensor&, double, Tensor, bool) {}
+
 // ------------------------------------------------------------------------------------------------ Wanda
 // acc (float64 [C], C = x's last dim) += the sum of squares over every other dim; scratch: dmxq_channel_sumsq_workspace_bytes bytes of
 // any contiguous device tensor
@@ -1285,6 +1330,8 @@ TORCH_LIBRARY(dmxq, m) {
   m.def("block_scaled_float_qdq(Tensor x, int group, int[] fmt, int[] scale_fmt, float scale_max, Tensor? tensor_scale, bool want_scale, bool want_code, ScalarType? out_dtype=None) -> (Tensor, Tensor, Tensor)");
   m.def("block_scaled_tensor_scale(Tensor x, float fmax, float scale_max) -> Tensor");
   m.def("lsq_backward(Tensor x, Tensor g, Tensor scale, Tensor zero_point, int segment, int whole_rows, int precision, int rounding, int qmin, int qmax, float grad_factor, bool want_dz, bool want_dx) -> (Tensor, Tensor, Tensor)");
+  m.def("codebook_qdq(Tensor x, int mode, int segment, Tensor levels, float norm, bool want_scale, bool want_index, ScalarType? out_dtype=None) -> (Tensor, Tensor, Tensor)");
+  m.def("codebook_accumulate(Tensor x, int mode, int segment, Tensor levels, float norm, Tensor(a!) acc, bool accumulate) -> ()");
 }
 
 #define DMXQ_IMPL(m, name) m.impl(#name, &name)
@@ -1296,7 +1343,7 @@ TORCH_LIBRARY(dmxq, m) {
   X(m, unary_cast); X(m, unary_cast_table); X(m, lut16_apply); X(m, softmax_cast); X(m, norm_cast); X(m, group_minmax_accumulate); X(m, gptq_block); X(m, hist_observe); X(m, hist_qparams); \
   X(m, error_stats); X(m, cast_error); X(m, hadamard_qdq); X(m, dynamic_fixed_qdq); X(m, gptq_block_dynamic); X(m, dynamic_float_qdq); \
   X(m, channel_sumsq); X(m, wanda_nm); X(m, channel_sumabs); X(m, awq_group_error); X(m, block_scaled_float_qdq); X(m, block_scaled_tensor_scale); \
-  X(m, lsq_backward)
+  X(m, lsq_backward); X(m, codebook_qdq); X(m, codebook_accumulate)
 
 // "CUDA" is the dispatch key of HIP tensors in a ROCm build of PyTorch
 TORCH_LIBRARY_IMPL(dmxq, CUDA, m) {
@@ -1361,4 +1408,7 @@ PYBIND11_MODULE(dmxq_fast, m) {
         py::arg("tensor_scale"), py::arg("want_scale"), py::arg("want_code"), py::arg("out_dtype") = py::none());
   m.def("block_scaled_tensor_scale", &block_scaled_tensor_scale);
   m.def("lsq_backward", &lsq_backward);
+  m.def("codebook_qdq", &codebook_qdq, py::arg("x"), py::arg("mode"), py::arg("segment"), py::arg("levels"), py::arg("norm"), py::arg("want_scale"),
+        py::arg("want_index"), py::arg("out_dtype") = py::none());
+  m.def("codebook_accumulate", &codebook_accumulate);
 }

@@ -33,6 +33,14 @@ def refuse_scaled_weight_cast(module):
                                   "dynamic integer cast (weight_dynamic)")
 
 
+def refuse_codebook_weight_cast(module, what):
+    """GPTQ, AWQ, Wanda and folding on a module whose weight cast is a codebook cast (CastTo.set_codebook): NotImplementedError"""
+    wc = getattr(module, "weight_cast", None)
+    if wc is not None and wc._codebook is not None:
+        raise NotImplementedError(f"{what} with a codebook weight cast (weight_codebook = {wc._codebook_repr()}) is not supported yet: these "
+                                  "procedures assume the format's own grid; clear the setting (set_codebook(None)) first")
+
+
 def refuse_learnable_weight_cast(module, what):
     """GPTQ, AWQ, Wanda and folding on a module whose weight cast has learned scales (CastTo.set_learnable): NotImplementedError"""
     wc = getattr(module, "weight_cast", None)
@@ -47,6 +55,7 @@ class OptimalBrainCompressor:
 
     def __init__(self, module):
         refuse_learnable_weight_cast(module, "GPTQ")
+        refuse_codebook_weight_cast(module, "GPTQ")
         self.module = module
         self.example_counter = 0
 
@@ -147,7 +156,7 @@ class OptimalBrainCompressor:
         wc, st = m.weight_cast, m.weight_storage_cast
         if st is not None and not (isinstance(st.format, Same) and not st.pre_transform):
             return None
-        if wc.pre_transform or wc.dynamic is not None or wc._scaling is not None or wc._learnable is not None or not wc._flag("fake_quant_enabled") or wc._flag("observer_enabled"):
+        if wc.pre_transform or wc._codebook is not None or wc.dynamic is not None or wc._scaling is not None or wc._learnable is not None or not wc._flag("fake_quant_enabled") or wc._flag("observer_enabled"):
             return None   # (a dynamic cast: its scale buffers are not what it casts with)
         per_row = False
         if isinstance(wc.format, FixedPoint):
@@ -449,6 +458,7 @@ class WandaCalibrator:
 
     def __init__(self, module, sumsq=None, n_tokens: int = 0):
         refuse_learnable_weight_cast(module, "Wanda")
+        refuse_codebook_weight_cast(module, "Wanda")
         self.module = module
         self.sumsq = sumsq
         self.n_tokens = int(n_tokens)
@@ -529,6 +539,7 @@ class AWQCalibrator:
 
     def __init__(self, module, hyperparams, sumabs=None, gram=None, n_tokens: int = 0):
         refuse_learnable_weight_cast(module, "AWQ")
+        refuse_codebook_weight_cast(module, "AWQ")
         self.module = module
         self.hyperparams = hyperparams
         self.sumabs, self.gram = sumabs, gram

@@ -57,7 +57,8 @@ const char* dmxq_status_string(int status);
  * dmxq_error_scratch_bytes, dmxq_hadamard_qdq, dmxq_dynamic_fixed_qdq, dmxq_dynamic_class, dmxq_gptq_block_dynamic,
  * dmxq_dynamic_float_qdq, dmxq_dynamic_float_class, dmxq_channel_sumsq_accumulate, dmxq_channel_sumsq_workspace_bytes, dmxq_wanda_nm,
  * dmxq_wanda_class, dmxq_row_class_of, dmxq_channel_sumabs_accumulate, dmxq_awq_group_error, dmxq_awq_class,
- * dmxq_block_scaled_float_qdq, dmxq_block_scaled_float_class, dmxq_block_scaled_tensor_scale, dmxq_nm_mask_class, dmxq_lsq_backward, dmxq_lsq_class, dmxq_lsq_scratch_bytes) leave it at 4: a caller built against 4 runs on
+ * dmxq_block_scaled_float_qdq, dmxq_block_scaled_float_class, dmxq_block_scaled_tensor_scale, dmxq_nm_mask_class, dmxq_lsq_backward, dmxq_lsq_class, dmxq_lsq_scratch_bytes,
+ * dmxq_codebook_qdq, dmxq_codebook_class, dmxq_codebook_accumulate, dmxq_codebook_workspace_bytes) leave it at 4: a caller built against 4 runs on
  * this library unchanged.  4 = round 5: + dmxq_float_qdq_multi, dmxq_fixed_float_qdq_multi; 3 = round 4: + dmxq_weight_hypernet_multi,
  * dmxq_unary_cast_table, dmxq_lut16_apply.  Nothing was ever removed or changed: a caller built against version n runs on any library >= n. */
 int dmxq_abi_version(void);
@@ -629,6 +630,32 @@ int dmxq_dynamic_float_class(int dtype, int mode, int64_t segment);
 int dmxq_dynamic_float_qdq(const void* in, void* out, int dtype_in, int dtype_out, int mode, int64_t n_segments, int64_t segment,
                            int64_t rows, int64_t cols, int man_bits, int exp_bits, int exp_bias, int flush_subnormal, int rounding,
                            int pow2_scale, float* scale_out, void* stream);
+
+/* Codebook casts (csrc/codebook.hip; DESIGN.md §8 "Codebook casts"): a small table of ARBITRARY levels under a per-segment absolute-maximum
+ * scale -- NF4, Lloyd-Max / k-means tables -- in ONE launch, and the weighted Lloyd statistics that fit a table on the device.  Not in
+ * the reference.  levels: a DEVICE array of K float32 levels, non-decreasing (never read back, taken as is); the kernels derive, in fp32,
+ * the thresholds t_j = (c_j + c_{j+1}) * 0.5f, the zero level z (the lowest index of the level with the smallest |c|) and, for
+ * norm <= 0, norm = max(|c_0|, |c_{K-1}|).  Per segment of the contiguous tensor, in fp32:
+ *   amax = max |x| (one NaN anywhere makes it NaN);  s = amax / norm (IEEE);  s = 1 when s is not finite or below 2^-126;
+ *   u = x / s (IEEE);  idx = #{ j : u > t_j } (a tie goes to the lower level; a NaN u takes idx = z);  out = c[idx] * s, one fp32
+ *   multiply, one rounding to dtype_out.
+ * mode: DMXQ_DYNF_GROUP -- n_segments groups of `segment` consecutive elements, a power of two from 16 to 256; DMXQ_DYNF_ROWS --
+ * n_segments rows of `segment` elements, any multiple of a 16-byte vector up to 16384.  scale_out: NULL or a DEVICE array of n_segments
+ * floats; index_out: NULL or a DEVICE array of one uint8 per element, 16-byte aligned.
+ * dmxq_codebook_accumulate: the Lloyd statistics of the same (scale, u, idx), float64 acc[K][3]: over the elements whose u is finite,
+ * acc[idx] (+)= { w u, w, 1 } with w = (double)s * (double)s; accumulate != 0 adds to acc, 0 overwrites it.  No floating-point atomics, a
+ * fixed order: the same input gives the same bits.  workspace: DEVICE memory of dmxq_codebook_workspace_bytes(...) bytes, 8-byte
+ * aligned, contents free.  An empty tensor launches nothing and leaves acc as it is.
+ * DMXQ_ERR_UNSUPPORTED, nothing launched (the caller runs its chain): dtype_in != dtype_out, K > 16, a segment outside the above, a base
+ * that is not 16-byte aligned.  DMXQ_ERR_BAD_ARG: null pointers, negative sizes, invalid dtype / mode (tiles are not taken), K outside
+ * 2 .. 256, a norm that is NaN or +Inf.  No allocation, no host synchronisation: capturable.
+ * dmxq_codebook_class: the geometry (dmxq_dynamic_geometry) the entries pick for `segment` under `mode`, no GPU involved. */
+int dmxq_codebook_class(int dtype, int mode, int64_t segment);
+int dmxq_codebook_qdq(const void* in, void* out, int dtype_in, int dtype_out, int mode, int64_t n_segments, int64_t segment,
+                      const float* levels, int K, float norm, float* scale_out, uint8_t* index_out, void* stream);
+int64_t dmxq_codebook_workspace_bytes(int dtype, int mode, int64_t n_segments, int64_t segment);
+int dmxq_codebook_accumulate(const void* in, int dtype_in, int mode, int64_t n_segments, int64_t segment, const float* levels, int K,
+                             float norm, double* acc, int accumulate, void* workspace, void* stream);
 
 /* Wanda (Sun et al., 2023): activation-aware N:M pruning calibrated on the device (csrc/wanda.hip; DESIGN.md §8 "Wanda").  Not in the
  * reference.  For a Linear weight W[rows, L] and calibration inputs X[n_tokens, L]:
