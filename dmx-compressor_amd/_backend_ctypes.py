@@ -948,6 +948,24 @@ def codebook_accumulate(x, mode, segment, levels, norm, acc, accumulate):
                                          int(bool(accumulate)), ptr(ws), stream_of(xc)), "dmxq_codebook_accumulate")
 
 
+# ------------------------------------------------------------------------------------------------ HQQ
+@_guarded
+def hqq_qdq(x, segment, rounding, qmin, qmax, lp_norm, beta, kappa, iters, want_qparams, want_codes, out_dtype=None):
+    """-> (out, scale float32 [n_segments], zero float32 [n_segments], codes uint8 in x's shape): empty unless wanted"""
+    xc = _prep(x, "hqq_qdq")
+    if segment < 1 or xc.numel() % segment != 0:
+        raise RuntimeError("hqq_qdq: the group size must divide the number of elements")
+    n = xc.numel() // segment
+    out = torch.empty(xc.shape, dtype=out_dtype or xc.dtype, device=xc.device)
+    sc = torch.empty(n if want_qparams else 0, dtype=torch.float32, device=xc.device)
+    zero = torch.empty(n if want_qparams else 0, dtype=torch.float32, device=xc.device)
+    codes = torch.empty(xc.shape if want_codes else 0, dtype=torch.uint8, device=xc.device)
+    check(lib().dmxq_hqq_qdq(ptr(xc), ptr(out), dtype_code(xc.dtype), dtype_code(out.dtype), n, segment, rounding, qmin, qmax, float(lp_norm),
+                             float(beta), float(kappa), int(iters), ptr(sc) if want_qparams else None, ptr(zero) if want_qparams else None,
+                             ptr(codes) if want_codes else None, stream_of(xc)), "dmxq_hqq_qdq")
+    return out, sc, zero, codes
+
+
 # ------------------------------------------------------------------------------------------------ Wanda
 def _channel_sum(x, acc, scratch, entry, what):
     xc = _prep(x, what)

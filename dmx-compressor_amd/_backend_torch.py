@@ -63,7 +63,9 @@ _FAST_CALIBRATION_NAMES = {"hist_observe": "hist_observe", "hist_qparams": "hist
                            # the learned step size backward: called from inside an autograd Function of the front end (_front.py)
                            "lsq_backward": "lsq_backward",
                            # the codebook cast and its Lloyd statistics: straight-through above the raw op (_front.py)
-                           "codebook_qdq": "codebook_qdq", "codebook_accumulate": "codebook_accumulate"}
+                           "codebook_qdq": "codebook_qdq", "codebook_accumulate": "codebook_accumulate",
+                           # HQQ: the same
+                           "hqq_qdq": "hqq_qdq"}
 FAST = None
 
 

@@ -27,6 +27,7 @@ __all__ = [
     "DYNAMIC_FLOAT_CHAIN_BY_DEFAULT",
     "codebook_qdq", "codebook_check", "codebook_class", "codebook_accumulate", "codebook_fit", "CODEBOOKS", "NF4", "CODEBOOK_GRANULARITIES",
     "CODEBOOK_KERNEL_LEVELS", "CODEBOOK_CHAIN_BY_DEFAULT",
+    "hqq_qdq", "hqq_check", "hqq_class", "HQQ_CHAIN_BY_DEFAULT", "HQQ_KERNEL_NORMS",
     "lsq_backward", "lsq_fixed_qdq", "lsq_class", "lsq_scratch_bytes", "lsq_grad_factor", "LSQ_CHAIN_BY_DEFAULT",
     "block_scaled_float_qdq", "block_scaled_tensor_scale", "block_scaled_float_class", "block_scaled_check", "NVFP4",
     "BLOCK_SCALED_CHAIN_BY_DEFAULT",
@@ -1808,6 +1809,202 @@ def codebook_fit(x, codebook="nf4", granularity: str = "per_group", group_size: 
             history.append(rel_error())
             return c, norm, torch.stack(history)
         return c, norm
+
+
+# ---------------------------------------------------------------------------------------------------- HQQ
+# Group classes of dmxq_hqq_qdq (hqq_class) that fused=None sends to the chain of torch operations although the kernel takes them:
+# DYNAMIC_CHAIN_BY_DEFAULT's rule -- a class goes to the kernel by default only where tools/bench_hqq.py MEASURED it faster than the chain
+# on the same buffers; a class that is not gets listed here with its row.  profiles/r21_hqq.txt (bf16 XP[4,0], lp_norm 0.5, us per call,
+# kernel against chain at iters = 20 and at iters = 0): group (64) [4096,4096] 428.9 against 24721.9 and 27.9 against 2449.9, [14336,4096]
+# 1478.6 against 86934.0 and 78.2 against 8513.7, [2048,768] 43.6 against 2721.2 and 4.8 against 252.8; group (128) [4096,4096] 429.7
+# against 16814.0 and 29.2 against 1403.5, [14336,4096] 1494.4 against 58455.9 and 76.1 against 4898.4, [2048,768] 43.8 against 2767.8 and
+# 4.4 against 197.2 -- every row is faster (39 - 109 x), the class is not listed.
+HQQ_CHAIN_BY_DEFAULT = frozenset()
+# which route the calls of this front end took, counted on the host: private, for the tests (fused=True must have run the kernel)
+_hqq_routes = {"fused": 0, "chain": 0}
+HQQ_KERNEL_NORMS = (0.5, 1.0)   # the l_p norms dmxq_hqq_qdq takes: their shrink needs no pow
+
+
+def hqq_check(fmt, group_size=64, lp_norm=0.5, beta=10.0, kappa=1.01, iters=20, what: str = "hqq_qdq"):
+    """-> (format, group_size, lp_norm, beta, kappa, iters) of an HQQ call, or ValueError: a clamped fraction-free FixedPoint format
+    with nearest rounding (observer.get_qmin_qmax gives its integer range), a positive integer group size, lp_norm in (0, 1], a finite
+    beta > 0, a finite kappa >= 1, an integer iters >= 0.  No GPU involved."""
+    from .format import Format
+    from .observer import get_qmin_qmax
+    fmt = Format.from_shorthand(fmt) if isinstance(fmt, str) else fmt
+    if not isinstance(fmt, Format) or get_qmin_qmax(fmt) == (None, None):
+        raise ValueError(f"{what}: HQQ solves the zero point of an integer grid, so it needs a clamped FixedPoint format without fraction "
+                         f"bits (XP[p,0](C..)), got {fmt!r}")
+    if fmt.rounding != "nearest":
+        raise ValueError(f"{what}: the definition rounds to nearest, got a format with {fmt.rounding!r} rounding: {fmt!r}")
+    if isinstance(group_size, bool) or not isinstance(group_size, int) or group_size < 1:
+        raise ValueError(f"{what}: group_size must be a positive integer, got {group_size!r}")
+
+    def real(v, name):
+        if isinstance(v, bool) or not isinstance(v, (int, float)) or not math.isfinite(v):
+            raise ValueError(f"{what}: {name} must be a finite number, got {v!r}")
+        return float(v)
+
+    lp_norm, beta, kappa = real(lp_norm, "lp_norm"), real(beta, "beta"), real(kappa, "kappa")
+    if not 0.0 < lp_norm <= 1.0:
+        raise ValueError(f"{what}: lp_norm must lie in (0, 1], got {lp_norm!r}")
+    if not beta > 0.0:
+        raise ValueError(f"{what}: beta must be positive, got {beta!r}")
+    if not kappa >= 1.0:
+        raise ValueError(f"{what}: kappa must be at least 1, got {kappa!r}")
+    if isinstance(iters, bool) or not isinstance(iters, int) or iters < 0:
+        raise ValueError(f"{what}: iters must be a non-negative integer, got {iters!r}")
+    return fmt, group_size, lp_norm, beta, kappa, iters
+
+
+def hqq_class(group_size: int, dtype: torch.dtype) -> Optional[str]:
+    """"group" where dmxq_hqq_qdq takes groups of `group_size` elements of `dtype` (a power of two from 16 to 256, whole 16-byte vectors
+    in adjacent lanes of a wave), None where it refuses them; asked of the library itself (dmxq_hqq_class; no GPU involved)"""
+    from ._lib import dtype_code, lib
+    return _DYNAMIC_CLASS_NAMES.get(lib().dmxq_hqq_class(dtype_code(dtype), int(group_size)))
+
+
+def _hqq_tree_sum(v):
+    """the adjacent-pair tree over the last dim (an odd length carries its last value up unchanged)"""
+    while v.shape[-1] > 1:
+        n = v.shape[-1]
+        h = v[..., 0:n - 1:2] + v[..., 1::2]
+        v = torch.cat([h, v[..., -1:]], -1) if n % 2 else h
+    return v[..., 0]
+
+
+def _hqq_betas(beta, kappa, iters):
+    """(beta_k, 1 / beta_k) for k < iters as Python floats holding float32 values: float32 products and IEEE float32 quotients,
+    formed on the host (they depend on the arguments alone)"""
+    import numpy as np
+    b, k, out = np.float32(beta), np.float32(kappa), []
+    for _ in range(iters):
+        out.append((float(b), float(np.float32(1.0) / b)))
+        b = np.float32(b * k)
+    return out
+
+
+def _hqq_chain(part, qmin, qmax, lp_norm, beta, kappa, iters, out_dtype, want_codes):
+    """DESIGN.md §8 "HQQ" on the rows of part [n, g] in torch operations -> (y [n, g], s [n], z_best [n], codes or None)"""
+    import numpy as np
+    n, g = part.shape
+    dev = part.device
+    mn, mx = _ops.group_minmax(part, 0, 1)
+    W = part.float()
+    s = _div_ieee(mx - mn, _one(qmax - qmin, dev))
+    s = torch.where(_usable_scale(s), s, torch.ones_like(s))
+    rs = _ops.scale_channels(torch.ones(n, 1, dtype=torch.float32, device=dev), s, 0, True, torch.float32).reshape(n)
+    z = (_one(qmin, dev) - mn * rs)[:, None]
+    s2, rs2 = s[:, None], rs[:, None]
+    inv_g = float(np.float32(1.0 / g))
+    betas = _hqq_betas(beta, kappa, iters)
+    zb = eb = None
+    for k in range(iters + 1):
+        q = torch.clamp(torch.round(W * rs2 + z), qmin, qmax)
+        d = W - (q - z) * s2
+        a = d.abs()
+        err = _hqq_tree_sum(a)[:, None]
+        if k == 0:
+            zb, eb = z, err
+        else:
+            better = err < eb
+            zb, eb = torch.where(better, z, zb), torch.where(better, err, eb)
+        if k == iters:
+            break
+        ib = betas[k][1]
+        if lp_norm == 1.0:
+            m = a - ib
+        elif lp_norm == 0.5:
+            m = a - torch.full_like(a, ib) / a.sqrt()
+        else:   # (torch.pow: not pinned to the bit)
+            m = a - a.pow(lp_norm - 1.0) * ib
+        e = torch.copysign(torch.clamp(m, min=0), d)
+        z = _hqq_tree_sum(q - (W - e) * rs2)[:, None] * inv_g
+    q = torch.clamp(torch.round(W * rs2 + zb), qmin, qmax)
+    y = ((q - zb) * s2).to(out_dtype)
+    codes = torch.where(q == q, q - qmin, torch.zeros_like(q)).to(torch.uint8) if want_codes else None
+    return y, s, zb.reshape(n), codes
+
+
+def hqq_qdq(x, fmt, group_size: int = 64, lp_norm: float = 0.5, beta: float = 10.0, kappa: float = 1.01, iters: int = 20,
+            out_dtype: Optional[torch.dtype] = None, return_qparams: bool = False, return_codes: bool = False, fused: Optional[bool] = None):
+    """Half-Quadratic Quantization (HQQ; Badri and Shaji, 2023; DESIGN.md §8 "HQQ", whose text is the contract; not in the reference): a
+    calibration-free integer Q->DQ of a weight.  Every group of `group_size` consecutive elements of the last dim keeps the min/max
+    scale of ops.dynamic_fixed_qdq and re-solves its float ZERO POINT with `iters` proximal steps under the l_p norm, beta_k = beta *
+    kappa^k, keeping the zero point whose summed |x - y| over the group was smallest: iters=0 is round-to-nearest on the min/max grid with
+    a float zero point, and no group's L1 error ever exceeds that one's.  Best-tracking is per group (upstream stops on a whole-tensor mean,
+    a host round trip per iteration).
+    lp_norm defaults to 0.5, not upstream's 0.7: at p = 0.5 the shrink is a square root and a division, both correctly rounded on every
+    device and host, so the kernel, the chain and a CPU reference agree to the bit; a general p needs pow, which differs between math
+    libraries (ops.smoothquant_scale's exponent has the same problem).  p = 1 needs neither.
+    ONE launch (dmxq_hqq_qdq: load a group once, iterate in registers, store once) for group_size a power of two from 16 to 256,
+    lp_norm 0.5 or 1, out_dtype == x.dtype and a 16-byte aligned tensor.  Otherwise the chain -- the definition in torch operations on
+    the device, with the library's own launches where torch would not give the bits (group_minmax, IEEE divisions through
+    scale_channels) -- same bits for lp_norm 0.5 and 1, and NOT pinned to the bit for any other lp_norm (torch.pow); on more than 65535
+    groups it runs on pieces of 32768.  fused=None: the kernel where it applies and its class (hqq_class) is not listed in
+    HQQ_CHAIN_BY_DEFAULT; True: NotImplementedError instead of falling back; False: the chain.
+    Returns y, followed by (scale, zero), float32 [n_groups], with return_qparams and codes = q - qmin (uint8, x's shape, formats of up
+    to 8 bits; 0 where q is NaN) with return_codes: y == ((codes + qmin) - zero) * scale in float32, rounded once to out_dtype.
+    ValueError (before any GPU use): hqq_check's, a group size that does not divide the last dim, codes of a wider format.  Autograd:
+    a straight-through estimator.  Nothing is read back to the host on either route: capturable."""
+    from .observer import get_qmin_qmax
+    fmt, group_size, lp_norm, beta, kappa, iters = hqq_check(fmt, group_size, lp_norm, beta, kappa, iters)
+    if x.dim() < 1:
+        raise ValueError("hqq_qdq: expects a tensor with at least one dimension")
+    if x.shape[-1] % group_size:
+        raise ValueError(f"hqq_qdq: the last dimension has {x.shape[-1]} elements, not a multiple of the group size {group_size}")
+    qmin, qmax = get_qmin_qmax(fmt)
+    if return_codes and qmax - qmin > 255:
+        raise ValueError(f"hqq_qdq: uint8 codes hold formats of up to 8 bits, got {fmt!r}")
+    require_gpu(x, "hqq_qdq")
+    out_dtype = out_dtype or x.dtype
+    g = group_size
+
+    def pick(y, sc, zero, codes):
+        out = (y,) + ((sc, zero) if return_qparams else ()) + ((codes,) if return_codes else ())
+        return out if len(out) > 1 else y
+
+    def run(xd):
+        xc = xd if xd.is_contiguous() else xd.contiguous()
+        if xc.numel() == 0:
+            e = torch.empty(0, dtype=torch.float32, device=xc.device)
+            return pick(torch.empty(xc.shape, dtype=out_dtype, device=xc.device), e, e.clone(),
+                        torch.empty(xc.shape, dtype=torch.uint8, device=xc.device))
+        if fused is not False:
+            cls = hqq_class(g, xc.dtype) if (lp_norm in HQQ_KERNEL_NORMS and out_dtype == xc.dtype and fmt.precision <= 22
+                                             and xc.data_ptr() % 16 == 0) else None
+            if cls is None and fused:
+                raise NotImplementedError(f"hqq_qdq: no fused kernel for groups of {g} {xc.dtype} elements -> {out_dtype} with {fmt!r} and "
+                                          f"lp_norm {lp_norm} (base address {xc.data_ptr() % 16} mod 16)")
+            if cls is not None and fused is None and cls in HQQ_CHAIN_BY_DEFAULT:
+                cls = None
+            if cls is not None:
+                try:
+                    y, sc, zero, codes = _ops.hqq_qdq(xc, g, ROUNDING_CODE[fmt.rounding], qmin, qmax, lp_norm, beta, kappa, iters,
+                                                      bool(return_qparams), bool(return_codes), out_dtype)
+                    _hqq_routes["fused"] += 1
+                    return pick(y, sc, zero, codes)
+                except NotImplementedError:   # (DMXQ_ERR_UNSUPPORTED, nothing launched)
+                    if fused:
+                        raise
+        _hqq_routes["chain"] += 1
+        x2 = xc.reshape(-1, g)
+
+        def chain(part):
+            return _hqq_chain(part, qmin, qmax, lp_norm, beta, kappa, iters, out_dtype, return_codes)
+
+        if x2.shape[0] <= DYNAMIC_CHAIN_MAX_SEGMENTS:
+            y, sc, zero, codes = chain(x2)
+        else:   # (dmxq_group_minmax takes 65535 groups: groups are independent, so the chain runs on pieces and the results are joined)
+            parts = [chain(x2[i:i + DYNAMIC_CHAIN_PIECE]) for i in range(0, x2.shape[0], DYNAMIC_CHAIN_PIECE)]
+            y, sc, zero = (torch.cat([p[k] for p in parts]) for k in range(3))
+            codes = torch.cat([p[3] for p in parts]) if return_codes else None
+        return pick(y.reshape(xc.shape), sc, zero, codes.reshape(xc.shape) if return_codes else None)
+
+    if x.requires_grad and torch.is_grad_enabled():
+        return _DynamicSTE.apply(x, run)
+    with torch.no_grad():
+        return run(x.detach())
 
 
 # ---------------------------------------------------------------------------------------------------- block-scaled float cast

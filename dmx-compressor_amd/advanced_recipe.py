@@ -6,7 +6,7 @@ from typing import Callable, Optional
 
 from .nn import DmxModule
 
-__all__ = ["DmxBaseRecipe", "DmxQuantizerCalibrationRecipe", "DmxSmoothQuantRecipe", "DmxGPTQRecipe", "DmxWandaRecipe", "DmxAWQRecipe"]
+__all__ = ["DmxBaseRecipe", "DmxQuantizerCalibrationRecipe", "DmxSmoothQuantRecipe", "DmxGPTQRecipe", "DmxWandaRecipe", "DmxAWQRecipe", "DmxHQQRecipe"]
 
 
 class DmxBaseRecipe:
@@ -69,3 +69,13 @@ class DmxAWQRecipe(DmxBaseRecipe):
     def __init__(self, hp_gen, **kwargs):
         super().__init__(hp_gen, **kwargs)
         self.recipe_context_manager = DmxModule.awq_scaling
+
+
+class DmxHQQRecipe(DmxBaseRecipe):
+    """HQQ (DmxModule.hqq_quantizing): hp_gen maps the model to {module: DmxHQQHyperparams}; needs no calibration batch -- on exit every
+    Linear / Conv2d among them has its weight replaced by ops.hqq_qdq of it, its `hqq_qparams` recorded and its weight cast's fake
+    quantisation switched off"""
+
+    def __init__(self, hp_gen, **kwargs):
+        super().__init__(hp_gen, **kwargs)
+        self.recipe_context_manager = DmxModule.hqq_quantizing

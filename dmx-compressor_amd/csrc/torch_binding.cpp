@@ -1155,6 +1155,34 @@ void codebook_accumulate(const Tensor& x, int64_t mode, int64_t segment, const T
 }
 void codebook_accumulate_meta(const Tensor&, int64_t, int64_t, const Tensor&, double, Tensor, bool) {}
 
+// ------------------------------------------------------------------------------------------------ HQQ
+// x: contiguous; segment: the group size -> (out, scale float32 [n_segments], zero float32 [n_segments], codes uint8 in x's shape; the
+// qparams empty unless want_qparams, the codes empty unless want_codes).
+// DMXQ_ERR_UNSUPPORTED (NotImplementedError, nothing launched): the front end runs its chain of torch operations.
+std::tuple<Tensor, Tensor, Tensor, Tensor> hqq_qdq(const Tensor& x, int64_t segment, int64_t rounding, int64_t qmin, int64_t qmax, double lp_norm,
+                                                   double beta, double kappa, int64_t iters, bool want_qparams, bool want_codes,
+                                                   OptDtype out_dtype) {
+  const Tensor xc = prep(x, "hqq_qdq");
+  TORCH_CHECK(segment >= 1 && xc.numel() % segment == 0, "hqq_qdq: the group size must divide the number of elements");
+  const int64_t n = xc.numel() / segment;
+  Tensor out = empty_like_shape(xc, out_dtype);
+  Tensor sc = at::empty({want_qparams ? n : 0}, xc.options().dtype(at::kFloat));
+  Tensor zero = at::empty({want_qparams ? n : 0}, xc.options().dtype(at::kFloat));
+  Tensor codes = want_codes ? empty_like_shape(xc, at::kByte) : at::empty({0}, xc.options().dtype(at::kByte));
+  Launch l(xc);
+  check(dmxq_hqq_qdq(xc.data_ptr(), out.data_ptr(), dt_code(xc.scalar_type()), dt_code(out.scalar_type()), n, segment, (int)rounding, (int)qmin,
+                     (int)qmax, (float)lp_norm, (float)beta, (float)kappa, (int)iters, want_qparams ? (float*)sc.data_ptr() : nullptr,
+                     want_qparams ? (float*)zero.data_ptr() : nullptr, want_codes ? (uint8_t*)codes.data_ptr() : nullptr, l.stream),
+        "dmxq_hqq_qdq");
+  return std::make_tuple(out, sc, zero, codes);
+}
+std::tuple<Tensor, Tensor, Tensor, Tensor> hqq_qdq_meta(const Tensor& x, int64_t segment, int64_t, int64_t, int64_t, double, double, double, int64_t,
+                                                        bool want_qparams, bool want_codes, OptDtype out_dtype) {
+  const int64_t n = (want_qparams && segment >= 1) ? x.numel() / segment : 0;
+  return std::make_tuple(empty_like_shape(x, out_dtype), at::empty({n}, x.options().dtype(at::kFloat)), at::empty({n}, x.options().dtype(at::kFloat)),
+                         want_codes ? empty_like_shape(x, at::kByte) : at::empty({0}, x.options().dtype(at::kByte)));
+}
+
 // ------------------------------------------------------------------------------------------------ Wanda
 // acc (float64 [C], C = x's last dim) += the sum of squares over every other dim; scratch: dmxq_channel_sumsq_workspace_bytes bytes of
 // any contiguous device tensor
@@ -1332,6 +1360,7 @@ TORCH_LIBRARY(dmxq, m) {
   m.def("lsq_backward(Tensor x, Tensor g, Tensor scale, Tensor zero_point, int segment, int whole_rows, int precision, int rounding, int qmin, int qmax, float grad_factor, bool want_dz, bool want_dx) -> (Tensor, Tensor, Tensor)");
   m.def("codebook_qdq(Tensor x, int mode, int segment, Tensor levels, float norm, bool want_scale, bool want_index, ScalarType? out_dtype=None) -> (Tensor, Tensor, Tensor)");
   m.def("codebook_accumulate(Tensor x, int mode, int segment, Tensor levels, float norm, Tensor(a!) acc, bool accumulate) -> ()");
+  m.def("hqq_qdq(Tensor x, int segment, int rounding, int qmin, int qmax, float lp_norm, float beta, float kappa, int iters, bool want_qparams, bool want_codes, ScalarType? out_dtype=None) -> (Tensor, Tensor, Tensor, Tensor)");
 }
 
 #define DMXQ_IMPL(m, name) m.impl(#name, &name)
@@ -1343,7 +1372,7 @@ TORCH_LIBRARY(dmxq, m) {
   X(m, unary_cast); X(m, unary_cast_table); X(m, lut16_apply); X(m, softmax_cast); X(m, norm_cast); X(m, group_minmax_accumulate); X(m, gptq_block); X(m, hist_observe); X(m, hist_qparams); \
   X(m, error_stats); X(m, cast_error); X(m, hadamard_qdq); X(m, dynamic_fixed_qdq); X(m, gptq_block_dynamic); X(m, dynamic_float_qdq); \
   X(m, channel_sumsq); X(m, wanda_nm); X(m, channel_sumabs); X(m, awq_group_error); X(m, block_scaled_float_qdq); X(m, block_scaled_tensor_scale); \
-  X(m, lsq_backward); X(m, codebook_qdq); X(m, codebook_accumulate)
+  X(m, lsq_backward); X(m, codebook_qdq); X(m, codebook_accumulate); X(m, hqq_qdq)
 
 // "CUDA" is the dispatch key of HIP tensors in a ROCm build of PyTorch
 TORCH_LIBRARY_IMPL(dmxq, CUDA, m) {
@@ -1411,4 +1440,6 @@ PYBIND11_MODULE(dmxq_fast, m) {
   m.def("codebook_qdq", &codebook_qdq, py::arg("x"), py::arg("mode"), py::arg("segment"), py::arg("levels"), py::arg("norm"), py::arg("want_scale"),
         py::arg("want_index"), py::arg("out_dtype") = py::none());
   m.def("codebook_accumulate", &codebook_accumulate);
+  m.def("hqq_qdq", &hqq_qdq, py::arg("x"), py::arg("segment"), py::arg("rounding"), py::arg("qmin"), py::arg("qmax"), py::arg("lp_norm"), py::arg("beta"),
+        py::arg("kappa"), py::arg("iters"), py::arg("want_qparams"), py::arg("want_codes"), py::arg("out_dtype") = py::none());
 }

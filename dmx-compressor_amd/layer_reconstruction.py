@@ -21,7 +21,7 @@ import torch.nn.functional as F
 
 from ._lib import DmxqError
 
-__all__ = ["OptimalBrainCompressor", "WandaCalibrator", "AWQCalibrator"]
+__all__ = ["OptimalBrainCompressor", "WandaCalibrator", "AWQCalibrator", "hqq_apply"]
 
 
 def refuse_scaled_weight_cast(module):
@@ -620,3 +620,52 @@ class AWQCalibrator:
         m.__dict__.pop("_live_weight", None)   # (a LiveWeightBatch result computed without the scale)
         m.awq_losses, m.awq_best, m.awq_x_mean, m.awq_n_tokens = losses, best, x_mean, self.n_tokens
         m.awq_sumabs, m.awq_gram = self.sumabs, self.gram
+
+
+# ---------------------------------------------------------------------------------------------------- HQQ
+def refuse_hqq(module):
+    """-> (format, the weight cast's own per-group size or None) of a module DmxModule.hqq_quantize takes, or the refusal"""
+    from .format import FixedPoint, Same
+    from .observer import get_qmin_qmax
+    wc, st = module.weight_cast, module.weight_storage_cast
+    if wc is None:
+        raise DmxqError("HQQ needs a weight cast: the module has none")
+    refuse_scaled_weight_cast_for(module, "HQQ")
+    refuse_learnable_weight_cast(module, "HQQ")
+    refuse_codebook_weight_cast(module, "HQQ")
+    if wc.pre_transform:
+        raise DmxqError(f"HQQ with a weight cast pre_transform {sorted(wc.pre_transform)} is not supported: the zero points would be solved "
+                        "for the rotated weight")
+    if st is not None and not (isinstance(st.format, Same) and not st.pre_transform):
+        raise DmxqError("HQQ needs a weight_storage_cast of SAME: the written weight must reach the GEMM as it is")
+    if wc._flag("observer_enabled"):
+        raise DmxqError("HQQ while the weight cast's observer is calibrating is not supported: leave calibrating_quantizers first")
+    fmt = wc.format
+    if not isinstance(fmt, FixedPoint) or get_qmin_qmax(fmt) == (None, None) or fmt.rounding != "nearest":
+        raise DmxqError(f"HQQ needs a weight format that is a clamped XP[p,0] with nearest rounding, got {fmt!r}")
+    own = wc._dynamic[1] if wc._dynamic is not None and wc._dynamic[0] == "per_group" else None
+    return fmt, own
+
+
+def refuse_scaled_weight_cast_for(module, what):
+    wc = getattr(module, "weight_cast", None)
+    if wc is not None and wc._scaling is not None:
+        raise NotImplementedError(f"{what} with a scaled float weight cast (weight_scaling = {wc.scaling!r}) is not supported: clear the "
+                                  "setting (set_scaling(None)) first")
+
+
+def hqq_apply(module, hp):
+    """DmxModule.hqq_quantize's work on a Linear / Conv2d: see there"""
+    from . import ops
+    fmt, own = refuse_hqq(module)   # (before anything is touched)
+    weight = module.weight
+    w2 = weight.data.reshape(weight.shape[0], -1)
+    g = hp.group_size if hp.group_size is not None else (own if own is not None else 64)
+    if w2.shape[1] % g:
+        raise ValueError(f"HQQ: the group size {g} must divide the {w2.shape[1]} input columns of the weight")
+    y, sc, zero = ops.hqq_qdq(w2, fmt, g, hp.lp_norm, hp.beta, hp.kappa, hp.iters, return_qparams=True)
+    with torch.no_grad():
+        weight.copy_(y.reshape(weight.shape))
+    G = w2.shape[1] // g
+    module.hqq_qparams = {"scale": sc.reshape(-1, G), "zero": zero.reshape(-1, G), "group_size": g}
+    module.weight_cast.disable_fake_quant()

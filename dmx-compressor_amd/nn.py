@@ -27,7 +27,7 @@ from .smoothquant import ActivationWeightSmoothQuant
 from .sparse import Dense, Sparsify
 
 __all__ = ["DmxModule", "DmxQuantizerCalibrationHyperparams", "DmxModuleQuantizerCalibrationHyperparams",
-           "DmxModuleSmoothQuantHyperparams", "DmxModuleGPTQHyperparams", "DmxWandaHyperparams", "DmxAWQHyperparams", "Linear", "Conv1d", "Conv2d", "ResAdd", "ActActMatMul", "Softmax", "LayerNorm", "GELU", "ReLU", "SiLU", "QuickGELU", "Exp", "Mul", "RMSNorm", "ApplyRotaryPosEmb",
+           "DmxModuleSmoothQuantHyperparams", "DmxModuleGPTQHyperparams", "DmxWandaHyperparams", "DmxAWQHyperparams", "DmxHQQHyperparams", "Linear", "Conv1d", "Conv2d", "ResAdd", "ActActMatMul", "Softmax", "LayerNorm", "GELU", "ReLU", "SiLU", "QuickGELU", "Exp", "Mul", "RMSNorm", "ApplyRotaryPosEmb",
            "MaxPool2d", "AvgPool2d", "Embedding", "ReLU6", "Tanh", "Dropout", "NewGELU", "FastGELU", "BloomGELU", "ClippedGELU", "AdaptiveAvgPool2d",
            "BatchNorm2d", "GroupNorm", "ConvTranspose2d", "BAddBMM", "ScaledDotProductAttention", "DmxConfigRule", "configure_model",
            "fold_weights_and_biases", "GraphedForward", "LiveWeightBatch", "link_consumer", "link_consumers_from_fx", "DmxTracer"]
@@ -115,6 +115,40 @@ class DmxAWQHyperparams:
             raise TypeError(f"DmxAWQHyperparams: fuse_to_weight must be a bool, got {self.fuse_to_weight!r}")
         if not isinstance(self.reset, bool):
             raise TypeError(f"DmxAWQHyperparams: reset must be a bool, got {self.reset!r}")
+
+
+@dataclass
+class DmxHQQHyperparams:
+    """HQQ (DmxModule.hqq_quantize; not in the reference): ops.hqq_qdq's arguments.  group_size None: the weight cast's own
+    `weight_dynamic` per-group size where it has one, else 64"""
+    group_size: Optional[int] = None
+    lp_norm: float = 0.5
+    beta: float = 10.0
+    kappa: float = 1.01
+    iters: int = 20
+
+    def __post_init__(self):
+        import math
+        if self.group_size is not None and (isinstance(self.group_size, bool) or not isinstance(self.group_size, int)):
+            raise TypeError(f"DmxHQQHyperparams: group_size must be an int or None, got {self.group_size!r}")
+        if self.group_size is not None and self.group_size < 1:
+            raise ValueError(f"DmxHQQHyperparams: group_size must be positive, got {self.group_size}")
+        for name in ("lp_norm", "beta", "kappa"):
+            v = getattr(self, name)
+            if isinstance(v, bool) or not isinstance(v, (int, float)):
+                raise TypeError(f"DmxHQQHyperparams: {name} must be a number, got {v!r}")
+            if not math.isfinite(v):
+                raise ValueError(f"DmxHQQHyperparams: {name} must be finite, got {v!r}")
+        if not 0.0 < self.lp_norm <= 1.0:
+            raise ValueError(f"DmxHQQHyperparams: lp_norm must lie in (0, 1], got {self.lp_norm}")
+        if not self.beta > 0.0:
+            raise ValueError(f"DmxHQQHyperparams: beta must be positive, got {self.beta}")
+        if not self.kappa >= 1.0:
+            raise ValueError(f"DmxHQQHyperparams: kappa must be at least 1, got {self.kappa}")
+        if isinstance(self.iters, bool) or not isinstance(self.iters, int):
+            raise TypeError(f"DmxHQQHyperparams: iters must be an int, got {self.iters!r}")
+        if self.iters < 0:
+            raise ValueError(f"DmxHQQHyperparams: iters must not be negative, got {self.iters}")
 
 
 def _learnable_args(setting) -> dict:
@@ -582,6 +616,28 @@ class DmxModule(FastAttr, torch.nn.Module):
         self.enable_awq(True, hyperparams)
         yield self
         self.enable_awq(False, hyperparams)
+
+    def hqq_quantize(self, hyperparams=None) -> None:
+        """HQQ (DESIGN.md §8 "HQQ"; no calibration data): on a Linear or a Conv2d (through the [out, -1] view of its weight; any other
+        module: nothing happens) whose weight cast's format is a clamped XP[p,0] with nearest rounding.  The weight is replaced IN PLACE
+        by ops.hqq_qdq of it, `hqq_qparams` = {"scale": float32 [out, G], "zero": float32 [out, G], "group_size": g} is recorded (G =
+        input width / g; a plain attribute, no state_dict key) and the weight cast's fake_quant_enabled flag is switched OFF, so that
+        forwards use the weight as written -- GPTQ's reason: the cast is not idempotent on its own output.  Refused: a weight cast with
+        a codebook, learnable, scaling or pre_transform setting (NotImplementedError / DmxqError), a storage cast other than SAME, an
+        observer that is calibrating, a group size that does not divide the input width (ValueError)."""
+        from .layer_reconstruction import hqq_apply
+        if hyperparams is None:
+            hyperparams = DmxHQQHyperparams()
+        if not isinstance(hyperparams, DmxHQQHyperparams):
+            raise TypeError(f"hqq_quantize takes a DmxHQQHyperparams, got {type(hyperparams).__name__}")
+        if isinstance(self, (torch.nn.Linear, torch.nn.Conv2d)):
+            hqq_apply(self, hyperparams)
+
+    @contextmanager
+    def hqq_quantizing(self, hyperparams=None):
+        """hqq_quantize on leaving the context (the shape DmxHQQRecipe needs; nothing is observed inside)"""
+        yield self
+        self.hqq_quantize(hyperparams)
 
     #: GPTQ's in-block column loop as one csrc/gptq.hip launch per column block when the weight format allows (False: the reference's
     #: per-microblock loop, for A/B comparisons)

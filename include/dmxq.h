@@ -58,7 +58,7 @@ const char* dmxq_status_string(int status);
  * dmxq_dynamic_float_qdq, dmxq_dynamic_float_class, dmxq_channel_sumsq_accumulate, dmxq_channel_sumsq_workspace_bytes, dmxq_wanda_nm,
  * dmxq_wanda_class, dmxq_row_class_of, dmxq_channel_sumabs_accumulate, dmxq_awq_group_error, dmxq_awq_class,
  * dmxq_block_scaled_float_qdq, dmxq_block_scaled_float_class, dmxq_block_scaled_tensor_scale, dmxq_nm_mask_class, dmxq_lsq_backward, dmxq_lsq_class, dmxq_lsq_scratch_bytes,
- * dmxq_codebook_qdq, dmxq_codebook_class, dmxq_codebook_accumulate, dmxq_codebook_workspace_bytes) leave it at 4: a caller built against 4 runs on
+ * dmxq_codebook_qdq, dmxq_codebook_class, dmxq_codebook_accumulate, dmxq_codebook_workspace_bytes, dmxq_hqq_qdq, dmxq_hqq_class) leave it at 4: a caller built against 4 runs on
  * this library unchanged.  4 = round 5: + dmxq_float_qdq_multi, dmxq_fixed_float_qdq_multi; 3 = round 4: + dmxq_weight_hypernet_multi,
  * dmxq_unary_cast_table, dmxq_lut16_apply.  Nothing was ever removed or changed: a caller built against version n runs on any library >= n. */
 int dmxq_abi_version(void);
@@ -656,6 +656,23 @@ int dmxq_codebook_qdq(const void* in, void* out, int dtype_in, int dtype_out, in
 int64_t dmxq_codebook_workspace_bytes(int dtype, int mode, int64_t n_segments, int64_t segment);
 int dmxq_codebook_accumulate(const void* in, int dtype_in, int mode, int64_t n_segments, int64_t segment, const float* levels, int K,
                              float norm, double* acc, int accumulate, void* workspace, void* stream);
+
+/* Half-Quadratic Quantization (HQQ; Badri and Shaji, 2023) in ONE launch (csrc/hqq.hip; DESIGN.md §8 "HQQ", whose text is the contract).
+ * Not in the reference.  Per group of `segment` consecutive elements of the contiguous tensor, every operation fp32 in the text's order:
+ *   (mn, mx) the extrema with dmxq_group_minmax's NaN rule;  s = (mx - mn) / (qmax - qmin), 1 when not finite or below 2^-126;
+ *   rs = 1 / s;  z_0 = qmin - mn * rs (a float, not rounded);  then `iters` proximal steps on z under the l_p norm (lp_norm) with
+ *   beta_k = beta * kappa^k, the group keeping the z whose L1 error sum |x - (q - z) s| was smallest (strictly; z_0 at a tie or a NaN);
+ *   q = clamp(rint(x * rs + z_best), qmin, qmax);  out = (q - z_best) * s, one rounding to dtype_out.
+ * The sums over a group are adjacent-pair trees.  scale_out, zero_out: NULL or DEVICE arrays of n_segments floats (s, z_best);
+ * codes_out: NULL or a DEVICE array of one uint8 per element, 8-byte aligned: q - qmin (0 where q is NaN), qmax - qmin <= 255.
+ * DMXQ_ERR_UNSUPPORTED, nothing launched (the caller runs its chain): a segment that is no power of two from 16 to 256, dtype_in !=
+ * dtype_out, a base that is not 16-byte aligned, rounding other than nearest, lp_norm other than 0.5 or 1, an integer range of 2^22 or
+ * more.  DMXQ_ERR_BAD_ARG: null data pointers, negative sizes or iters, invalid dtype / rounding, qmax <= qmin, lp_norm outside (0, 1],
+ * beta <= 0, kappa < 1, codes_out with a range above 255.  No workspace, no allocation, no host synchronisation: capturable.
+ * dmxq_hqq_class: DMXQ_DYN_GROUP where the entry takes groups of `segment` elements of `dtype`, DMXQ_DYN_NONE otherwise; no GPU involved. */
+int dmxq_hqq_class(int dtype, int64_t segment);
+int dmxq_hqq_qdq(const void* in, void* out, int dtype_in, int dtype_out, int64_t n_segments, int64_t segment, int rounding, int qmin, int qmax,
+                 float lp_norm, float beta, float kappa, int iters, float* scale_out, float* zero_out, uint8_t* codes_out, void* stream);
 
 /* Wanda (Sun et al., 2023): activation-aware N:M pruning calibrated on the device (csrc/wanda.hip; DESIGN.md §8 "Wanda").  Not in the
  * reference.  For a Linear weight W[rows, L] and calibration inputs X[n_tokens, L]:
