@@ -966,6 +966,31 @@ def hqq_qdq(x, segment, rounding, qmin, qmax, lp_norm, beta, kappa, iters, want_
     return out, sc, zero, codes
 
 
+# ------------------------------------------------------------------------------------------------ outlier-aware dynamic cast
+@_guarded
+def outlier_fixed_qdq(x, segment, k, precision, fraction, clamp, symmetric, rounding, qmin, qmax, symmetric_qscheme, outlier_fmt, want_qparams,
+                      want_outliers, out_dtype=None):
+    """-> (out, scale float32 [n_segments], zero_point int64 [n_segments], idx int32 [n_segments, k], val [n_segments, k]): empty unless wanted"""
+    xc = _prep(x, "outlier_fixed_qdq")
+    if segment < 1 or xc.numel() % segment != 0:
+        raise RuntimeError("outlier_fixed_qdq: the segment must divide the number of elements")
+    if k < 0:
+        raise RuntimeError("outlier_fixed_qdq: k must not be negative")
+    n = xc.numel() // segment
+    out = torch.empty(xc.shape, dtype=out_dtype or xc.dtype, device=xc.device)
+    sc = torch.empty(n if want_qparams else 0, dtype=torch.float32, device=xc.device)
+    zp = torch.empty(n if want_qparams else 0, dtype=torch.int64, device=xc.device)
+    idx = torch.empty((n, k) if want_outliers else (0, k), dtype=torch.int32, device=xc.device)
+    val = torch.empty((n, k) if want_outliers else (0, k), dtype=out.dtype, device=xc.device)
+    (fo,), _keep = _fmt_ptrs(outlier_fmt)
+    check(lib().dmxq_outlier_fixed_qdq(ptr(xc), ptr(out), dtype_code(xc.dtype), dtype_code(out.dtype), n, segment, int(k), precision, fraction,
+                                       int(clamp), int(symmetric), rounding, qmin, qmax, int(symmetric_qscheme), fo,
+                                       ptr(sc) if want_qparams else None, ptr(zp) if want_qparams else None,
+                                       ptr(idx) if want_outliers else None, ptr(val) if want_outliers else None, stream_of(xc)),
+          "dmxq_outlier_fixed_qdq")
+    return out, sc, zp, idx, val
+
+
 # ------------------------------------------------------------------------------------------------ Wanda
 def _channel_sum(x, acc, scratch, entry, what):
     xc = _prep(x, what)

@@ -65,7 +65,9 @@ _FAST_CALIBRATION_NAMES = {"hist_observe": "hist_observe", "hist_qparams": "hist
                            # the codebook cast and its Lloyd statistics: straight-through above the raw op (_front.py)
                            "codebook_qdq": "codebook_qdq", "codebook_accumulate": "codebook_accumulate",
                            # HQQ: the same
-                           "hqq_qdq": "hqq_qdq"}
+                           "hqq_qdq": "hqq_qdq",
+                           # the outlier-aware dynamic cast: the same
+                           "outlier_fixed_qdq": "outlier_fixed_qdq"}
 FAST = None
 
 

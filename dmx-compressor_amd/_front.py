@@ -28,6 +28,7 @@ __all__ = [
     "codebook_qdq", "codebook_check", "codebook_class", "codebook_accumulate", "codebook_fit", "CODEBOOKS", "NF4", "CODEBOOK_GRANULARITIES",
     "CODEBOOK_KERNEL_LEVELS", "CODEBOOK_CHAIN_BY_DEFAULT",
     "hqq_qdq", "hqq_check", "hqq_class", "HQQ_CHAIN_BY_DEFAULT", "HQQ_KERNEL_NORMS",
+    "outlier_fixed_qdq", "outlier_check", "outlier_class", "outlier_bits_per_element", "OUTLIER_CHAIN_BY_DEFAULT", "OUTLIER_KERNEL_MAX_K",
     "lsq_backward", "lsq_fixed_qdq", "lsq_class", "lsq_scratch_bytes", "lsq_grad_factor", "LSQ_CHAIN_BY_DEFAULT",
     "block_scaled_float_qdq", "block_scaled_tensor_scale", "block_scaled_float_class", "block_scaled_check", "NVFP4",
     "BLOCK_SCALED_CHAIN_BY_DEFAULT",
@@ -2000,6 +2001,160 @@ def hqq_qdq(x, fmt, group_size: int = 64, lp_norm: float = 0.5, beta: float = 10
             y, sc, zero = (torch.cat([p[k] for p in parts]) for k in range(3))
             codes = torch.cat([p[3] for p in parts]) if return_codes else None
         return pick(y.reshape(xc.shape), sc, zero, codes.reshape(xc.shape) if return_codes else None)
+
+    if x.requires_grad and torch.is_grad_enabled():
+        return _DynamicSTE.apply(x, run)
+    with torch.no_grad():
+        return run(x.detach())
+
+
+# ---------------------------------------------------------------------------------------------------- outlier-aware dynamic cast
+# Group classes of dmxq_outlier_fixed_qdq (outlier_class) that fused=None sends to the chain although the kernel takes them:
+# DYNAMIC_CHAIN_BY_DEFAULT's rule -- a class goes to the kernel by default only where tools/bench_outlier.py MEASURED it faster than the
+# chain on the same buffers; a class that is not gets listed here with its row.  profiles/r22_outlier.txt (bf16 XP[4,0] affine, us per call,
+# kernel at k = 1 / 2 / 4 against chain at k = 1 / 2 / 4): group (64) [4096,4096] 26.3 / 29.4 / 32.7 against 1373.7 / 1373.6 / 1373.4,
+# [14336,4096] 80.2 / 87.5 / 100.8 against 4751.4 / 4743.8 / 4747.9, [2048,768] 5.8 / 5.2 / 5.4 against 175.6 / 176.9 / 176.7; group (128)
+# [4096,4096] 26.2 / 29.5 / 33.0 against 778.6 / 782.6 / 782.0, [14336,4096] 80.0 / 89.4 / 99.4 against 2680.5 / 2681.4 / 2679.1, [2048,768]
+# 5.7 / 5.1 / 5.5 against 121.0 / 121.2 / 121.7 -- every row is faster (21 - 59 x), the class is not listed.
+OUTLIER_CHAIN_BY_DEFAULT = frozenset()
+# which route the calls of this front end took, counted on the host: private, for the tests (fused=True must have run the kernel)
+_outlier_routes = {"fused": 0, "chain": 0}
+OUTLIER_KERNEL_MAX_K = 8   # the most outliers per group dmxq_outlier_fixed_qdq selects in registers (the chain: any k < S)
+OUTLIER_GRANULARITIES = ("per_group", "per_token")
+
+
+def outlier_check(fmt, group_size, k, outlier_format=None, granularity="per_group", what: str = "outlier_fixed_qdq"):
+    """-> (format, group_size, k, outlier_format) of an outlier-aware cast, or ValueError: dynamic_check's format rule (a clamped
+    FixedPoint format without fraction bits), granularity "per_group" with a positive integer group size or "per_token" with none, an
+    integer k with 0 <= k (and k < group_size where the group size is given; the row length is checked with the tensor), an
+    outlier_format that is None or a FloatingPoint format with fewer than 23 mantissa bits.  No GPU involved."""
+    from .format import FloatingPoint, Format
+    if granularity not in OUTLIER_GRANULARITIES:
+        raise ValueError(f"{what}: granularity must be one of {OUTLIER_GRANULARITIES}, got {granularity!r}")
+    fmt, _, group_size = dynamic_check(fmt, granularity, group_size, what)
+    if isinstance(k, bool) or not isinstance(k, int) or k < 0:
+        raise ValueError(f"{what}: k must be a non-negative integer, got {k!r}")
+    if group_size is not None and k >= group_size:
+        raise ValueError(f"{what}: k must be smaller than the segment, got k = {k} with segments of {group_size}")
+    if outlier_format is not None:
+        outlier_format = Format.from_shorthand(outlier_format) if isinstance(outlier_format, str) else outlier_format
+        if not isinstance(outlier_format, FloatingPoint):
+            raise ValueError(f"{what}: outlier_format must be None (the value itself) or a per-element FloatingPoint format, got "
+                             f"{outlier_format!r}")
+        if outlier_format.mantissa > 22:
+            raise ValueError(f"{what}: a 23-bit mantissa through float_qdq is undefined, got {outlier_format!r}; pass None for the value itself")
+    return fmt, group_size, k, outlier_format
+
+
+def outlier_class(group_size: int, dtype: torch.dtype) -> Optional[str]:
+    """"group" where dmxq_outlier_fixed_qdq takes groups of `group_size` elements of `dtype` (dynamic_class's group rule: a power of
+    two from 16 to 256, whole 16-byte vectors in adjacent lanes of a wave), None where it refuses them; asked of the library itself
+    (dmxq_outlier_class; no GPU involved)"""
+    from ._lib import dtype_code, lib
+    return _DYNAMIC_CLASS_NAMES.get(lib().dmxq_outlier_class(dtype_code(dtype), int(group_size)))
+
+
+def outlier_bits_per_element(fmt, group_size: int, k: int, outlier_bits: int = 16, scale_bits: int = 16, zero_point_bits: Optional[int] = None,
+                             symmetric_qscheme: bool = False) -> float:
+    """the storage cost of the outlier-aware cast in bits per element: p + (scale_bits + zp_bits + k (outlier_bits + ceil(log2 S))) / S
+    for a p-bit format on segments of S = group_size elements -- per segment one scale, one zero point and k (value, position) pairs.
+    zero_point_bits defaults to p under an affine scheme and to 0 under a symmetric one.  XP[4,0] affine, S = 128, k = 2:
+    4 + (16 + 4 + 2 * 23) / 128.  A host helper: what a user compares k against a wider format with."""
+    fmt, group_size, k, _ = outlier_check(fmt, group_size, k, None, "per_group", "outlier_bits_per_element")
+    p = int(fmt.precision)
+    zp_bits = (0 if symmetric_qscheme else p) if zero_point_bits is None else int(zero_point_bits)
+    pos_bits = (group_size - 1).bit_length()   # ceil(log2 S)
+    return p + (int(scale_bits) + zp_bits + k * (int(outlier_bits) + pos_bits)) / group_size
+
+
+def outlier_fixed_qdq(x, fmt, group_size: Optional[int] = None, k: int = 0, symmetric_qscheme: bool = False, outlier_format=None,
+                      granularity: str = "per_group", out_dtype: Optional[torch.dtype] = None, return_qparams: bool = False,
+                      return_outliers: bool = False, fused: Optional[bool] = None):
+    """Outlier-aware dynamic integer Q->DQ (DESIGN.md §8 "Outlier-aware dynamic cast", whose text is the contract; SpQR, Dettmers et al.
+    2023; SqueezeLLM, Kim et al. 2023; not in the reference): every segment keeps its k largest magnitudes at higher precision and
+    casts the rest on a range that no longer has to cover them.  A segment is S consecutive elements of the last dim of the contiguous
+    tensor: `group_size` elements with "per_group" (it must divide the last dim), the row with "per_token".  With x2 = x.reshape(-1, S):
+        key = x2.float().abs() viewed as int32 (a NaN ranks above Inf, Inf above every finite value); the outliers of a segment are the
+        first k positions of torch.sort(key, dim=1, descending=True, stable=True): equal keys go to the lower index; mask is True there
+        xin = where(mask, +0.0, x2);  y_in, sc, zp = dynamic_fixed_qdq(xin, fmt, "per_token", symmetric_qscheme, return_qparams=True)
+        (qparams take min(mn, 0) and max(mx, 0), so the zeros give exactly the qparams of the inliers alone; NaN / Inf beyond the k
+        outliers follow dynamic_fixed_qdq's rule)
+        y = where(mask, O(x2), y_in):  O(v) = v itself for outlier_format None (the same bits when out_dtype == x.dtype, .to(out_dtype)
+        otherwise), ops.float_qdq(v, outlier_format...) for a per-element FloatingPoint format.
+    k = 0 is dynamic_fixed_qdq itself on every route.
+    ONE launch (dmxq_outlier_fixed_qdq: the selection runs in registers, k rounds of an integer maximum over the group's lanes) for
+    per_group with group_size a power of two from 16 to 256, 1 <= k <= 8, a nearest-rounding format, out_dtype == x.dtype, a 16-byte
+    aligned tensor and outlier_format None or a signed nearest-rounding FloatingPoint format.  Otherwise the chain: the definition above in
+    torch operations and library calls on the device, same bits.  fused=None: the kernel where it applies and its class (outlier_class) is
+    not listed in OUTLIER_CHAIN_BY_DEFAULT; True: NotImplementedError instead of falling back; False: the chain.
+    Returns y, followed by (scale float32 [n_seg], zero_point int64 [n_seg]) with return_qparams and (idx int32 [n_seg, k], val out_dtype
+    [n_seg, k]) with return_outliers: the outliers' positions in their segment and O(x), in rank order; the same on both routes.
+    ValueError (before any GPU use): outlier_check's, a k that is not smaller than the segment, a segment that does not divide the last
+    dim.  Autograd: a straight-through estimator.  Nothing is read back to the host on either route."""
+    from .observer import get_qmin_qmax
+    fmt, group_size, k, ofmt = outlier_check(fmt, group_size, k, outlier_format, granularity)
+    if x.dim() < 1:
+        raise ValueError("outlier_fixed_qdq: expects a tensor with at least one dimension")
+    L = x.shape[-1]
+    if granularity == "per_group" and L % group_size:
+        raise ValueError(f"outlier_fixed_qdq: the last dimension has {L} elements, not a multiple of the group size {group_size}")
+    S = group_size if granularity == "per_group" else L
+    if k and k >= S:
+        raise ValueError(f"outlier_fixed_qdq: k must be smaller than the segment, got k = {k} with segments of {S}")
+    require_gpu(x, "outlier_fixed_qdq")
+    qmin, qmax = get_qmin_qmax(fmt)
+    sym = bool(symmetric_qscheme)
+    out_dtype = out_dtype or x.dtype
+    ofields = [] if ofmt is None else [ofmt.mantissa, ofmt.exponent, ofmt.bias, int(bool(ofmt.flush_subnormal))]
+    okernel = ofmt is None or (ofmt.rounding == "nearest" and not ofmt.unsigned)
+
+    def pick(y, sc, zp, idx, val):
+        out = (y,) + ((sc, zp) if return_qparams else ()) + ((idx, val) if return_outliers else ())
+        return out if len(out) > 1 else y
+
+    def run(xd):
+        xc = xd if xd.is_contiguous() else xd.contiguous()
+        n_seg = xc.numel() // S if S else 0
+        if xc.numel() == 0 or k == 0:   # (k = 0: the dynamic cast itself, by its own routing -- fused is passed on)
+            idx = torch.empty((n_seg, k), dtype=torch.int32, device=xc.device)
+            val = torch.empty((n_seg, k), dtype=out_dtype, device=xc.device)
+            if xc.numel() == 0:
+                y = torch.empty(xc.shape, dtype=out_dtype, device=xc.device)
+                return pick(y, y.new_empty(0, dtype=torch.float32), y.new_empty(0, dtype=torch.int64), idx, val)
+            y, sc, zp = dynamic_fixed_qdq(xc, fmt, granularity, group_size if granularity == "per_group" else None, sym, out_dtype, True, fused)
+            return pick(y, sc, zp, idx, val)
+        if fused is not False:
+            cls = outlier_class(S, xc.dtype) if (granularity == "per_group" and k <= OUTLIER_KERNEL_MAX_K and okernel and fmt.rounding == "nearest"
+                                                 and out_dtype == xc.dtype and fmt.precision <= 22 and xc.data_ptr() % 16 == 0) else None
+            if cls is None and fused:
+                raise NotImplementedError(f"outlier_fixed_qdq: no fused kernel for {granularity} segments of {S} {xc.dtype} elements -> "
+                                          f"{out_dtype} with {fmt!r}, k = {k} and outlier format {ofmt!r} (base address "
+                                          f"{xc.data_ptr() % 16} mod 16)")
+            if cls is not None and fused is None and cls in OUTLIER_CHAIN_BY_DEFAULT:
+                cls = None
+            if cls is not None:
+                try:
+                    y, sc, zp, idx, val = _ops.outlier_fixed_qdq(xc, S, k, fmt.precision, fmt.fraction, bool(fmt.clamp), bool(fmt.symmetric),
+                                                                 ROUNDING_CODE[fmt.rounding], qmin, qmax, sym, ofields, bool(return_qparams),
+                                                                 bool(return_outliers), out_dtype)
+                    _outlier_routes["fused"] += 1
+                    return pick(y, sc, zp, idx, val)
+                except NotImplementedError:   # (DMXQ_ERR_UNSUPPORTED, nothing launched)
+                    if fused:
+                        raise
+        _outlier_routes["chain"] += 1
+        x2 = xc.reshape(-1, S)
+        key = x2.float().abs().view(torch.int32)
+        order = torch.sort(key, dim=1, descending=True, stable=True).indices[:, :k]
+        mask = torch.zeros(x2.shape, dtype=torch.bool, device=x2.device).scatter_(1, order, True)
+        xin = torch.where(mask, torch.zeros((), dtype=x2.dtype, device=x2.device), x2)
+        y_in, sc, zp = dynamic_fixed_qdq(xin, fmt, "per_token", None, sym, out_dtype, True)
+        if ofmt is None:
+            ox = x2 if out_dtype == x2.dtype else x2.to(out_dtype)
+        else:
+            ox = float_qdq(x2, ofmt.mantissa, ofmt.exponent, ofmt.bias, bool(ofmt.flush_subnormal), bool(ofmt.unsigned), ofmt.rounding, out_dtype)
+        y = torch.where(mask, ox, y_in).reshape(xc.shape)
+        return pick(y, sc, zp, order.to(torch.int32), ox.gather(1, order) if return_outliers else None)
 
     if x.requires_grad and torch.is_grad_enabled():
         return _DynamicSTE.apply(x, run)

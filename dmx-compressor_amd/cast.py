@@ -107,6 +107,28 @@ def _parse_dynamic(granularity, group_size=None):
     return granularity, group_size
 
 
+_OUTLIER_KEYS = ("outliers", "outlier_format")
+
+
+def _parse_outliers(setting):
+    """set_dynamic's dict spellings with "outliers" -> (the setting without the outlier keys, None or {"k", "outlier_format"}):
+    {"per_group": g, "outliers": k} and {"granularity": "per_token", "outliers": k}, each optionally with "outlier_format" (None or a
+    per-element FloatingPoint format).  Every other setting passes through with None."""
+    if not isinstance(setting, dict) or not set(setting) & set(_OUTLIER_KEYS):
+        return setting, None
+    if "outliers" not in setting:
+        raise ValueError(f"set_dynamic: 'outlier_format' goes with 'outliers', got {setting!r}")
+    d = dict(setting)
+    k, ofmt = d.pop("outliers"), d.pop("outlier_format", None)
+    if set(d) == {"granularity"}:
+        if d["granularity"] != "per_token":
+            raise ValueError(f"set_dynamic: outliers go with {{'per_group': g}} or {{'granularity': 'per_token'}}, got {setting!r}")
+        d = "per_token"
+    elif set(d) != {"per_group"}:
+        raise ValueError(f"set_dynamic: outliers go with {{'per_group': g}} or {{'granularity': 'per_token'}}, got {setting!r}")
+    return d, {"k": k, "outlier_format": ofmt}
+
+
 def _parse_scaling(granularity, group_size=None, pow2_scale=False):
     """set_scaling's arguments -> None or (granularity, group_size, pow2_scale).  granularity: None / False, "per_token", "per_tensor",
     "per_group" or "per_tile" (these two with group_size as the second argument), the pair ("per_group" | "per_tile", g), or a dict
@@ -168,6 +190,9 @@ class CastTo(HostFlags, torch.nn.Module):
     #: None, or (granularity, group_size): scale and zero point are derived from every tensor itself (set_dynamic).  A plain
     #: attribute, not a buffer: the state_dict of a module does not change.
     _dynamic = None
+    #: None, or {"k", "outlier_format"} beside a per_group / per_token _dynamic: every segment keeps its k largest magnitudes exact, or in
+    #: the per-element float format (ops.outlier_fixed_qdq; DESIGN.md §8 "Outlier-aware dynamic cast").  A plain attribute as well.
+    _outliers = None
     #: None, or (granularity, group_size, pow2_scale): a float format is cast with a scale derived from every tensor itself (set_scaling;
     #: DESIGN.md §8).  A plain attribute as well.
     _scaling = None
@@ -224,6 +249,9 @@ class CastTo(HostFlags, torch.nn.Module):
             format = Format.from_shorthand(format)
         if self._dynamic is not None and not isinstance(format, Same):
             ops.dynamic_check(format, *self._dynamic, what="CastTo.set_format on a dynamic cast")
+            if self._outliers is not None:
+                ops.outlier_check(format, self._dynamic[1], self._outliers["k"], self._outliers["outlier_format"], self._dynamic[0],
+                                  what="CastTo.set_format on a dynamic cast with outliers")
         if self._scaling is not None and not isinstance(format, Same):
             ops.dynamic_float_check(format, *self._scaling[:2], what="CastTo.set_format on a scaled cast")
             if self._block_scale is not None:
@@ -264,7 +292,11 @@ class CastTo(HostFlags, torch.nn.Module):
         consecutive elements of it ("per_group", or {"per_group": g}) or for the whole tensor ("per_tensor").  The scale / zero_point
         buffers and the observer are neither read nor written.  None switches back to the stored scales.  While the observer is enabled the
         calibration path runs as ever.  ValueError for an unknown granularity and for a format without an integer range -- here, or in
-        set_format when the format comes later (a cast that is still SAME accepts the setting)."""
+        set_format when the format comes later (a cast that is still SAME accepts the setting).
+        Outliers (DESIGN.md §8 "Outlier-aware dynamic cast"): {"per_group": g, "outliers": k} or {"granularity": "per_token", "outliers": k},
+        each optionally with "outlier_format" (None: the value itself; or a per-element FloatingPoint format), keep every segment's k largest
+        magnitudes at that precision and derive the scale from the rest (ops.outlier_fixed_qdq); "outliers": 0 is the plain setting."""
+        granularity, out = _parse_outliers(granularity)
         dyn = _parse_dynamic(granularity, group_size)
         if dyn is not None and self._codebook is not None:
             raise ValueError("CastTo.set_dynamic: " + _CODEBOOK_EXCLUSIVE)
@@ -275,18 +307,33 @@ class CastTo(HostFlags, torch.nn.Module):
                 ops.dynamic_check("XP[8,0](CSN)", *dyn, what="CastTo.set_dynamic")   # (the granularity alone)
             else:
                 ops.dynamic_check(self.format, *dyn, what="CastTo.set_dynamic")
+        if out is not None:
+            _, _, k_, ofmt_ = ops.outlier_check("XP[8,0](CSN)" if isinstance(self.format, Same) else self.format, dyn[1], out["k"],
+                                                   out["outlier_format"], dyn[0], what="CastTo.set_dynamic")
+            out = {"k": k_, "outlier_format": ofmt_} if k_ else None
         self._dynamic = dyn
+        self._outliers = out
 
     @property
     def dynamic(self):
-        """None, "per_token", "per_tensor" or {"per_group": g} (set_dynamic)"""
+        """None, "per_token", "per_tensor" or {"per_group": g} (set_dynamic); with outliers set, the dict {"per_group": g, "outliers": k} or
+        {"granularity": "per_token", "outliers": k}, with "outlier_format" (its shorthand) where one is set"""
         dyn = self._dynamic
         if dyn is None:
             return None
+        if self._outliers is not None:
+            d = {"per_group": dyn[1]} if dyn[0] == "per_group" else {"granularity": dyn[0]}
+            d["outliers"] = self._outliers["k"]
+            if self._outliers["outlier_format"] is not None:
+                d["outlier_format"] = repr(self._outliers["outlier_format"])
+            return d
         return {"per_group": dyn[1]} if dyn[0] == "per_group" else dyn[0]
 
     def _dynamic_cast(self, x, out_dtype):
         g, gs = self._dynamic
+        if self._outliers is not None:
+            return ops.outlier_fixed_qdq(x, self.format, gs, self._outliers["k"], symmetric_qscheme=self.qscheme in _SYMMETRIC,
+                                         outlier_format=self._outliers["outlier_format"], granularity=g, out_dtype=out_dtype)
         return ops.dynamic_fixed_qdq(x, self.format, g, gs, symmetric_qscheme=self.qscheme in _SYMMETRIC, out_dtype=out_dtype)
 
     # ------------------------------------------------------------------ learned step size (LSQ / LSQ+)
@@ -845,10 +892,11 @@ class CastToDict(torch.nn.ModuleDict):
             self[k].set_pre_transform(t)
 
     def set_dynamic(self, dynamic):
-        """one setting (None, "per_token", "per_tensor", {"per_group": g}) for every cast, or a list / dict of settings over the casts the
-        way set_pre_transform takes them"""
-        if dynamic is None or isinstance(dynamic, str) or (isinstance(dynamic, dict) and set(dynamic) == {"per_group"}
-                                                           and "per_group" not in self.keys()):
+        """one setting (None, "per_token", "per_tensor", {"per_group": g}, or a dict with "outliers" as CastTo.set_dynamic takes it) for every
+        cast, or a list / dict of settings over the casts the way set_pre_transform takes them"""
+        one = isinstance(dynamic, dict) and (set(dynamic) == {"per_group"} or ("outliers" in dynamic and set(dynamic) <= {
+            "per_group", "granularity", *_OUTLIER_KEYS})) and not set(dynamic) & set(self.keys())
+        if dynamic is None or isinstance(dynamic, str) or one:
             for c in self.values():
                 c.set_dynamic(dynamic)
             return

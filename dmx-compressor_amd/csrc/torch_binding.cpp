@@ -1183,6 +1183,44 @@ std::tuple<Tensor, Tensor, Tensor, Tensor> hqq_qdq_meta(const Tensor& x, int64_t
                          want_codes ? empty_like_shape(x, at::kByte) : at::empty({0}, x.options().dtype(at::kByte)));
 }
 
+// ------------------------------------------------------------------------------------------------ outlier-aware dynamic cast
+// x: contiguous; segment: the group size; k: outliers per group; outlier_fmt: [man_bits, exp_bits, exp_bias, flush_subnormal] or empty = the
+// input's own bits -> (out, scale float32 [n_segments], zero_point int64 [n_segments], idx int32 [n_segments, k], val [n_segments, k] of
+// out's dtype; the qparams empty unless want_qparams, idx / val empty unless want_outliers).
+// DMXQ_ERR_UNSUPPORTED (NotImplementedError, nothing launched): the front end runs its chain.
+std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor> outlier_fixed_qdq(const Tensor& x, int64_t segment, int64_t k, int64_t precision, int64_t fraction,
+                                                                     bool clamp, bool symmetric, int64_t rounding, int64_t qmin, int64_t qmax,
+                                                                     bool symmetric_qscheme, at::IntArrayRef outlier_fmt, bool want_qparams,
+                                                                     bool want_outliers, OptDtype out_dtype) {
+  const Tensor xc = prep(x, "outlier_fixed_qdq");
+  TORCH_CHECK(segment >= 1 && xc.numel() % segment == 0, "outlier_fixed_qdq: the segment must divide the number of elements");
+  TORCH_CHECK(k >= 0, "outlier_fixed_qdq: k must not be negative");
+  const int64_t n = xc.numel() / segment;
+  Tensor out = empty_like_shape(xc, out_dtype);
+  Tensor sc = at::empty({want_qparams ? n : 0}, xc.options().dtype(at::kFloat));
+  Tensor zp = at::empty({want_qparams ? n : 0}, xc.options().dtype(at::kLong));
+  Tensor idx = at::empty({want_outliers ? n : 0, k}, xc.options().dtype(at::kInt));
+  Tensor val = at::empty({want_outliers ? n : 0, k}, out.options());
+  dmxq_float_fmt fo;
+  Launch l(xc);
+  check(dmxq_outlier_fixed_qdq(xc.data_ptr(), out.data_ptr(), dt_code(xc.scalar_type()), dt_code(out.scalar_type()), n, segment, (int)k,
+                               (int)precision, (int)fraction, clamp ? 1 : 0, symmetric ? 1 : 0, (int)rounding, (int)qmin, (int)qmax,
+                               symmetric_qscheme ? 1 : 0, fmt_of(outlier_fmt, &fo), want_qparams ? (float*)sc.data_ptr() : nullptr,
+                               want_qparams ? (int64_t*)zp.data_ptr() : nullptr, want_outliers ? (int32_t*)idx.data_ptr() : nullptr,
+                               want_outliers ? val.data_ptr() : nullptr, l.stream),
+        "dmxq_outlier_fixed_qdq");
+  return std::make_tuple(out, sc, zp, idx, val);
+}
+std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor> outlier_fixed_qdq_meta(const Tensor& x, int64_t segment, int64_t k, int64_t, int64_t, bool, bool,
+                                                                          int64_t, int64_t, int64_t, bool, at::IntArrayRef, bool want_qparams,
+                                                                          bool want_outliers, OptDtype out_dtype) {
+  const int64_t all = segment >= 1 ? x.numel() / segment : 0;
+  const int64_t n = want_qparams ? all : 0, m = want_outliers ? all : 0;
+  Tensor out = empty_like_shape(x, out_dtype);
+  return std::make_tuple(out, at::empty({n}, x.options().dtype(at::kFloat)), at::empty({n}, x.options().dtype(at::kLong)),
+                         at::empty({m, k}, x.options().dtype(at::kInt)), at::empty({m, k}, out.options()));
+}
+
 // ------------------------------------------------------------------------------------------------ Wanda
 // acc (float64 [C], C = x's last dim) += the sum of squares over every other dim; scratch: dmxq_channel_sumsq_workspace_bytes bytes of
 // any contiguous device tensor
@@ -1361,6 +1399,7 @@ TORCH_LIBRARY(dmxq, m) {
   m.def("codebook_qdq(Tensor x, int mode, int segment, Tensor levels, float norm, bool want_scale, bool want_index, ScalarType? out_dtype=None) -> (Tensor, Tensor, Tensor)");
   m.def("codebook_accumulate(Tensor x, int mode, int segment, Tensor levels, float norm, Tensor(a!) acc, bool accumulate) -> ()");
   m.def("hqq_qdq(Tensor x, int segment, int rounding, int qmin, int qmax, float lp_norm, float beta, float kappa, int iters, bool want_qparams, bool want_codes, ScalarType? out_dtype=None) -> (Tensor, Tensor, Tensor, Tensor)");
+  m.def("outlier_fixed_qdq(Tensor x, int segment, int k, int precision, int fraction, bool clamp, bool symmetric, int rounding, int qmin, int qmax, bool symmetric_qscheme, int[] outlier_fmt, bool want_qparams, bool want_outliers, ScalarType? out_dtype=None) -> (Tensor, Tensor, Tensor, Tensor, Tensor)");
 }
 
 #define DMXQ_IMPL(m, name) m.impl(#name, &name)
@@ -1372,7 +1411,7 @@ TORCH_LIBRARY(dmxq, m) {
   X(m, unary_cast); X(m, unary_cast_table); X(m, lut16_apply); X(m, softmax_cast); X(m, norm_cast); X(m, group_minmax_accumulate); X(m, gptq_block); X(m, hist_observe); X(m, hist_qparams); \
   X(m, error_stats); X(m, cast_error); X(m, hadamard_qdq); X(m, dynamic_fixed_qdq); X(m, gptq_block_dynamic); X(m, dynamic_float_qdq); \
   X(m, channel_sumsq); X(m, wanda_nm); X(m, channel_sumabs); X(m, awq_group_error); X(m, block_scaled_float_qdq); X(m, block_scaled_tensor_scale); \
-  X(m, lsq_backward); X(m, codebook_qdq); X(m, codebook_accumulate); X(m, hqq_qdq)
+  X(m, lsq_backward); X(m, codebook_qdq); X(m, codebook_accumulate); X(m, hqq_qdq); X(m, outlier_fixed_qdq)
 
 // "CUDA" is the dispatch key of HIP tensors in a ROCm build of PyTorch
 TORCH_LIBRARY_IMPL(dmxq, CUDA, m) {
@@ -1442,4 +1481,7 @@ PYBIND11_MODULE(dmxq_fast, m) {
   m.def("codebook_accumulate", &codebook_accumulate);
   m.def("hqq_qdq", &hqq_qdq, py::arg("x"), py::arg("segment"), py::arg("rounding"), py::arg("qmin"), py::arg("qmax"), py::arg("lp_norm"), py::arg("beta"),
         py::arg("kappa"), py::arg("iters"), py::arg("want_qparams"), py::arg("want_codes"), py::arg("out_dtype") = py::none());
+  m.def("outlier_fixed_qdq", &outlier_fixed_qdq, py::arg("x"), py::arg("segment"), py::arg("k"), py::arg("precision"), py::arg("fraction"), py::arg("clamp"),
+        py::arg("symmetric"), py::arg("rounding"), py::arg("qmin"), py::arg("qmax"), py::arg("symmetric_qscheme"), py::arg("outlier_fmt"),
+        py::arg("want_qparams"), py::arg("want_outliers"), py::arg("out_dtype") = py::none());
 }

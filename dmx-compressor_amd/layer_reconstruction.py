@@ -50,12 +50,21 @@ def refuse_learnable_weight_cast(module, what):
                                   "(set_learnable(None)) first")
 
 
+def refuse_outlier_weight_cast(module, what):
+    """GPTQ, AWQ and HQQ on a module whose dynamic weight cast keeps outliers (CastTo.set_dynamic with "outliers"): NotImplementedError"""
+    wc = getattr(module, "weight_cast", None)
+    if wc is not None and wc._outliers is not None:
+        raise NotImplementedError(f"{what} with an outlier-aware weight cast (weight_dynamic = {wc.dynamic!r}) is not supported: it would "
+                                  "reproduce the cast without its outliers; clear the outliers (set_dynamic without \"outliers\") first")
+
+
 class OptimalBrainCompressor:
     H = None
 
     def __init__(self, module):
         refuse_learnable_weight_cast(module, "GPTQ")
         refuse_codebook_weight_cast(module, "GPTQ")
+        refuse_outlier_weight_cast(module, "GPTQ")
         self.module = module
         self.example_counter = 0
 
@@ -540,6 +549,7 @@ class AWQCalibrator:
     def __init__(self, module, hyperparams, sumabs=None, gram=None, n_tokens: int = 0):
         refuse_learnable_weight_cast(module, "AWQ")
         refuse_codebook_weight_cast(module, "AWQ")
+        refuse_outlier_weight_cast(module, "AWQ")   # (neither ops.awq_scaled_error nor its chain selects outliers)
         self.module = module
         self.hyperparams = hyperparams
         self.sumabs, self.gram = sumabs, gram
@@ -633,6 +643,7 @@ def refuse_hqq(module):
     refuse_scaled_weight_cast_for(module, "HQQ")
     refuse_learnable_weight_cast(module, "HQQ")
     refuse_codebook_weight_cast(module, "HQQ")
+    refuse_outlier_weight_cast(module, "HQQ")
     if wc.pre_transform:
         raise DmxqError(f"HQQ with a weight cast pre_transform {sorted(wc.pre_transform)} is not supported: the zero points would be solved "
                         "for the rotated weight")

@@ -246,8 +246,10 @@ class DmxModule(FastAttr, torch.nn.Module):
             self.output_casts.set_format(config["output_formats"])
         if "pre_output_transform" in config:
             self.output_casts.set_pre_transform(config["pre_output_transform"])
-        # dynamic scales for the integer casts (CastTo.set_dynamic): None, "per_token", "per_tensor" or {"per_group": g} -- one setting
-        # for every cast of the group, or a list / dict over them; after the formats of the same config, which they are checked against
+        # dynamic scales for the integer casts (CastTo.set_dynamic): None, "per_token", "per_tensor" or {"per_group": g}, the last also as
+        # {"per_group": g, "outliers": k} / {"granularity": "per_token", "outliers": k} with an optional "outlier_format" (the k largest
+        # magnitudes of a segment kept at higher precision: ops.outlier_fixed_qdq) -- one setting for every cast of the group, or a list /
+        # dict over them; after the formats of the same config, which they are checked against
         if "input_dynamic" in config:
             self.input_casts.set_dynamic(config["input_dynamic"])
         if "output_dynamic" in config:

@@ -58,7 +58,8 @@ const char* dmxq_status_string(int status);
  * dmxq_dynamic_float_qdq, dmxq_dynamic_float_class, dmxq_channel_sumsq_accumulate, dmxq_channel_sumsq_workspace_bytes, dmxq_wanda_nm,
  * dmxq_wanda_class, dmxq_row_class_of, dmxq_channel_sumabs_accumulate, dmxq_awq_group_error, dmxq_awq_class,
  * dmxq_block_scaled_float_qdq, dmxq_block_scaled_float_class, dmxq_block_scaled_tensor_scale, dmxq_nm_mask_class, dmxq_lsq_backward, dmxq_lsq_class, dmxq_lsq_scratch_bytes,
- * dmxq_codebook_qdq, dmxq_codebook_class, dmxq_codebook_accumulate, dmxq_codebook_workspace_bytes, dmxq_hqq_qdq, dmxq_hqq_class) leave it at 4: a caller built against 4 runs on
+ * dmxq_codebook_qdq, dmxq_codebook_class, dmxq_codebook_accumulate, dmxq_codebook_workspace_bytes, dmxq_hqq_qdq, dmxq_hqq_class,
+ * dmxq_outlier_fixed_qdq, dmxq_outlier_class) leave it at 4: a caller built against 4 runs on
  * this library unchanged.  4 = round 5: + dmxq_float_qdq_multi, dmxq_fixed_float_qdq_multi; 3 = round 4: + dmxq_weight_hypernet_multi,
  * dmxq_unary_cast_table, dmxq_lut16_apply.  Nothing was ever removed or changed: a caller built against version n runs on any library >= n. */
 int dmxq_abi_version(void);
@@ -673,6 +674,29 @@ int dmxq_codebook_accumulate(const void* in, int dtype_in, int mode, int64_t n_s
 int dmxq_hqq_class(int dtype, int64_t segment);
 int dmxq_hqq_qdq(const void* in, void* out, int dtype_in, int dtype_out, int64_t n_segments, int64_t segment, int rounding, int qmin, int qmax,
                  float lp_norm, float beta, float kappa, int iters, float* scale_out, float* zero_out, uint8_t* codes_out, void* stream);
+
+/* Outlier-aware dynamic integer cast in ONE launch (csrc/outlier_quant.hip; DESIGN.md §8 "Outlier-aware dynamic cast", whose text is the
+ * contract; SpQR, Dettmers et al. 2023; SqueezeLLM, Kim et al. 2023).  Not in the reference.  Per group of `segment` consecutive elements
+ * of the contiguous tensor:
+ *   rank     by the bit pattern of |x| as float32 (a NaN above Inf above every finite value), equal patterns to the LOWER index; the
+ *            first k are the group's outliers;
+ *   inliers  the group with +0.0 in the outliers' places through dmxq_dynamic_fixed_qdq's arithmetic, (scale, zero point) included:
+ *            qparams take min(mn, 0) / max(mx, 0), so they are those of the other elements alone;
+ *   outliers O(x) in their places: the input's own bits (outlier_format NULL or exp_bits == 0), or the nearest cast to the signed float
+ *            format as dmxq_float_qdq computes it, rounded once to the tensor's dtype.
+ * scale_out / zp_out: each NULL, or a DEVICE array of n_segments entries.  idx_out (int32) and val_out (the tensor's dtype): both NULL, or
+ * DEVICE arrays of n_segments * k entries, 4-byte aligned: the outliers' positions in the group and O(x), in rank order.
+ * DMXQ_ERR_UNSUPPORTED, nothing launched (the caller runs its chain): k outside 1 .. 8, a segment that is no power of two from 16 to
+ * 256, dtype_in != dtype_out, a base that is not 16-byte aligned, rounding other than nearest, fraction != 0, no clamp, precision > 22,
+ * an outlier format outside 1 .. 8 exponent and 0 .. 22 mantissa bits.  DMXQ_ERR_BAD_ARG: null data pointers, negative sizes, invalid
+ * dtype / rounding, qmax <= qmin, k < 0 or k >= segment, one of idx_out / val_out without the other.  No workspace, no allocation, no
+ * host synchronisation: capturable.
+ * dmxq_outlier_class: DMXQ_DYN_GROUP where the entry takes groups of `segment` elements of `dtype`, DMXQ_DYN_NONE otherwise; no GPU involved. */
+int dmxq_outlier_class(int dtype, int64_t segment);
+int dmxq_outlier_fixed_qdq(const void* in, void* out, int dtype_in, int dtype_out, int64_t n_segments, int64_t segment, int k, int precision,
+                           int fraction, int clamp, int symmetric, int rounding, int qmin, int qmax, int symmetric_qscheme,
+                           const dmxq_float_fmt* outlier_format, float* scale_out, int64_t* zp_out, int32_t* idx_out, void* val_out,
+                           void* stream);
 
 /* Wanda (Sun et al., 2023): activation-aware N:M pruning calibrated on the device (csrc/wanda.hip; DESIGN.md §8 "Wanda").  Not in the
  * reference.  For a Linear weight W[rows, L] and calibration inputs X[n_tokens, L]:
