@@ -1057,6 +1057,29 @@ def awq_group_error(w, s, group, precision, fraction, clamp, symmetric, qmin, qm
     return d, wq
 
 
+@_guarded
+def awq_clip(w, blocks, ratios, y, group, precision, fraction, clamp, symmetric, qmin, qmax, symmetric_qscheme, want_best, want_clip, want_losses):
+    """y (w's dtype and shape, may be w) is written -> (best uint8 [rows, G], clip float32 [rows, G], losses float32 [rows, G, n]): empty
+    unless wanted"""
+    wc = _prep(w, "awq_clip")
+    if wc.dim() != 2 or group < 1 or wc.shape[1] % group != 0:
+        raise RuntimeError("awq_clip: the weight must be a [rows, L] matrix with the group size dividing L")
+    rows, G, n = wc.shape[0], wc.shape[1] // group, ratios.numel()
+    for t, shape, what in ((blocks, (G, group, group), "blocks"), (ratios, (n,), "ratios")):
+        if not (t.is_cuda and t.device == wc.device and t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == shape):
+            raise RuntimeError(f"awq_clip: {what} must be a contiguous float32 {list(shape)} tensor on the weight's device")
+    if not (y.is_cuda and y.device == wc.device and y.dtype == wc.dtype and y.is_contiguous() and y.shape == wc.shape):
+        raise RuntimeError("awq_clip: y must be a contiguous tensor of the weight's dtype and shape on its device")
+    best = torch.empty((rows, G) if want_best else 0, dtype=torch.uint8, device=wc.device)
+    clip = torch.empty((rows, G) if want_clip else 0, dtype=torch.float32, device=wc.device)
+    losses = torch.empty((rows, G, n) if want_losses else 0, dtype=torch.float32, device=wc.device)
+    check(lib().dmxq_awq_clip(ptr(wc), dtype_code(wc.dtype), ptr(blocks), ptr(ratios), n, ptr(y), ptr(best) if want_best else None,
+                              ptr(clip) if want_clip else None, ptr(losses) if want_losses else None, rows, wc.shape[1], group, precision,
+                              fraction, int(bool(clamp)), int(bool(symmetric)), qmin, qmax, int(bool(symmetric_qscheme)), stream_of(wc)),
+          "dmxq_awq_clip")
+    return best, clip, losses
+
+
 # ------------------------------------------------------------------------------------------------ block-scaled float cast
 @_guarded
 def block_scaled_float_qdq(x, group, fmt, scale_fmt, scale_max, tensor_scale, want_scale, want_code, out_dtype=None):

@@ -67,7 +67,9 @@ _FAST_CALIBRATION_NAMES = {"hist_observe": "hist_observe", "hist_qparams": "hist
                            # HQQ: the same
                            "hqq_qdq": "hqq_qdq",
                            # the outlier-aware dynamic cast: the same
-                           "outlier_fixed_qdq": "outlier_fixed_qdq"}
+                           "outlier_fixed_qdq": "outlier_fixed_qdq",
+                           # the AWQ clip search: no autograd to lose
+                           "awq_clip": "awq_clip"}
 FAST = None
 
 

@@ -34,6 +34,7 @@ __all__ = [
     "BLOCK_SCALED_CHAIN_BY_DEFAULT",
     "channel_sumsq", "channel_sumsq_workspace_bytes", "wanda_score", "wanda_nm_sparsify", "wanda_class", "WANDA_CHAIN_BY_DEFAULT",
     "channel_sumabs", "awq_candidate_scales", "awq_scaled_error", "awq_class", "awq_search", "AWQ_CHAIN_BY_DEFAULT",
+    "awq_clip", "awq_clip_check", "awq_clip_class", "awq_clip_ratios", "awq_gram_blocks", "AWQ_CLIP_CHAIN_BY_DEFAULT", "AWQ_CLIP_MAX_RATIOS",
 ]
 
 _ops = None   # the raw namespace: set by bind()
@@ -2686,3 +2687,193 @@ def awq_search(w, gram, scales, error_fn):
         best = torch.where(finite, losses, torch.full_like(losses, float("inf"))).argmin()
         best = torch.where(finite.any(), best, torch.zeros_like(best))
         return losses, best
+
+
+# ---------------------------------------------------------------------------------------------------- AWQ clipping
+# Group sizes of dmxq_awq_clip that fused=None sends to the chain although the kernel takes them: AWQ_CHAIN_BY_DEFAULT's rule, a class
+# goes to the kernel by default only where tools/bench_awq_clip.py MEASURED it faster than the pinned chain on the same buffers
+# (profiles/r23_awq_clip.txt).
+AWQ_CLIP_CHAIN_BY_DEFAULT = frozenset()
+AWQ_CLIP_MAX_RATIOS = 32
+# which route the calls of this front end took, counted on the host: private, for the tests (fused=True must have run the kernel)
+_awq_clip_routes = {"fused": 0, "chain": 0}
+_awq_clip_ratio_cache = {}   # (the ratios' bytes, device) -> the device copy: a capture replays without a host-to-device copy
+
+
+def awq_clip_ratios(n_grid: int = 20, max_shrink: float = 0.5):
+    """AutoAWQ's list of clipping ratios as a float32 CPU tensor: 1 - i / n_grid for i = 0 .. int(max_shrink * n_grid) - 1, each formed
+    in double and rounded once to float32 (the defaults: 1.0, 0.95, .. 0.55).  ValueError: a list that would be empty or longer than 32."""
+    if isinstance(n_grid, bool) or not isinstance(n_grid, int) or n_grid < 1:
+        raise ValueError(f"awq_clip_ratios: n_grid must be a positive integer, got {n_grid!r}")
+    if isinstance(max_shrink, bool) or not isinstance(max_shrink, (int, float)) or not 0.0 < max_shrink <= 1.0:
+        raise ValueError(f"awq_clip_ratios: max_shrink must lie in (0, 1], got {max_shrink!r}")
+    n = int(max_shrink * n_grid)
+    if not 1 <= n <= AWQ_CLIP_MAX_RATIOS:
+        raise ValueError(f"awq_clip_ratios: int(max_shrink * n_grid) must lie in 1 .. {AWQ_CLIP_MAX_RATIOS}, got {n}")
+    return torch.tensor([1.0 - i / n_grid for i in range(n)], dtype=torch.float64).to(torch.float32)
+
+
+def awq_gram_blocks(gram, g: int):
+    """the float32 [L / g, g, g] diagonal blocks of a float32 [L, L] matrix, contiguous: blocks[k][j][l] = gram[k g + j][k g + l]"""
+    if not isinstance(gram, torch.Tensor) or gram.dim() != 2 or gram.shape[0] != gram.shape[1] or gram.dtype != torch.float32:
+        raise ValueError("awq_gram_blocks: gram must be a square float32 matrix")
+    if isinstance(g, bool) or not isinstance(g, int) or g < 1 or gram.shape[0] % g:
+        raise ValueError(f"awq_gram_blocks: the group size must be a positive integer dividing {gram.shape[0]}, got {g!r}")
+    G = gram.shape[0] // g
+    return gram.reshape(G, g, G, g).permute(1, 3, 0, 2).diagonal(dim1=2, dim2=3).permute(2, 0, 1).contiguous()
+
+
+def awq_clip_class(dtype: torch.dtype, L: int, group: int) -> bool:
+    """whether dmxq_awq_clip takes rows of L elements of `dtype` with groups of `group` in its one-launch kernel, asked of the library
+    itself (dmxq_awq_clip_class; no GPU involved): group 16, 32, 64 or 128 dividing L"""
+    from ._lib import dtype_code, lib
+    return bool(lib().dmxq_awq_clip_class(dtype_code(dtype), int(L), int(group)))
+
+
+def awq_clip_check(w, blocks, fmt, group_size, ratios=None, out=None, what: str = "awq_clip"):
+    """-> (format, group_size, ratios) of an AWQ clip call, or the argument error (ValueError / TypeError), before any GPU use: a clamped
+    fraction-free FixedPoint format with nearest rounding, a group size dividing the weight's columns, float32 [G, g, g] contiguous
+    blocks, and ratios -- None (awq_clip_ratios()), a sequence or a float32 tensor of 1 .. 32 entries; held on the host they are checked
+    (first entry 1.0, every entry in (0, 1], non-increasing) and come back as a float32 CPU tensor, a tensor on a device comes back as it
+    is (its values are the caller's contract: reading them would synchronise)."""
+    fmt, _, group_size = dynamic_check(fmt, "per_group", group_size, what=what)
+    if fmt.rounding != "nearest":
+        raise ValueError(f"{what}: the definition rounds to nearest, got a format with {fmt.rounding!r} rounding: {fmt!r}")
+    if not isinstance(w, torch.Tensor) or w.dim() != 2:
+        raise ValueError(f"{what}: the weight must be an [out, in] matrix")
+    if w.dtype not in (torch.float32, torch.float16, torch.bfloat16):
+        raise TypeError(f"{what}: the weight must be float32, float16 or bfloat16, got {w.dtype}")
+    L = w.shape[1]
+    if L % group_size:
+        raise ValueError(f"{what}: the last dimension has {L} elements, not a multiple of the group size {group_size}")
+    G = L // group_size
+    if not isinstance(blocks, torch.Tensor) or blocks.dtype != torch.float32:
+        raise TypeError(f"{what}: blocks must be a float32 tensor, got {getattr(blocks, 'dtype', type(blocks))}")
+    if tuple(blocks.shape) != (G, group_size, group_size) or not blocks.is_contiguous():
+        raise ValueError(f"{what}: blocks must be a contiguous [{G}, {group_size}, {group_size}] tensor, got {tuple(blocks.shape)}")
+    if ratios is None:
+        ratios = awq_clip_ratios()
+    elif isinstance(ratios, torch.Tensor):
+        if ratios.dtype != torch.float32:
+            raise TypeError(f"{what}: ratios must be float32, got {ratios.dtype}")
+    else:
+        try:
+            ratios = torch.tensor([float(r) for r in ratios], dtype=torch.float64).to(torch.float32)
+        except (TypeError, ValueError):
+            raise TypeError(f"{what}: ratios must be None, a sequence of numbers or a float32 tensor, got {ratios!r}") from None
+    if ratios.dim() != 1 or not 1 <= ratios.numel() <= AWQ_CLIP_MAX_RATIOS:
+        raise ValueError(f"{what}: ratios must hold 1 .. {AWQ_CLIP_MAX_RATIOS} entries in one dimension, got {tuple(ratios.shape)}")
+    if not ratios.is_cuda:
+        r = ratios.tolist()
+        if r[0] != 1.0 or not all(0.0 < v <= 1.0 for v in r) or any(b > a for a, b in zip(r, r[1:])):
+            raise ValueError(f"{what}: ratios must start at 1.0, lie in (0, 1] and never increase, got {r}")
+    if out is not None:
+        if not isinstance(out, torch.Tensor) or out.shape != w.shape or out.dtype != w.dtype or not out.is_contiguous():
+            raise ValueError(f"{what}: out must be a contiguous tensor of the weight's shape and dtype")
+    return fmt, group_size, ratios
+
+
+def _awq_clip_device_ratios(ratios, device):
+    if ratios.is_cuda:
+        return ratios if ratios.is_contiguous() else ratios.contiguous()
+    key = (ratios.numpy().tobytes(), device)
+    r = _awq_clip_ratio_cache.get(key)
+    if r is None:
+        if len(_awq_clip_ratio_cache) >= 64:
+            _awq_clip_ratio_cache.clear()
+        r = _awq_clip_ratio_cache[key] = ratios.to(device)
+    return r
+
+
+def _awq_clip_chain(wc, blocks, r, fmt, g, sym):
+    """DESIGN.md §8 "AWQ clipping" as written, in torch operations and library calls -> (y, best, clip, losses)"""
+    rows, L = wc.shape
+    G, n, T = L // g, r.numel(), wc.dtype
+    W = wc.float().reshape(rows, G, g)
+    a = W.abs().amax(dim=-1, keepdim=True)
+    ordinary = torch.isfinite(a) & (a > 0)
+    nan = torch.full_like(a, float("nan"))
+    y, clip = wc.reshape(rows, G, g).clone(), a.clone()
+    best = torch.zeros(rows, G, 1, dtype=torch.uint8, device=wc.device)
+    best_loss = torch.full_like(a, float("inf"))
+    losses = torch.empty(rows, G, n, dtype=torch.float32, device=wc.device)
+    for i in range(n):
+        c = (a * r[i]).to(T).float()
+        v = torch.where(W > c, c, torch.where(W < -c, -c, W)).to(T)
+        q = dynamic_fixed_qdq(v.reshape(rows, L), fmt, "per_group", g, symmetric_qscheme=sym).float().reshape(rows, G, g)
+        d = q - W
+        t = blocks[:, :, 0] * d[:, :, 0:1]
+        for l in range(1, g):   # (the sum in index order: 2 (g - 1) launches per candidate -- slow by construction)
+            t = t + blocks[:, :, l] * d[:, :, l:l + 1]
+        p = d * t
+        while p.shape[-1] > 1:
+            p = p[..., 0::2] + p[..., 1::2]
+        loss = torch.where(ordinary, p, nan)
+        losses[:, :, i:i + 1] = loss
+        better = torch.isfinite(loss) & (loss < best_loss)
+        best_loss = torch.where(better, loss, best_loss)
+        y = torch.where(better, v, y)
+        clip = torch.where(better, c, clip)
+        best = torch.where(better, torch.full_like(best, i), best)
+    return y.reshape(rows, L), best.reshape(rows, G), clip.reshape(rows, G), losses
+
+
+def awq_clip(w, blocks, fmt, group_size: int, ratios=None, symmetric_qscheme: bool = False, return_best: bool = False, return_clip: bool = False,
+             return_losses: bool = False, out=None, fused: Optional[bool] = None):
+    """AWQ weight clipping (AutoAWQ's clip search; DESIGN.md §8 "AWQ clipping"): every group of group_size columns of every row of the
+    [out, in] weight w keeps the clipping range c = T(max|W| * ratio), among the candidate `ratios`, whose per-group dynamic integer cast
+    q = dynamic_fixed_qdq(clamp(W, -c, c)) disturbs the layer's output least: loss = d^T blocks[k] d with d = q - W and blocks the float32
+    [G, g, g] diagonal blocks of the calibration inputs' second moment (awq_gram_blocks).  Returns y, the clamped weight in w's dtype
+    (written into `out` when given; out may be w), followed by those asked for of best (uint8 [out, G], the chosen candidate), clip
+    (float32 [out, G], its c) and losses (float32 [out, G, n]).  Candidate 0 is no clip, and no group's loss rises above its unclipped
+    one; the guarantee is per group -- the off-diagonal blocks of the second moment are not looked at.
+    ONE launch (dmxq_awq_clip) for group_size 16, 32, 64 or 128 and 16-byte aligned tensors; the chain of torch operations that spells
+    the definition otherwise -- any group size, unaligned views, same bits, and slow by construction (2 (g - 1) launches per candidate
+    for the sum in index order alone).  fused=None: the kernel where it applies and group_size is not listed in
+    AWQ_CLIP_CHAIN_BY_DEFAULT; True: NotImplementedError instead of falling back; False: the chain.
+    ValueError / TypeError before any GPU use: see awq_clip_check."""
+    from .observer import get_qmin_qmax
+    fmt, group_size, ratios = awq_clip_check(w, blocks, fmt, group_size, ratios, out)
+    require_gpu(w, "awq_clip")
+    require_gpu(blocks, "awq_clip")
+    if out is not None:
+        require_gpu(out, "awq_clip")
+    qmin, qmax = get_qmin_qmax(fmt)
+    sym = bool(symmetric_qscheme)
+    with torch.no_grad():
+        wc = w.detach()
+        wc = wc if wc.is_contiguous() else wc.contiguous()
+        rows, L = wc.shape
+        G, n = L // group_size, ratios.numel()
+        y = out.detach() if out is not None else torch.empty_like(wc)
+
+        def result(best, clip, losses):
+            got = tuple(t for t, want in ((y, True), (best, return_best), (clip, return_clip), (losses, return_losses)) if want)
+            return got[0] if len(got) == 1 else got
+
+        if wc.numel() == 0:
+            return result(torch.empty(rows, G, dtype=torch.uint8, device=wc.device), torch.empty(rows, G, dtype=torch.float32, device=wc.device),
+                          torch.empty(rows, G, n, dtype=torch.float32, device=wc.device))
+        r = _awq_clip_device_ratios(ratios, wc.device)
+        if fused is not False:
+            ok = (fmt.precision <= 22 and awq_clip_class(wc.dtype, L, group_size)
+                  and all(t.data_ptr() % 16 == 0 for t in (wc, blocks, r, y)))
+            if not ok and fused:
+                raise NotImplementedError(f"awq_clip: no one-launch kernel for groups of {group_size} in rows of {L} {wc.dtype} elements with "
+                                          f"{fmt!r} (weight base address {wc.data_ptr() % 16} mod 16)")
+            if ok and fused is None and group_size in AWQ_CLIP_CHAIN_BY_DEFAULT:
+                ok = False
+            if ok:
+                try:
+                    best, clip, losses = _ops.awq_clip(wc, blocks.detach(), r, y, int(group_size), fmt.precision, fmt.fraction, bool(fmt.clamp),
+                                                       bool(fmt.symmetric), qmin, qmax, sym, bool(return_best), bool(return_clip),
+                                                       bool(return_losses))
+                    _awq_clip_routes["fused"] += 1
+                    return result(best, clip, losses)
+                except NotImplementedError:   # (DMXQ_ERR_UNSUPPORTED, nothing launched)
+                    if fused:
+                        raise
+        _awq_clip_routes["chain"] += 1
+        yc, best, clip, losses = _awq_clip_chain(wc, blocks.detach(), r, fmt, group_size, sym)
+        y.copy_(yc)
+        return result(best, clip, losses)

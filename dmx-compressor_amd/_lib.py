@@ -105,6 +105,8 @@ SIGNATURES = {
     "dmxq_hqq_qdq": [_vp, _vp, _i32, _i32, _i64, _i64, _i32, _i32, _i32, _f32, _f32, _f32, _i32, _vp, _vp, _vp, _vp],
     "dmxq_outlier_class": [_i32, _i64],
     "dmxq_outlier_fixed_qdq": [_vp, _vp, _i32, _i32, _i64, _i64, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp],
+    "dmxq_awq_clip_class": [_i32, _i64, _i64],
+    "dmxq_awq_clip": [_vp, _i32, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp],
     "dmxq_row_class_of": [_i32, _i32, _i32, _i32, _i64, _i64, _vp, _vp, _vp, _vp, _i32, _i64, _vp],
 }
 

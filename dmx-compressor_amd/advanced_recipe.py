@@ -6,7 +6,7 @@ from typing import Callable, Optional
 
 from .nn import DmxModule
 
-__all__ = ["DmxBaseRecipe", "DmxQuantizerCalibrationRecipe", "DmxSmoothQuantRecipe", "DmxGPTQRecipe", "DmxWandaRecipe", "DmxAWQRecipe", "DmxHQQRecipe"]
+__all__ = ["DmxBaseRecipe", "DmxQuantizerCalibrationRecipe", "DmxSmoothQuantRecipe", "DmxGPTQRecipe", "DmxWandaRecipe", "DmxAWQRecipe", "DmxAWQClipRecipe", "DmxHQQRecipe"]
 
 
 class DmxBaseRecipe:
@@ -69,6 +69,15 @@ class DmxAWQRecipe(DmxBaseRecipe):
     def __init__(self, hp_gen, **kwargs):
         super().__init__(hp_gen, **kwargs)
         self.recipe_context_manager = DmxModule.awq_scaling
+
+
+class DmxAWQClipRecipe(DmxBaseRecipe):
+    """AWQ weight clipping (DmxModule.awq_clipping): hp_gen maps the model to {module: DmxAWQClipHyperparams}; the calibration forwards
+    run inside the context, and on exit every Linear among them has its weight clamped group by group (ops.awq_clip)"""
+
+    def __init__(self, hp_gen, **kwargs):
+        super().__init__(hp_gen, **kwargs)
+        self.recipe_context_manager = DmxModule.awq_clipping
 
 
 class DmxHQQRecipe(DmxBaseRecipe):

@@ -19,51 +19,12 @@
 // No workspace, no allocation, no synchronisation with the host: capturable.
 #include <math.h>
 
+#include "awq_lane4.hpp"
 #include "dynamic_geom.hpp"
 #include "dynamic_quant.hpp"
 
 namespace dmxq {
 namespace {
-
-constexpr int kAwqV = 4;   // elements per lane
-
-// four consecutive elements of dtype DT, raw: 16 bytes (fp32) or 8 (16-bit); plain loads -- a search reads the same weight once per candidate
-template <int DT>
-__device__ __forceinline__ u32x4 awq_load4(const void* p, int64_t vec) {
-  if (DT == DMXQ_F32) return *(const u32x4*)((const char*)p + vec * 16);
-  const u32x2 v = *(const u32x2*)((const char*)p + vec * 8);
-  return u32x4{v.x, v.y, 0u, 0u};
-}
-template <int DT>
-__device__ __forceinline__ void awq_widen4(const u32x4& v, float (&x)[kAwqV]) {
-  if (DT == DMXQ_F32) {
-#pragma unroll
-    for (int j = 0; j < 4; j++) x[j] = u2f(v[j]);
-  } else {
-#pragma unroll
-    for (int j = 0; j < 2; j++) {
-      if (DT == DMXQ_BF16) { x[2 * j] = u2f(v[j] << 16); x[2 * j + 1] = u2f(v[j] & 0xFFFF0000u); }
-      else { x[2 * j] = half_lo(v[j]); x[2 * j + 1] = half_hi(v[j]); }
-    }
-  }
-}
-// fp32 -> DT (one rounding, the store's) -> fp32: the value the next launch of the chain would read back; the packed words are kept
-template <int DT>
-__device__ __forceinline__ u32x4 awq_round4(float (&x)[kAwqV]) {
-  u32x4 r;
-  if (DT == DMXQ_F32) {
-    r = u32x4{f2u(x[0]), f2u(x[1]), f2u(x[2]), f2u(x[3])};
-  } else {
-    r = u32x4{pack2<DT>(x[0], x[1]), pack2<DT>(x[2], x[3]), 0u, 0u};
-    awq_widen4<DT>(r, x);
-  }
-  return r;
-}
-template <int DT>
-__device__ __forceinline__ void awq_store4(void* p, int64_t vec, const u32x4& r) {
-  if (DT == DMXQ_F32) *(u32x4*)((char*)p + vec * 16) = r;
-  else *(u32x2*)((char*)p + vec * 8) = u32x2{r.x, r.y};
-}
 
 // groups of `lanes` adjacent lanes; nvec lane-vectors in all (a multiple of `lanes`); wave w takes vectors [w U 64, (w + 1) U 64)
 template <int DT, int U>

@@ -33,36 +33,6 @@ struct HqqArgs {
   int iters, code_bias;      // codes = q - qmin
 };
 
-// the sum over aligned groups of `lanes` adjacent lanes, every lane of a group ending with the same bits: the stages run
-// unconditionally and are kept or dropped by a select on a scalar condition (dyn_group_minmax's form)
-__device__ __forceinline__ float hqq_group_sum(float v, int lanes) {
-#define DMXQ_HQQ_DPP(ctrl, n)                                                                                   \
-  {                                                                                                              \
-    const float o = u2f((uint32_t)__builtin_amdgcn_update_dpp((int)f2u(v), (int)f2u(v), ctrl, 0xF, 0xF, false)); \
-    const float a = v + o;                                                                                       \
-    v = lanes >= n ? a : v;                                                                                      \
-  }
-  DMXQ_HQQ_DPP(0xB1, 2)    // quad_perm 1,0,3,2
-  DMXQ_HQQ_DPP(0x4E, 4)    // quad_perm 2,3,0,1
-  DMXQ_HQQ_DPP(0x141, 8)   // row_half_mirror
-  DMXQ_HQQ_DPP(0x140, 16)  // row_mirror
-#undef DMXQ_HQQ_DPP
-  if (lanes >= 32) v = v + __shfl_xor(v, 16);
-  if (lanes >= 64) v = v + __shfl_xor(v, 32);
-  return v;
-}
-
-// the adjacent-pair tree inside a lane's vector
-template <int V>
-__device__ __forceinline__ float hqq_vec_sum(float (&t)[V]) {
-#pragma unroll
-  for (int w = V / 2; w >= 1; w /= 2) {
-#pragma unroll
-    for (int k = 0; k < w; k++) t[k] = t[2 * k] + t[2 * k + 1];
-  }
-  return t[0];
-}
-
 // clamp(rint(x * rs + z), qmin, qmax): a NaN stays a NaN (torch.clamp's rule)
 __device__ __forceinline__ float hqq_q(float x, float rs, float z, const HqqArgs& a) {
   const float v = rintf(x * rs + z);

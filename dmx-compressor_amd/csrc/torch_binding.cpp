@@ -1289,6 +1289,39 @@ std::tuple<Tensor, Tensor> awq_group_error_meta(const Tensor& w, const Tensor&, 
   return std::make_tuple(empty_like_shape(w, at::kFloat), want_wq ? empty_like_shape(w, w.scalar_type()) : none_like(w));
 }
 
+// y (w's dtype and shape, may be w itself) is written -> (best uint8 [rows, G], clip float32 [rows, G], losses float32 [rows, G, n]): empty
+// 1-d tensors unless wanted.  DMXQ_ERR_UNSUPPORTED (NotImplementedError, nothing launched): the front end runs its chain.
+std::tuple<Tensor, Tensor, Tensor> awq_clip(const Tensor& w, const Tensor& blocks, const Tensor& ratios, Tensor y, int64_t group, int64_t precision,
+                                            int64_t fraction, bool clamp, bool symmetric, int64_t qmin, int64_t qmax, bool symmetric_qscheme,
+                                            bool want_best, bool want_clip, bool want_losses) {
+  const Tensor wc = prep(w, "awq_clip");
+  TORCH_CHECK(wc.dim() == 2 && group >= 1 && wc.size(1) % group == 0, "awq_clip: the weight must be a [rows, L] matrix with the group size dividing L");
+  const int64_t rows = wc.size(0), G = wc.size(1) / group, n = ratios.numel();
+  TORCH_CHECK(blocks.is_cuda() && blocks.device() == wc.device() && blocks.scalar_type() == at::kFloat && blocks.is_contiguous() &&
+                  blocks.dim() == 3 && blocks.size(0) == G && blocks.size(1) == group && blocks.size(2) == group,
+              "awq_clip: blocks must be a contiguous float32 [", G, ", ", group, ", ", group, "] tensor on the weight's device");
+  TORCH_CHECK(ratios.is_cuda() && ratios.device() == wc.device() && ratios.scalar_type() == at::kFloat && ratios.is_contiguous() && ratios.dim() == 1,
+              "awq_clip: ratios must be a contiguous float32 [n] tensor on the weight's device");
+  TORCH_CHECK(y.is_cuda() && y.device() == wc.device() && y.scalar_type() == wc.scalar_type() && y.is_contiguous() && y.sizes() == wc.sizes(),
+              "awq_clip: y must be a contiguous tensor of the weight's dtype and shape on its device");
+  Tensor best = want_best ? at::empty({rows, G}, wc.options().dtype(at::kByte)) : at::empty({0}, wc.options().dtype(at::kByte));
+  Tensor clip = want_clip ? at::empty({rows, G}, wc.options().dtype(at::kFloat)) : at::empty({0}, wc.options().dtype(at::kFloat));
+  Tensor losses = want_losses ? at::empty({rows, G, n}, wc.options().dtype(at::kFloat)) : at::empty({0}, wc.options().dtype(at::kFloat));
+  Launch l(wc);
+  check(dmxq_awq_clip(wc.data_ptr(), dt_code(wc.scalar_type()), (const float*)blocks.data_ptr(), (const float*)ratios.data_ptr(), (int)n, y.data_ptr(),
+                      want_best ? (uint8_t*)best.data_ptr() : nullptr, want_clip ? (float*)clip.data_ptr() : nullptr,
+                      want_losses ? (float*)losses.data_ptr() : nullptr, rows, wc.size(1), group, (int)precision, (int)fraction, clamp, symmetric,
+                      (int)qmin, (int)qmax, symmetric_qscheme, l.stream), "dmxq_awq_clip");
+  return std::make_tuple(best, clip, losses);
+}
+std::tuple<Tensor, Tensor, Tensor> awq_clip_meta(const Tensor& w, const Tensor&, const Tensor& ratios, Tensor, int64_t group, int64_t, int64_t, bool, bool,
+                                                 int64_t, int64_t, bool, bool want_best, bool want_clip, bool want_losses) {
+  const int64_t rows = w.size(0), G = group >= 1 ? w.size(1) / group : 0, n = ratios.numel();
+  return std::make_tuple(want_best ? at::empty({rows, G}, w.options().dtype(at::kByte)) : at::empty({0}, w.options().dtype(at::kByte)),
+                         want_clip ? at::empty({rows, G}, w.options().dtype(at::kFloat)) : at::empty({0}, w.options().dtype(at::kFloat)),
+                         want_losses ? at::empty({rows, G, n}, w.options().dtype(at::kFloat)) : at::empty({0}, w.options().dtype(at::kFloat)));
+}
+
 // ------------------------------------------------------------------------------------------------ block-scaled float cast
 // x: contiguous; groups of `group` consecutive elements; fmt / scale_fmt: (man, exp, bias, flush, rounding); tensor_scale: None (t = 1) or
 // ONE float32 on x's device, read by the kernel only -> (out, scale, scale_code_value: float32 [n_groups], empty unless wanted).
@@ -1393,6 +1426,7 @@ TORCH_LIBRARY(dmxq, m) {
   m.def("wanda_nm(Tensor w, Tensor act_norm, int K, int M, bool want_score, bool want_mask, bool want_y, ScalarType? mask_dtype=None, ScalarType? y_dtype=None) -> (Tensor, Tensor, Tensor)");
   m.def("channel_sumabs(Tensor x, Tensor(a!) acc, Tensor(b!) scratch) -> ()");
   m.def("awq_group_error(Tensor w, Tensor s, int group, int precision, int fraction, bool clamp, bool symmetric, int qmin, int qmax, bool symmetric_qscheme, bool want_wq) -> (Tensor, Tensor)");
+  m.def("awq_clip(Tensor w, Tensor blocks, Tensor ratios, Tensor(a!) y, int group, int precision, int fraction, bool clamp, bool symmetric, int qmin, int qmax, bool symmetric_qscheme, bool want_best, bool want_clip, bool want_losses) -> (Tensor, Tensor, Tensor)");
   m.def("block_scaled_float_qdq(Tensor x, int group, int[] fmt, int[] scale_fmt, float scale_max, Tensor? tensor_scale, bool want_scale, bool want_code, ScalarType? out_dtype=None) -> (Tensor, Tensor, Tensor)");
   m.def("block_scaled_tensor_scale(Tensor x, float fmax, float scale_max) -> Tensor");
   m.def("lsq_backward(Tensor x, Tensor g, Tensor scale, Tensor zero_point, int segment, int whole_rows, int precision, int rounding, int qmin, int qmax, float grad_factor, bool want_dz, bool want_dx) -> (Tensor, Tensor, Tensor)");
@@ -1411,7 +1445,7 @@ TORCH_LIBRARY(dmxq, m) {
   X(m, unary_cast); X(m, unary_cast_table); X(m, lut16_apply); X(m, softmax_cast); X(m, norm_cast); X(m, group_minmax_accumulate); X(m, gptq_block); X(m, hist_observe); X(m, hist_qparams); \
   X(m, error_stats); X(m, cast_error); X(m, hadamard_qdq); X(m, dynamic_fixed_qdq); X(m, gptq_block_dynamic); X(m, dynamic_float_qdq); \
   X(m, channel_sumsq); X(m, wanda_nm); X(m, channel_sumabs); X(m, awq_group_error); X(m, block_scaled_float_qdq); X(m, block_scaled_tensor_scale); \
-  X(m, lsq_backward); X(m, codebook_qdq); X(m, codebook_accumulate); X(m, hqq_qdq); X(m, outlier_fixed_qdq)
+  X(m, lsq_backward); X(m, codebook_qdq); X(m, codebook_accumulate); X(m, hqq_qdq); X(m, outlier_fixed_qdq); X(m, awq_clip)
 
 // "CUDA" is the dispatch key of HIP tensors in a ROCm build of PyTorch
 TORCH_LIBRARY_IMPL(dmxq, CUDA, m) {
@@ -1484,4 +1518,5 @@ PYBIND11_MODULE(dmxq_fast, m) {
   m.def("outlier_fixed_qdq", &outlier_fixed_qdq, py::arg("x"), py::arg("segment"), py::arg("k"), py::arg("precision"), py::arg("fraction"), py::arg("clamp"),
         py::arg("symmetric"), py::arg("rounding"), py::arg("qmin"), py::arg("qmax"), py::arg("symmetric_qscheme"), py::arg("outlier_fmt"),
         py::arg("want_qparams"), py::arg("want_outliers"), py::arg("out_dtype") = py::none());
+  m.def("awq_clip", &awq_clip);
 }

@@ -21,7 +21,7 @@ import torch.nn.functional as F
 
 from ._lib import DmxqError
 
-__all__ = ["OptimalBrainCompressor", "WandaCalibrator", "AWQCalibrator", "hqq_apply"]
+__all__ = ["OptimalBrainCompressor", "WandaCalibrator", "AWQCalibrator", "AWQClipCalibrator", "hqq_apply"]
 
 
 def refuse_scaled_weight_cast(module):
@@ -550,6 +550,8 @@ class AWQCalibrator:
         refuse_learnable_weight_cast(module, "AWQ")
         refuse_codebook_weight_cast(module, "AWQ")
         refuse_outlier_weight_cast(module, "AWQ")   # (neither ops.awq_scaled_error nor its chain selects outliers)
+        # the clip that follows the fuse: its refusals now, before any state is touched (SmoothQuant's own state is refuse_awq's matter)
+        self.clip_plan = refuse_awq_clip(module, after_awq_scaling=True) if hyperparams.clip is not None else None
         self.module = module
         self.hyperparams = hyperparams
         self.sumabs, self.gram = sumabs, gram
@@ -627,9 +629,119 @@ class AWQCalibrator:
         sq.enable(True)
         if self.hyperparams.fuse_to_weight:
             sq.fuse_to_weight(m.weight)
+        if self.clip_plan is not None:   # (fuse_to_weight holds: DmxAWQHyperparams): the GEMM now sees x / s, whose second moment is
+            with torch.no_grad():        # gram / s / s^T -- two float32 divisions in this order
+                s = sq.scale.detach().to(self.gram.device, torch.float32)
+                g = self.clip_plan[1]
+                blocks = ops.awq_gram_blocks(self.gram / s[:, None] / s[None, :], g)
+            awq_clip_apply(m, self.clip_plan, self.hyperparams.clip, blocks, self.n_tokens)
         m.__dict__.pop("_live_weight", None)   # (a LiveWeightBatch result computed without the scale)
         m.awq_losses, m.awq_best, m.awq_x_mean, m.awq_n_tokens = losses, best, x_mean, self.n_tokens
         m.awq_sumabs, m.awq_gram = self.sumabs, self.gram
+
+
+# ---------------------------------------------------------------------------------------------------- AWQ clipping
+def awq_clip_applies(module) -> bool:
+    """AWQ clipping acts on a Linear with a 2-D weight; on anything else nothing happens"""
+    return isinstance(module, torch.nn.Linear) and getattr(module, "weight", None) is not None and module.weight.dim() == 2
+
+
+def refuse_awq_clip(module, after_awq_scaling: bool = False):
+    """-> (format, group size, symmetric_qscheme) of a module DmxModule.awq_clipping takes, or the refusal as a DmxqError before any state
+    is touched.  after_awq_scaling: asked by an awq_scaling context that will fuse its scale and then clip -- SmoothQuant's state and the
+    active AWQ context are that context's own"""
+    from .cast import _SYMMETRIC
+    from .format import FixedPoint, Same
+    from .sparse import Dense
+    wc, st = module.weight_cast, module.weight_storage_cast
+    if wc is None:
+        raise DmxqError("AWQ clipping needs a weight cast: the module has none")
+    for what, setting in (("an outlier-aware", wc._outliers), ("a codebook", wc._codebook), ("a learnable", wc._learnable), ("a scaled float", wc._scaling)):
+        if setting is not None:
+            raise DmxqError(f"AWQ clipping with {what} weight cast is not supported: the search reproduces the plain per-group dynamic "
+                            "integer cast; clear the setting first")
+    if wc.pre_transform:
+        raise DmxqError(f"AWQ clipping with a weight cast pre_transform {sorted(wc.pre_transform)} is not supported: the clamp would act on "
+                        "the weight, the cast on its rotation")
+    if st is not None and not (isinstance(st.format, Same) and not st.pre_transform):
+        raise DmxqError("AWQ clipping needs a weight_storage_cast of SAME: the clamped weight must reach the weight cast as it is")
+    if (wc._dynamic is None or wc._dynamic[0] != "per_group" or not isinstance(wc.format, FixedPoint) or wc.format.rounding != "nearest"
+            or not wc._flag("fake_quant_enabled") or wc._flag("observer_enabled")):
+        raise DmxqError(f"AWQ clipping needs a weight cast that is a nearest-rounding dynamic per-group integer cast (weight_dynamic = "
+                        f"{{'per_group': g}} on XP[p,0](C.N)) and runs as such (fake quantisation on, no observer), got {wc.format!r} with "
+                        f"weight_dynamic = {wc.dynamic!r}")
+    sp = module.weight_sparsifier
+    if sp is not None and not isinstance(sp.sparseness, Dense):
+        raise DmxqError(f"AWQ clipping with a weight sparseness {sp.sparseness!r} is not supported: the search casts the dense weight")
+    if module.weight.dtype not in (torch.float32, torch.float16, torch.bfloat16) or module.weight.shape[1] % wc._dynamic[1]:
+        raise DmxqError(f"AWQ clipping needs a float32, float16 or bfloat16 weight whose {module.weight.shape[1]} columns are a multiple of "
+                        f"the group size {wc._dynamic[1]}")
+    if module.obc is not None:
+        raise DmxqError("AWQ clipping inside optimal_brain_compressing on the same module is not supported: both rewrite the weight")
+    if not after_awq_scaling:
+        sq = module.smoothquant
+        if sq is not None and (sq._flag("enabled") and not sq._flag("fused_to_weight") or sq._flag("dynamic") or sq.calibrating):
+            raise DmxqError("AWQ clipping with SmoothQuant enabled and not fused to the weight, dynamic or calibrating is not supported: the "
+                            "weight cast sees W * s, not the weight that would be clamped; fuse the scale to the weight or disable it")
+        if module.awq is not None:
+            raise DmxqError("AWQ clipping inside awq_scaling on the same module is not supported: the scale search would see a moving "
+                            "weight; ask for the clip through DmxAWQHyperparams(clip=...) instead")
+    return wc.format, wc._dynamic[1], wc.qscheme in _SYMMETRIC
+
+
+def awq_clip_apply(module, plan, hp, blocks, n_tokens):
+    """clip the module's weight in place with ops.awq_clip and record the outcome as plain attributes (no buffer, no state_dict key)"""
+    from . import ops
+    fmt, g, sym = plan
+    ratios = ops.awq_clip_ratios(hp.n_grid, hp.max_shrink)
+    w = module.weight.detach()
+    y, best, clip = ops.awq_clip(w, blocks.to(w.device), fmt, g, ratios, symmetric_qscheme=sym, return_best=True, return_clip=True)
+    with torch.no_grad():
+        module.weight.copy_(y)
+    module.awq_clip = {"clip": clip, "best": best, "group_size": g, "ratios": ratios}
+    module.awq_clip_blocks, module.awq_clip_n_tokens = blocks, n_tokens
+    module.__dict__.pop("_live_weight", None)   # (a LiveWeightBatch result computed from the unclipped weight)
+
+
+class AWQClipCalibrator:
+    """AWQ weight clipping (AutoAWQ's clip search; DESIGN.md §8 "AWQ clipping"): while DmxModule.awq_clipping is active, `observe` folds
+    the inputs that reach the GEMM into a float32 [G, g, g] running mean over the tokens of the DIAGONAL BLOCKS of x^T x (one baddbmm_,
+    AWQCalibrator's formula per block: a 14336-column layer keeps 7 MB at g = 128 instead of the 822 MB of the whole matrix), counting the
+    tokens on the host -- nothing is read back; `apply` clips the weight in place with ops.awq_clip.  The weight cast stays dynamic: it
+    re-derives its scale from the clamped weight, which is the scale the search used."""
+
+    def __init__(self, module, hyperparams, blocks=None, n_tokens: int = 0):
+        self.plan = refuse_awq_clip(module)
+        self.module = module
+        self.hyperparams = hyperparams
+        self.blocks = blocks
+        self.n_tokens = int(n_tokens)
+
+    def observe(self, inp):
+        from . import ops
+        C, g = inp.shape[-1], self.plan[1]
+        t = inp.numel() // C if C else 0
+        if t == 0:
+            return
+        if self.blocks is None or self.blocks.device != inp.device:
+            prev = self.blocks
+            self.blocks = torch.zeros(C // g, g, g, dtype=torch.float32, device=inp.device)
+            if prev is not None:
+                self.blocks += prev.to(inp.device)
+        with torch.no_grad():
+            n = self.n_tokens
+            x = inp.detach().reshape(-1, C).float() * (1.0 / math.sqrt(n + t))
+            x = x.reshape(t, C // g, g).transpose(0, 1)   # [G, tokens, g]
+            self.blocks *= n / (n + t)
+            with ops._front._full_fp32_matmul():
+                self.blocks.baddbmm_(x.transpose(1, 2), x)
+        self.n_tokens = n + t
+
+    def apply(self):
+        if self.n_tokens == 0:
+            raise RuntimeError("AWQ clipping: no calibration token was observed inside awq_clipping (run at least one forward of the "
+                               "module); the weight is left as it was")
+        awq_clip_apply(self.module, self.plan, self.hyperparams, self.blocks, self.n_tokens)
 
 
 # ---------------------------------------------------------------------------------------------------- HQQ

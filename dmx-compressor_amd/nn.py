@@ -27,7 +27,7 @@ from .smoothquant import ActivationWeightSmoothQuant
 from .sparse import Dense, Sparsify
 
 __all__ = ["DmxModule", "DmxQuantizerCalibrationHyperparams", "DmxModuleQuantizerCalibrationHyperparams",
-           "DmxModuleSmoothQuantHyperparams", "DmxModuleGPTQHyperparams", "DmxWandaHyperparams", "DmxAWQHyperparams", "DmxHQQHyperparams", "Linear", "Conv1d", "Conv2d", "ResAdd", "ActActMatMul", "Softmax", "LayerNorm", "GELU", "ReLU", "SiLU", "QuickGELU", "Exp", "Mul", "RMSNorm", "ApplyRotaryPosEmb",
+           "DmxModuleSmoothQuantHyperparams", "DmxModuleGPTQHyperparams", "DmxWandaHyperparams", "DmxAWQHyperparams", "DmxAWQClipHyperparams", "DmxHQQHyperparams", "Linear", "Conv1d", "Conv2d", "ResAdd", "ActActMatMul", "Softmax", "LayerNorm", "GELU", "ReLU", "SiLU", "QuickGELU", "Exp", "Mul", "RMSNorm", "ApplyRotaryPosEmb",
            "MaxPool2d", "AvgPool2d", "Embedding", "ReLU6", "Tanh", "Dropout", "NewGELU", "FastGELU", "BloomGELU", "ClippedGELU", "AdaptiveAvgPool2d",
            "BatchNorm2d", "GroupNorm", "ConvTranspose2d", "BAddBMM", "ScaledDotProductAttention", "DmxConfigRule", "configure_model",
            "fold_weights_and_biases", "GraphedForward", "LiveWeightBatch", "link_consumer", "link_consumers_from_fx", "DmxTracer"]
@@ -97,14 +97,39 @@ class DmxWandaHyperparams:
 
 
 @dataclass
+class DmxAWQClipHyperparams:
+    """AWQ weight clipping (DmxModule.awq_clipping, DmxAWQHyperparams.clip; not in the reference).  n_grid, max_shrink: the candidate
+    ratios ops.awq_clip_ratios(n_grid, max_shrink) = 1 - i / n_grid for i < int(max_shrink * n_grid), 1 .. 32 of them (candidate 0 is no
+    clip); reset: entering the context zeroes the statistics of an earlier context (False: the blocks of the second moment and the token
+    count continue from where the last context left them)"""
+    n_grid: int = 20
+    max_shrink: float = 0.5
+    reset: bool = True
+
+    def __post_init__(self):
+        if isinstance(self.n_grid, bool) or not isinstance(self.n_grid, int):
+            raise TypeError(f"DmxAWQClipHyperparams: n_grid must be an int, got {self.n_grid!r}")
+        if isinstance(self.max_shrink, bool) or not isinstance(self.max_shrink, (int, float)):
+            raise TypeError(f"DmxAWQClipHyperparams: max_shrink must be a number, got {self.max_shrink!r}")
+        if self.n_grid < 1 or not 0.0 < self.max_shrink <= 1.0 or not 1 <= int(self.max_shrink * self.n_grid) <= 32:
+            raise ValueError(f"DmxAWQClipHyperparams: n_grid must be positive, max_shrink in (0, 1] and int(max_shrink * n_grid) in 1 .. 32, "
+                             f"got n_grid {self.n_grid}, max_shrink {self.max_shrink}")
+        if not isinstance(self.reset, bool):
+            raise TypeError(f"DmxAWQClipHyperparams: reset must be a bool, got {self.reset!r}")
+
+
+@dataclass
 class DmxAWQHyperparams:
     """AWQ scaling (DmxModule.awq_scaling; not in the reference).  n_grid: the number of candidate scale vectors, x_mean ** (k / n_grid)
     for k = 0 .. n_grid - 1 (candidate 0 is plain round-to-nearest); fuse_to_weight: fold the chosen scale into the weight on leaving
     the context (SmoothQuant's fuse_to_weight); reset: entering the context zeroes the statistics of an earlier context (False: the
-    sums, the second moment and the token count continue from where the last context left them)"""
+    sums, the second moment and the token count continue from where the last context left them); clip: None, or the
+    DmxAWQClipHyperparams of the weight clip that follows the fuse (needs fuse_to_weight=True; its `reset` is not looked at: the clip
+    uses this context's second moment, divided by the chosen scale on both sides)"""
     n_grid: int = 20
     fuse_to_weight: bool = False
     reset: bool = True
+    clip: Optional[DmxAWQClipHyperparams] = None
 
     def __post_init__(self):
         if isinstance(self.n_grid, bool) or not isinstance(self.n_grid, int):
@@ -115,6 +140,11 @@ class DmxAWQHyperparams:
             raise TypeError(f"DmxAWQHyperparams: fuse_to_weight must be a bool, got {self.fuse_to_weight!r}")
         if not isinstance(self.reset, bool):
             raise TypeError(f"DmxAWQHyperparams: reset must be a bool, got {self.reset!r}")
+        if self.clip is not None:
+            if not isinstance(self.clip, DmxAWQClipHyperparams):
+                raise TypeError(f"DmxAWQHyperparams: clip must be a DmxAWQClipHyperparams or None, got {self.clip!r}")
+            if not self.fuse_to_weight:
+                raise ValueError("DmxAWQHyperparams: clip needs fuse_to_weight=True (the clip acts on the weight the weight cast sees)")
 
 
 @dataclass
@@ -208,6 +238,12 @@ class DmxModule(FastAttr, torch.nn.Module):
     awq = None
     awq_losses = awq_best = awq_x_mean = awq_sumabs = awq_gram = None
     awq_n_tokens = 0
+    #: the AWQClipCalibrator while `awq_clipping` is active (layer_reconstruction.py), else None; after a clip (this context's, or the
+    #: one DmxAWQHyperparams.clip asks for) `awq_clip` = {"clip": float32 [out, G], "best": uint8 [out, G], "group_size": g, "ratios":
+    #: float32 [n] on the host}, the float32 [G, g, g] blocks of the second moment and the token count stay as plain attributes
+    awq_clipper = None
+    awq_clip = awq_clip_blocks = None
+    awq_clip_n_tokens = 0
 
     def _dmx_init(self, n_inputs: int = 1, input_names=("input_cast",), sparsifiable: bool = False):
         pnames = [n for n, _ in self.named_parameters(recurse=False)]
@@ -619,6 +655,33 @@ class DmxModule(FastAttr, torch.nn.Module):
         yield self
         self.enable_awq(False, hyperparams)
 
+    def enable_awq_clip(self, state: bool, hyperparams=None) -> None:
+        """AWQ weight clipping (DESIGN.md §8 "AWQ clipping"): on a Linear with a 2-D weight (any other module: nothing happens) whose weight
+        cast is a nearest-rounding dynamic per-group integer cast.  Entering starts observing the inputs as `_forward` receives them (after
+        the input casts, whose switches stay as they are); leaving clamps every group of the weight IN PLACE to the range, among the
+        candidates, whose cast disturbs the layer's output on those inputs least (ops.awq_clip), and records `awq_clip`.  The weight cast
+        is not touched: it stays dynamic and re-derives the scale the search used from the clamped weight.  The guarantee is per group."""
+        from .layer_reconstruction import AWQClipCalibrator, awq_clip_applies
+        if hyperparams is None:
+            hyperparams = DmxAWQClipHyperparams()
+        if not isinstance(hyperparams, DmxAWQClipHyperparams):
+            raise TypeError(f"awq_clipping takes a DmxAWQClipHyperparams, got {type(hyperparams).__name__}")
+        if state:
+            if not awq_clip_applies(self):
+                return
+            keep = not hyperparams.reset and self.awq_clip_blocks is not None
+            self.awq_clipper = AWQClipCalibrator(self, hyperparams, self.awq_clip_blocks.clone() if keep else None,
+                                                 self.awq_clip_n_tokens if keep else 0)   # (refuses before any state is touched)
+        elif self.awq_clipper is not None:
+            clipper, self.awq_clipper = self.awq_clipper, None
+            clipper.apply()
+
+    @contextmanager
+    def awq_clipping(self, hyperparams=None):
+        self.enable_awq_clip(True, hyperparams)
+        yield self
+        self.enable_awq_clip(False, hyperparams)
+
     def hqq_quantize(self, hyperparams=None) -> None:
         """HQQ (DESIGN.md §8 "HQQ"; no calibration data): on a Linear or a Conv2d (through the [out, -1] view of its weight; any other
         module: nothing happens) whose weight cast's format is a clamped XP[p,0] with nearest rounding.  The weight is replaced IN PLACE
@@ -873,6 +936,8 @@ class DmxModule(FastAttr, torch.nn.Module):
             self.wanda.observe(_input)
         if self.awq is not None:
             self.awq.observe(_input)
+        if self.awq_clipper is not None:
+            self.awq_clipper.observe(_input)
         _output = self._forward(_input, *args, **kwargs)
         # (a GEMM-bearing module's output cast is a launch of its own; when the linked consumer applies the SAME cast to this value as
         #  its first input cast -- inside its fused kernel -- the cast here is redundant: FloatingPoint casts are projections)

@@ -59,7 +59,7 @@ const char* dmxq_status_string(int status);
  * dmxq_wanda_class, dmxq_row_class_of, dmxq_channel_sumabs_accumulate, dmxq_awq_group_error, dmxq_awq_class,
  * dmxq_block_scaled_float_qdq, dmxq_block_scaled_float_class, dmxq_block_scaled_tensor_scale, dmxq_nm_mask_class, dmxq_lsq_backward, dmxq_lsq_class, dmxq_lsq_scratch_bytes,
  * dmxq_codebook_qdq, dmxq_codebook_class, dmxq_codebook_accumulate, dmxq_codebook_workspace_bytes, dmxq_hqq_qdq, dmxq_hqq_class,
- * dmxq_outlier_fixed_qdq, dmxq_outlier_class) leave it at 4: a caller built against 4 runs on
+ * dmxq_outlier_fixed_qdq, dmxq_outlier_class, dmxq_awq_clip, dmxq_awq_clip_class) leave it at 4: a caller built against 4 runs on
  * this library unchanged.  4 = round 5: + dmxq_float_qdq_multi, dmxq_fixed_float_qdq_multi; 3 = round 4: + dmxq_weight_hypernet_multi,
  * dmxq_unary_cast_table, dmxq_lut16_apply.  Nothing was ever removed or changed: a caller built against version n runs on any library >= n. */
 int dmxq_abi_version(void);
@@ -751,6 +751,28 @@ int dmxq_channel_sumabs_accumulate(const void* in, int dtype_in, int64_t rows, i
 int dmxq_awq_class(int dtype_w, int64_t L, int64_t group);
 int dmxq_awq_group_error(const void* w, int dtype_w, const float* s, float* d_out, void* wq_out, int64_t rows, int64_t L, int64_t group,
                          int precision, int fraction, int clamp, int symmetric, int qmin, int qmax, int symmetric_qscheme, void* stream);
+
+/* AWQ weight clipping (AutoAWQ's clip search after the scale) in ONE launch (csrc/awq_clip.hip; DESIGN.md §8 "AWQ clipping", whose text
+ * is the contract).  Not in the reference.  w[rows, L] of dtype_w, contiguous; blocks: DEVICE float32 [L / group, group, group], the
+ * diagonal blocks of the calibration inputs' second moment, used as given; ratios: DEVICE float32 [n_ratios], 1 <= n_ratios <= 32,
+ * ratios[0] == 1, non-increasing in (0, 1] (the values are the caller's contract: the host never reads them).  Per group of `group`
+ * consecutive columns of a row, every operation fp32 and none contracted:
+ *   a = max |W| (NaN if any element is);  a group whose a is not finite and positive keeps its bits, best = 0, clip = a, NaN losses;
+ *   candidate i: c = fp32(dtype_w(a * ratios[i]));  v = W > c ? c : (W < -c ? -c : W);  q = the per-group dynamic integer cast of
+ *   dmxq_dynamic_fixed_qdq on v (the same device code; (qmin, qmax, symmetric_qscheme) as there);  d = fp32(q) - W;
+ *   t_j = sum_l blocks[k][j][l] * d_l in index order from the first product;  loss_i = the adjacent-pair tree sum of d_j * t_j;
+ *   best = the lowest i among the minimal finite losses (0 when none is finite);  y = dtype_w(v of best);  clip = c of best.
+ * y_out: dtype_w [rows, L], may be w itself; best_out: NULL or uint8 [rows, L / group]; clip_out: NULL or float32 [rows, L / group];
+ * losses_out: NULL or float32 [rows, L / group, n_ratios].
+ * dmxq_awq_clip_class(dtype_w, L, group): 1 where the kernel takes the geometry -- group 16, 32, 64 or 128 dividing L -- else 0; a host
+ * function, no GPU involved.  DMXQ_ERR_UNSUPPORTED, nothing launched (the caller runs its chain, same bits): class 0, fraction != 0, no
+ * clamp, precision > 22, a pointer that is not 16-byte aligned.  DMXQ_ERR_BAD_ARG: invalid dtype, negative sizes, qmax <= qmin,
+ * n_ratios outside 1 .. 32, null w / blocks / ratios / y_out.  No workspace, no allocation, no host synchronisation, no float
+ * atomics: capturable. */
+int dmxq_awq_clip_class(int dtype_w, int64_t L, int64_t group);
+int dmxq_awq_clip(const void* w, int dtype_w, const float* blocks, const float* ratios, int n_ratios, void* y_out, uint8_t* best_out,
+                  float* clip_out, float* losses_out, int64_t rows, int64_t L, int64_t group, int precision, int fraction, int clamp,
+                  int symmetric, int qmin, int qmax, int symmetric_qscheme, void* stream);
 
 /* Two-level BLOCK-SCALED float cast (csrc/block_scaled_float.hip; DESIGN.md §8 "Block-scaled float cast"): the group scale of
  * dmxq_dynamic_float_qdq QUANTISED to a low-bit float format, under one float32 scale per tensor -- the numerics of a stored block-scaled
