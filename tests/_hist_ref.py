@@ -15,7 +15,16 @@ def histc(x, bins, lo, hi):
         lo, hi = float(x.min()), float(x.max())
         if lo == hi:
             lo, hi = lo - 1.0, hi + 1.0
-    return torch.histc(x, bins, min=torch.tensor(lo, dtype=torch.float32).item(), max=torch.tensor(hi, dtype=torch.float32).item())
+    lo, hi = torch.tensor(lo, dtype=torch.float32), torch.tensor(hi, dtype=torch.float32)
+    # a range wider than FLT_MAX / bins (far past the 2^63 where the reference's torch.histc refuses the range: DESIGN.md §8): the
+    # numerator (x - lo) * bins overflows, ATen's bin is then an out-of-range float -> int64 conversion (undefined; bin 0 on x86-64),
+    # dmxq_histc's a saturating one clamped to the last bin -- restated here, so that the copy stays defined
+    over = (x >= lo) & (x <= hi) & torch.isinf((x.float() - lo) * float(bins))
+    if bool(over.any()):
+        h = torch.histc(x[~over], bins, min=lo.item(), max=hi.item())
+        h[-1] += over.sum()
+        return h
+    return torch.histc(x, bins, min=lo.item(), max=hi.item())
 
 
 def qparams(mn, mx, qmin, qmax, symmetric):
