@@ -14,9 +14,9 @@ from .format import (ROUNDING_MODE, BlockFloatingPoint, FixedPoint, FloatingPoin
 from . import nn
 from .approximate import Approximate, ApproximationFunction, NoApproximation, TorchFunctionApproximation
 from .nn import (DmxConfigRule, DmxModule, DmxModuleGPTQHyperparams, DmxModuleQuantizerCalibrationHyperparams,
-                 DmxModuleSmoothQuantHyperparams, DmxQuantizerCalibrationHyperparams, DmxWandaHyperparams, DmxAWQHyperparams, DmxAWQClipHyperparams, DmxHQQHyperparams, configure_model)
-from .layer_reconstruction import AWQCalibrator, AWQClipCalibrator, OptimalBrainCompressor, WandaCalibrator
-from .advanced_recipe import DmxBaseRecipe, DmxGPTQRecipe, DmxQuantizerCalibrationRecipe, DmxSmoothQuantRecipe, DmxWandaRecipe, DmxAWQRecipe, DmxAWQClipRecipe, DmxHQQRecipe
+                 DmxModuleSmoothQuantHyperparams, DmxQuantizerCalibrationHyperparams, DmxWandaHyperparams, DmxAWQHyperparams, DmxAWQClipHyperparams, DmxHQQHyperparams, DmxAdaRoundHyperparams, configure_model)
+from .layer_reconstruction import AdaRoundCalibrator, AWQCalibrator, AWQClipCalibrator, OptimalBrainCompressor, WandaCalibrator
+from .advanced_recipe import DmxBaseRecipe, DmxGPTQRecipe, DmxQuantizerCalibrationRecipe, DmxSmoothQuantRecipe, DmxWandaRecipe, DmxAWQRecipe, DmxAWQClipRecipe, DmxHQQRecipe, DmxAdaRoundRecipe
 from .observer import DummyObserver, HistogramObserver, MinMaxObserver, PercentileObserver
 from .smoothquant import ActivationWeightSmoothQuant
 from .config import apply_legacy_config, load_legacy_config

@@ -1080,6 +1080,47 @@ def awq_clip(w, blocks, ratios, y, group, precision, fraction, clamp, symmetric,
     return best, clip, losses
 
 
+# ------------------------------------------------------------------------------------------------ AdaRound
+def _adaround_args(wc, V, scale, zero_point, segment, what):
+    if segment < 1 or wc.numel() % segment != 0:
+        raise RuntimeError(f"{what}: the segment must divide the number of elements")
+    n = wc.numel() // segment
+    if not (V.is_cuda and V.device == wc.device and V.dtype == torch.float32 and V.is_contiguous() and V.numel() == wc.numel()):
+        raise RuntimeError(f"{what}: V must be a contiguous float32 tensor of the weight's element count on its GPU")
+    for t in (scale, zero_point):
+        if not (t.is_cuda and t.device == wc.device and t.dtype == torch.float32 and t.is_contiguous() and t.numel() == n):
+            raise RuntimeError(f"{what}: scale and zero_point must be contiguous float32 tensors of {n} entries on the weight's GPU")
+    return n
+
+
+@_guarded
+def adaround_forward(w, V, scale, zero_point, segment, qmin, qmax, hard, out_dtype=None):
+    """-> y in out_dtype (the weight's dtype by default) and w's shape"""
+    wc = _prep(w, "adaround_forward")
+    n = _adaround_args(wc, V, scale, zero_point, segment, "adaround_forward")
+    y = torch.empty(wc.shape, dtype=out_dtype or wc.dtype, device=wc.device)
+    check(lib().dmxq_adaround_forward(ptr(wc), ptr(V), ptr(y), dtype_code(wc.dtype), dtype_code(y.dtype), n, segment, qmin, qmax, ptr(scale),
+                                      ptr(zero_point), int(bool(hard)), stream_of(wc)), "dmxq_adaround_forward")
+    return y
+
+
+@_guarded
+def adaround_backward(w, V, g, scale, zero_point, segment, qmin, qmax, beta, reg_weight, want_reg):
+    """-> (dV float32 in w's shape; reg float64 [1], empty unless want_reg)"""
+    wc, gc = _prep(w, "adaround_backward"), _prep(g, "adaround_backward")
+    if gc.device != wc.device or gc.numel() != wc.numel():
+        raise RuntimeError("adaround_backward: w and g must hold the same number of elements on one device")
+    n = _adaround_args(wc, V, scale, zero_point, segment, "adaround_backward")
+    dV = torch.empty(wc.shape, dtype=torch.float32, device=wc.device)
+    reg = torch.empty(1 if want_reg else 0, dtype=torch.float64, device=wc.device)
+    sb = int(lib().dmxq_adaround_scratch_bytes(wc.numel())) if want_reg else 0
+    scratch = torch.empty(sb // 8, dtype=torch.float64, device=wc.device)
+    check(lib().dmxq_adaround_backward(ptr(wc), ptr(V), ptr(gc), ptr(dV), dtype_code(wc.dtype), dtype_code(gc.dtype), n, segment, qmin, qmax,
+                                       ptr(scale), ptr(zero_point), float(beta), float(reg_weight), ptr(reg) if want_reg else None,
+                                       ptr(scratch) if sb else None, sb, stream_of(wc)), "dmxq_adaround_backward")
+    return dV, reg
+
+
 # ------------------------------------------------------------------------------------------------ block-scaled float cast
 @_guarded
 def block_scaled_float_qdq(x, group, fmt, scale_fmt, scale_max, tensor_scale, want_scale, want_code, out_dtype=None):

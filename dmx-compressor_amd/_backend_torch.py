@@ -69,7 +69,9 @@ _FAST_CALIBRATION_NAMES = {"hist_observe": "hist_observe", "hist_qparams": "hist
                            # the outlier-aware dynamic cast: the same
                            "outlier_fixed_qdq": "outlier_fixed_qdq",
                            # the AWQ clip search: no autograd to lose
-                           "awq_clip": "awq_clip"}
+                           "awq_clip": "awq_clip",
+                           # AdaRound: both passes are called from inside an autograd Function of the front end (_front.py)
+                           "adaround_forward": "adaround_forward", "adaround_backward": "adaround_backward"}
 FAST = None
 
 

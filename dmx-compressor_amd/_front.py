@@ -35,6 +35,8 @@ __all__ = [
     "channel_sumsq", "channel_sumsq_workspace_bytes", "wanda_score", "wanda_nm_sparsify", "wanda_class", "WANDA_CHAIN_BY_DEFAULT",
     "channel_sumabs", "awq_candidate_scales", "awq_scaled_error", "awq_class", "awq_search", "AWQ_CHAIN_BY_DEFAULT",
     "awq_clip", "awq_clip_check", "awq_clip_class", "awq_clip_ratios", "awq_gram_blocks", "AWQ_CLIP_CHAIN_BY_DEFAULT", "AWQ_CLIP_MAX_RATIOS",
+    "adaround_check", "adaround_class", "adaround_scratch_bytes", "adaround_init", "adaround_qdq", "adaround_backward",
+    "ADAROUND_CHAIN_BY_DEFAULT",
 ]
 
 _ops = None   # the raw namespace: set by bind()
@@ -2877,3 +2879,284 @@ def awq_clip(w, blocks, fmt, group_size: int, ratios=None, symmetric_qscheme: bo
         yc, best, clip, losses = _awq_clip_chain(wc, blocks.detach(), r, fmt, group_size, sym)
         y.copy_(yc)
         return result(best, clip, losses)
+
+
+# ---------------------------------------------------------------------------------------------------- AdaRound (learned weight rounding)
+# Classes of dmxq_adaround_forward / dmxq_adaround_backward (adaround_class) that fused=None sends to the chain of torch operations
+# although the kernels take them: DYNAMIC_CHAIN_BY_DEFAULT's rule -- a class goes to the kernel by default only where
+# tools/bench_adaround.py MEASURED it faster than the chain on the same buffers; a class that is not gets listed here with its row.
+ADAROUND_CHAIN_BY_DEFAULT = frozenset()
+# which route the calls of this front end took, counted on the host: private, for the tests (fused=True must have run the kernel)
+_adaround_routes = {"fused": 0, "chain": 0}
+_ADAROUND_CLASS_NAMES = {1: "shift", 2: "divide"}   # dmxq_adaround_geometry (include/dmxq.h)
+
+
+def _f32(v) -> float:
+    """the float32 nearest to v, as a Python float"""
+    return torch.tensor(v, dtype=torch.float32).item()
+
+
+# the stretch constants, float32: G = -0.1f, ZG = 1.1f - (-0.1f) (one float32 subtraction; equals float32(1.2))
+ADAROUND_G = _f32(-0.1)
+ADAROUND_ZG = (torch.tensor(1.1, dtype=torch.float32) - torch.tensor(-0.1, dtype=torch.float32)).item()
+
+
+def adaround_check(fmt, granularity="per_group", group_size=None, what: str = "adaround_qdq"):
+    """-> (format, granularity, group_size) of an AdaRound cast, or ValueError: dynamic_check's cases (a clamped XP[p,0] format, a known
+    granularity, a positive group size with per_group and none otherwise) and nearest rounding.  No GPU involved."""
+    fmt, granularity, group_size = dynamic_check(fmt, granularity, group_size, what=what)
+    if fmt.rounding != "nearest":
+        raise ValueError(f"{what}: learned rounding replaces nearest rounding and is defined for it alone, got {fmt!r}")
+    return fmt, granularity, group_size
+
+
+def adaround_class(segment: int, dtype: torch.dtype, granularity: str = "per_group") -> Optional[str]:
+    """how a 16-byte vector of dmxq_adaround_forward / dmxq_adaround_backward finds its segment, asked of the library itself
+    (dmxq_adaround_class; no GPU involved), or None when the kernels refuse segments of `segment` elements of `dtype`: "shift" (a
+    power-of-two number of vectors per segment), "divide" (any other whole number), "tensor" (per_tensor: ONE segment, no lookup
+    arithmetic)"""
+    from ._lib import dtype_code, lib
+    if granularity not in DYNAMIC_GRANULARITIES:
+        raise ValueError(f"adaround_class: granularity must be one of {DYNAMIC_GRANULARITIES}, got {granularity!r}")
+    name = _ADAROUND_CLASS_NAMES.get(lib().dmxq_adaround_class(dtype_code(dtype), int(segment)))
+    return "tensor" if name is not None and granularity == "per_tensor" else name
+
+
+def adaround_scratch_bytes(n: int) -> int:
+    """dmxq_adaround_scratch_bytes: the scratch dmxq_adaround_backward needs for the regulariser's sum over n elements (8 bytes per
+    workgroup).  A host function: no GPU involved."""
+    from ._lib import lib
+    return int(lib().dmxq_adaround_scratch_bytes(int(n)))
+
+
+def _adaround_segment(w, V, scale, zero_point, fmt, granularity, group_size, what):
+    """-> (format, S, n_seg): every ValueError of the front end, before any GPU use"""
+    fmt, granularity, group_size = adaround_check(fmt, granularity, group_size, what=what)
+    if not isinstance(w, torch.Tensor) or not w.is_floating_point() or w.dim() < 1:
+        raise ValueError(f"{what}: expects a floating point weight with at least one dimension")
+    L = w.shape[-1]
+    if granularity == "per_group" and L % group_size:
+        raise ValueError(f"{what}: the last dimension has {L} elements, not a multiple of the group size {group_size}")
+    S = {"per_token": L, "per_group": group_size, "per_tensor": w.numel()}[granularity]
+    n_seg = w.numel() // S if S else 0
+    if not isinstance(scale, torch.Tensor) or not scale.is_floating_point() or scale.numel() != n_seg:
+        raise ValueError(f"{what}: scale must be a floating point tensor of {n_seg} entries (one per segment), got "
+                         f"{tuple(scale.shape) if isinstance(scale, torch.Tensor) else scale!r}")
+    if not isinstance(zero_point, torch.Tensor) or zero_point.dtype == torch.bool or zero_point.numel() != n_seg:
+        raise ValueError(f"{what}: zero_point must be a tensor of {n_seg} integer entries (one per segment), got "
+                         f"{tuple(zero_point.shape) if isinstance(zero_point, torch.Tensor) else zero_point!r}")
+    if V is not None and (not isinstance(V, torch.Tensor) or V.shape != w.shape or V.dtype != torch.float32):
+        raise ValueError(f"{what}: V must be a float32 tensor of the weight's shape {tuple(w.shape)}, got "
+                         f"{(tuple(V.shape), V.dtype) if isinstance(V, torch.Tensor) else V!r}")
+    return fmt, S, n_seg
+
+
+def _adaround_beta(beta, reg_weight, what):
+    if isinstance(reg_weight, bool) or not isinstance(reg_weight, (int, float)) or not math.isfinite(reg_weight):
+        raise ValueError(f"{what}: reg_weight must be a finite number, got {reg_weight!r}")
+    if beta is not None and (isinstance(beta, bool) or not isinstance(beta, (int, float)) or not math.isfinite(beta) or beta < 1.0):
+        raise ValueError(f"{what}: beta must be a finite number of at least 1 (a^(beta - 1) at a = 0), got {beta!r}")
+
+
+def adaround_init(w, scale, zero_point, fmt, granularity: str = "per_group", group_size: Optional[int] = None):
+    """The rounding variable that starts AdaRound at the weight itself: V0 = -log(ZG / (frac - G) - 1) with v = w / s, frac = v - floor(v),
+    a float32 torch chain on w's device (CPU tensors are served too; it runs once).  The soft cast of V0 gives h = frac up to rounding,
+    so y = w where nothing clips; the hard cast of V0 is round-HALF-UP of v (frac = 0.5 gives V0 = -0.0, which counts as >= 0): it
+    differs from the cast's own round-to-nearest only at exact ties.  -> float32, w's shape.  ValueError as adaround_qdq."""
+    fmt, S, _ = _adaround_segment(w, None, scale, zero_point, fmt, granularity, group_size, "adaround_init")
+    with torch.no_grad():
+        if w.numel() == 0:
+            return torch.empty(w.shape, dtype=torch.float32, device=w.device)
+        v = w.detach().reshape(-1, S).float() / scale.detach().float().reshape(-1, 1).to(w.device)
+        frac = v - torch.floor(v)
+        return (-torch.log(ADAROUND_ZG / (frac - ADAROUND_G) - 1.0)).reshape(w.shape)
+
+
+def _adaround_operands(w, V, scale, zero_point, S):
+    wd = w.detach()
+    wc = wd if wd.is_contiguous() else wd.contiguous()
+    Vd = V.detach()
+    Vc = Vd if Vd.is_contiguous() else Vd.contiguous()
+    s = scale.detach().to(wc.device, torch.float32).reshape(-1).contiguous()
+    z = zero_point.detach().to(wc.device, torch.float32).reshape(-1).contiguous()
+    return wc, Vc, s, z
+
+
+def _adaround_soft(V2):
+    """(sg, hr, h) of the definition, float32 torch operations in its order"""
+    sg = 1.0 / (1.0 + torch.exp(-V2))
+    hr = sg * ADAROUND_ZG + ADAROUND_G
+    return sg, hr, torch.clamp(hr, 0.0, 1.0)
+
+
+def _adaround_forward(wc, Vc, s, z, S, qmin, qmax, hard, out_dtype, fused, granularity):
+    """y of the contiguous operands: the kernel where it applies, else the chain"""
+    if fused is not False:
+        cls = adaround_class(S, wc.dtype, granularity) if (out_dtype in (wc.dtype, torch.float32) and wc.data_ptr() % 16 == 0
+                                                            and Vc.data_ptr() % 16 == 0) else None
+        if cls is None and fused:
+            raise NotImplementedError(f"adaround_qdq: no fused kernel for segments of {S} {wc.dtype} elements with a {out_dtype} output "
+                                      f"(base addresses {wc.data_ptr() % 16} / {Vc.data_ptr() % 16} mod 16)")
+        if cls is not None and fused is None and cls in ADAROUND_CHAIN_BY_DEFAULT:
+            cls = None
+        if cls is not None:
+            try:
+                y = _ops.adaround_forward(wc, Vc, s, z, S, qmin, qmax, bool(hard), out_dtype)
+                _adaround_routes["fused"] += 1
+                return y
+            except NotImplementedError:   # (DMXQ_ERR_UNSUPPORTED, nothing launched)
+                if fused:
+                    raise
+    _adaround_routes["chain"] += 1
+    # the definition, spelled in torch on the device
+    w2, V2 = wc.reshape(-1, S).float(), Vc.reshape(-1, S)
+    sc, zq = s[:, None], z[:, None]
+    f = torch.floor(w2 / sc)
+    h = (V2 >= 0).to(torch.float32) if hard else _adaround_soft(V2)[2]
+    q = torch.clamp((f + h) + zq, qmin, qmax)
+    return ((q - zq) * sc).to(out_dtype).reshape(wc.shape)
+
+
+def adaround_backward(w, V, g, scale, zero_point, fmt, granularity: str = "per_group", group_size: Optional[int] = None, beta: float = 2.0,
+                      reg_weight: float = 0.0, reg_out=None, want_reg: bool = True, fused: Optional[bool] = None):
+    """The backward pass of the AdaRound soft cast (DESIGN.md §8 "AdaRound") -> (dV, reg): dV float32 in w's shape, the gradient of
+    sum(g * y) + reg_weight * reg with respect to V (the weight is frozen); reg = sum(1 - |2 h - 1|^beta) over the tensor, a float64
+    0-d tensor on the device (None without want_reg and reg_out), also copied into reg_out (float64, one element) when given.
+    Per element, every operation float32 in this order:
+        v = w / s;  f = floor(v);  sg = 1 / (1 + exp(-V));  hr = sg * ZG + G;  h = clamp(hr, 0, 1)
+        in01 = 0 < hr < 1;  cell = qmin <= f + zq <= qmax - 1;  dh = (sg * (1 - sg)) * ZG;  rec = (in01 and cell) ? (g * s) * dh : 0
+        t2 = 2 h - 1;  a = |t2|;  p1 = pow(a, beta - 1);  r = 1 - p1 * a;  dreg = in01 ? reg_weight * (((-2 beta * p1) * sign(t2)) * dh) : 0
+        dV = rec + dreg (rec alone when reg_weight == 0)
+    ONE launch (dmxq_adaround_backward) plus the small fold of the partial sums, where g has the weight's dtype or float32, the
+    segment is whole 16-byte vectors of the weight and everything is 16-byte aligned; else the chain: the same definition in torch
+    operations.  The same call twice gives the same bits, reg included.  fused: None -- the kernel where it applies and its class is
+    not listed in ADAROUND_CHAIN_BY_DEFAULT; True -- NotImplementedError instead of falling back; False -- the chain.  ValueError before
+    any GPU use."""
+    from .observer import get_qmin_qmax
+    fmt, S, n_seg = _adaround_segment(w, V, scale, zero_point, fmt, granularity, group_size, "adaround_backward")
+    if not isinstance(g, torch.Tensor) or g.shape != w.shape:
+        raise ValueError(f"adaround_backward: g must have the weight's shape {tuple(w.shape)}")
+    _adaround_beta(beta, reg_weight, "adaround_backward")
+    if beta is None:
+        raise ValueError("adaround_backward: beta must be a number")
+    if reg_out is not None and not (isinstance(reg_out, torch.Tensor) and reg_out.dtype == torch.float64 and reg_out.numel() == 1):
+        raise ValueError("adaround_backward: reg_out must be a float64 tensor of one element")
+    require_gpu(w, "adaround_backward")
+    require_gpu(V, "adaround_backward")
+    require_gpu(g, "adaround_backward")
+    qmin, qmax = get_qmin_qmax(fmt)
+    want = bool(want_reg) or reg_out is not None
+    with torch.no_grad():
+        wc, Vc, s, z = _adaround_operands(w, V, scale, zero_point, S)
+        gd = g.detach()
+        gc = gd if gd.is_contiguous() else gd.contiguous()
+
+        def done(dV, reg):
+            if reg_out is not None:
+                reg_out.copy_(reg.reshape(reg_out.shape))
+            return dV, (reg if want else None)
+
+        if wc.numel() == 0:
+            return done(torch.empty(wc.shape, dtype=torch.float32, device=wc.device), torch.zeros((), dtype=torch.float64, device=wc.device))
+        if fused is not False:
+            cls = adaround_class(S, wc.dtype, granularity) if (gc.dtype in (wc.dtype, torch.float32) and wc.data_ptr() % 16 == 0
+                                                                and Vc.data_ptr() % 16 == 0 and gc.data_ptr() % 16 == 0) else None
+            if cls is None and fused:
+                raise NotImplementedError(f"adaround_backward: no fused kernel for segments of {S} {wc.dtype} elements with a {gc.dtype} "
+                                          f"gradient (base addresses {wc.data_ptr() % 16} / {Vc.data_ptr() % 16} / {gc.data_ptr() % 16} mod 16)")
+            if cls is not None and fused is None and cls in ADAROUND_CHAIN_BY_DEFAULT:
+                cls = None
+            if cls is not None:
+                try:
+                    dV, reg = _ops.adaround_backward(wc, Vc, gc, s, z, S, qmin, qmax, float(beta), float(reg_weight), want)
+                    _adaround_routes["fused"] += 1
+                    return done(dV, reg.reshape(()) if want else None)
+                except NotImplementedError:   # (DMXQ_ERR_UNSUPPORTED, nothing launched)
+                    if fused:
+                        raise
+        _adaround_routes["chain"] += 1
+        # the definition, spelled in torch on the device
+        w2, V2, g2 = wc.reshape(-1, S).float(), Vc.reshape(-1, S), gc.reshape(-1, S).float()
+        sc, zq = s[:, None], z[:, None]
+        fz = torch.floor(w2 / sc) + zq
+        cell = (fz >= qmin) & (fz <= qmax - 1)
+        sg, hr, h = _adaround_soft(V2)
+        in01 = (hr > 0) & (hr < 1)
+        dh = (sg * (1.0 - sg)) * ADAROUND_ZG
+        zero = torch.zeros_like(dh)
+        dV = torch.where(in01 & cell, (g2 * sc) * dh, zero)
+        reg = None
+        rw = _f32(reg_weight)
+        if rw != 0.0 or want:
+            b = torch.tensor(float(beta), dtype=torch.float32)
+            bm1, m2b = (b - 1.0).item(), (-2.0 * b).item()
+            t2 = 2.0 * h - 1.0
+            a = torch.abs(t2)
+            p1 = torch.pow(a, bm1)
+            if rw != 0.0:
+                dV = dV + torch.where(in01, rw * (((m2b * p1) * torch.sign(t2)) * dh), zero)
+            if want:
+                reg = (1.0 - p1 * a).sum(dtype=torch.float64)
+        return done(dV.reshape(wc.shape), reg)
+
+
+class _AdaRoundCast(torch.autograd.Function):
+    """forward: the soft (or hard) cast; backward: adaround_backward -- the gradient of V alone"""
+
+    @staticmethod
+    def forward(ctx, w, V, scale, zero_point, fmt, granularity, group_size, S, hard, beta, reg_weight, reg_out, out_dtype, fused):
+        from .observer import get_qmin_qmax
+        qmin, qmax = get_qmin_qmax(fmt)
+        wc, Vc, s, z = _adaround_operands(w, V, scale, zero_point, S)
+        if wc.numel() == 0:
+            y = torch.empty(wc.shape, dtype=out_dtype, device=wc.device)
+        else:
+            y = _adaround_forward(wc, Vc, s, z, S, qmin, qmax, hard, out_dtype, fused, granularity)
+        ctx.save_for_backward(wc, Vc, s, z)
+        ctx.args = (fmt, granularity, group_size, beta, reg_weight, reg_out, fused, hard)
+        return y
+
+    @staticmethod
+    def backward(ctx, g):
+        wc, Vc, s, z = ctx.saved_tensors
+        fmt, granularity, group_size, beta, reg_weight, reg_out, fused, hard = ctx.args
+        dV = None
+        if ctx.needs_input_grad[1]:
+            if hard:
+                raise RuntimeError("adaround_qdq: the hard cast has no gradient; optimise the soft cast (hard=False)")
+            if g.dtype not in (wc.dtype, torch.float32):
+                g = g.to(torch.float32)
+            dV, _ = adaround_backward(wc, Vc, g, s, z, fmt, granularity, group_size, beta=2.0 if beta is None else beta, reg_weight=reg_weight,
+                                      reg_out=reg_out, want_reg=False, fused=fused)
+        return (None, dV) + (None,) * 12
+
+
+def adaround_qdq(w, V, scale, zero_point, fmt, granularity: str = "per_group", group_size: Optional[int] = None, hard: bool = False,
+                 beta: Optional[float] = None, reg_weight: float = 0.0, reg_out=None, out_dtype: Optional[torch.dtype] = None,
+                 fused: Optional[bool] = None):
+    """The AdaRound cast (Nagel et al., 2020; DESIGN.md §8 "AdaRound"): the weight on the grid of an integer cast with one (scale,
+    integer zero point) per segment (segments as in lsq_fixed_qdq), rounded down or up per element by the float32 variable V.  Per
+    element, every operation float32 in this order, G = -0.1f, ZG = 1.1f - (-0.1f):
+        v = w / s;  f = floor(v);  h = clamp((1 / (1 + exp(-V))) * ZG + G, 0, 1)   (hard=True: h = V >= 0 ? 1 : 0)
+        y = (clamp((f + h) + zq, qmin, qmax) - zq) * s, rounded once more to out_dtype (default: w's dtype)
+    An autograd Function: its backward is adaround_backward and forms ONLY the gradient of V -- w, scale and zero_point get none -- as
+    the gradient of sum(g * y) + reg_weight * sum(1 - |2 h - 1|^beta); the regulariser's VALUE is written into reg_out (float64, one
+    element) during the backward when given.  beta None: no regulariser (reg_weight must be 0 and reg_out None).
+    ONE launch (dmxq_adaround_forward) where out_dtype is w's dtype or float32, the segment is whole 16-byte vectors of the weight and
+    w / V are 16-byte aligned; else the chain of torch operations that spells the definition (any S, unaligned views, any out_dtype).
+    fused: None -- the kernel where it applies and its class is not listed in ADAROUND_CHAIN_BY_DEFAULT; True -- NotImplementedError
+    instead of falling back; False -- the chain.  ValueError before any GPU use: a format that is not a clamped XP[p,0] with nearest
+    rounding, a group size that does not divide the last dimension, parameters that are not one entry per segment, a V of another shape
+    or dtype."""
+    fmt, S, _ = _adaround_segment(w, V, scale, zero_point, fmt, granularity, group_size, "adaround_qdq")
+    _adaround_beta(beta, reg_weight, "adaround_qdq")
+    if beta is None and (reg_weight != 0 or reg_out is not None):
+        raise ValueError("adaround_qdq: the regulariser (reg_weight, reg_out) needs beta")
+    if reg_out is not None and not (isinstance(reg_out, torch.Tensor) and reg_out.dtype == torch.float64 and reg_out.numel() == 1):
+        raise ValueError("adaround_qdq: reg_out must be a float64 tensor of one element")
+    if out_dtype is not None and not (isinstance(out_dtype, torch.dtype) and out_dtype.is_floating_point):
+        raise ValueError(f"adaround_qdq: out_dtype must be a floating point dtype, got {out_dtype!r}")
+    require_gpu(w, "adaround_qdq")
+    require_gpu(V, "adaround_qdq")
+    return _AdaRoundCast.apply(w, V, scale, zero_point, fmt, granularity, group_size, S, bool(hard), beta, float(reg_weight), reg_out,
+                               out_dtype or w.dtype, fused)

@@ -6,7 +6,7 @@ from typing import Callable, Optional
 
 from .nn import DmxModule
 
-__all__ = ["DmxBaseRecipe", "DmxQuantizerCalibrationRecipe", "DmxSmoothQuantRecipe", "DmxGPTQRecipe", "DmxWandaRecipe", "DmxAWQRecipe", "DmxAWQClipRecipe", "DmxHQQRecipe"]
+__all__ = ["DmxBaseRecipe", "DmxQuantizerCalibrationRecipe", "DmxSmoothQuantRecipe", "DmxGPTQRecipe", "DmxWandaRecipe", "DmxAWQRecipe", "DmxAWQClipRecipe", "DmxHQQRecipe", "DmxAdaRoundRecipe"]
 
 
 class DmxBaseRecipe:
@@ -88,3 +88,13 @@ class DmxHQQRecipe(DmxBaseRecipe):
     def __init__(self, hp_gen, **kwargs):
         super().__init__(hp_gen, **kwargs)
         self.recipe_context_manager = DmxModule.hqq_quantizing
+
+
+class DmxAdaRoundRecipe(DmxBaseRecipe):
+    """AdaRound (DmxModule.adaround_reconstructing): hp_gen maps the model to {module: DmxAdaRoundHyperparams}; the calibration
+    forwards run inside the context, and on exit every Linear among them has its weight rounded element by element on its weight cast's
+    own grid (ops.adaround_qdq) and its `adaround` record written"""
+
+    def __init__(self, hp_gen, **kwargs):
+        super().__init__(hp_gen, **kwargs)
+        self.recipe_context_manager = DmxModule.adaround_reconstructing

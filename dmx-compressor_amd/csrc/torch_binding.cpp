@@ -1322,6 +1322,57 @@ std::tuple<Tensor, Tensor, Tensor> awq_clip_meta(const Tensor& w, const Tensor&,
                          want_losses ? at::empty({rows, G, n}, w.options().dtype(at::kFloat)) : at::empty({0}, w.options().dtype(at::kFloat)));
 }
 
+// ------------------------------------------------------------------------------------------------ AdaRound
+// w: contiguous, numel % segment == 0; V: contiguous float32 of w's element count; scale, zero_point: float32 [n_segments] (the zero
+// points integers).  DMXQ_ERR_UNSUPPORTED (NotImplementedError, nothing launched): the front end runs its chain of torch operations.
+static int64_t adaround_args(const Tensor& wc, const Tensor& V, const Tensor& scale, const Tensor& zero_point, int64_t segment, const char* what) {
+  TORCH_CHECK(segment >= 1 && wc.numel() % segment == 0, what, ": the segment must divide the number of elements");
+  const int64_t n = wc.numel() / segment;
+  TORCH_CHECK(V.is_cuda() && V.device() == wc.device() && V.scalar_type() == at::kFloat && V.is_contiguous() && V.numel() == wc.numel(), what,
+              ": V must be a contiguous float32 tensor of the weight's element count on its GPU");
+  TORCH_CHECK(scale.is_cuda() && scale.device() == wc.device() && scale.scalar_type() == at::kFloat && scale.is_contiguous() && scale.numel() == n &&
+              zero_point.is_cuda() && zero_point.device() == wc.device() && zero_point.scalar_type() == at::kFloat && zero_point.is_contiguous() &&
+              zero_point.numel() == n, what, ": scale and zero_point must be contiguous float32 tensors of ", n, " entries on the weight's GPU");
+  return n;
+}
+Tensor adaround_forward(const Tensor& w, const Tensor& V, const Tensor& scale, const Tensor& zero_point, int64_t segment, int64_t qmin, int64_t qmax,
+                        bool hard, c10::optional<at::ScalarType> out_dtype) {
+  const Tensor wc = prep(w, "adaround_forward");
+  const int64_t n = adaround_args(wc, V, scale, zero_point, segment, "adaround_forward");
+  Tensor y = empty_like_shape(wc, out_dtype);
+  Launch l(wc);
+  check(dmxq_adaround_forward(wc.data_ptr(), (const float*)V.data_ptr(), y.data_ptr(), dt_code(wc.scalar_type()), dt_code(y.scalar_type()), n, segment,
+                              (int)qmin, (int)qmax, (const float*)scale.data_ptr(), (const float*)zero_point.data_ptr(), hard ? 1 : 0, l.stream),
+        "dmxq_adaround_forward");
+  return y;
+}
+Tensor adaround_forward_meta(const Tensor& w, const Tensor&, const Tensor&, const Tensor&, int64_t, int64_t, int64_t, bool,
+                             c10::optional<at::ScalarType> out_dtype) {
+  return empty_like_shape(w, out_dtype);
+}
+// -> (dV float32 in w's shape; reg float64 [1], empty unless want_reg: then no sum is formed).  The partial sums' scratch is allocated here.
+std::tuple<Tensor, Tensor> adaround_backward(const Tensor& w, const Tensor& V, const Tensor& g, const Tensor& scale, const Tensor& zero_point,
+                                             int64_t segment, int64_t qmin, int64_t qmax, double beta, double reg_weight, bool want_reg) {
+  const Tensor wc = prep(w, "adaround_backward"), gc = prep(g, "adaround_backward");
+  TORCH_CHECK(gc.device() == wc.device() && gc.numel() == wc.numel(), "adaround_backward: w and g must hold the same number of elements on one device");
+  const int64_t n = adaround_args(wc, V, scale, zero_point, segment, "adaround_backward");
+  Tensor dV = empty_like_shape(wc, at::kFloat);
+  Tensor reg = at::empty({want_reg ? 1 : 0}, wc.options().dtype(at::kDouble));
+  const int64_t sb = want_reg ? dmxq_adaround_scratch_bytes(wc.numel()) : 0;
+  Tensor scratch = at::empty({sb / 8}, wc.options().dtype(at::kDouble));
+  Launch l(wc);
+  check(dmxq_adaround_backward(wc.data_ptr(), (const float*)V.data_ptr(), gc.data_ptr(), (float*)dV.data_ptr(), dt_code(wc.scalar_type()),
+                               dt_code(gc.scalar_type()), n, segment, (int)qmin, (int)qmax, (const float*)scale.data_ptr(),
+                               (const float*)zero_point.data_ptr(), (float)beta, (float)reg_weight, want_reg ? (double*)reg.data_ptr() : nullptr,
+                               sb ? scratch.data_ptr() : nullptr, sb, l.stream),
+        "dmxq_adaround_backward");
+  return std::make_tuple(dV, reg);
+}
+std::tuple<Tensor, Tensor> adaround_backward_meta(const Tensor& w, const Tensor&, const Tensor&, const Tensor&, const Tensor&, int64_t, int64_t, int64_t,
+                                                  double, double, bool want_reg) {
+  return std::make_tuple(empty_like_shape(w, at::kFloat), at::empty({want_reg ? 1 : 0}, w.options().dtype(at::kDouble)));
+}
+
 // ------------------------------------------------------------------------------------------------ block-scaled float cast
 // x: contiguous; groups of `group` consecutive elements; fmt / scale_fmt: (man, exp, bias, flush, rounding); tensor_scale: None (t = 1) or
 // ONE float32 on x's device, read by the kernel only -> (out, scale, scale_code_value: float32 [n_groups], empty unless wanted).
@@ -1434,6 +1485,8 @@ TORCH_LIBRARY(dmxq, m) {
   m.def("codebook_accumulate(Tensor x, int mode, int segment, Tensor levels, float norm, Tensor(a!) acc, bool accumulate) -> ()");
   m.def("hqq_qdq(Tensor x, int segment, int rounding, int qmin, int qmax, float lp_norm, float beta, float kappa, int iters, bool want_qparams, bool want_codes, ScalarType? out_dtype=None) -> (Tensor, Tensor, Tensor, Tensor)");
   m.def("outlier_fixed_qdq(Tensor x, int segment, int k, int precision, int fraction, bool clamp, bool symmetric, int rounding, int qmin, int qmax, bool symmetric_qscheme, int[] outlier_fmt, bool want_qparams, bool want_outliers, ScalarType? out_dtype=None) -> (Tensor, Tensor, Tensor, Tensor, Tensor)");
+  m.def("adaround_forward(Tensor w, Tensor V, Tensor scale, Tensor zero_point, int segment, int qmin, int qmax, bool hard, ScalarType? out_dtype=None) -> Tensor");
+  m.def("adaround_backward(Tensor w, Tensor V, Tensor g, Tensor scale, Tensor zero_point, int segment, int qmin, int qmax, float beta, float reg_weight, bool want_reg) -> (Tensor, Tensor)");
 }
 
 #define DMXQ_IMPL(m, name) m.impl(#name, &name)
@@ -1445,7 +1498,8 @@ TORCH_LIBRARY(dmxq, m) {
   X(m, unary_cast); X(m, unary_cast_table); X(m, lut16_apply); X(m, softmax_cast); X(m, norm_cast); X(m, group_minmax_accumulate); X(m, gptq_block); X(m, hist_observe); X(m, hist_qparams); \
   X(m, error_stats); X(m, cast_error); X(m, hadamard_qdq); X(m, dynamic_fixed_qdq); X(m, gptq_block_dynamic); X(m, dynamic_float_qdq); \
   X(m, channel_sumsq); X(m, wanda_nm); X(m, channel_sumabs); X(m, awq_group_error); X(m, block_scaled_float_qdq); X(m, block_scaled_tensor_scale); \
-  X(m, lsq_backward); X(m, codebook_qdq); X(m, codebook_accumulate); X(m, hqq_qdq); X(m, outlier_fixed_qdq); X(m, awq_clip)
+  X(m, lsq_backward); X(m, codebook_qdq); X(m, codebook_accumulate); X(m, hqq_qdq); X(m, outlier_fixed_qdq); X(m, awq_clip); \
+  X(m, adaround_forward); X(m, adaround_backward)
 
 // "CUDA" is the dispatch key of HIP tensors in a ROCm build of PyTorch
 TORCH_LIBRARY_IMPL(dmxq, CUDA, m) {
@@ -1519,4 +1573,7 @@ PYBIND11_MODULE(dmxq_fast, m) {
         py::arg("symmetric"), py::arg("rounding"), py::arg("qmin"), py::arg("qmax"), py::arg("symmetric_qscheme"), py::arg("outlier_fmt"),
         py::arg("want_qparams"), py::arg("want_outliers"), py::arg("out_dtype") = py::none());
   m.def("awq_clip", &awq_clip);
+  m.def("adaround_forward", &adaround_forward, py::arg("w"), py::arg("V"), py::arg("scale"), py::arg("zero_point"), py::arg("segment"), py::arg("qmin"),
+        py::arg("qmax"), py::arg("hard"), py::arg("out_dtype") = py::none());
+  m.def("adaround_backward", &adaround_backward);
 }

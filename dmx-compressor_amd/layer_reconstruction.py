@@ -21,7 +21,7 @@ import torch.nn.functional as F
 
 from ._lib import DmxqError
 
-__all__ = ["OptimalBrainCompressor", "WandaCalibrator", "AWQCalibrator", "AWQClipCalibrator", "hqq_apply"]
+__all__ = ["OptimalBrainCompressor", "WandaCalibrator", "AWQCalibrator", "AWQClipCalibrator", "hqq_apply", "AdaRoundCalibrator"]
 
 
 def refuse_scaled_weight_cast(module):
@@ -792,3 +792,171 @@ def hqq_apply(module, hp):
     G = w2.shape[1] // g
     module.hqq_qparams = {"scale": sc.reshape(-1, G), "zero": zero.reshape(-1, G), "group_size": g}
     module.weight_cast.disable_fake_quant()
+
+
+# ---------------------------------------------------------------------------------------------------- AdaRound
+def adaround_applies(module) -> bool:
+    """AdaRound acts on a Linear with a 2-D weight; on anything else nothing happens"""
+    return isinstance(module, torch.nn.Linear) and getattr(module, "weight", None) is not None and module.weight.dim() == 2
+
+
+def refuse_adaround(module):
+    """-> (format, granularity, group size, dynamic, symmetric_qscheme) of a module DmxModule.adaround_reconstructing takes, or the
+    refusal as a DmxqError before any state is touched"""
+    from .cast import _SYMMETRIC
+    from .format import FixedPoint, Same
+    from .observer import get_qmin_qmax
+    from .sparse import Dense
+    wc, st = module.weight_cast, module.weight_storage_cast
+    if wc is None:
+        raise DmxqError("AdaRound needs a weight cast: the module has none")
+    for what, setting in (("an outlier-aware", wc._outliers), ("a codebook", wc._codebook), ("a learnable", wc._learnable), ("a scaled float", wc._scaling)):
+        if setting is not None:
+            raise DmxqError(f"AdaRound with {what} weight cast is not supported: it rounds on the grid of a plain integer cast; clear the "
+                            "setting first")
+    if wc.pre_transform:
+        raise DmxqError(f"AdaRound with a weight cast pre_transform {sorted(wc.pre_transform)} is not supported: the grid would be the "
+                        "rotated weight's")
+    if st is not None and not (isinstance(st.format, Same) and not st.pre_transform):
+        raise DmxqError("AdaRound needs a weight_storage_cast of SAME: the written weight must reach the weight cast as it is")
+    sp = module.weight_sparsifier
+    if sp is not None and not isinstance(sp.sparseness, Dense):
+        raise DmxqError(f"AdaRound with a weight sparseness {sp.sparseness!r} is not supported: it rounds the dense weight")
+    sq = module.smoothquant
+    if sq is not None and sq._flag("enabled") and not sq._flag("fused_to_weight"):
+        raise DmxqError("AdaRound with SmoothQuant enabled and not fused to the weight is not supported: the weight cast sees W * s, not "
+                        "the weight that would be rounded; fuse the scale to the weight or disable it")
+    for name, ctx in (("optimal_brain_compressing", module.obc), ("awq_scaling", module.awq), ("awq_clipping", module.awq_clipper)):
+        if ctx is not None:
+            raise DmxqError(f"AdaRound inside {name} on the same module is not supported: both rewrite what the weight cast sees")
+    if wc._flag("observer_enabled"):
+        raise DmxqError("AdaRound while the weight cast's observer is calibrating is not supported: leave calibrating_quantizers first")
+    fmt = wc.format
+    if not isinstance(fmt, FixedPoint) or get_qmin_qmax(fmt) == (None, None) or fmt.rounding != "nearest":
+        raise DmxqError(f"AdaRound needs a weight format that is a clamped XP[p,0] with nearest rounding, got {fmt!r}")
+    if not wc._flag("fake_quant_enabled"):
+        raise DmxqError("AdaRound needs a weight cast that runs: its fake quantisation is switched off")
+    w = module.weight
+    if w.dtype not in (torch.float32, torch.float16, torch.bfloat16):
+        raise DmxqError(f"AdaRound needs a float32, float16 or bfloat16 weight, got {w.dtype}")
+    sym = wc.qscheme in _SYMMETRIC
+    if wc._dynamic is not None:
+        gran, g = wc._dynamic
+        if gran == "per_group" and w.shape[1] % g:
+            raise DmxqError(f"AdaRound: the group size {g} of weight_dynamic does not divide the weight's {w.shape[1]} columns")
+        return fmt, gran, g, True, sym
+    if wc.group_size:
+        raise DmxqError(f"AdaRound with a static group_size ({wc.group_size}) weight cast is not supported: take weight_dynamic per group, "
+                        "or a static per-tensor or per-output-channel cast")
+    if wc.is_per_channel:
+        if wc.ch_axis % 2 != 0 or wc.scale.numel() != w.shape[0] or wc.zero_point.numel() != w.shape[0]:
+            raise DmxqError(f"AdaRound with a static per-channel weight cast needs one calibrated scale per OUTPUT channel (ch_axis 0, "
+                            f"{w.shape[0]} entries), got ch_axis {wc.ch_axis} with {wc.scale.numel()} entries")
+        return fmt, "per_token", None, False, sym
+    if wc.scale.numel() != 1 or wc.zero_point.numel() != 1:
+        raise DmxqError(f"AdaRound with a static per-tensor weight cast needs ONE scale, got {wc.scale.numel()}")
+    return fmt, "per_tensor", None, False, sym
+
+
+def adaround_schedule(hp, step: int):
+    """(reg_weight, beta) of Adam step `step` of hp.iters: no regulariser during the first int(warmup * iters) steps, then hp.reg_weight
+    with beta going from beta[0] to beta[1] by a cosine over the remaining steps"""
+    warm = int(hp.warmup * hp.iters)
+    if step < warm:
+        return 0.0, hp.beta[0]
+    rel = (step - warm) / max(1, hp.iters - warm)
+    return hp.reg_weight, hp.beta[1] + 0.5 * (hp.beta[0] - hp.beta[1]) * (1.0 + math.cos(math.pi * rel))
+
+
+class AdaRoundCalibrator:
+    """AdaRound (Nagel et al., 2020; DESIGN.md §8 "AdaRound"): while DmxModule.adaround_reconstructing is active, `observe` folds the
+    inputs that reach the GEMM into the float32 [in, in] running mean over the tokens of x^T x (AWQCalibrator's formula, one addmm_),
+    counting the tokens on the host -- nothing is read back; `apply` learns the rounding of every weight element on the weight cast's own
+    grid against that moment and writes the hard-rounded weight in place.  The loop has no sampling: the same calibration gives the same
+    bits twice."""
+
+    def __init__(self, module, hyperparams):
+        self.plan = refuse_adaround(module)
+        self.module = module
+        self.hyperparams = hyperparams
+        self.gram = None
+        self.n_tokens = 0
+
+    def observe(self, inp):
+        from . import ops
+        C = inp.shape[-1]
+        t = inp.numel() // C if C else 0
+        if t == 0:
+            return
+        if self.gram is None or self.gram.device != inp.device:
+            prev = self.gram
+            self.gram = torch.zeros(C, C, dtype=torch.float32, device=inp.device)
+            if prev is not None:
+                self.gram += prev.to(inp.device)
+        with torch.no_grad():
+            n = self.n_tokens
+            x = inp.detach().reshape(-1, C).float() * (1.0 / math.sqrt(n + t))
+            self.gram *= n / (n + t)
+            with ops._front._full_fp32_matmul():
+                self.gram.addmm_(x.t(), x)
+        self.n_tokens = n + t
+
+    def qparams(self, W):
+        """(scale float32 [n_seg], zero point int64 [n_seg]) of the weight cast for the contiguous weight W: a dynamic cast's own two
+        steps (group_minmax -> qparams), a static cast's buffers"""
+        from .observer import get_qmin_qmax
+        fmt, gran, g, dynamic, sym = self.plan
+        wc = self.module.weight_cast
+        if not dynamic:
+            return wc.scale.detach().to(W.device, torch.float32).reshape(-1).contiguous(), wc.zero_point.detach().to(W.device, torch.int64).reshape(-1).contiguous()
+        qmin, qmax = get_qmin_qmax(fmt)
+        S = {"per_token": W.shape[1], "per_group": g, "per_tensor": W.numel()}[gran]
+        sc, zp = OptimalBrainCompressor._segment_qparams(W.reshape(-1, S), qmin, qmax, sym)
+        return sc.reshape(-1).float().contiguous(), zp.reshape(-1).to(torch.int64).contiguous()
+
+    def apply(self):
+        from . import ops
+        m, hp = self.module, self.hyperparams
+        if self.n_tokens == 0:
+            raise RuntimeError("AdaRound: no calibration token was observed inside adaround_reconstructing (run at least one forward of "
+                               "the module); the weight is left as it was")
+        fmt, gran, g, dynamic, _ = self.plan
+        with torch.no_grad():
+            W = m.weight.detach()
+            W = W if W.is_contiguous() else W.contiguous()
+            out = W.shape[0]
+            G = self.gram.to(W.device)
+            W32 = W.float()
+            sc, zp = self.qparams(W)
+            zf = zp.to(torch.float32)
+
+            def loss_of(Wq):
+                D = Wq.float() - W32
+                with ops._front._full_fp32_matmul():
+                    return ((D @ G) * D).sum(dtype=torch.float64) / out
+
+            W_rtn = m.weight_cast(W).to(W.dtype)   # the module's own round-to-nearest cast
+            V = ops.adaround_init(W, sc, zp, fmt, gran, g)
+            opt = torch.optim.Adam([V], lr=hp.lr)
+            for step in range(hp.iters):
+                rw, beta = adaround_schedule(hp, step)
+                D = ops.adaround_qdq(W, V, sc, zf, fmt, gran, g, out_dtype=torch.float32) - W32
+                with ops._front._full_fp32_matmul():
+                    gD = (D @ G) * (2.0 / out)   # (the gradient of sum((D G) * D) / out in D: G is symmetric)
+                V.grad, _ = ops.adaround_backward(W, V, gD, sc, zf, fmt, gran, g, beta=beta, reg_weight=rw, want_reg=False)
+                opt.step()
+            W_hard = ops.adaround_qdq(W, V, sc, zf, fmt, gran, g, hard=True)
+            loss_rtn, loss_hard = loss_of(W_rtn), loss_of(W_hard)
+            if hp.keep_best:
+                kept = loss_hard < loss_rtn   # (ties go to round-to-nearest; decided on the device)
+                W_new = torch.where(kept, W_hard, W_rtn)
+                loss = torch.where(kept, loss_hard, loss_rtn)
+            else:
+                kept, W_new, loss = torch.ones((), dtype=torch.bool, device=W.device), W_hard, loss_hard
+            flipped = (W_new != W_rtn).sum()
+            m.weight.copy_(W_new)
+        m.adaround = {"loss_rtn": loss_rtn, "loss_hard": loss_hard, "loss": loss, "kept": kept, "flipped": flipped, "scale": sc, "zero_point": zp,
+                      "group_size": g if gran == "per_group" else None, "granularity": gran}
+        if dynamic:
+            m.weight_cast.disable_fake_quant()
+        m.__dict__.pop("_live_weight", None)   # (a LiveWeightBatch result computed from the weight before rounding)

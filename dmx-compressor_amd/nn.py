@@ -27,7 +27,7 @@ from .smoothquant import ActivationWeightSmoothQuant
 from .sparse import Dense, Sparsify
 
 __all__ = ["DmxModule", "DmxQuantizerCalibrationHyperparams", "DmxModuleQuantizerCalibrationHyperparams",
-           "DmxModuleSmoothQuantHyperparams", "DmxModuleGPTQHyperparams", "DmxWandaHyperparams", "DmxAWQHyperparams", "DmxAWQClipHyperparams", "DmxHQQHyperparams", "Linear", "Conv1d", "Conv2d", "ResAdd", "ActActMatMul", "Softmax", "LayerNorm", "GELU", "ReLU", "SiLU", "QuickGELU", "Exp", "Mul", "RMSNorm", "ApplyRotaryPosEmb",
+           "DmxModuleSmoothQuantHyperparams", "DmxModuleGPTQHyperparams", "DmxWandaHyperparams", "DmxAWQHyperparams", "DmxAWQClipHyperparams", "DmxHQQHyperparams", "DmxAdaRoundHyperparams", "Linear", "Conv1d", "Conv2d", "ResAdd", "ActActMatMul", "Softmax", "LayerNorm", "GELU", "ReLU", "SiLU", "QuickGELU", "Exp", "Mul", "RMSNorm", "ApplyRotaryPosEmb",
            "MaxPool2d", "AvgPool2d", "Embedding", "ReLU6", "Tanh", "Dropout", "NewGELU", "FastGELU", "BloomGELU", "ClippedGELU", "AdaptiveAvgPool2d",
            "BatchNorm2d", "GroupNorm", "ConvTranspose2d", "BAddBMM", "ScaledDotProductAttention", "DmxConfigRule", "configure_model",
            "fold_weights_and_biases", "GraphedForward", "LiveWeightBatch", "link_consumer", "link_consumers_from_fx", "DmxTracer"]
@@ -181,6 +181,49 @@ class DmxHQQHyperparams:
             raise ValueError(f"DmxHQQHyperparams: iters must not be negative, got {self.iters}")
 
 
+@dataclass
+class DmxAdaRoundHyperparams:
+    """AdaRound (DmxModule.adaround_reconstructing; not in the reference).  iters: full-batch Adam steps on the rounding variable V;
+    lr: Adam's step size; reg_weight: the weight of the regulariser sum(1 - |2 h - 1|^beta), zero during the first `warmup` share of the
+    steps; beta: (first, last) exponent, annealed by a cosine over the steps after the warm-up; keep_best: keep the module's own
+    round-to-nearest weight where the learned rounding does not have the strictly lower loss on the calibration moment"""
+    iters: int = 1000
+    lr: float = 1e-2
+    reg_weight: float = 0.01
+    beta: tuple = (20.0, 2.0)
+    warmup: float = 0.2
+    keep_best: bool = True
+
+    def __post_init__(self):
+        import math
+        if isinstance(self.iters, bool) or not isinstance(self.iters, int):
+            raise TypeError(f"DmxAdaRoundHyperparams: iters must be an int, got {self.iters!r}")
+        if self.iters < 0:
+            raise ValueError(f"DmxAdaRoundHyperparams: iters must not be negative, got {self.iters}")
+        for name in ("lr", "reg_weight", "warmup"):
+            v = getattr(self, name)
+            if isinstance(v, bool) or not isinstance(v, (int, float)):
+                raise TypeError(f"DmxAdaRoundHyperparams: {name} must be a number, got {v!r}")
+            if not math.isfinite(v):
+                raise ValueError(f"DmxAdaRoundHyperparams: {name} must be finite, got {v!r}")
+        if not self.lr > 0.0:
+            raise ValueError(f"DmxAdaRoundHyperparams: lr must be positive, got {self.lr}")
+        if self.reg_weight < 0.0:
+            raise ValueError(f"DmxAdaRoundHyperparams: reg_weight must not be negative, got {self.reg_weight}")
+        if not 0.0 <= self.warmup < 1.0:
+            raise ValueError(f"DmxAdaRoundHyperparams: warmup must lie in [0, 1), got {self.warmup}")
+        if not isinstance(self.beta, (tuple, list)) or len(self.beta) != 2:
+            raise TypeError(f"DmxAdaRoundHyperparams: beta must be a pair (first, last), got {self.beta!r}")
+        for v in self.beta:
+            if isinstance(v, bool) or not isinstance(v, (int, float)):
+                raise TypeError(f"DmxAdaRoundHyperparams: beta must hold two numbers, got {self.beta!r}")
+            if not math.isfinite(v) or v < 1.0:
+                raise ValueError(f"DmxAdaRoundHyperparams: both exponents of beta must be finite and at least 1, got {self.beta!r}")
+        self.beta = (float(self.beta[0]), float(self.beta[1]))
+        if not isinstance(self.keep_best, bool):
+            raise TypeError(f"DmxAdaRoundHyperparams: keep_best must be a bool, got {self.keep_best!r}")
+
+
 def _learnable_args(setting) -> dict:
     """configure's *_learnable value -> CastTo.set_learnable's keyword arguments: None, "per_token", "per_tensor", {"per_group": g}, or
     {"granularity": one of those, "learn_zero_point": bool, "grad_scale": "lsq" | None | float, "init": "minmax" | "lsq"}"""
@@ -244,6 +287,11 @@ class DmxModule(FastAttr, torch.nn.Module):
     awq_clipper = None
     awq_clip = awq_clip_blocks = None
     awq_clip_n_tokens = 0
+    #: the AdaRoundCalibrator while `adaround_reconstructing` is active (layer_reconstruction.py), else None; after a context `adaround` =
+    #: {"loss_rtn", "loss_hard", "loss": float64 0-d, "kept": bool 0-d (the learned rounding was written), "flipped": int64 0-d (elements that differ
+    #: from round-to-nearest), all on the device, "scale": float32 [n_seg], "zero_point": int64 [n_seg], "group_size"}: a plain attribute
+    adarounder = None
+    adaround = None
 
     def _dmx_init(self, n_inputs: int = 1, input_names=("input_cast",), sparsifiable: bool = False):
         pnames = [n for n, _ in self.named_parameters(recurse=False)]
@@ -682,6 +730,35 @@ class DmxModule(FastAttr, torch.nn.Module):
         yield self
         self.enable_awq_clip(False, hyperparams)
 
+    def enable_adaround(self, state: bool, hyperparams=None) -> None:
+        """AdaRound (Nagel et al., 2020; DESIGN.md §8 "AdaRound"): on a Linear with a 2-D weight (any other module: nothing happens)
+        whose weight cast is a nearest-rounding XP[p,0] integer cast -- dynamic per group, per token or per tensor, or static per tensor
+        or per output channel.  Entering starts folding the inputs as `_forward` receives them into the float32 running mean of x^T x;
+        leaving learns, per weight element, whether to round down or up on the cast's own grid so that the layer's output error on those
+        inputs is smallest (`hyperparams.iters` Adam steps on ops.adaround_qdq), writes the hard-rounded weight IN PLACE and records
+        `adaround`.  With keep_best the module's own round-to-nearest weight is written instead where it has the lower (or an equal)
+        loss, so a layer never gets worse on its calibration moment.  A dynamic weight cast has its fake quantisation switched OFF
+        afterwards (GPTQ's and HQQ's reason: it would derive new scales from the written weight); a static cast is idempotent on the
+        written grid and stays on."""
+        from .layer_reconstruction import AdaRoundCalibrator, adaround_applies
+        if hyperparams is None:
+            hyperparams = DmxAdaRoundHyperparams()
+        if not isinstance(hyperparams, DmxAdaRoundHyperparams):
+            raise TypeError(f"adaround_reconstructing takes a DmxAdaRoundHyperparams, got {type(hyperparams).__name__}")
+        if state:
+            if not adaround_applies(self):
+                return
+            self.adarounder = AdaRoundCalibrator(self, hyperparams)   # (refuses before any state is touched)
+        elif self.adarounder is not None:
+            rounder, self.adarounder = self.adarounder, None
+            rounder.apply()
+
+    @contextmanager
+    def adaround_reconstructing(self, hyperparams=None):
+        self.enable_adaround(True, hyperparams)
+        yield self
+        self.enable_adaround(False, hyperparams)
+
     def hqq_quantize(self, hyperparams=None) -> None:
         """HQQ (DESIGN.md §8 "HQQ"; no calibration data): on a Linear or a Conv2d (through the [out, -1] view of its weight; any other
         module: nothing happens) whose weight cast's format is a clamped XP[p,0] with nearest rounding.  The weight is replaced IN PLACE
@@ -938,6 +1015,8 @@ class DmxModule(FastAttr, torch.nn.Module):
             self.awq.observe(_input)
         if self.awq_clipper is not None:
             self.awq_clipper.observe(_input)
+        if self.adarounder is not None:
+            self.adarounder.observe(_input)
         _output = self._forward(_input, *args, **kwargs)
         # (a GEMM-bearing module's output cast is a launch of its own; when the linked consumer applies the SAME cast to this value as
         #  its first input cast -- inside its fused kernel -- the cast here is redundant: FloatingPoint casts are projections)

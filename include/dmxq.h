@@ -59,7 +59,8 @@ const char* dmxq_status_string(int status);
  * dmxq_wanda_class, dmxq_row_class_of, dmxq_channel_sumabs_accumulate, dmxq_awq_group_error, dmxq_awq_class,
  * dmxq_block_scaled_float_qdq, dmxq_block_scaled_float_class, dmxq_block_scaled_tensor_scale, dmxq_nm_mask_class, dmxq_lsq_backward, dmxq_lsq_class, dmxq_lsq_scratch_bytes,
  * dmxq_codebook_qdq, dmxq_codebook_class, dmxq_codebook_accumulate, dmxq_codebook_workspace_bytes, dmxq_hqq_qdq, dmxq_hqq_class,
- * dmxq_outlier_fixed_qdq, dmxq_outlier_class, dmxq_awq_clip, dmxq_awq_clip_class) leave it at 4: a caller built against 4 runs on
+ * dmxq_outlier_fixed_qdq, dmxq_outlier_class, dmxq_awq_clip, dmxq_awq_clip_class, dmxq_adaround_forward, dmxq_adaround_backward,
+ * dmxq_adaround_class, dmxq_adaround_scratch_bytes) leave it at 4: a caller built against 4 runs on
  * this library unchanged.  4 = round 5: + dmxq_float_qdq_multi, dmxq_fixed_float_qdq_multi; 3 = round 4: + dmxq_weight_hypernet_multi,
  * dmxq_unary_cast_table, dmxq_lut16_apply.  Nothing was ever removed or changed: a caller built against version n runs on any library >= n. */
 int dmxq_abi_version(void);
@@ -773,6 +774,36 @@ int dmxq_awq_clip_class(int dtype_w, int64_t L, int64_t group);
 int dmxq_awq_clip(const void* w, int dtype_w, const float* blocks, const float* ratios, int n_ratios, void* y_out, uint8_t* best_out,
                   float* clip_out, float* losses_out, int64_t rows, int64_t L, int64_t group, int precision, int fraction, int clamp,
                   int symmetric, int qmin, int qmax, int symmetric_qscheme, void* stream);
+
+/* AdaRound (Nagel et al. 2020): the soft cast of learned weight rounding and its backward pass, each ONE streaming launch
+ * (csrc/adaround.hip; DESIGN.md §8 "AdaRound").  Not in the reference.  w: the contiguous [n_segments, segment] weight (bf16 / f16 /
+ * f32); V: DEVICE float32, one per element; scale: DEVICE float32 [n_segments]; zero_point: DEVICE float32 [n_segments] holding the
+ * INTEGER zero points; y: dtype_out, g: dtype_g -- each the weight's dtype or float32; dV: float32.  Per element, every operation one
+ * fp32 operation in this order, G = -0.1f, ZG = 1.1f - (-0.1f):
+ *   v = w / s (IEEE division);  f = floorf(v);  sg = 1 / (1 + expf(-V));  hr = sg * ZG + G;
+ *   h = clamp(hr, 0, 1), or with hard != 0: h = V >= 0 ? 1 : 0 (no transcendental);
+ *   q = clamp((f + h) + zq, qmin, qmax);  y = (q - zq) * s, rounded once more to dtype_out.
+ * Backward, the gradient of V alone (bm1 = beta - 1 and m2b = -2 * beta formed once in fp32):
+ *   in01 = 0 < hr < 1;  cell = qmin <= f + zq <= qmax - 1;  dh = (sg * (1 - sg)) * ZG;  rec = (in01 && cell) ? (g * s) * dh : 0;
+ *   t2 = 2 * h - 1;  a = |t2|;  p1 = powf(a, bm1);  r = 1 - p1 * a;  dreg = in01 ? reg_weight * (((m2b * p1) * sign(t2)) * dh) : 0;
+ *   dV = rec + dreg (rec alone when reg_weight == 0);  reg_out[0] = sum (double)r over the tensor.
+ * The sum is float64 without floating-point atomics: one partial sum per workgroup in `scratch` (dmxq_adaround_scratch_bytes(n) bytes
+ * of device memory for n elements, 8-byte aligned, contents free) and a second small launch that folds them in a fixed order; the order
+ * depends on the shape alone.  reg_out == NULL: no sum, scratch unused (may be NULL).  NaN / Inf: csrc/adaround.hip's header.
+ * dmxq_adaround_class: how a 16-byte vector finds its segment -- SHIFT where segment / vector is a power of two, DIVIDE for any other
+ * whole number of vectors, NONE where the entries refuse; dmxq_adaround_scratch_bytes: both host functions, no GPU involved.
+ * DMXQ_ERR_UNSUPPORTED, nothing launched (the caller runs its chain of torch operations): a segment that is not whole 16-byte vectors
+ * of the weight, a pointer that is not 16-byte aligned (scratch, reg_out: 8-byte), dtype_out / dtype_g neither the weight's dtype nor
+ * float32.  DMXQ_ERR_BAD_ARG: null pointers, negative sizes, an invalid dtype, qmax <= qmin, a scratch smaller than the query says.
+ * No allocation, no host synchronisation: capturable. */
+typedef enum { DMXQ_ADAROUND_NONE = 0, DMXQ_ADAROUND_SHIFT = 1, DMXQ_ADAROUND_DIVIDE = 2 } dmxq_adaround_geometry;
+int dmxq_adaround_class(int dtype, int64_t segment);
+int64_t dmxq_adaround_scratch_bytes(int64_t n);
+int dmxq_adaround_forward(const void* w, const float* V, void* y, int dtype_w, int dtype_out, int64_t n_segments, int64_t segment, int qmin,
+                          int qmax, const float* scale, const float* zero_point, int hard, void* stream);
+int dmxq_adaround_backward(const void* w, const float* V, const void* g, float* dV, int dtype_w, int dtype_g, int64_t n_segments,
+                           int64_t segment, int qmin, int qmax, const float* scale, const float* zero_point, float beta, float reg_weight,
+                           double* reg_out /* double[1], may be NULL */, void* scratch, int64_t scratch_bytes, void* stream);
 
 /* Two-level BLOCK-SCALED float cast (csrc/block_scaled_float.hip; DESIGN.md §8 "Block-scaled float cast"): the group scale of
  * dmxq_dynamic_float_qdq QUANTISED to a low-bit float format, under one float32 scale per tensor -- the numerics of a stored block-scaled
