@@ -948,6 +948,47 @@ def codebook_accumulate(x, mode, segment, levels, norm, acc, accumulate):
                                          int(bool(accumulate)), ptr(ws), stream_of(xc)), "dmxq_codebook_accumulate")
 
 
+# ------------------------------------------------------------------------------------------------ vector codebook casts
+def _vq_args(xc, segment, table, what):
+    if segment < 1 or xc.numel() % segment != 0:
+        raise RuntimeError(f"{what}: the segment must divide the number of elements")
+    if not (table.is_cuda and table.device == xc.device and table.dtype == torch.float32 and table.is_contiguous() and table.dim() == 2
+            and table.shape[1] >= 1):
+        raise RuntimeError(f"{what}: the table must be a contiguous float32 [K, d] tensor on x's GPU")
+    if xc.dim() < 1 or xc.shape[-1] % table.shape[1] != 0:
+        raise RuntimeError(f"{what}: the last dimension must be a multiple of the table's d")
+
+
+@_guarded
+def vq_qdq(x, mode, segment, table, norm, want_scale, want_index, out_dtype=None):
+    """-> (out, scale float32 [n_segments], index uint8 x.shape[:-1] + (L / d,)): the last two empty unless wanted"""
+    xc = _prep(x, "vq_qdq")
+    _vq_args(xc, segment, table, "vq_qdq")
+    K, d = table.shape
+    n = xc.numel() // segment
+    out = torch.empty(xc.shape, dtype=out_dtype or xc.dtype, device=xc.device)
+    sc = torch.empty(n if want_scale else 0, dtype=torch.float32, device=xc.device)
+    idx = torch.empty(tuple(xc.shape[:-1]) + (xc.shape[-1] // d,) if want_index else 0, dtype=torch.uint8, device=xc.device)
+    check(lib().dmxq_vq_qdq(ptr(xc), ptr(out), dtype_code(xc.dtype), dtype_code(out.dtype), mode, n, segment, ptr(table), d, K, float(norm),
+                            ptr(sc) if want_scale else None, ptr(idx) if want_index else None, stream_of(xc)), "dmxq_vq_qdq")
+    return out, sc, idx
+
+
+@_guarded
+def vq_accumulate(x, mode, segment, table, norm, acc, accumulate):
+    """acc (float64 [K, d + 2]) (+)= the k-means statistics of x under the table; the partial blocks' workspace is allocated here"""
+    xc = _prep(x, "vq_accumulate")
+    _vq_args(xc, segment, table, "vq_accumulate")
+    K, d = table.shape
+    if not (acc.is_cuda and acc.device == xc.device and acc.dtype == torch.float64 and acc.is_contiguous() and acc.numel() == K * (d + 2)):
+        raise RuntimeError("vq_accumulate: acc must be a contiguous float64 [K, d + 2] tensor on x's GPU")
+    n = xc.numel() // segment
+    wb = int(lib().dmxq_vq_workspace_bytes(dtype_code(xc.dtype), mode, n, segment, d, K))
+    ws = torch.empty(wb // 8 + 1, dtype=torch.float64, device=xc.device)
+    check(lib().dmxq_vq_accumulate(ptr(xc), dtype_code(xc.dtype), mode, n, segment, ptr(table), d, K, float(norm), ptr(acc),
+                                   int(bool(accumulate)), ptr(ws), stream_of(xc)), "dmxq_vq_accumulate")
+
+
 # ------------------------------------------------------------------------------------------------ HQQ
 @_guarded
 def hqq_qdq(x, segment, rounding, qmin, qmax, lp_norm, beta, kappa, iters, want_qparams, want_codes, out_dtype=None):

@@ -71,7 +71,9 @@ _FAST_CALIBRATION_NAMES = {"hist_observe": "hist_observe", "hist_qparams": "hist
                            # the AWQ clip search: no autograd to lose
                            "awq_clip": "awq_clip",
                            # AdaRound: both passes are called from inside an autograd Function of the front end (_front.py)
-                           "adaround_forward": "adaround_forward", "adaround_backward": "adaround_backward"}
+                           "adaround_forward": "adaround_forward", "adaround_backward": "adaround_backward",
+                           # the vector codebook cast and its k-means statistics: straight-through above the raw op (_front.py)
+                           "vq_qdq": "vq_qdq", "vq_accumulate": "vq_accumulate"}
 FAST = None
 
 

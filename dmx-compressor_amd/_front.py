@@ -27,6 +27,7 @@ __all__ = [
     "DYNAMIC_FLOAT_CHAIN_BY_DEFAULT",
     "codebook_qdq", "codebook_check", "codebook_class", "codebook_accumulate", "codebook_fit", "CODEBOOKS", "NF4", "CODEBOOK_GRANULARITIES",
     "CODEBOOK_KERNEL_LEVELS", "CODEBOOK_CHAIN_BY_DEFAULT",
+    "vq_qdq", "vq_check", "vq_grid", "vq_class", "vq_accumulate", "vq_fit", "VQ_DIMS", "VQ_CHAIN_BY_DEFAULT", "VQ_CHAIN_PIECE_ENTRIES",
     "hqq_qdq", "hqq_check", "hqq_class", "HQQ_CHAIN_BY_DEFAULT", "HQQ_KERNEL_NORMS",
     "outlier_fixed_qdq", "outlier_check", "outlier_class", "outlier_bits_per_element", "OUTLIER_CHAIN_BY_DEFAULT", "OUTLIER_KERNEL_MAX_K",
     "lsq_backward", "lsq_fixed_qdq", "lsq_class", "lsq_scratch_bytes", "lsq_grad_factor", "LSQ_CHAIN_BY_DEFAULT",
@@ -1809,6 +1810,429 @@ def codebook_fit(x, codebook="nf4", granularity: str = "per_group", group_size: 
             for t in xs:
                 codebook_accumulate(t, c, granularity, group_size, norm, acc=A, accumulate=True, fused=fused)
             c = torch.where(A[:, 2] > 0, (A[:, 0] / A[:, 1]).float(), c)
+        if return_history:
+            history.append(rel_error())
+            return c, norm, torch.stack(history)
+        return c, norm
+
+
+# ---------------------------------------------------------------------------------------------------- vector codebook casts
+VQ_DIMS = (2, 4, 8)
+# Launch geometries of dmxq_vq_qdq (vq_class) that fused=None sends to the chain although the kernel takes them: CODEBOOK_CHAIN_BY_DEFAULT's
+# rule -- a class goes to the kernel by default only where tools/bench_vq.py MEASURED it faster than the chain on the same buffers; a
+# class that is not gets listed here with its row.
+# profiles/r25_vq.txt (bf16, us per call, kernel against chain, tables [16,2] / [256,2] / [256,4] / [256,8]): group per_group 64 [4096,4096]
+# 39.4 / 346.8 / 289.7 / 284.1 against 4145.6 / 28499.5 / 26168.5 / 27105.2, [14336,4096] 117.6 / 1205.6 / 987.6 / 976.2 against 14152.1 /
+# 99508.5 / 91211.6 / 94449.5, [2048,768] 6.5 / 40.2 / 34.8 / 39.2 against 450.0 / 2719.1 / 2494.4 / 2599.1; wave_row per_token [4096,4096]
+# 37.6 / 351.6 / 293.1 / 293.1 against 2500.4 / 26738.1 / 24441.1 / 25391.7, [14336,4096] 110.1 / 1194.4 / 989.9 / 977.0 against 8514.9 /
+# 92825.1 / 85643.1 / 88395.6, [2048,768] 7.5 / 50.8 / 43.6 / 41.4 against 343.0 / 2610.1 / 2388.9 / 2504.7; block_row per_token
+# [2048,8192], tables [16,2] / [256,4] / [256,8], 62.7 / 541.9 / 535.9 against 2500.6 / 24410.9 / 25365.5; short_row per_token [60000,48]
+# 65.8 / 489.3 / 487.2 against 820.5 / 4530.0 / 4742.2 -- every class is faster (9 - 120 x), none is listed.
+VQ_CHAIN_BY_DEFAULT = frozenset()
+# which route the calls of this front end took, counted on the host: private, for the tests (fused=True must have run the kernel)
+_vq_routes = {"fused": 0, "chain": 0}
+_vq_accumulate_routes = {"fused": 0, "chain": 0}
+#: the chain's bound: its search forms float32 [vectors, K] distance tensors (never [vectors, K, d]: the components are subtracted, squared
+#: and added one at a time) on pieces of at most this many entries -- 64 MiB each, three alive at a time
+VQ_CHAIN_PIECE_ENTRIES = 1 << 24
+_vq_device_cache = {}   # (rows, device) -> float32 [K, d] tensor: a host table is uploaded once per device
+
+
+def vq_grid(levels, dim: int):
+    """the product table of a scalar codebook: every dim-tuple of its levels as a row, rows in lexicographic order (the first component
+    varies slowest) -> float32 CPU tensor [len(levels) ** dim, dim].  levels: a name of ops.CODEBOOKS ("nf4", "uniform4", ...) or a
+    list of levels, checked as codebook_check checks them.  ValueError when dim is not 2, 4 or 8 or the table would exceed 256 rows:
+    vq_grid("uniform4", 4) and vq_grid("nf4", 2) are the two largest common ones."""
+    import itertools
+    if isinstance(dim, bool) or not isinstance(dim, int) or dim not in VQ_DIMS:
+        raise ValueError(f"vq_grid: dim must be one of {VQ_DIMS}, got {dim!r}")
+    if isinstance(levels, torch.Tensor) and levels.is_cuda:
+        raise ValueError("vq_grid: the levels are a name, a list or a CPU tensor (a device tensor would have to be read back)")
+    lv = _codebook_host_levels(levels, "vq_grid")
+    if len(lv) ** dim > 256:
+        raise ValueError(f"vq_grid: {len(lv)} levels in {dim} dimensions give {len(lv) ** dim} rows, more than 256")
+    return torch.tensor(list(itertools.product(lv, repeat=dim)), dtype=torch.float32)
+
+
+def _vq_host_rows(codebook, what):
+    """a list of rows or a CPU tensor [K, d] -> the checked tuple of tuples of float32 values (ValueError); a device tensor -> None"""
+    if isinstance(codebook, torch.Tensor):
+        if codebook.dim() != 2 or not codebook.is_floating_point():
+            raise ValueError(f"{what}: a table tensor must be a 2-d float tensor [K, d], got shape {tuple(codebook.shape)} {codebook.dtype}")
+        if codebook.is_cuda:
+            return None
+        rows = codebook.detach().to(torch.float32).tolist()
+    elif isinstance(codebook, (list, tuple)):
+        try:
+            rows = [[float(v) for v in r] for r in codebook]
+        except (TypeError, ValueError):
+            raise ValueError(f"{what}: a table is a list of rows of numbers, got {codebook!r}") from None
+        if len({len(r) for r in rows}) > 1:
+            raise ValueError(f"{what}: the rows of a table must have one length, got lengths {sorted({len(r) for r in rows})}")
+        if rows and rows[0]:
+            rows = torch.tensor(rows, dtype=torch.float32).tolist()   # (rounded to float32 once, here)
+    else:
+        raise ValueError(f"{what}: a table is a list of rows, a [K, d] tensor or {{'grid': name, 'dim': d}}, got {type(codebook).__name__}")
+    return tuple(tuple(r) for r in rows)
+
+
+def vq_check(codebook, dim=None, granularity="per_group", group_size=64, norm=None, what: str = "vq_qdq"):
+    """-> (table, K, d, granularity, group_size, norm) of a vector codebook cast, or ValueError before any GPU use.  `table`: the checked
+    tuple of K rows of d float32 values of a list of rows or a CPU tensor [K, d] (or of {"grid": levels, "dim": d}: vq_grid) -- finite,
+    2 <= K <= 256, d in {2, 4, 8}; no order is required, duplicate rows are allowed -- or a device tensor as it is ([K, d] by its shape;
+    never read back).  dim: None, or the d the table must have.  A known granularity; with per_group a positive integer group_size that is
+    a multiple of d (that it divides the last dimension is checked against the tensor); norm None or a positive finite number."""
+    if isinstance(codebook, dict):
+        if set(codebook) != {"grid", "dim"}:
+            raise ValueError(f"{what}: a table given as a dict is {{'grid': levels, 'dim': d}}, got {codebook!r}")
+        codebook = vq_grid(codebook["grid"], codebook["dim"])
+    rows = _vq_host_rows(codebook, what)
+    K, d = (len(rows), len(rows[0]) if rows else 0) if rows is not None else tuple(codebook.shape)
+    if not 2 <= K <= 256:
+        raise ValueError(f"{what}: a table has 2 to 256 rows, got {K}")
+    if d not in VQ_DIMS:
+        raise ValueError(f"{what}: the rows of a table have {VQ_DIMS} components, got {d}")
+    if dim is not None and (isinstance(dim, bool) or not isinstance(dim, int) or dim != d):
+        raise ValueError(f"{what}: dim={dim!r} beside a table whose rows have {d} components")
+    if rows is not None and not all(math.isfinite(v) for r in rows for v in r):
+        raise ValueError(f"{what}: the entries of a table must be finite")
+    if granularity not in CODEBOOK_GRANULARITIES:
+        raise ValueError(f"{what}: granularity must be one of {CODEBOOK_GRANULARITIES}, got {granularity!r}")
+    if granularity == "per_group":
+        if isinstance(group_size, bool) or not isinstance(group_size, int) or group_size < 1:
+            raise ValueError(f"{what}: per_group needs a positive integer group_size, got {group_size!r}")
+        if group_size % d:
+            raise ValueError(f"{what}: the group size {group_size} is not a multiple of the table's d = {d}: a vector would straddle two groups")
+    else:
+        group_size = None   # (the default group_size of the signature means nothing without per_group)
+    if norm is not None:
+        if isinstance(norm, bool) or not isinstance(norm, (int, float)) or not (0.0 < float(norm) < math.inf):
+            raise ValueError(f"{what}: norm must be None (the table's own largest magnitude) or a positive finite number, got {norm!r}")
+        norm = float(torch.tensor(float(norm), dtype=torch.float32))   # (the float32 value the kernel receives)
+        if not (0.0 < norm < math.inf):
+            raise ValueError(f"{what}: norm is not a positive finite float32 number")
+    return (rows if rows is not None else codebook), K, d, granularity, group_size, norm
+
+
+def _vq_tensor(table, device):
+    """the float32 [K, d] device tensor of a checked table: a device tensor as it is (converted on the device if need be), a host tuple
+    uploaded once per device and kept (a later call, also inside a graph capture, copies nothing)"""
+    if isinstance(table, torch.Tensor):
+        t = table.detach()
+        t = t if t.dtype == torch.float32 else t.float()
+        t = t if t.device == device else t.to(device)
+        return t if t.is_contiguous() else t.contiguous()
+    key = (table, str(device))
+    t = _vq_device_cache.get(key)
+    if t is None:
+        t = _vq_device_cache[key] = torch.tensor(table, dtype=torch.float32, device=device)
+    return t
+
+
+def vq_class(segment: int, dtype: torch.dtype, dim: int, K: int, whole_rows: bool = False) -> Optional[str]:
+    """the launch geometry dmxq_vq_qdq / dmxq_vq_accumulate pick for segments of `segment` elements of `dtype` under a [K, dim] table
+    (whole_rows: per_token / per_tensor), asked of the library itself (no GPU involved), or None where they refuse: codebook_class's
+    names.  float32 takes dim 2 and 4; the sixteen-bit dtypes 2, 4 and 8."""
+    from ._lib import dtype_code, lib
+    return _DYNAMIC_CLASS_NAMES.get(lib().dmxq_vq_class(dtype_code(dtype), _DYNF_ROWS if whole_rows else _DYNF_GROUP, int(segment), int(dim), int(K)))
+
+
+def _vq_segment(x, d, granularity, group_size, what):
+    if x.dim() < 1:
+        raise ValueError(f"{what}: {granularity} expects a tensor with at least 1 dimension")
+    L = x.shape[-1]
+    if granularity == "per_group" and L % group_size:
+        raise ValueError(f"{what}: the last dimension has {L} elements, not a multiple of the group size {group_size}")
+    if granularity == "per_token" and L % d:
+        raise ValueError(f"{what}: the last dimension has {L} elements, not a multiple of the table's d = {d}")
+    if granularity == "per_tensor" and x.numel() % d:
+        raise ValueError(f"{what}: the tensor has {x.numel()} elements, not a multiple of the table's d = {d}")
+    return {"per_token": L, "per_group": group_size, "per_tensor": x.numel()}[granularity]
+
+
+def _vq_distances(uv, c):
+    """D_k(u) of the definition for the vectors uv [n, d] against the table c [K, d] -> float32 [n, K]: per component one subtract and one
+    multiply, the products added left to right -- separate torch launches, each rounded on its own"""
+    acc = None
+    for j in range(c.shape[1]):
+        t = uv[:, j:j + 1] - c[:, j][None, :]
+        p = t * t
+        acc = p if acc is None else acc + p
+    return acc
+
+
+def _vq_choose(uv, c, z):
+    """the row choice: NaN distances count as +Inf, argmin takes the first minimum (the lowest index), a vector whose minimum is +Inf takes z"""
+    D = _vq_distances(uv, c)
+    D = torch.where(torch.isnan(D), torch.full_like(D, math.inf), D)
+    idx = torch.argmin(D, dim=1)
+    best = D.gather(1, idx[:, None])[:, 0]
+    return torch.where(best == math.inf, z, idx)
+
+
+def _vq_zero_row(c):
+    """z, the lowest index minimising D_k(0), as a 0-d int64 device tensor"""
+    return _vq_choose(torch.zeros(1, c.shape[1], dtype=torch.float32, device=c.device), c, torch.zeros((), dtype=torch.int64, device=c.device))[0]
+
+
+def _vq_chain(x2, c, norm_t, want_lookup=True, out_dtype=None):
+    """the definition on the rows of x2 [n, S] as a chain of launches -> (y or None, scale [n], u [n, S] float32, idx int64 [n, S / d]).
+    Segments are independent: the chain runs on pieces of at most DYNAMIC_CHAIN_PIECE segments (dmxq_group_minmax takes 65535), and the
+    search inside a piece on at most VQ_CHAIN_PIECE_ENTRIES // K vectors at a time."""
+    K, d = c.shape
+    z = _vq_zero_row(c)
+    step = max(1, VQ_CHAIN_PIECE_ENTRIES // K)
+
+    def chain(part):
+        mn, mx = _ops.group_minmax(part, 0, 1)
+        sc = _scale_from_amax(torch.maximum(mn.abs(), mx.abs()), norm_t, False)
+        u = _ops.scale_channels(part, sc, 0, True, torch.float32)
+        uv = u.reshape(-1, d)
+        idx = torch.cat([_vq_choose(uv[i:i + step], c, z) for i in range(0, uv.shape[0], step)]) if uv.shape[0] > step else _vq_choose(uv, c, z)
+        y = _ops.scale_channels(c[idx].reshape(part.shape), sc, 0, False, out_dtype) if want_lookup else sc
+        return y, sc, u, idx.reshape(part.shape[0], -1)
+
+    if x2.shape[0] <= DYNAMIC_CHAIN_MAX_SEGMENTS:
+        y, sc, u, idx = chain(x2)
+    else:
+        parts = [chain(x2[i:i + DYNAMIC_CHAIN_PIECE]) for i in range(0, x2.shape[0], DYNAMIC_CHAIN_PIECE)]
+        y, sc, u, idx = (torch.cat([p[k] for p in parts]) for k in range(4))
+    return (y if want_lookup else None), sc, u, idx
+
+
+def _vq_norm_tensor(c, norm):
+    """the [1] float32 device tensor the chain divides the maxima by: the given norm, or max |c_kj| formed on the device"""
+    if norm is not None:
+        return torch.full((1,), norm, dtype=torch.float32, device=c.device)
+    return c.abs().max().reshape(1)
+
+
+def _vq_kernel_class(xc, S, d, K, mode, same_dtype=True):
+    """the kernel's geometry for the call, or None where the front end must run the chain"""
+    if not same_dtype or xc.data_ptr() % 16:
+        return None
+    return vq_class(S, xc.dtype, d, K, mode == _DYNF_ROWS)
+
+
+def vq_qdq(x, codebook, granularity: str = "per_group", group_size: Optional[int] = 64, norm: Optional[float] = None,
+           out_dtype: Optional[torch.dtype] = None, return_scale: bool = False, return_index: bool = False, fused: Optional[bool] = None,
+           per_group: Optional[int] = None):
+    """Q->DQ onto the rows of a [K, d] table under a per-segment absolute-maximum scale (DESIGN.md §8 "Vector codebook casts"; not in the
+    reference): d consecutive elements of the last dimension are replaced together by one row -- GPTVQ / AQLM / QuIP#-style vector
+    quantisation (d = 2, K = 256: 4 bits per weight; d = 4: 2 bits; d = 8: 1 bit).  `codebook`: a list of rows or CPU tensor [K, d]
+    (checked: ValueError), {"grid": levels, "dim": d} (ops.vq_grid), or a device tensor (taken as is, never read back); 2 <= K <= 256,
+    d in {2, 4, 8}.  In fp32, every operation rounded on its own:
+        D_k(u) = (((t_0 t_0) + t_1 t_1) + ...) + t_{d-1} t_{d-1}, t_j = u_j - c_kj;  z = the lowest k minimising D_k(0);
+    and per segment (codebook_qdq's segments; per_group needs g % d == 0, per_token L % d == 0, per_tensor numel % d == 0):
+        amax, s = amax / norm (norm=None: max |c_kj|, formed on the device) and the fallback s = 1 as codebook_qdq;  u = x / s (IEEE);
+        per vector: best = +Inf, idx = z, for k = 0 .. K-1: D_k(u) < best takes k -- a tie keeps the lower index, a vector whose distances
+        are all NaN or +Inf takes z;  y_j = c[idx][j] * s: one fp32 multiply, one rounding to out_dtype.
+    ONE launch (dmxq_vq_qdq) where vq_class takes the call, out_dtype == x.dtype and the base is 16-byte aligned.  Otherwise the chain,
+    same bits: group_minmax -> the scale rule in torch -> scale_channels (divide, float32) -> per component subtract, multiply and
+    left-to-right adds into a [vectors, K] distance tensor -> where(isnan(D), inf, D) -> argmin (the first minimum) -> the z override where
+    the minimum is +Inf -> gather -> scale_channels (multiply, out_dtype); on pieces of 32768 segments above 65535 segments and of
+    VQ_CHAIN_PIECE_ENTRIES // K vectors, so that no temporary exceeds 64 MiB.  fused=None: the kernel where it applies and its geometry
+    is not listed in VQ_CHAIN_BY_DEFAULT; True: NotImplementedError instead of falling back; False: the chain.  per_group=g spells
+    granularity="per_group", group_size=g.
+    Returns y, followed by scale (float32 [n_segments]) with return_scale and index (uint8, x.shape[:-1] + (L / d,)) with return_index.
+    Autograd: a straight-through estimator.  Nothing is read back to the host on either route."""
+    granularity, group_size = _codebook_per_group(granularity, group_size, per_group, "vq_qdq")
+    table, K, d, granularity, group_size, norm = vq_check(codebook, None, granularity, group_size, norm)
+    S = _vq_segment(x, d, granularity, group_size, "vq_qdq")
+    require_gpu(x, "vq_qdq")
+    out_dtype = out_dtype or x.dtype
+    mode = _DYNF_GROUP if granularity == "per_group" else _DYNF_ROWS
+
+    def pick(y, sc, idx):
+        out = (y,) + ((sc,) if return_scale else ()) + ((idx,) if return_index else ())
+        return out if len(out) > 1 else y
+
+    def run(xd):
+        xc = xd if xd.is_contiguous() else xd.contiguous()
+        ishape = tuple(xc.shape[:-1]) + (xc.shape[-1] // d,)
+        if xc.numel() == 0:
+            return pick(torch.empty(xc.shape, dtype=out_dtype, device=xc.device), torch.empty(0, dtype=torch.float32, device=xc.device),
+                        torch.empty(ishape, dtype=torch.uint8, device=xc.device))
+        c = _vq_tensor(table, xc.device)
+        if fused is not False:
+            cls = _vq_kernel_class(xc, S, d, K, mode, out_dtype == xc.dtype)
+            if cls is None and fused:
+                raise NotImplementedError(f"vq_qdq: no fused kernel for {granularity} segments of {S} {xc.dtype} elements -> {out_dtype} "
+                                          f"with a [{K}, {d}] table (base address {xc.data_ptr() % 16} mod 16)")
+            if cls is not None and fused is None and cls in VQ_CHAIN_BY_DEFAULT:
+                cls = None
+            if cls is not None:
+                try:
+                    y, sc, idx = _ops.vq_qdq(xc, mode, S, c, 0.0 if norm is None else norm, bool(return_scale), bool(return_index), out_dtype)
+                    _vq_routes["fused"] += 1
+                    return pick(y, sc, idx)
+                except NotImplementedError:   # (DMXQ_ERR_UNSUPPORTED, nothing launched)
+                    if fused:
+                        raise
+        _vq_routes["chain"] += 1
+        y, sc, _, idx = _vq_chain(xc.reshape(-1, S), c, _vq_norm_tensor(c, norm), True, out_dtype)
+        return pick(y.reshape(xc.shape), sc, idx.to(torch.uint8).reshape(ishape) if return_index else None)
+
+    if x.requires_grad and torch.is_grad_enabled():
+        return _DynamicSTE.apply(x, run)
+    with torch.no_grad():
+        return run(x.detach())
+
+
+def vq_accumulate(x, codebook, granularity: str = "per_group", group_size: Optional[int] = 64, norm: Optional[float] = None, acc=None,
+                  accumulate: bool = False, fused: Optional[bool] = None, per_group: Optional[int] = None):
+    """The weighted k-means statistics of x under a [K, d] table (DESIGN.md §8 "Vector codebook casts"), float64 [K, d + 2] on the
+    device: with scale s, quotients u and index idx formed exactly as vq_qdq forms them, over the vectors whose d quotients are all finite,
+        A[idx, j] += w u_j;  A[idx, d] += w;  A[idx, d + 1] += 1,   w = (double)s * (double)s
+    -- the true-MSE form: a vector's error is s^2 |u - c|^2, so the best row of a cell is A[k, :d] / A[k, d].  accumulate=True adds into
+    `acc` (several tensors or batches under one table), else `acc` (or a fresh tensor) is overwritten.  ONE pass over x plus a fold launch
+    (dmxq_vq_accumulate: no floating-point atomics, a fixed order, the same input gives the same bits) where vq_qdq's kernel applies;
+    otherwise the chain's (s, u, idx) and torch index_add_.  fused: as vq_qdq.  Nothing is read back to the host."""
+    granularity, group_size = _codebook_per_group(granularity, group_size, per_group, "vq_accumulate")
+    table, K, d, granularity, group_size, norm = vq_check(codebook, None, granularity, group_size, norm, what="vq_accumulate")
+    S = _vq_segment(x, d, granularity, group_size, "vq_accumulate")
+    if acc is not None and (acc.dtype != torch.float64 or tuple(acc.shape) != (K, d + 2) or not acc.is_contiguous()):
+        raise ValueError(f"vq_accumulate: acc must be a contiguous float64 [{K}, {d + 2}] tensor on x's device")
+    if accumulate and acc is None:
+        raise ValueError("vq_accumulate: accumulate=True needs acc")
+    require_gpu(x, "vq_accumulate")
+    if acc is not None and acc.device != x.device:
+        raise ValueError(f"vq_accumulate: acc must be a contiguous float64 [{K}, {d + 2}] tensor on x's device")
+    mode = _DYNF_GROUP if granularity == "per_group" else _DYNF_ROWS
+    with torch.no_grad():
+        xd = x.detach()
+        xc = xd if xd.is_contiguous() else xd.contiguous()
+        if acc is None:
+            acc = torch.zeros(K, d + 2, dtype=torch.float64, device=xc.device)
+        elif not accumulate and xc.numel() == 0:
+            acc.zero_()
+        if xc.numel() == 0:
+            return acc
+        c = _vq_tensor(table, xc.device)
+        if fused is not False:
+            cls = _vq_kernel_class(xc, S, d, K, mode)
+            if cls is None and fused:
+                raise NotImplementedError(f"vq_accumulate: no fused kernel for {granularity} segments of {S} {xc.dtype} elements with a "
+                                          f"[{K}, {d}] table (base address {xc.data_ptr() % 16} mod 16)")
+            if cls is not None and fused is None and cls in VQ_CHAIN_BY_DEFAULT:
+                cls = None
+            if cls is not None:
+                try:
+                    _ops.vq_accumulate(xc, mode, S, c, 0.0 if norm is None else norm, acc, bool(accumulate))
+                    _vq_accumulate_routes["fused"] += 1
+                    return acc
+                except NotImplementedError:   # (DMXQ_ERR_UNSUPPORTED, nothing launched)
+                    if fused:
+                        raise
+        _vq_accumulate_routes["chain"] += 1
+        _, sc, u, idx = _vq_chain(xc.reshape(-1, S), c, _vq_norm_tensor(c, norm), False)
+        uv = u.reshape(-1, d)
+        fin = torch.isfinite(uv).all(dim=1, keepdim=True)
+        w = (sc.double() * sc.double())[:, None].expand(-1, S // d).reshape(-1, 1)
+        zero = torch.zeros((), dtype=torch.float64, device=xc.device)
+        terms = torch.cat([torch.where(fin, w * uv.double(), zero), torch.where(fin, w, zero), fin.double()], dim=1)
+        # index_add_ adds with atomics: onto K rows alone every vector meets every other one, so the rows are kept in R copies, vector i
+        # adding to copy i mod R, and the copies are summed (codebook_accumulate's form; R shrinks with K to bound the copies)
+        n = uv.shape[0]
+        R = max(1, min(_CODEBOOK_ACC_REPLICAS, 65536 // K, n))
+        rows = idx.reshape(-1) + K * (torch.arange(n, device=xc.device) % R)
+        A = torch.zeros(R * K, d + 2, dtype=torch.float64, device=xc.device).index_add_(0, rows, terms).reshape(R, K, d + 2).sum(dim=0)
+        if accumulate:
+            acc += A
+        else:
+            acc.copy_(A)
+        return acc
+
+
+def _vq_update(c, A):
+    """the k-means update of the table from the statistics: c_k <- float(A[k, :d] / A[k, d]) where A[k, d + 1] > 0, else c_k stays"""
+    d = c.shape[1]
+    return torch.where(A[:, d + 1:d + 2] > 0, (A[:, :d] / A[:, d:d + 1]).float(), c)
+
+
+def _vq_sample_init(x, K, d, granularity, group_size, norm):
+    """the deterministic sample init: row i = the quotient vector number floor((2 i + 1) n / (2 K)) of x (u under `norm`), n vectors in all"""
+    S = _vq_segment(x, d, granularity, group_size, "vq_fit")
+    xd = x.detach()
+    xc = xd if xd.is_contiguous() else xd.contiguous()
+    x2 = xc.reshape(-1, S)
+    norm_t = torch.full((1,), norm, dtype=torch.float32, device=xc.device)
+
+    def quotients(part):
+        mn, mx = _ops.group_minmax(part, 0, 1)
+        return _ops.scale_channels(part, _scale_from_amax(torch.maximum(mn.abs(), mx.abs()), norm_t, False), 0, True, torch.float32)
+
+    if x2.shape[0] <= DYNAMIC_CHAIN_MAX_SEGMENTS:
+        u = quotients(x2)
+    else:
+        u = torch.cat([quotients(x2[i:i + DYNAMIC_CHAIN_PIECE]) for i in range(0, x2.shape[0], DYNAMIC_CHAIN_PIECE)])
+    uv = u.reshape(-1, d)
+    n = uv.shape[0]
+    pick = torch.tensor([(2 * i + 1) * n // (2 * K) for i in range(K)], dtype=torch.int64).to(xc.device)
+    return uv[pick].contiguous()
+
+
+def vq_fit(x, K: Optional[int] = None, dim: Optional[int] = None, codebook=None, granularity: str = "per_group", group_size: Optional[int] = 64,
+           norm: Optional[float] = None, iters: int = 8, return_history: bool = False, fused: Optional[bool] = None,
+           per_group: Optional[int] = None):
+    """Fits a [K, d] table to a tensor (or a list of tensors sharing it) by weighted k-means iterations on the device (DESIGN.md §8
+    "Vector codebook casts") -> (table float32 [K, d] on the device, norm) or (table, norm, history).  Every iteration: A = vq_accumulate
+    over the tensors, then c_k <- float(A[k, :d] / A[k, d]) where A[k, d + 1] > 0 (an empty row keeps its value) -- the minimiser of the
+    true squared error sum s^2 |u - c|^2 over every cell.  The update is torch on the [K, d] table on the device: no host synchronisation
+    inside the loop, an iteration is capturable.  The start: `codebook` when one is given (K, dim: None or its shape); otherwise the
+    deterministic sample init -- with n quotient vectors in the FIRST tensor, row i is vector number floor((2 i + 1) n / (2 K)) of it, u
+    under the fit's norm.  `norm` stays FIXED across the iterations and is returned -- pass it when casting with the fitted table: the
+    given one; else 1.0 for the sample init; else resolved ONCE from the given table, max |c_kj| (the one read of a device table, before
+    the loop).  return_history: the relative L2 error sqrt(sum_sq_err / sum_sq_ref) (ops.error_stats rows) before every iteration and
+    after the last, float64 [iters + 1] on the device."""
+    xs = list(x) if isinstance(x, (list, tuple)) else [x]
+    if not xs:
+        raise ValueError("vq_fit: no tensor to fit the table to")
+    if isinstance(iters, bool) or not isinstance(iters, int) or iters < 0:
+        raise ValueError(f"vq_fit: iters must be a non-negative integer, got {iters!r}")
+    granularity, group_size = _codebook_per_group(granularity, group_size, per_group, "vq_fit")
+    if codebook is None:
+        if isinstance(K, bool) or not isinstance(K, int) or not 2 <= K <= 256:
+            raise ValueError(f"vq_fit: without a codebook K must be an integer from 2 to 256, got {K!r}")
+        if isinstance(dim, bool) or not isinstance(dim, int) or dim not in VQ_DIMS:
+            raise ValueError(f"vq_fit: without a codebook dim must be one of {VQ_DIMS}, got {dim!r}")
+        # (the remaining arguments are checked against a stand-in table of the same shape)
+        _, _, d, granularity, group_size, norm = vq_check([[0.0] * dim] * K, dim, granularity, group_size, norm, what="vq_fit")
+        table = None
+        norm = 1.0 if norm is None else norm
+    else:
+        table, Kc, d, granularity, group_size, norm = vq_check(codebook, dim, granularity, group_size, norm, what="vq_fit")
+        if K is not None and K != Kc:
+            raise ValueError(f"vq_fit: K={K!r} beside a codebook of {Kc} rows")
+        K = Kc
+    for t in xs:
+        _vq_segment(t, d, granularity, group_size, "vq_fit")
+        require_gpu(t, "vq_fit")
+    if xs[0].numel() // d < 1 and table is None:
+        raise ValueError("vq_fit: the sample init needs a non-empty first tensor")
+    if norm is None:
+        norm = float(table.detach().abs().max().float()) if isinstance(table, torch.Tensor) else max(abs(v) for r in table for v in r)
+        norm = float(torch.tensor(norm, dtype=torch.float32))
+        if not (0.0 < norm < math.inf):
+            raise ValueError(f"vq_fit: the initial table gives norm {norm!r}; pass a positive finite norm")
+    with torch.no_grad():
+        c = _vq_tensor(table, xs[0].device).clone() if table is not None else _vq_sample_init(xs[0], K, d, granularity, group_size, norm)
+
+        def rel_error():
+            row = None
+            for t in xs:
+                y = vq_qdq(t.detach(), c, granularity, group_size, norm, fused=fused)
+                row = error_stats(t.detach(), y, out=row, accumulate=row is not None)
+            return torch.sqrt(row[0] / row[1])
+
+        history = []
+        for _ in range(iters):
+            if return_history:
+                history.append(rel_error())
+            A = torch.zeros(K, d + 2, dtype=torch.float64, device=c.device)
+            for t in xs:
+                vq_accumulate(t, c, granularity, group_size, norm, acc=A, accumulate=True, fused=fused)
+            c = _vq_update(c, A)
         if return_history:
             history.append(rel_error())
             return c, norm, torch.stack(history)

@@ -107,6 +107,10 @@ SIGNATURES = {
     "dmxq_outlier_fixed_qdq": [_vp, _vp, _i32, _i32, _i64, _i64, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp],
     "dmxq_awq_clip_class": [_i32, _i64, _i64],
     "dmxq_awq_clip": [_vp, _i32, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp],
+    "dmxq_vq_class": [_i32, _i32, _i64, _i32, _i32],
+    "dmxq_vq_qdq": [_vp, _vp, _i32, _i32, _i32, _i64, _i64, _vp, _i32, _i32, _f32, _vp, _vp, _vp],
+    "dmxq_vq_workspace_bytes": [_i32, _i32, _i64, _i64, _i32, _i32],
+    "dmxq_vq_accumulate": [_vp, _i32, _i32, _i64, _i64, _vp, _i32, _i32, _f32, _vp, _i32, _vp, _vp],
     "dmxq_adaround_class": [_i32, _i64],
     "dmxq_adaround_scratch_bytes": [_i64],
     "dmxq_adaround_forward": [_vp, _vp, _vp, _i32, _i32, _i64, _i64, _i32, _i32, _vp, _vp, _i32, _vp],
@@ -190,6 +194,7 @@ def lib():
         L.dmxq_lsq_scratch_bytes.restype = ctypes.c_int64
         L.dmxq_codebook_workspace_bytes.restype = ctypes.c_int64
         L.dmxq_adaround_scratch_bytes.restype = ctypes.c_int64
+        L.dmxq_vq_workspace_bytes.restype = ctypes.c_int64
         L.dmxq_status_string.argtypes = [ctypes.c_int]
         L.dmxq_status_string.restype = ctypes.c_char_p
         L.dmxq_abi_version.restype = ctypes.c_int

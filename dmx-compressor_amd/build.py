@@ -15,7 +15,7 @@ LIB = os.path.join(HERE, "lib", "libdmxq.so")
 TORCH_LIB = os.path.join(HERE, "lib", "dmxq_torch.so")
 # "file.hip" or "file.hip#N": the file compiled with -DDMXQ_EW_PART=N into file_pN.o (elementwise.hip: three objects, approx.hip: two, in parallel);
 # the slowest compilations first (gptq.hip: 18 unrolled kernels; gptq_dynamic.hip: 5 more)
-SOURCES = ["gptq.hip", "gptq_dynamic.hip", "hist_observer.hip", "error_stats.hip", "bfp.hip#1", "approx.hip#3", "approx.hip#5", "approx.hip#1", "approx.hip#2", "approx.hip#4", "elementwise.hip#2", "elementwise.hip#1", "elementwise.hip#3", "bfp_cols.hip#1", "bfp_cols.hip#2", "bfp_cols.hip#3", "bfp.hip#2", "bfp.hip#3", "bfp_urows.hip", "bfp_smallinner.hip", "bfp_slab.hip", "blockfmt.hip", "bfp_pack.hip", "hypernet.hip", "hypernet_multi.hip", "nm_mask.hip", "topk.hip", "reduce.hip", "unary.hip", "act_cast.hip", "lut16.hip", "fixed_multi.hip", "rope.hip", "hadamard.hip", "dynamic_quant.hip", "dynamic_float.hip", "wanda.hip", "awq.hip", "block_scaled_float.hip", "lsq.hip", "codebook.hip", "hqq.hip", "outlier_quant.hip", "awq_clip.hip", "adaround.hip"]
+SOURCES = ["vq.hip", "gptq.hip", "gptq_dynamic.hip", "hist_observer.hip", "error_stats.hip", "bfp.hip#1", "approx.hip#3", "approx.hip#5", "approx.hip#1", "approx.hip#2", "approx.hip#4", "elementwise.hip#2", "elementwise.hip#1", "elementwise.hip#3", "bfp_cols.hip#1", "bfp_cols.hip#2", "bfp_cols.hip#3", "bfp.hip#2", "bfp.hip#3", "bfp_urows.hip", "bfp_smallinner.hip", "bfp_slab.hip", "blockfmt.hip", "bfp_pack.hip", "hypernet.hip", "hypernet_multi.hip", "nm_mask.hip", "topk.hip", "reduce.hip", "unary.hip", "act_cast.hip", "lut16.hip", "fixed_multi.hip", "rope.hip", "hadamard.hip", "dynamic_quant.hip", "dynamic_float.hip", "wanda.hip", "awq.hip", "block_scaled_float.hip", "lsq.hip", "codebook.hip", "hqq.hip", "outlier_quant.hip", "awq_clip.hip", "adaround.hip"]
 # bit-exact fp32: no fast-math, no fma contraction; fp32 denormals stay on (gfx950 default).
 # --offload-compress (round 5): the gfx950 code objects are stored zstd-compressed inside the fat binary and unpacked by the HIP runtime at
 # load: libdmxq.so 88 MB -> 17 MB (what a gpurun snapshot pushes, what a wheel would ship), load time and kernels unchanged
@@ -64,7 +64,10 @@ NO_SCRATCH = {"lut16.hip": ["lut16_apply_kernel"], "fixed_multi.hip": ["stream_m
               # the loop over the candidates (csrc/awq_clip.hip)
               "awq_clip.hip": ["awq_clip_kernel"],
               # AdaRound: a lane's units in flight and its fp64 accumulator stay in registers through expf and powf (csrc/adaround.hip)
-              "adaround.hip": ["adaround_forward_kernel", "adaround_backward_kernel"]}
+              "adaround.hip": ["adaround_forward_kernel", "adaround_backward_kernel"],
+              # the vector codebook cast and its k-means statistics: a lane's raw vectors, a batch's quotients and running (best, idx) and
+              # the owner thread's sums stay in registers; the table and the staged batch live in LDS (csrc/vq.hip)
+              "vq.hip": ["vq_group_kernel", "vq_rows_kernel", "vq_acc_group_kernel", "vq_acc_rows_kernel"]}
 
 
 def _check_no_scratch(src, remarks_file):
@@ -84,7 +87,7 @@ def _check_no_scratch(src, remarks_file):
                                    f"wrong; the multi-tensor kernels: every wave of a launch pays for a spilling body; "
                                    f"the error statistics: the format table must stay in registers; the Hadamard rotation: a lane's vector "
                                    f"must stay in registers; the dynamic cast: a segment's vectors must stay in registers; GPTQ with dynamic scales: a "
-                                   f"microblock must stay in registers; Wanda: the accumulators and a unit's scores must stay in registers; AWQ: a lane's slots must stay in registers; the block-scaled float cast: a lane's vectors must stay in registers; the learned step size backward: a lane's vectors and accumulators must stay in registers; the codebook cast: a lane's vectors, the table and the accumulators must stay in registers; HQQ: a lane's vector must stay in registers through the iterations; the outlier-aware cast: a lane's vector and its marks must stay in registers through the selection rounds; the AWQ clip search: a lane's weights, errors and sums must stay in registers through the candidates; AdaRound: a lane's units must stay in registers through expf and powf) -- build.py NO_SCRATCH")
+                                   f"microblock must stay in registers; Wanda: the accumulators and a unit's scores must stay in registers; AWQ: a lane's slots must stay in registers; the block-scaled float cast: a lane's vectors must stay in registers; the learned step size backward: a lane's vectors and accumulators must stay in registers; the codebook cast: a lane's vectors, the table and the accumulators must stay in registers; HQQ: a lane's vector must stay in registers through the iterations; the outlier-aware cast: a lane's vector and its marks must stay in registers through the selection rounds; the AWQ clip search: a lane's weights, errors and sums must stay in registers through the candidates; AdaRound: a lane's units must stay in registers through expf and powf; the vector codebook cast: a lane's vectors and a batch's running choices must stay in registers) -- build.py NO_SCRATCH")
     if not seen:
         raise RuntimeError(f"{src}: no kernel matching {wanted} in the compiler's resource remarks: the NO_SCRATCH check did not run")
 

@@ -22,6 +22,9 @@ __all__ = ["CastToFormat", "CastTo", "CastToDict"]
 _LEARNED_SCALE_MIN = float(torch.finfo(torch.float32).eps)   # learned_scale is clamped from below to this before every forward
 _CODEBOOK_HADAMARD = ("CastTo: a codebook (set_codebook) under a 'hadamard' pre_transform is not supported: the fused rotated cast runs the "
                       "format's arithmetic, not a table's")
+_VQ_HADAMARD = ("CastTo: a vector codebook (set_vq) under a 'hadamard' pre_transform is not supported: the fused rotated cast runs the "
+                "format's own arithmetic with the stored scales; drop one of the two")
+_VQ_EXCLUSIVE = ("this cast has a vector codebook (set_vq), which replaces the format's arithmetic and its scales: set_vq(None) first")
 _CODEBOOK_EXCLUSIVE = ("this cast has a codebook (set_codebook), which replaces the format's arithmetic and its scales: "
                        "set_codebook(None) first")
 _LEARNABLE_HADAMARD = ("CastTo: learned scales (set_learnable) under a 'hadamard' pre_transform are not supported: the fused rotated cast "
@@ -207,6 +210,9 @@ class CastTo(HostFlags, torch.nn.Module):
     #: None, or {"granularity", "group_size", "norm", "name"}: the cast runs ops.codebook_qdq with the float32 buffer `codebook` in place of
     #: the format's arithmetic (set_codebook; DESIGN.md §8 "Codebook casts").  The buffer exists only while this is set.
     _codebook = None
+    #: None, or {"granularity", "group_size", "norm", "grid"}: the cast runs ops.vq_qdq with the float32 buffer `vq_codebook` [K, d] in place
+    #: of the format's arithmetic (set_vq; DESIGN.md §8 "Vector codebook casts").  The buffers exist only while this is set.
+    _vq = None
 
     def __init__(self, format="SAME", observer=DummyObserver, group_size=None, block_dim=-1,
                  qscheme=torch.per_tensor_affine, ch_axis=-1, **observer_kwargs):
@@ -284,6 +290,9 @@ class CastTo(HostFlags, torch.nn.Module):
             if self._codebook is not None:
                 self.pre_transform.pop("hadamard")
                 raise ValueError(_CODEBOOK_HADAMARD)
+            if self._vq is not None:
+                self.pre_transform.pop("hadamard")
+                raise ValueError(_VQ_HADAMARD)
 
     def set_dynamic(self, granularity=None, group_size=None):
         """Dynamic scales (not in the reference): with fake-quant on and the observer off, an integer format is cast with a
@@ -300,6 +309,8 @@ class CastTo(HostFlags, torch.nn.Module):
         dyn = _parse_dynamic(granularity, group_size)
         if dyn is not None and self._codebook is not None:
             raise ValueError("CastTo.set_dynamic: " + _CODEBOOK_EXCLUSIVE)
+        if dyn is not None and self._vq is not None:
+            raise ValueError("CastTo.set_dynamic: " + _VQ_EXCLUSIVE)
         if dyn is not None and self._learnable is not None:
             raise ValueError("CastTo.set_dynamic: this cast has learned scales (set_learnable), an exclusive source: set_learnable(None) first")
         if dyn is not None:
@@ -366,6 +377,8 @@ class CastTo(HostFlags, torch.nn.Module):
             raise ValueError(_LEARNABLE_HADAMARD)
         if self._codebook is not None:
             raise ValueError("CastTo.set_learnable: " + _CODEBOOK_EXCLUSIVE)
+        if self._vq is not None:
+            raise ValueError("CastTo.set_learnable: " + _VQ_EXCLUSIVE)
         if self._dynamic is not None or self._scaling is not None:
             raise ValueError("CastTo.set_learnable: this cast derives its scales from every tensor (set_dynamic / set_scaling); a learned "
                              "scale is a third, exclusive source: switch that off first")
@@ -448,6 +461,13 @@ class CastTo(HostFlags, torch.nn.Module):
             if prefix + "codebook_norm" in state_dict:
                 v = float(state_dict[prefix + "codebook_norm"].detach().float().cpu().reshape(-1)[0])
                 cb["norm"] = v if v > 0.0 else None
+        vq = self._vq
+        if vq is not None and prefix + "vq_codebook" in state_dict:   # (the same for a vector codebook: a loaded table is no longer the grid)
+            if vq["grid"] is not None and not torch.equal(state_dict[prefix + "vq_codebook"].detach().float().cpu(), ops.vq_grid(*vq["grid"])):
+                vq["grid"] = None
+            if prefix + "vq_norm" in state_dict:
+                v = float(state_dict[prefix + "vq_norm"].detach().float().cpu().reshape(-1)[0])
+                vq["norm"] = v if v > 0.0 else None
         if self._learnable is not None and prefix + "learned_scale" in state_dict:
             self._learnable_pending = False   # (the loaded values are the initial values)
         super()._load_from_state_dict(state_dict, prefix, *args, **kwargs)
@@ -470,6 +490,8 @@ class CastTo(HostFlags, torch.nn.Module):
         sc = _parse_scaling(granularity, group_size, pow2_scale)
         if sc is not None and self._codebook is not None:
             raise ValueError("CastTo.set_scaling: " + _CODEBOOK_EXCLUSIVE)
+        if sc is not None and self._vq is not None:
+            raise ValueError("CastTo.set_scaling: " + _VQ_EXCLUSIVE)
         if sc is not None and self._learnable is not None:
             raise ValueError("CastTo.set_scaling: this cast has learned scales (set_learnable), an exclusive source: set_learnable(None) first")
         if block is not None:
@@ -539,6 +561,8 @@ class CastTo(HostFlags, torch.nn.Module):
             if g != "per_group" and gs is not None:
                 raise ValueError(f"set_codebook: group_size goes with granularity 'per_group', got {setting!r}")
         levels, g, gs, norm = ops.codebook_check(setting["codebook"], g, gs, setting.get("norm"), what="CastTo.set_codebook")
+        if self._vq is not None:
+            raise ValueError("CastTo.set_codebook: " + _VQ_EXCLUSIVE)
         if self._dynamic is not None or self._scaling is not None or self._learnable is not None:
             raise ValueError("CastTo.set_codebook: this cast already takes its scales from set_dynamic / set_scaling / set_learnable; a codebook "
                              "replaces the format's arithmetic and is exclusive with them: switch that off first")
@@ -587,6 +611,90 @@ class CastTo(HostFlags, torch.nn.Module):
         cb = self._codebook
         c = self.codebook if self.codebook.device == x.device else self.codebook.to(x.device)
         return ops.codebook_qdq(x, c, cb["granularity"], cb["group_size"], cb["norm"], out_dtype=out_dtype)
+
+    # ------------------------------------------------------------------ vector codebook casts
+    def set_vq(self, setting=None):
+        """Vector codebook cast (not in the reference; DESIGN.md §8 "Vector codebook casts"): with fake-quant on and the observer off, every
+        d consecutive elements of the last dimension are replaced together by one row of a [K, d] table under a per-segment
+        absolute-maximum scale (ops.vq_qdq) IN PLACE of the format's arithmetic; a SAME cast stays the identity.  setting: None, or a dict
+        {"codebook": a list of rows | a [K, d] tensor | {"grid": levels, "dim": d} (ops.vq_grid), "per_group": g | "granularity":
+        "per_token" / "per_tensor" / "per_group" (with "group_size"), "norm": None or a positive number}.  The table is registered HERE as
+        the float32 buffer `vq_codebook` [K, d], beside `vq_norm` [1] (the pinned norm, 0 for none), so that a fitted table (fit_vq) is
+        saved and loaded with the module -- into a cast that was given a table of the same shape; None removes both.  Exclusive with
+        set_codebook, set_dynamic, set_scaling, set_learnable and a "hadamard" pre_transform (ValueError in either order).  ValueError for
+        everything ops.vq_check refuses."""
+        if setting is None:
+            for n in ("vq_codebook", "vq_norm"):
+                if n in self._buffers:
+                    del self._buffers[n]
+            self._vq = None
+            return
+        if not isinstance(setting, dict) or "codebook" not in setting or not set(setting) <= {"codebook", "per_group", "granularity", "group_size", "norm"}:
+            raise ValueError(f"set_vq: expected None or a dict with 'codebook' and optionally 'per_group' / 'granularity' / 'group_size' / "
+                             f"'norm', got {setting!r}")
+        if "per_group" in setting:
+            if setting.get("granularity", "per_group") != "per_group" or "group_size" in setting:
+                raise ValueError(f"set_vq: 'per_group' names the granularity and its group size by itself, got {setting!r}")
+            g, gs = "per_group", setting["per_group"]
+        else:
+            g, gs = setting.get("granularity", "per_group"), setting.get("group_size", 64 if setting.get("granularity", "per_group") == "per_group" else None)
+            if g != "per_group" and gs is not None:
+                raise ValueError(f"set_vq: group_size goes with granularity 'per_group', got {setting!r}")
+        table, K, d, g, gs, norm = ops.vq_check(setting["codebook"], None, g, gs, setting.get("norm"), what="CastTo.set_vq")
+        if self._codebook is not None:
+            raise ValueError("CastTo.set_vq: " + _CODEBOOK_EXCLUSIVE)
+        if self._dynamic is not None or self._scaling is not None or self._learnable is not None:
+            raise ValueError("CastTo.set_vq: this cast already takes its scales from set_dynamic / set_scaling / set_learnable; a vector "
+                             "codebook replaces the format's arithmetic and is exclusive with them: switch that off first")
+        if "hadamard" in self.pre_transform:
+            raise ValueError(_VQ_HADAMARD)
+        t = table.detach().to(torch.float32).clone() if isinstance(table, torch.Tensor) else torch.tensor(table, dtype=torch.float32)
+        for n in ("vq_codebook", "vq_norm"):
+            if n in self._buffers:
+                del self._buffers[n]
+        self.register_buffer("vq_codebook", t.to(t.device if t.is_cuda else self.scale.device))
+        # the pinned norm travels with the table (0: none pinned, the table's own largest magnitude); the cast itself reads the host copy
+        self.register_buffer("vq_norm", torch.tensor([0.0 if norm is None else norm], dtype=torch.float32, device=self.vq_codebook.device))
+        grid = setting["codebook"] if isinstance(setting["codebook"], dict) else None
+        self._vq = {"granularity": g, "group_size": gs, "norm": norm,
+                    "grid": (grid["grid"] if isinstance(grid["grid"], str) else tuple(grid["grid"]), grid["dim"]) if grid is not None else None}
+
+    @property
+    def vq_setting(self):
+        """None, or the setting in the spelling set_vq accepts: {"codebook": the grid it was set by, or the buffer's rows as a list of
+        lists, "per_group": g | "granularity": ..., and "norm" where one is pinned}.  A fitted table reads back as its rows."""
+        vq = self._vq
+        if vq is None:
+            return None
+        grid = vq["grid"]
+        out = {"codebook": {"grid": grid[0] if isinstance(grid[0], str) else list(grid[0]), "dim": grid[1]} if grid is not None
+               else self.vq_codebook.detach().cpu().tolist()}
+        out.update({"per_group": vq["group_size"]} if vq["granularity"] == "per_group" else {"granularity": vq["granularity"]})
+        if vq["norm"] is not None:
+            out["norm"] = vq["norm"]
+        return out
+
+    def fit_vq(self, x, iters: int = 8):
+        """replaces the table IN PLACE by ops.vq_fit's result for the tensor x (or list of tensors), started from the current table, and
+        pins the norm the fit used: the cast then reproduces the fitted error.  -> the buffer"""
+        if self._vq is None:
+            raise ValueError("CastTo.fit_vq: no vector codebook is set (set_vq first)")
+        vq = self._vq
+        first = x[0] if isinstance(x, (list, tuple)) else x
+        if self.vq_codebook.device != first.device:
+            self.vq_codebook = self.vq_codebook.to(first.device)
+            self.vq_norm = self.vq_norm.to(first.device)
+        c, norm = ops.vq_fit(x, codebook=self.vq_codebook, granularity=vq["granularity"], group_size=vq["group_size"], norm=vq["norm"], iters=iters)
+        with torch.no_grad():
+            self.vq_codebook.copy_(c)
+            self.vq_norm.fill_(norm)
+        vq["norm"], vq["grid"] = norm, None
+        return self.vq_codebook
+
+    def _vq_cast(self, x, out_dtype):
+        vq = self._vq
+        c = self.vq_codebook if self.vq_codebook.device == x.device else self.vq_codebook.to(x.device)
+        return ops.vq_qdq(x, c, vq["granularity"], vq["group_size"], vq["norm"], out_dtype=out_dtype)
 
     def enable_calibration(self, state: bool = True, observer_cls: ObserverBase = HistogramObserver,
                            qscheme_to_overload: Optional[torch.qscheme] = None, group_size: int = None,
@@ -670,6 +778,8 @@ class CastTo(HostFlags, torch.nn.Module):
         ste = torch.is_grad_enabled() and x.requires_grad
         if self._codebook is not None and not self.__dict__["_h_observer_enabled"]:
             return self._codebook_cast(x, out_dtype)  # (a straight-through estimator under autograd by itself)
+        if self._vq is not None and not self.__dict__["_h_observer_enabled"]:
+            return self._vq_cast(x, out_dtype)        # (the same)
         if self._dynamic is not None and isinstance(fmt, FixedPoint) and not self.__dict__["_h_observer_enabled"]:
             return self._dynamic_cast(x, out_dtype)   # (a straight-through estimator under autograd by itself)
         if self._scaling is not None and isinstance(fmt, FloatingPoint) and not self.__dict__["_h_observer_enabled"]:
@@ -797,6 +907,7 @@ class CastTo(HostFlags, torch.nn.Module):
             raise NotImplementedError("CastTo.measure_error: a cast with a pre_transform other than hadamard (shaping / shortcut / pre-format)")
         fmt, x = self.format, x.detach()
         dyn_cast = self._codebook_cast if self._codebook is not None and isinstance(fmt, Format) and not isinstance(fmt, Same) else \
+            self._vq_cast if self._vq is not None and isinstance(fmt, Format) and not isinstance(fmt, Same) else \
             self._dynamic_cast if self._dynamic is not None and isinstance(fmt, FixedPoint) else \
             self._scaled_cast if self._scaling is not None and isinstance(fmt, FloatingPoint) else \
             self._learnable_cast if self._learnable is not None and isinstance(fmt, FixedPoint) else None
@@ -843,7 +954,18 @@ class CastTo(HostFlags, torch.nn.Module):
                + (f", dynamic = {self.dynamic!r}" if self._dynamic is not None else "") \
                + (f", scaling = {self.scaling!r}" if self._scaling is not None else "") \
                + (f", learnable = {self.learnable!r}" if self._learnable is not None else "") \
-               + (f", codebook = {self._codebook_repr()}" if self._codebook is not None else "")
+               + (f", codebook = {self._codebook_repr()}" if self._codebook is not None else "") \
+               + (f", vq = {self._vq_repr()}" if self._vq is not None else "")
+
+    def _vq_repr(self):
+        vq = self._vq   # (no device read: a table that is no grid shows its shape)
+        grid = vq["grid"]
+        out = {"codebook": {"grid": grid[0] if isinstance(grid[0], str) else list(grid[0]), "dim": grid[1]} if grid is not None
+               else f"<{self.vq_codebook.shape[0]} rows of {self.vq_codebook.shape[1]}>"}
+        out.update({"per_group": vq["group_size"]} if vq["granularity"] == "per_group" else {"granularity": vq["granularity"]})
+        if vq["norm"] is not None:
+            out["norm"] = vq["norm"]
+        return repr(out)
 
     def _codebook_repr(self):
         cb = self._codebook   # (no device read: a table without a name shows its size)
@@ -949,6 +1071,25 @@ class CastToDict(torch.nn.ModuleDict):
             if k not in self.keys():
                 raise RuntimeError(f"No CastTo with key {k}!")
             self[k].set_codebook(t)
+
+    def set_vq(self, vq):
+        """one setting (None, or a dict with "codebook": rows, a [K, d] tensor or {"grid": ..., "dim": d}) for every cast, or a list / dict
+        of settings over the casts the way set_codebook takes them"""
+        one = isinstance(vq, dict) and "codebook" in vq and not set(vq) & set(self.keys())
+        if vq is None or one:
+            for c in self.values():
+                c.set_vq(vq)
+            return
+        if isinstance(vq, (tuple, list)):
+            if len(vq) != len(self):
+                raise ValueError(f"set_vq: {len(vq)} settings for {len(self)} casts")
+            vq = dict(zip(self.keys(), vq))
+        elif not isinstance(vq, dict):
+            raise ValueError(f"set_vq: expected a setting, or a list or dict of settings, got {vq!r}")
+        for k, t in vq.items():
+            if k not in self.keys():
+                raise RuntimeError(f"No CastTo with key {k}!")
+            self[k].set_vq(t)
 
     def set_format(self, format):
         for k, f in self.pack_to_dict(format).items():

@@ -1155,6 +1155,58 @@ void codebook_accumulate(const Tensor& x, int64_t mode, int64_t segment, const T
 }
 void codebook_accumulate_meta(const Tensor&, int64_t, int64_t, const Tensor&, double, Tensor, bool) {}
 
+// ------------------------------------------------------------------------------------------------ vector codebook casts
+// x: contiguous; mode: DMXQ_DYNF_GROUP / DMXQ_DYNF_ROWS; table: contiguous float32 [K, d] on x's GPU; norm <= 0: the table's own maximum
+// -> (out, scale float32 [n_segments], index uint8 x.shape[:-1] + (L / d,); the last two empty unless wanted).
+// DMXQ_ERR_UNSUPPORTED (NotImplementedError, nothing launched): the front end runs its chain of torch operations.
+void vq_args(const Tensor& xc, int64_t segment, const Tensor& table, const char* what) {
+  TORCH_CHECK(segment >= 1 && xc.numel() % segment == 0, what, ": the segment must divide the number of elements");
+  TORCH_CHECK(table.is_cuda() && table.device() == xc.device() && table.scalar_type() == at::kFloat && table.is_contiguous() &&
+              table.dim() == 2 && table.size(1) >= 1, what, ": the table must be a contiguous float32 [K, d] tensor on x's GPU");
+  TORCH_CHECK(xc.dim() >= 1 && xc.size(-1) % table.size(1) == 0, what, ": the last dimension must be a multiple of the table's d");
+}
+Tensor vq_index_like(const Tensor& x, int64_t d, bool want) {
+  if (!want) return at::empty({0}, x.options().dtype(at::kByte));
+  std::vector<int64_t> shape = x.sizes().vec();
+  shape.back() /= d;
+  return at::empty(shape, x.options().dtype(at::kByte));
+}
+std::tuple<Tensor, Tensor, Tensor> vq_qdq(const Tensor& x, int64_t mode, int64_t segment, const Tensor& table, double norm, bool want_scale,
+                                          bool want_index, OptDtype out_dtype) {
+  const Tensor xc = prep(x, "vq_qdq");
+  vq_args(xc, segment, table, "vq_qdq");
+  const int64_t n = xc.numel() / segment;
+  Tensor out = empty_like_shape(xc, out_dtype);
+  Tensor sc = at::empty({want_scale ? n : 0}, xc.options().dtype(at::kFloat));
+  Tensor idx = vq_index_like(xc, table.size(1), want_index);
+  Launch l(xc);
+  check(dmxq_vq_qdq(xc.data_ptr(), out.data_ptr(), dt_code(xc.scalar_type()), dt_code(out.scalar_type()), (int)mode, n, segment,
+                    (const float*)table.data_ptr(), (int)table.size(1), (int)table.size(0), (float)norm,
+                    want_scale ? (float*)sc.data_ptr() : nullptr, want_index ? (uint8_t*)idx.data_ptr() : nullptr, l.stream), "dmxq_vq_qdq");
+  return std::make_tuple(out, sc, idx);
+}
+std::tuple<Tensor, Tensor, Tensor> vq_qdq_meta(const Tensor& x, int64_t, int64_t segment, const Tensor& table, double, bool want_scale,
+                                               bool want_index, OptDtype out_dtype) {
+  const int64_t n = (want_scale && segment >= 1) ? x.numel() / segment : 0;
+  return std::make_tuple(empty_like_shape(x, out_dtype), at::empty({n}, x.options().dtype(at::kFloat)),
+                         vq_index_like(x, table.size(1), want_index));
+}
+// acc (float64 [K, d + 2]) (+)= the k-means statistics of x under the table; the partial blocks' workspace is allocated here
+void vq_accumulate(const Tensor& x, int64_t mode, int64_t segment, const Tensor& table, double norm, Tensor acc, bool accumulate) {
+  const Tensor xc = prep(x, "vq_accumulate");
+  vq_args(xc, segment, table, "vq_accumulate");
+  TORCH_CHECK(acc.is_cuda() && acc.device() == xc.device() && acc.scalar_type() == at::kDouble && acc.is_contiguous() &&
+              acc.numel() == table.size(0) * (table.size(1) + 2), "vq_accumulate: acc must be a contiguous float64 [K, d + 2] tensor on x's GPU");
+  const int64_t n = xc.numel() / segment;
+  const int64_t wb = dmxq_vq_workspace_bytes(dt_code(xc.scalar_type()), (int)mode, n, segment, (int)table.size(1), (int)table.size(0));
+  Tensor ws = at::empty({wb / 8 + 1}, xc.options().dtype(at::kDouble));
+  Launch l(xc);
+  check(dmxq_vq_accumulate(xc.data_ptr(), dt_code(xc.scalar_type()), (int)mode, n, segment, (const float*)table.data_ptr(),
+                           (int)table.size(1), (int)table.size(0), (float)norm, (double*)acc.data_ptr(), accumulate ? 1 : 0, ws.data_ptr(),
+                           l.stream), "dmxq_vq_accumulate");
+}
+void vq_accumulate_meta(const Tensor&, int64_t, int64_t, const Tensor&, double, Tensor, bool) {}
+
 // ------------------------------------------------------------------------------------------------ HQQ
 // x: contiguous; segment: the group size -> (out, scale float32 [n_segments], zero float32 [n_segments], codes uint8 in x's shape; the
 // qparams empty unless want_qparams, the codes empty unless want_codes).
@@ -1483,6 +1535,8 @@ TORCH_LIBRARY(dmxq, m) {
   m.def("lsq_backward(Tensor x, Tensor g, Tensor scale, Tensor zero_point, int segment, int whole_rows, int precision, int rounding, int qmin, int qmax, float grad_factor, bool want_dz, bool want_dx) -> (Tensor, Tensor, Tensor)");
   m.def("codebook_qdq(Tensor x, int mode, int segment, Tensor levels, float norm, bool want_scale, bool want_index, ScalarType? out_dtype=None) -> (Tensor, Tensor, Tensor)");
   m.def("codebook_accumulate(Tensor x, int mode, int segment, Tensor levels, float norm, Tensor(a!) acc, bool accumulate) -> ()");
+  m.def("vq_qdq(Tensor x, int mode, int segment, Tensor table, float norm, bool want_scale, bool want_index, ScalarType? out_dtype=None) -> (Tensor, Tensor, Tensor)");
+  m.def("vq_accumulate(Tensor x, int mode, int segment, Tensor table, float norm, Tensor(a!) acc, bool accumulate) -> ()");
   m.def("hqq_qdq(Tensor x, int segment, int rounding, int qmin, int qmax, float lp_norm, float beta, float kappa, int iters, bool want_qparams, bool want_codes, ScalarType? out_dtype=None) -> (Tensor, Tensor, Tensor, Tensor)");
   m.def("outlier_fixed_qdq(Tensor x, int segment, int k, int precision, int fraction, bool clamp, bool symmetric, int rounding, int qmin, int qmax, bool symmetric_qscheme, int[] outlier_fmt, bool want_qparams, bool want_outliers, ScalarType? out_dtype=None) -> (Tensor, Tensor, Tensor, Tensor, Tensor)");
   m.def("adaround_forward(Tensor w, Tensor V, Tensor scale, Tensor zero_point, int segment, int qmin, int qmax, bool hard, ScalarType? out_dtype=None) -> Tensor");
@@ -1499,7 +1553,7 @@ TORCH_LIBRARY(dmxq, m) {
   X(m, error_stats); X(m, cast_error); X(m, hadamard_qdq); X(m, dynamic_fixed_qdq); X(m, gptq_block_dynamic); X(m, dynamic_float_qdq); \
   X(m, channel_sumsq); X(m, wanda_nm); X(m, channel_sumabs); X(m, awq_group_error); X(m, block_scaled_float_qdq); X(m, block_scaled_tensor_scale); \
   X(m, lsq_backward); X(m, codebook_qdq); X(m, codebook_accumulate); X(m, hqq_qdq); X(m, outlier_fixed_qdq); X(m, awq_clip); \
-  X(m, adaround_forward); X(m, adaround_backward)
+  X(m, adaround_forward); X(m, adaround_backward); X(m, vq_qdq); X(m, vq_accumulate)
 
 // "CUDA" is the dispatch key of HIP tensors in a ROCm build of PyTorch
 TORCH_LIBRARY_IMPL(dmxq, CUDA, m) {
@@ -1567,6 +1621,9 @@ PYBIND11_MODULE(dmxq_fast, m) {
   m.def("codebook_qdq", &codebook_qdq, py::arg("x"), py::arg("mode"), py::arg("segment"), py::arg("levels"), py::arg("norm"), py::arg("want_scale"),
         py::arg("want_index"), py::arg("out_dtype") = py::none());
   m.def("codebook_accumulate", &codebook_accumulate);
+  m.def("vq_qdq", &vq_qdq, py::arg("x"), py::arg("mode"), py::arg("segment"), py::arg("table"), py::arg("norm"), py::arg("want_scale"),
+        py::arg("want_index"), py::arg("out_dtype") = py::none());
+  m.def("vq_accumulate", &vq_accumulate);
   m.def("hqq_qdq", &hqq_qdq, py::arg("x"), py::arg("segment"), py::arg("rounding"), py::arg("qmin"), py::arg("qmax"), py::arg("lp_norm"), py::arg("beta"),
         py::arg("kappa"), py::arg("iters"), py::arg("want_qparams"), py::arg("want_codes"), py::arg("out_dtype") = py::none());
   m.def("outlier_fixed_qdq", &outlier_fixed_qdq, py::arg("x"), py::arg("segment"), py::arg("k"), py::arg("precision"), py::arg("fraction"), py::arg("clamp"),

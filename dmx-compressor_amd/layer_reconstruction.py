@@ -33,6 +33,15 @@ def refuse_scaled_weight_cast(module):
                                   "dynamic integer cast (weight_dynamic)")
 
 
+def refuse_vq_weight_cast(module, what):
+    """GPTQ, AWQ, the AWQ clip, Wanda, HQQ, AdaRound and folding on a module whose weight cast is a vector codebook cast (CastTo.set_vq):
+    NotImplementedError"""
+    wc = getattr(module, "weight_cast", None)
+    if wc is not None and wc._vq is not None:
+        raise NotImplementedError(f"{what} with a vector codebook weight cast (weight_vq = {wc._vq_repr()}) is not supported yet: these "
+                                  "procedures assume the format's own scalar grid; clear the setting (set_vq(None)) first")
+
+
 def refuse_codebook_weight_cast(module, what):
     """GPTQ, AWQ, Wanda and folding on a module whose weight cast is a codebook cast (CastTo.set_codebook): NotImplementedError"""
     wc = getattr(module, "weight_cast", None)
@@ -64,6 +73,7 @@ class OptimalBrainCompressor:
     def __init__(self, module):
         refuse_learnable_weight_cast(module, "GPTQ")
         refuse_codebook_weight_cast(module, "GPTQ")
+        refuse_vq_weight_cast(module, "GPTQ")
         refuse_outlier_weight_cast(module, "GPTQ")
         self.module = module
         self.example_counter = 0
@@ -165,7 +175,7 @@ class OptimalBrainCompressor:
         wc, st = m.weight_cast, m.weight_storage_cast
         if st is not None and not (isinstance(st.format, Same) and not st.pre_transform):
             return None
-        if wc.pre_transform or wc._codebook is not None or wc.dynamic is not None or wc._scaling is not None or wc._learnable is not None or not wc._flag("fake_quant_enabled") or wc._flag("observer_enabled"):
+        if wc.pre_transform or wc._codebook is not None or wc._vq is not None or wc.dynamic is not None or wc._scaling is not None or wc._learnable is not None or not wc._flag("fake_quant_enabled") or wc._flag("observer_enabled"):
             return None   # (a dynamic cast: its scale buffers are not what it casts with)
         per_row = False
         if isinstance(wc.format, FixedPoint):
@@ -468,6 +478,7 @@ class WandaCalibrator:
     def __init__(self, module, sumsq=None, n_tokens: int = 0):
         refuse_learnable_weight_cast(module, "Wanda")
         refuse_codebook_weight_cast(module, "Wanda")
+        refuse_vq_weight_cast(module, "Wanda")
         self.module = module
         self.sumsq = sumsq
         self.n_tokens = int(n_tokens)
@@ -549,6 +560,7 @@ class AWQCalibrator:
     def __init__(self, module, hyperparams, sumabs=None, gram=None, n_tokens: int = 0):
         refuse_learnable_weight_cast(module, "AWQ")
         refuse_codebook_weight_cast(module, "AWQ")
+        refuse_vq_weight_cast(module, "AWQ")
         refuse_outlier_weight_cast(module, "AWQ")   # (neither ops.awq_scaled_error nor its chain selects outliers)
         # the clip that follows the fuse: its refusals now, before any state is touched (SmoothQuant's own state is refuse_awq's matter)
         self.clip_plan = refuse_awq_clip(module, after_awq_scaling=True) if hyperparams.clip is not None else None
@@ -656,6 +668,7 @@ def refuse_awq_clip(module, after_awq_scaling: bool = False):
     wc, st = module.weight_cast, module.weight_storage_cast
     if wc is None:
         raise DmxqError("AWQ clipping needs a weight cast: the module has none")
+    refuse_vq_weight_cast(module, "AWQ clipping")
     for what, setting in (("an outlier-aware", wc._outliers), ("a codebook", wc._codebook), ("a learnable", wc._learnable), ("a scaled float", wc._scaling)):
         if setting is not None:
             raise DmxqError(f"AWQ clipping with {what} weight cast is not supported: the search reproduces the plain per-group dynamic "
@@ -755,6 +768,7 @@ def refuse_hqq(module):
     refuse_scaled_weight_cast_for(module, "HQQ")
     refuse_learnable_weight_cast(module, "HQQ")
     refuse_codebook_weight_cast(module, "HQQ")
+    refuse_vq_weight_cast(module, "HQQ")
     refuse_outlier_weight_cast(module, "HQQ")
     if wc.pre_transform:
         raise DmxqError(f"HQQ with a weight cast pre_transform {sorted(wc.pre_transform)} is not supported: the zero points would be solved "
@@ -810,6 +824,7 @@ def refuse_adaround(module):
     wc, st = module.weight_cast, module.weight_storage_cast
     if wc is None:
         raise DmxqError("AdaRound needs a weight cast: the module has none")
+    refuse_vq_weight_cast(module, "AdaRound")
     for what, setting in (("an outlier-aware", wc._outliers), ("a codebook", wc._codebook), ("a learnable", wc._learnable), ("a scaled float", wc._scaling)):
         if setting is not None:
             raise DmxqError(f"AdaRound with {what} weight cast is not supported: it rounds on the grid of a plain integer cast; clear the "

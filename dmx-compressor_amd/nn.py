@@ -357,6 +357,14 @@ class DmxModule(FastAttr, torch.nn.Module):
             self.output_casts.set_codebook(config["output_codebook"])
         if self.weight_cast is not None and "weight_codebook" in config:
             self.weight_cast.set_codebook(config["weight_codebook"])   # (per_token: per output channel of the [out, in] view)
+        # vector codebook casts (CastTo.set_vq): None, or a dict {"codebook": rows | tensor | {"grid": name, "dim": d}, "per_group": g |
+        # "granularity": ..., "norm": ...}
+        if "input_vq" in config:
+            self.input_casts.set_vq(config["input_vq"])
+        if "output_vq" in config:
+            self.output_casts.set_vq(config["output_vq"])
+        if self.weight_cast is not None and "weight_vq" in config:
+            self.weight_cast.set_vq(config["weight_vq"])   # (per_token: per output channel of the [out, in] view)
         # learned scales for the integer casts (CastTo.set_learnable; LSQ / LSQ+): *_dynamic's spellings, or a dict {"granularity": one of
         # them, "learn_zero_point", "grad_scale", "init"}.  Activation casts take "per_tensor" only; the weight cast sizes its parameters
         # from the weight (further down, after the weight_format of this config, so that a weight on the GPU initialises them at once)
@@ -429,7 +437,7 @@ class DmxModule(FastAttr, torch.nn.Module):
         wc, st = self.weight_cast, self.weight_storage_cast
         fmt = wc.format
         nd = _w.dim()
-        if (not isinstance(fmt, BlockFloatingPoint) or fmt.rounding != "nearest" or wc.pre_transform or wc._codebook is not None or not -nd <= wc.block_dim < nd
+        if (not isinstance(fmt, BlockFloatingPoint) or fmt.rounding != "nearest" or wc.pre_transform or wc._codebook is not None or wc._vq is not None or not -nd <= wc.block_dim < nd
                 or not wc._flag("fake_quant_enabled") or wc._flag("observer_enabled")):
             return None
         bd = wc.block_dim % nd
@@ -548,9 +556,10 @@ class DmxModule(FastAttr, torch.nn.Module):
         return self.weight_sparsifier(self.weight) if self.weight_sparsifier is not None else self.weight
 
     def fold_weight_and_bias(self) -> None:
-        from .layer_reconstruction import refuse_codebook_weight_cast, refuse_learnable_weight_cast
+        from .layer_reconstruction import refuse_codebook_weight_cast, refuse_learnable_weight_cast, refuse_vq_weight_cast
         refuse_learnable_weight_cast(self, "folding the weight")
         refuse_codebook_weight_cast(self, "folding the weight")
+        refuse_vq_weight_cast(self, "folding the weight")
         with torch.no_grad():
             if self.bias_cast is not None and not isinstance(self.bias_format, Same) and self.bias is not None:
                 self.bias.data = self.bias_cast(self.bias.data)
@@ -802,7 +811,7 @@ class DmxModule(FastAttr, torch.nn.Module):
         if ic is None:
             return None
         fmt = ic.format
-        if (not isinstance(fmt, BlockFloatingPoint) or fmt.rounding != "nearest" or fmt.block_size < 8 or ic.pre_transform or ic._codebook is not None
+        if (not isinstance(fmt, BlockFloatingPoint) or fmt.rounding != "nearest" or fmt.block_size < 8 or ic.pre_transform or ic._codebook is not None or ic._vq is not None
                 or ic.block_dim not in (-1, x.dim() - 1) or not ic._flag("fake_quant_enabled") or ic._flag("observer_enabled")):
             return None
         from . import ops
@@ -833,7 +842,7 @@ class DmxModule(FastAttr, torch.nn.Module):
             return False
         oc = self.output_casts[next(iter(self.output_casts.keys()))]
         f = oc.format
-        if (not isinstance(f, FloatingPoint) or f.rounding != "nearest" or f.unsigned or oc.pre_transform or oc._codebook is not None or oc._scaling is not None
+        if (not isinstance(f, FloatingPoint) or f.rounding != "nearest" or f.unsigned or oc.pre_transform or oc._codebook is not None or oc._vq is not None or oc._scaling is not None
                 or not oc._flag("fake_quant_enabled") or oc._flag("observer_enabled")):
             return False
         for c, idx in consumers:
@@ -842,7 +851,7 @@ class DmxModule(FastAttr, torch.nn.Module):
             if nc is None or (sq is not None and (sq._flag("enabled") or sq._flag("dynamic") or sq.calibrating)):
                 return False
             g = nc.format
-            if (not isinstance(g, FloatingPoint) or g.rounding != "nearest" or g.unsigned or nc.pre_transform or nc._codebook is not None or nc._scaling is not None
+            if (not isinstance(g, FloatingPoint) or g.rounding != "nearest" or g.unsigned or nc.pre_transform or nc._codebook is not None or nc._vq is not None or nc._scaling is not None
                     or not nc._flag("fake_quant_enabled") or nc._flag("observer_enabled")
                     or (g.mantissa, g.exponent, g.bias, bool(g.flush_subnormal)) != (f.mantissa, f.exponent, f.bias, bool(f.flush_subnormal))):
                 return False
@@ -865,7 +874,7 @@ class DmxModule(FastAttr, torch.nn.Module):
             if nc is None or (sq is not None and (sq._flag("enabled") or sq._flag("dynamic") or sq.calibrating)):
                 return None
             fmt = nc.format
-            if (not isinstance(fmt, BlockFloatingPoint) or fmt.rounding != "nearest" or not fmt.symmetric or nc.pre_transform or nc._codebook is not None
+            if (not isinstance(fmt, BlockFloatingPoint) or fmt.rounding != "nearest" or not fmt.symmetric or nc.pre_transform or nc._codebook is not None or nc._vq is not None
                     or nc.block_dim not in (-1, x.dim() - 1) or not nc._flag("fake_quant_enabled") or nc._flag("observer_enabled")):
                 return None
             if fmt0 is not None and (fmt.precision != fmt0.precision or fmt.block_size != fmt0.block_size):
@@ -1133,7 +1142,7 @@ def _range_only_format(cast, dtype):
     fmt = cast.format
     if isinstance(fmt, Same):
         return (not cast.pre_transform), None
-    if (not isinstance(fmt, FloatingPoint) or cast.pre_transform or cast._codebook is not None or cast._scaling is not None   # (a scaled cast is no pure range cast)
+    if (not isinstance(fmt, FloatingPoint) or cast.pre_transform or cast._codebook is not None or cast._vq is not None or cast._scaling is not None   # (a scaled cast is no pure range cast)
             or not cast._flag("fake_quant_enabled") or cast._flag("observer_enabled")):
         return False, None
     # format.py:209-212: the dtype's own format passes the tensor through untouched (no flush, NaN stays NaN) -- SAME for the kernel
@@ -1843,7 +1852,7 @@ def _weight_batches(mods):
     with torch.no_grad():
         for m in mods:
             wc, st, sp, sq = m.weight_cast, m.weight_storage_cast, m.weight_sparsifier, m.smoothquant
-            if (wc is None or wc.pre_transform or wc._codebook is not None or wc.dynamic is not None or wc._scaling is not None or wc._learnable is not None or not wc._flag("fake_quant_enabled") or wc._flag("observer_enabled") or not m.weight.is_cuda
+            if (wc is None or wc.pre_transform or wc._codebook is not None or wc._vq is not None or wc.dynamic is not None or wc._scaling is not None or wc._learnable is not None or not wc._flag("fake_quant_enabled") or wc._flag("observer_enabled") or not m.weight.is_cuda
                     or (sp is not None and not isinstance(sp.sparseness, Dense))
                     or (sq is not None and not sq._flag("fused_to_weight") and sq._flag("enabled"))
                     or (st is not None and not (isinstance(st.format, Same) and not st.pre_transform))):
@@ -1882,7 +1891,7 @@ def _bias_batches(mods):
     groups = {}
     for m in mods:
         bc, b = getattr(m, "bias_cast", None), getattr(m, "bias", None)
-        if bc is None or b is None or not b.is_cuda or bc.pre_transform or bc._codebook is not None or bc._scaling is not None or not bc._flag("fake_quant_enabled") or bc._flag("observer_enabled"):
+        if bc is None or b is None or not b.is_cuda or bc.pre_transform or bc._codebook is not None or bc._vq is not None or bc._scaling is not None or not bc._flag("fake_quant_enabled") or bc._flag("observer_enabled"):
             continue
         fmt = bc.format
         if isinstance(fmt, FloatingPoint) and fmt.rounding == "nearest" and fmt.mantissa < 23 and fmt.native_of() != b.dtype:

@@ -60,7 +60,7 @@ const char* dmxq_status_string(int status);
  * dmxq_block_scaled_float_qdq, dmxq_block_scaled_float_class, dmxq_block_scaled_tensor_scale, dmxq_nm_mask_class, dmxq_lsq_backward, dmxq_lsq_class, dmxq_lsq_scratch_bytes,
  * dmxq_codebook_qdq, dmxq_codebook_class, dmxq_codebook_accumulate, dmxq_codebook_workspace_bytes, dmxq_hqq_qdq, dmxq_hqq_class,
  * dmxq_outlier_fixed_qdq, dmxq_outlier_class, dmxq_awq_clip, dmxq_awq_clip_class, dmxq_adaround_forward, dmxq_adaround_backward,
- * dmxq_adaround_class, dmxq_adaround_scratch_bytes) leave it at 4: a caller built against 4 runs on
+ * dmxq_adaround_class, dmxq_adaround_scratch_bytes, dmxq_vq_qdq, dmxq_vq_class, dmxq_vq_accumulate, dmxq_vq_workspace_bytes) leave it at 4: a caller built against 4 runs on
  * this library unchanged.  4 = round 5: + dmxq_float_qdq_multi, dmxq_fixed_float_qdq_multi; 3 = round 4: + dmxq_weight_hypernet_multi,
  * dmxq_unary_cast_table, dmxq_lut16_apply.  Nothing was ever removed or changed: a caller built against version n runs on any library >= n. */
 int dmxq_abi_version(void);
@@ -658,6 +658,35 @@ int dmxq_codebook_qdq(const void* in, void* out, int dtype_in, int dtype_out, in
 int64_t dmxq_codebook_workspace_bytes(int dtype, int mode, int64_t n_segments, int64_t segment);
 int dmxq_codebook_accumulate(const void* in, int dtype_in, int mode, int64_t n_segments, int64_t segment, const float* levels, int K,
                              float norm, double* acc, int accumulate, void* workspace, void* stream);
+
+/* Vector codebook casts (csrc/vq.hip; DESIGN.md §8 "Vector codebook casts", whose text is the contract): `dim` consecutive elements are
+ * replaced together by one row of a [K, dim] table under a per-segment absolute-maximum scale -- GPTVQ / AQLM / QuIP#-style tables -- in
+ * ONE launch, and the weighted k-means statistics that fit such a table on the device.  Not in the reference.  table: a DEVICE array of
+ * K * dim float32 entries, row-major, finite (never read back, taken as is), 2 <= K <= 256, dim 2, 4 or 8; no order is required and
+ * duplicate rows are allowed.  In fp32, every operation rounded on its own:
+ *   D_k(u) = (((t_0 t_0) + t_1 t_1) + ...) + t_{dim-1} t_{dim-1}, t_j = u_j - c_kj;  z = the lowest k minimising D_k(0);  for norm <= 0,
+ *   norm = max |c_kj|.  Per segment: amax, s = amax / norm and the fallback s = 1 as dmxq_codebook_qdq;  u = x / s (IEEE);  per
+ *   dim-vector: best = +Inf, idx = z, for k = 0 .. K-1: D_k(u) < best takes k (a tie keeps the lower index; a vector whose distances
+ *   are all NaN or +Inf takes z);  out_j = c[idx][j] * s, one fp32 multiply, one rounding to dtype_out.
+ * mode and segment: as dmxq_codebook_qdq; `segment` is a multiple of dim, so that a vector never straddles a segment.  scale_out: NULL or
+ * a DEVICE array of n_segments floats; index_out: NULL or a DEVICE array of one uint8 per dim-vector (n_segments * segment / dim),
+ * 16-byte aligned.
+ * dmxq_vq_accumulate: float64 acc[K][dim + 2]: over the vectors whose dim quotients are all finite, acc[idx] (+)= { w u_0, ...,
+ * w u_{dim-1}, w, 1 } with w = (double)s * (double)s; accumulate != 0 adds to acc, 0 overwrites it.  No floating-point atomics: a row's
+ * owner thread adds its vectors in a fixed slot order, workgroups write partial blocks, a second launch adds the blocks in workgroup
+ * order (csrc/vq.hip's header) -- the same input gives the same bits.  workspace: DEVICE memory of dmxq_vq_workspace_bytes(...) bytes,
+ * 8-byte aligned, contents free.  An empty tensor launches nothing and leaves acc as it is.
+ * DMXQ_ERR_UNSUPPORTED, nothing launched (the caller runs its chain): dtype_in != dtype_out, float32 with dim 8, a segment outside
+ * dmxq_codebook_qdq's, a base that is not 16-byte aligned.  DMXQ_ERR_BAD_ARG: null pointers, negative sizes, invalid dtype / mode, dim
+ * outside {2, 4, 8}, a segment that is no multiple of dim, K outside 2 .. 256, a norm that is NaN or +Inf.  No allocation, no host
+ * synchronisation: capturable.
+ * dmxq_vq_class: the geometry (dmxq_dynamic_geometry) the entries pick, DMXQ_DYN_NONE where they refuse; no GPU involved. */
+int dmxq_vq_class(int dtype, int mode, int64_t segment, int dim, int K);
+int dmxq_vq_qdq(const void* in, void* out, int dtype_in, int dtype_out, int mode, int64_t n_segments, int64_t segment, const float* table,
+                int dim, int K, float norm, float* scale_out, uint8_t* index_out, void* stream);
+int64_t dmxq_vq_workspace_bytes(int dtype, int mode, int64_t n_segments, int64_t segment, int dim, int K);
+int dmxq_vq_accumulate(const void* in, int dtype_in, int mode, int64_t n_segments, int64_t segment, const float* table, int dim, int K,
+                       float norm, double* acc, int accumulate, void* workspace, void* stream);
 
 /* Half-Quadratic Quantization (HQQ; Badri and Shaji, 2023) in ONE launch (csrc/hqq.hip; DESIGN.md §8 "HQQ", whose text is the contract).
  * Not in the reference.  Per group of `segment` consecutive elements of the contiguous tensor, every operation fp32 in the text's order:
