@@ -837,6 +837,26 @@ def hadamard_qdq(x, size, inverse, fmt, scale, zero_point, out_dtype=None):
     return out
 
 
+# ------------------------------------------------------------------------------------------------ full-row Hadamard rotation
+@_guarded
+def hadamard_row_qdq(x, transpose, inverse, precision, symmetric, segment, want_qparams, out_dtype=None):
+    xc = _prep(x, "hadamard_row_qdq")
+    if xc.dim() < 1:
+        raise RuntimeError("hadamard_row_qdq: expects a tensor with at least one dimension")
+    n = xc.shape[-1]
+    rows = xc.numel() // n if n else 0
+    if precision and (segment < 1 or n % segment != 0):
+        raise RuntimeError("hadamard_row_qdq: the segment must divide the row")
+    nq = rows * (n // segment) if (want_qparams and precision > 0) else 0
+    out = torch.empty(xc.shape, dtype=out_dtype or xc.dtype, device=xc.device)
+    sc = torch.empty(nq, dtype=torch.float32, device=xc.device)
+    zp = torch.empty(nq, dtype=torch.int64, device=xc.device)
+    check(lib().dmxq_hadamard_row_qdq(ptr(xc), ptr(out), dtype_code(xc.dtype), dtype_code(out.dtype), rows, n, int(bool(transpose)),
+                                      int(bool(inverse)), precision, symmetric, segment, ptr(sc) if nq else None, ptr(zp) if nq else None,
+                                      stream_of(xc)), "dmxq_hadamard_row_qdq")
+    return out, sc, zp
+
+
 # ------------------------------------------------------------------------------------------------ dynamic integer cast
 @_guarded
 def dynamic_fixed_qdq(x, segment, whole_rows, precision, fraction, clamp, symmetric, rounding, qmin, qmax, symmetric_qscheme, want_qparams,

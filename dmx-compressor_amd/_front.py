@@ -22,6 +22,8 @@ __all__ = [
     "smoothquant_scale", "scale_channels", "gelu", "silu", "quick_gelu", "exp", "silu_experimental", "rope", "softmax", "layernorm",
     "rmsnorm", "histc", "gptq_fields", "gptq_block", "gptq_block_dynamic", "hist_observe", "hist_scratch_words", "hist_qparams", "error_stats", "cast_error",
     "error_scratch_bytes", "cast_error_entry", "hadamard", "hadamard_qdq", "hadamard_check_size", "HADAMARD_SIZES",
+    "hadamard_matrix", "hadamard_row_check", "hadamard_row_class", "hadamard_row", "hadamard_row_dynamic_qdq", "HADAMARD_ROW_FACTORS",
+    "HADAMARD_ROW_CHAIN_BY_DEFAULT",
     "dynamic_fixed_qdq", "dynamic_check", "dynamic_class", "DYNAMIC_GRANULARITIES", "DYNAMIC_CHAIN_BY_DEFAULT",
     "dynamic_float_qdq", "dynamic_float_check", "dynamic_float_class", "dynamic_float_fmax", "DYNAMIC_FLOAT_GRANULARITIES",
     "DYNAMIC_FLOAT_CHAIN_BY_DEFAULT",
@@ -969,6 +971,235 @@ def hadamard_qdq(x, size: int, fmt, block_dim: int = -1, inverse: bool = True, s
         return _RotatedCast.apply(x, run, size, d, bool(inverse))
     with torch.no_grad():
         return run(x.detach())
+
+
+# ---------------------------------------------------------------------------------------------------- full-row Hadamard rotation
+HADAMARD_ROW_FACTORS = (1, 12, 20, 28)          # m of a row of n = m 2^k elements (dmxq_hadamard_row_qdq)
+HADAMARD_ROW_MIN, HADAMARD_ROW_MAX = 512, 16384  # the rows the kernel takes; the chain takes every n = m 2^k
+# Classes of dmxq_hadamard_row_qdq (hadamard_row_class) that fused=None sends to the chain although the kernel takes them.  The rule: a
+# class goes to the kernel by default only where tools/bench_hadamard_row.py MEASURED it faster than its same-bits chain on the same
+# buffers (profiles/r26_hadamard_row.txt); a class that is not gets listed here with its row.  bf16, us per call, kernel against chain:
+# block [8192,4096] rotation 57.8 against 1737.6, + INT4 per token 62.5 / 101.9 (inverse) against 1763.6 / 3377.7, per group 128 61.5 /
+# 102.5 against 1771.8 / 3457.8; [8192,14336] 490.1, 484.4 / 895.3, 558.2 / 969.0 against 14044.2, 14164.3 / 27890.3, 14151.3 / 27560.7;
+# [8192,5120] 121.0, 134.9 / 242.4, 159.3 / 270.6 against 3706.8, 3732.9 / 7275.9, 3744.1 / 7302.5; wave [2048,768] 7.5, 8.8 / 12.1 against
+# 1104.3, 1176.0 / 2161.3 -- both classes are faster, none is listed.
+HADAMARD_ROW_CHAIN_BY_DEFAULT = frozenset()
+_hadamard_row_routes = {"fused": 0, "chain": 0}   # which route the calls took, counted on the host: private, for the tests
+_HADAMARD_ROW_CLASS_NAMES = {1: "wave", 2: "block"}   # dmxq_hadamard_row_geometry (include/dmxq.h)
+_hadamard_tables = {}
+
+
+def hadamard_matrix(m: int) -> torch.Tensor:
+    """the int8 [m, m] table of +-1 of H_m, m in HADAMARD_ROW_FACTORS, as the library builds it from Legendre symbols (Paley I for 12 and
+    20, Paley II for 28; dmxq_hadamard_matrix, a host function: no GPU involved).  H_m H_m^T = m I."""
+    import ctypes
+    from ._lib import lib
+    if isinstance(m, bool) or not isinstance(m, int) or m not in HADAMARD_ROW_FACTORS:
+        raise ValueError(f"hadamard_matrix: m must be one of {HADAMARD_ROW_FACTORS}, got {m!r}")
+    if m not in _hadamard_tables:
+        buf = (ctypes.c_int8 * (m * m))()
+        if lib().dmxq_hadamard_matrix(m, ctypes.cast(buf, ctypes.c_void_p)) != 0:
+            raise DmxqError(f"dmxq_hadamard_matrix({m}) failed")
+        _hadamard_tables[m] = torch.tensor(list(buf), dtype=torch.int8).reshape(m, m)
+    return _hadamard_tables[m].clone()
+
+
+def hadamard_row_check(n, what: str = "hadamard_row"):
+    """-> (m, k) with n = m 2^k, m in HADAMARD_ROW_FACTORS and k >= 3, or ValueError.  Any such n has a chain; the kernel takes
+    HADAMARD_ROW_MIN <= n <= HADAMARD_ROW_MAX."""
+    if isinstance(n, bool) or not isinstance(n, int) or n < 8:
+        raise ValueError(f"{what}: the row length must be an integer m * 2^k with m in {HADAMARD_ROW_FACTORS}, got {n!r}")
+    odd = n
+    while odd % 2 == 0:
+        odd //= 2
+    m = 1 if odd == 1 else 4 * odd
+    if odd not in (1, 3, 5, 7) or n % m or n // m < 8:
+        raise ValueError(f"{what}: the row length must be m * 2^k with m in {HADAMARD_ROW_FACTORS} and k >= 3, got {n}")
+    return m, (n // m).bit_length() - 1
+
+
+def hadamard_row_class(n: int, dtype: torch.dtype, segment: Optional[int] = None) -> Optional[str]:
+    """the geometry dmxq_hadamard_row_qdq picks for rows of n elements of `dtype` cast in segments of `segment` elements (None: no cast,
+    or the row itself), asked of the library (dmxq_hadamard_row_class, THE routing rule; no GPU involved), or None when it refuses:
+    "wave" (a 64-thread workgroup per row of up to 256 vectors), "block" (a 256-thread workgroup per row)"""
+    from ._lib import dtype_code, lib
+    return _HADAMARD_ROW_CLASS_NAMES.get(lib().dmxq_hadamard_row_class(int(n), dtype_code(dtype), int(segment or 0)))
+
+
+def _rotate_row_chain(v, transpose):
+    """R (or R^T) of the last dimension of the float32 tensor v in torch operations, the bits of the definition: reshaped adds /
+    subtracts for the butterflies, a left-to-right loop for the m-point stage, one multiply"""
+    n = v.shape[-1]
+    m, k = hadamard_row_check(n)
+    P = 1 << k
+    shape = v.shape
+    v = v.reshape(-1, n)
+
+    def mstage(v):
+        H = hadamard_matrix(m).tolist()
+        cols = v.reshape(-1, m, P)
+        out = torch.empty_like(cols)
+        for a in range(m):
+            sign = [H[b][a] if transpose else H[a][b] for b in range(m)]
+            acc = cols[:, 0] if sign[0] > 0 else -cols[:, 0]
+            for b in range(1, m):
+                acc = acc + cols[:, b] if sign[b] > 0 else acc - cols[:, b]
+            out[:, a] = acc
+        return out.reshape(-1, n)
+
+    if transpose and m > 1:
+        v = mstage(v)
+    s = 1
+    while s < P:
+        t = v.reshape(-1, P // (2 * s), 2, s)
+        a, b = t[:, :, 0, :], t[:, :, 1, :]
+        v = torch.stack((a + b, a - b), dim=2).reshape(-1, n)
+        s *= 2
+    if not transpose and m > 1:
+        v = mstage(v)
+    c = float(torch.tensor(1.0 / math.sqrt(n), dtype=torch.float64).to(torch.float32))   # (a host number: nothing is copied, capturable)
+    return (v * c).reshape(shape)
+
+
+def _rotate_row(x, d, transpose, out_dtype, fused=None):
+    xl = _to_last(x.detach(), d)
+    n = xl.shape[-1]
+    if fused is not False and xl.numel() and hadamard_row_class(n, xl.dtype) is not None and out_dtype in (xl.dtype, torch.float32):
+        xc = xl if xl.is_contiguous() else xl.contiguous()
+        if xc.data_ptr() % 16 == 0 and (fused or hadamard_row_class(n, xl.dtype) not in HADAMARD_ROW_CHAIN_BY_DEFAULT):
+            try:
+                y = _ops.hadamard_row_qdq(xc, bool(transpose), False, 0, 0, n, False, out_dtype)[0]
+                _hadamard_row_routes["fused"] += 1
+                return _from_last(y, d)
+            except NotImplementedError:   # (DMXQ_ERR_UNSUPPORTED, nothing launched)
+                if fused:
+                    raise
+    if fused:
+        raise NotImplementedError(f"hadamard_row: no fused kernel for rows of {n} {xl.dtype} elements -> {out_dtype} "
+                                  f"(base address {xl.data_ptr() % 16} mod 16)")
+    _hadamard_row_routes["chain"] += 1
+    return _from_last(_rotate_row_chain(xl.to(torch.float32), transpose).to(out_dtype), d)
+
+
+class _RowRotation(torch.autograd.Function):
+    """R is orthonormal: the gradient of R(x) is R^T(grad) -- the rotation with `transpose` flipped"""
+
+    @staticmethod
+    def forward(ctx, x, d, transpose, out_dtype, fused):
+        ctx.set_materialize_grads(False)
+        ctx.rot = (d, transpose, x.dtype, fused)
+        return _rotate_row(x, d, transpose, out_dtype, fused)
+
+    @staticmethod
+    def backward(ctx, g):
+        d, transpose, dt, fused = ctx.rot
+        return (None if g is None else _rotate_row(g, d, not transpose, dt, None if fused else fused)), None, None, None, None
+
+
+def hadamard_row(x, dim: int = -1, transpose: bool = False, out_dtype: Optional[torch.dtype] = None, fused: Optional[bool] = None):
+    """The orthonormal Hadamard rotation of the WHOLE dimension `dim` (DESIGN.md §8 "Full-row Hadamard rotation"): n = m 2^k elements, m
+    in HADAMARD_ROW_FACTORS; R = (H_m (x) H_{2^k}) / sqrt(n) -- the k butterfly stages of ops.hadamard inside each of the m chunks, the
+    m-point stage across the chunks (left to right, one float32 operation per term), one multiply by float32(1 / sqrt(n)); rounded once
+    to out_dtype (default x.dtype).  transpose=True: R^T, the inverse of R (the m-point stage first, with H_m^T).  One launch
+    (dmxq_hadamard_row_qdq) for 512 <= n <= 16384, a 16-byte aligned tensor and out_dtype x.dtype or float32; the chain of torch operations
+    otherwise, same bits (fused=True: NotImplementedError instead; fused=False: always the chain).  A `dim` other than the last is
+    transposed to the last with a contiguous copy and back: a slow path.  Differentiable: the gradient is hadamard_row(grad) with
+    `transpose` flipped.  ValueError: a dimension that is not m 2^k."""
+    if x.dim() < 1 or not -x.dim() <= dim < x.dim():
+        raise ValueError(f"hadamard_row: dimension {dim} of a tensor of shape {tuple(x.shape)}")
+    d = dim % x.dim()
+    hadamard_row_check(int(x.shape[d]), "hadamard_row")
+    require_gpu(x, "hadamard_row")
+    out_dtype = out_dtype or x.dtype
+    if x.requires_grad and torch.is_grad_enabled():
+        return _RowRotation.apply(x, d, bool(transpose), out_dtype, fused)
+    return _rotate_row(x, d, bool(transpose), out_dtype, fused)
+
+
+def hadamard_row_dynamic_qdq(x, fmt, granularity: str = "per_token", group_size: Optional[int] = None, inverse: bool = True,
+                             out_dtype: Optional[torch.dtype] = None, fused: Optional[bool] = None, return_qparams: bool = False,
+                             symmetric_qscheme: bool = False, transpose: bool = False):
+    """Rotate the whole last dimension, quantize dynamically, and rotate back (inverse=True) or stay in the rotated basis:
+        y = round_to(out_dtype, R^T(Q(R(x))))   or   round_to(out_dtype, Q(R(x)))
+    with R = hadamard_row in float32 (transpose=True swaps R and R^T) and Q = ops.dynamic_fixed_qdq of the rotated float32 tensor --
+    fmt an integer-range XP[p,0](C..) format, "per_token" (the row is the segment) or "per_group" (group_size a power of two 16 .. 256
+    dividing 2^k), symmetric_qscheme as there -- float32 out; ONE rounding to out_dtype (default x.dtype) at the end.
+    ONE launch (dmxq_hadamard_row_qdq) for 512 <= n <= 16384, nearest rounding, out_dtype == x.dtype and a 16-byte aligned tensor, unless
+    its class is listed in HADAMARD_ROW_CHAIN_BY_DEFAULT; otherwise -- rows outside that range, unaligned views, mixed dtypes, other
+    rounding modes -- the chain hadamard_row (float32) -> dynamic_fixed_qdq (float32) -> hadamard_row(transpose flipped): the same bits.
+    fused=True raises NotImplementedError instead of falling back; fused=False forces the chain.
+    return_qparams: (y, scale float32 [n_segments], zero_point int64 [n_segments]) on both routes.
+    ValueError (before any GPU use): a row that is not m 2^k, a format without an integer range, a group size that is no power of two
+    from 16 to 256 dividing 2^k.  Autograd: a straight-through estimator -- the identity with inverse, the rotation with `transpose`
+    flipped applied to the gradient without."""
+    if granularity not in ("per_token", "per_group"):
+        raise ValueError(f"hadamard_row_dynamic_qdq: granularity must be 'per_token' or 'per_group', got {granularity!r}")
+    fmt, granularity, group_size = dynamic_check(fmt, granularity, group_size, "hadamard_row_dynamic_qdq")
+    if x.dim() < 1:
+        raise ValueError("hadamard_row_dynamic_qdq: expects a tensor with at least one dimension")
+    n = int(x.shape[-1])
+    m, k = hadamard_row_check(n, "hadamard_row_dynamic_qdq")
+    if granularity == "per_group" and (group_size < 16 or group_size > 256 or group_size & (group_size - 1) or (1 << k) % group_size):
+        raise ValueError(f"hadamard_row_dynamic_qdq: the group size must be a power of two from 16 to 256 dividing 2^k = {1 << k}, "
+                         f"got {group_size}")
+    require_gpu(x, "hadamard_row_dynamic_qdq")
+    out_dtype = out_dtype or x.dtype
+    S = n if granularity == "per_token" else group_size
+    sym, tr, inv = bool(symmetric_qscheme), bool(transpose), bool(inverse)
+
+    def run(xd):
+        xc = xd if xd.is_contiguous() else xd.contiguous()
+        if xc.numel() == 0:
+            y = torch.empty(xc.shape, dtype=out_dtype, device=xc.device)
+            return (y, y.new_empty(0, dtype=torch.float32), y.new_empty(0, dtype=torch.int64)) if return_qparams else y
+        if fused is not False:
+            cls = hadamard_row_class(n, xc.dtype, S) if (fmt.rounding == "nearest" and out_dtype == xc.dtype and 2 <= fmt.precision <= 22
+                                                         and xc.data_ptr() % 16 == 0) else None
+            if cls is None and fused:
+                raise NotImplementedError(f"hadamard_row_dynamic_qdq: no fused kernel for rows of {n} {xc.dtype} elements in segments of "
+                                          f"{S} -> {out_dtype} with {fmt!r} (base address {xc.data_ptr() % 16} mod 16)")
+            if cls is not None and fused is None and cls in HADAMARD_ROW_CHAIN_BY_DEFAULT:
+                cls = None
+            if cls is not None:
+                try:
+                    y, sc, zp = _ops.hadamard_row_qdq(xc, tr, inv, fmt.precision, (1 if sym else 0) | (2 if fmt.symmetric else 0), S,
+                                                      bool(return_qparams), out_dtype)
+                    _hadamard_row_routes["fused"] += 1
+                    return (y, sc, zp) if return_qparams else y
+                except NotImplementedError:   # (DMXQ_ERR_UNSUPPORTED, nothing launched)
+                    if fused:
+                        raise
+        _hadamard_row_routes["chain"] += 1
+        r = _rotate_row_chain(xc.to(torch.float32), tr)
+        q, sc, zp = dynamic_fixed_qdq(r, fmt, granularity, group_size, sym, torch.float32, True)
+        y = (_rotate_row_chain(q, not tr) if inv else q).to(out_dtype)
+        return (y, sc, zp) if return_qparams else y
+
+    if x.requires_grad and torch.is_grad_enabled():
+        return _RowRotatedSTE.apply(x, run, tr, inv)
+    with torch.no_grad():
+        return run(x.detach())
+
+
+class _RowRotatedSTE(torch.autograd.Function):
+    """rotate -> dynamic cast (-> rotate back): the cast is a straight-through estimator, so the backward is the identity with the
+    inverse rotation and the transposed rotation of the gradient without it"""
+
+    @staticmethod
+    def forward(ctx, x, run, transpose, inverse):
+        ctx.set_materialize_grads(False)
+        ctx.rot = (x.dtype, transpose, inverse)
+        out = run(x.detach())
+        if isinstance(out, tuple):
+            ctx.mark_non_differentiable(*out[1:])
+        return out
+
+    @staticmethod
+    def backward(ctx, g, *_):
+        dt, transpose, inverse = ctx.rot
+        if g is not None:
+            g = (g if g.dtype == dt else g.to(dt)) if inverse else _rotate_row(g, g.dim() - 1, not transpose, dt)
+        return g, None, None, None
 
 
 # ---------------------------------------------------------------------------------------------------- dynamic integer cast

@@ -96,6 +96,15 @@ def _parse_hadamard(spec):
     return {"size": ops.hadamard_check_size(size, "pre_transform['hadamard']"), "inverse": inverse}
 
 
+def _parse_hadamard_row(spec):
+    """pre_transform["hadamard_row"]: True or {"inverse": bool} -> {"inverse"} (inverse defaults to True)"""
+    if spec is True:
+        return {"inverse": True}
+    if not isinstance(spec, dict) or set(spec) - {"inverse"} or not isinstance(spec.get("inverse", True), bool):
+        raise ValueError(f"pre_transform['hadamard_row']: expected True or {{'inverse': bool}}, got {spec!r}")
+    return {"inverse": spec.get("inverse", True)}
+
+
 def _parse_dynamic(granularity, group_size=None):
     """set_dynamic's arguments -> None or (granularity, group_size): None / False, "per_token", "per_tensor", ("per_group", g) or
     {"per_group": g}"""
@@ -293,6 +302,17 @@ class CastTo(HostFlags, torch.nn.Module):
             if self._vq is not None:
                 self.pre_transform.pop("hadamard")
                 raise ValueError(_VQ_HADAMARD)
+        if "hadamard_row" in self.pre_transform:
+            # the orthonormal Hadamard rotation of the WHOLE last dimension around the cast (ops.hadamard_row): True, or
+            # {"inverse": False} to leave the result in the rotated basis; the row length is validated at the first forward
+            spec = self.pre_transform.pop("hadamard_row")
+            if "hadamard" in self.pre_transform:
+                self.pre_transform.pop("hadamard")
+                raise ValueError("pre_transform: 'hadamard' (blocks) or 'hadamard_row' (the whole last dimension), not both")
+            for other, msg in ((self._learnable, _LEARNABLE_HADAMARD), (self._codebook, _CODEBOOK_HADAMARD), (self._vq, _VQ_HADAMARD)):
+                if other is not None:
+                    raise ValueError(msg)
+            self.pre_transform["hadamard_row"] = _parse_hadamard_row(spec)
 
     def set_dynamic(self, granularity=None, group_size=None):
         """Dynamic scales (not in the reference): with fake-quant on and the observer off, an integer format is cast with a
@@ -373,7 +393,7 @@ class CastTo(HostFlags, torch.nn.Module):
                     del self._parameters[n]
             self._learnable, self._learnable_pending = None, False
             return
-        if "hadamard" in self.pre_transform:
+        if "hadamard" in self.pre_transform or "hadamard_row" in self.pre_transform:
             raise ValueError(_LEARNABLE_HADAMARD)
         if self._codebook is not None:
             raise ValueError("CastTo.set_learnable: " + _CODEBOOK_EXCLUSIVE)
@@ -566,7 +586,7 @@ class CastTo(HostFlags, torch.nn.Module):
         if self._dynamic is not None or self._scaling is not None or self._learnable is not None:
             raise ValueError("CastTo.set_codebook: this cast already takes its scales from set_dynamic / set_scaling / set_learnable; a codebook "
                              "replaces the format's arithmetic and is exclusive with them: switch that off first")
-        if "hadamard" in self.pre_transform:
+        if "hadamard" in self.pre_transform or "hadamard_row" in self.pre_transform:
             raise ValueError(_CODEBOOK_HADAMARD)
         t = levels.detach().to(torch.float32).clone() if isinstance(levels, torch.Tensor) else torch.tensor(levels, dtype=torch.float32)
         for n in ("codebook", "codebook_norm"):
@@ -646,7 +666,7 @@ class CastTo(HostFlags, torch.nn.Module):
         if self._dynamic is not None or self._scaling is not None or self._learnable is not None:
             raise ValueError("CastTo.set_vq: this cast already takes its scales from set_dynamic / set_scaling / set_learnable; a vector "
                              "codebook replaces the format's arithmetic and is exclusive with them: switch that off first")
-        if "hadamard" in self.pre_transform:
+        if "hadamard" in self.pre_transform or "hadamard_row" in self.pre_transform:
             raise ValueError(_VQ_HADAMARD)
         t = table.detach().to(torch.float32).clone() if isinstance(table, torch.Tensor) else torch.tensor(table, dtype=torch.float32)
         for n in ("vq_codebook", "vq_norm"):
@@ -832,7 +852,7 @@ class CastTo(HostFlags, torch.nn.Module):
         -> inverse rotation.  With fake-quant off nothing is cast: the input comes back as it is (inverse) or rotated (no inverse)."""
         d = self.__dict__
         fmt = self.format
-        r = ops.hadamard(x, had["size"], self.block_dim, out_dtype=torch.float32)
+        r = self._rotation(x, had, torch.float32)
         if d["_h_observer_enabled"] and not isinstance(fmt, Same):
             self._observer_step(r)
         if not d["_h_fake_quant_enabled"]:
@@ -842,7 +862,24 @@ class CastTo(HostFlags, torch.nn.Module):
                             "not part of the accelerated hot path")
         if not had["inverse"]:
             return self._quantize(r, self.physical_dtype)
-        return ops.hadamard(self._quantize(r, torch.float32), had["size"], self.block_dim, out_dtype=self.physical_dtype)
+        return self._rotation(self._quantize(r, torch.float32), had, self.physical_dtype, back=True)
+
+    def _rotation(self, x, had, out_dtype, back=False):
+        """the rotation of a "hadamard" (blocks along block_dim; its own inverse) or "hadamard_row" (the whole last dimension; back: the
+        transposed rotation, its inverse) pre_transform"""
+        if "size" in had:
+            return ops.hadamard(x, had["size"], self.block_dim, out_dtype=out_dtype)
+        return ops.hadamard_row(x, -1, transpose=back, out_dtype=out_dtype)
+
+    def _hadamard_row_fused(self, x):
+        """whether this cast under a "hadamard_row" pre_transform runs as the one-launch ops.hadamard_row_dynamic_qdq: a dynamic per-token
+        or per-group integer cast, the group a power of two 16 .. 256 dividing 2^k; the row length is validated here (ValueError)"""
+        _, k = ops.hadamard_row_check(int(x.shape[-1]) if x.dim() else 0, "CastTo with a 'hadamard_row' pre_transform")
+        dyn = self._dynamic
+        if dyn is None or self._outliers is not None or self._scaling is not None or not isinstance(self.format, FixedPoint):
+            return False
+        g, gs = dyn
+        return g == "per_token" or (g == "per_group" and 16 <= gs <= 256 and gs & (gs - 1) == 0 and (1 << k) % gs == 0)
 
     def forward(self, x):
         d = self.__dict__  # (plain attributes: nn.Module.__setattr__ costs several microseconds per assignment)
@@ -864,6 +901,11 @@ class CastTo(HostFlags, torch.nn.Module):
         if had is not None and len(pt) == 1 and d["_h_fake_quant_enabled"] and not d["_h_observer_enabled"] and isinstance(fmt, Format) \
                 and not isinstance(fmt, Same) and self._dynamic is None and self._scaling is None:   # (a dynamic / scaled cast: the step-by-step route below)
             return self._hadamard_qdq(x, had, x.dtype)   # rotation, cast and inverse rotation: one call
+        if had is None:
+            had = pt.get("hadamard_row")
+            if had is not None and len(pt) == 1 and d["_h_fake_quant_enabled"] and not d["_h_observer_enabled"] and self._hadamard_row_fused(x):
+                return ops.hadamard_row_dynamic_qdq(x, fmt, *self._dynamic, inverse=had["inverse"], out_dtype=x.dtype,
+                                                    symmetric_qscheme=self.qscheme in _SYMMETRIC)   # one call
         inverse_shaping = None
         shortcut = None
         if "shaping" in pt:

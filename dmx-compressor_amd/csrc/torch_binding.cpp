@@ -1011,6 +1011,32 @@ Tensor hadamard_qdq_meta(const Tensor& x, int64_t, bool, at::IntArrayRef, const 
   return empty_like_shape(x, out_dtype);
 }
 
+// ------------------------------------------------------------------------------------------------ full-row Hadamard rotation
+// x: [rows, n] (any leading dims; the whole last dim is rotated); precision 0: rotation only; segment: n (per token) or the group size;
+// -> (out, scale [rows * n / segment] float32, zero_point int64), the last two empty unless want_qparams.
+// DMXQ_ERR_UNSUPPORTED (NotImplementedError, nothing launched): the front end runs its chain.
+std::tuple<Tensor, Tensor, Tensor> hadamard_row_qdq(const Tensor& x, bool transpose, bool inverse, int64_t precision, int64_t symmetric,
+                                                    int64_t segment, bool want_qparams, OptDtype out_dtype) {
+  const Tensor xc = prep(x, "hadamard_row_qdq");
+  TORCH_CHECK(xc.dim() >= 1, "hadamard_row_qdq: expects a tensor with at least one dimension");
+  const int64_t n = xc.size(-1), rows = n ? xc.numel() / n : 0;
+  TORCH_CHECK(precision == 0 || (segment >= 1 && n % segment == 0), "hadamard_row_qdq: the segment must divide the row");
+  const int64_t nq = (want_qparams && precision > 0) ? rows * (n / segment) : 0;
+  Tensor out = empty_like_shape(xc, out_dtype);
+  Tensor sc = at::empty({nq}, xc.options().dtype(at::kFloat));
+  Tensor zp = at::empty({nq}, xc.options().dtype(at::kLong));
+  Launch l(xc);
+  check(dmxq_hadamard_row_qdq(xc.data_ptr(), out.data_ptr(), dt_code(xc.scalar_type()), dt_code(out.scalar_type()), rows, n, transpose ? 1 : 0,
+                              inverse ? 1 : 0, (int)precision, (int)symmetric, segment, nq ? (float*)sc.data_ptr() : nullptr,
+                              nq ? (int64_t*)zp.data_ptr() : nullptr, l.stream), "dmxq_hadamard_row_qdq");
+  return std::make_tuple(out, sc, zp);
+}
+std::tuple<Tensor, Tensor, Tensor> hadamard_row_qdq_meta(const Tensor& x, bool, bool, int64_t precision, int64_t, int64_t segment,
+                                                         bool want_qparams, OptDtype out_dtype) {
+  const int64_t nq = (want_qparams && precision > 0 && segment >= 1) ? x.numel() / segment : 0;
+  return std::make_tuple(empty_like_shape(x, out_dtype), at::empty({nq}, x.options().dtype(at::kFloat)), at::empty({nq}, x.options().dtype(at::kLong)));
+}
+
 // ------------------------------------------------------------------------------------------------ dynamic integer cast
 // x: contiguous, numel % segment == 0; -> (out, scale [n_segments] float32, zero_point [n_segments] int64), the last two empty unless
 // want_qparams.  DMXQ_ERR_UNSUPPORTED (NotImplementedError, nothing launched): the front end runs the three-launch chain.
@@ -1523,6 +1549,7 @@ TORCH_LIBRARY(dmxq, m) {
   m.def("error_stats(Tensor ref, Tensor test, bool accumulate, Tensor(a!) stats, Tensor(b!) scratch) -> ()");
   m.def("cast_error(Tensor x, int[] fmts, Tensor? scale, Tensor? zero_point, bool accumulate, Tensor(a!) stats, Tensor(b!) scratch) -> ()");
   m.def("hadamard_qdq(Tensor x, int size, bool inverse, int[] fmt, Tensor? scale, Tensor? zero_point, ScalarType? out_dtype=None) -> Tensor");
+  m.def("hadamard_row_qdq(Tensor x, bool transpose, bool inverse, int precision, int symmetric, int segment, bool want_qparams, ScalarType? out_dtype=None) -> (Tensor, Tensor, Tensor)");
   m.def("dynamic_fixed_qdq(Tensor x, int segment, bool whole_rows, int precision, int fraction, bool clamp, bool symmetric, int rounding, int qmin, int qmax, bool symmetric_qscheme, bool want_qparams, ScalarType? out_dtype=None) -> (Tensor, Tensor, Tensor)");
   m.def("dynamic_float_qdq(Tensor x, int mode, int segment, int man, int exp, int bias, bool flush_subnormal, int rounding, bool pow2_scale, bool want_scale, ScalarType? out_dtype=None) -> (Tensor, Tensor)");
   m.def("channel_sumsq(Tensor x, Tensor(a!) acc, Tensor(b!) scratch) -> ()");
@@ -1553,7 +1580,7 @@ TORCH_LIBRARY(dmxq, m) {
   X(m, error_stats); X(m, cast_error); X(m, hadamard_qdq); X(m, dynamic_fixed_qdq); X(m, gptq_block_dynamic); X(m, dynamic_float_qdq); \
   X(m, channel_sumsq); X(m, wanda_nm); X(m, channel_sumabs); X(m, awq_group_error); X(m, block_scaled_float_qdq); X(m, block_scaled_tensor_scale); \
   X(m, lsq_backward); X(m, codebook_qdq); X(m, codebook_accumulate); X(m, hqq_qdq); X(m, outlier_fixed_qdq); X(m, awq_clip); \
-  X(m, adaround_forward); X(m, adaround_backward); X(m, vq_qdq); X(m, vq_accumulate)
+  X(m, adaround_forward); X(m, adaround_backward); X(m, vq_qdq); X(m, vq_accumulate); X(m, hadamard_row_qdq)
 
 // "CUDA" is the dispatch key of HIP tensors in a ROCm build of PyTorch
 TORCH_LIBRARY_IMPL(dmxq, CUDA, m) {
@@ -1609,6 +1636,8 @@ PYBIND11_MODULE(dmxq_fast, m) {
   m.def("cast_error", &cast_error);
   m.def("hadamard_qdq", &hadamard_qdq, py::arg("x"), py::arg("size"), py::arg("inverse"), py::arg("fmt"), py::arg("scale"), py::arg("zero_point"),
         py::arg("out_dtype") = py::none());
+  m.def("hadamard_row_qdq", &hadamard_row_qdq, py::arg("x"), py::arg("transpose"), py::arg("inverse"), py::arg("precision"), py::arg("symmetric"),
+        py::arg("segment"), py::arg("want_qparams"), py::arg("out_dtype") = py::none());
   m.def("dynamic_fixed_qdq", &dynamic_fixed_qdq, py::arg("x"), py::arg("segment"), py::arg("whole_rows"), py::arg("precision"), py::arg("fraction"),
         py::arg("clamp"), py::arg("symmetric"), py::arg("rounding"), py::arg("qmin"), py::arg("qmax"), py::arg("symmetric_qscheme"),
         py::arg("want_qparams"), py::arg("out_dtype") = py::none());

@@ -60,7 +60,8 @@ const char* dmxq_status_string(int status);
  * dmxq_block_scaled_float_qdq, dmxq_block_scaled_float_class, dmxq_block_scaled_tensor_scale, dmxq_nm_mask_class, dmxq_lsq_backward, dmxq_lsq_class, dmxq_lsq_scratch_bytes,
  * dmxq_codebook_qdq, dmxq_codebook_class, dmxq_codebook_accumulate, dmxq_codebook_workspace_bytes, dmxq_hqq_qdq, dmxq_hqq_class,
  * dmxq_outlier_fixed_qdq, dmxq_outlier_class, dmxq_awq_clip, dmxq_awq_clip_class, dmxq_adaround_forward, dmxq_adaround_backward,
- * dmxq_adaround_class, dmxq_adaround_scratch_bytes, dmxq_vq_qdq, dmxq_vq_class, dmxq_vq_accumulate, dmxq_vq_workspace_bytes) leave it at 4: a caller built against 4 runs on
+ * dmxq_adaround_class, dmxq_adaround_scratch_bytes, dmxq_vq_qdq, dmxq_vq_class, dmxq_vq_accumulate, dmxq_vq_workspace_bytes,
+ * dmxq_hadamard_row_qdq, dmxq_hadamard_row_class, dmxq_hadamard_matrix) leave it at 4: a caller built against 4 runs on
  * this library unchanged.  4 = round 5: + dmxq_float_qdq_multi, dmxq_fixed_float_qdq_multi; 3 = round 4: + dmxq_weight_hypernet_multi,
  * dmxq_unary_cast_table, dmxq_lut16_apply.  Nothing was ever removed or changed: a caller built against version n runs on any library >= n. */
 int dmxq_abi_version(void);
@@ -555,6 +556,34 @@ int dmxq_cast_error(const void* in, int dtype, int64_t rows, int64_t L, const dm
  * outside the above (the caller runs rotation, cast and rotation as three launches). */
 int dmxq_hadamard_qdq(const void* in, void* out, int dtype_in, int dtype_out, int64_t rows, int64_t L, int64_t size, int inverse,
                       const dmxq_gptq_format* fmt, const float* scale, const int64_t* zero_point, void* stream);
+
+/* Full-row Hadamard rotation fused with the dynamic integer cast (csrc/hadamard_row.hip; DESIGN.md §8 "Full-row Hadamard rotation").
+ * Not in the reference: the online rotation of QuaRot / SpinQuant over the whole hidden or intermediate dimension, one read and one
+ * write per element instead of a dense [n, n] matmul followed by the three-launch dynamic chain.
+ * in / out: [rows, n] contiguous; n = m 2^k, m in {1, 12, 20, 28}, 512 <= n <= 16384.  R = (H_m (x) H_{2^k}) / sqrt(n) on the row widened
+ * to fp32: the k butterfly stages of dmxq_hadamard_qdq (strides ascending, inside each of the m chunks of 2^k elements), then for m > 1
+ * the m-point stage across the chunks (w[a] = sum_a' H_m[a][a'] v[a' 2^k + b], left to right from +-v[b], one fp32 operation per term,
+ * from the old values), then ONE fp32 multiply by (float)(1 / sqrt((double)n)).  H_12, H_20: Paley I (q = 11, 19); H_28: Paley II
+ * (q = 13); dmxq_hadamard_matrix writes the m x m table of +-1 (m = 1, 12, 20, 28; a host function).  R^T -- the inverse of R -- runs the
+ * m-point stage FIRST, with H_m^T, then the butterflies, then the multiply.  `transpose` swaps R and R^T in what follows:
+ *   precision == 0               out = round_to(dtype_out, R(x))            (inverse must be 0; dtype_out = dtype_in or float32)
+ *   precision  > 0, no inverse   out = round_to(dtype_out, Q(R(x)))         (dtype_out = dtype_in)
+ *   precision  > 0, inverse      out = round_to(dtype_out, R^T(Q(R(x))))
+ * Q: dmxq_dynamic_fixed_qdq's arithmetic on the rotated fp32 row, bit for bit, for the clamped nearest-rounding format XP[precision,0]:
+ * segment == n: the row is the segment (per token); otherwise groups of `segment` elements, a power of two from 16 to 256 dividing 2^k.
+ * symmetric: bit 0 = symmetric scale scheme (zero point 0: dmxq_qparams' symmetric_qscheme), bit 1 = the format's own symmetric range
+ * (qmin = -2^(precision-1) + 1).  scale_out / zero_point_out: each NULL, or a DEVICE array of rows * n / segment entries.
+ * in == out is allowed when both dtypes have one width.  No allocation, no host synchronisation: capturable.
+ * dmxq_hadamard_row_class: the ONE routing rule (a host function; the entry calls it): 0 = not taken, WAVE = a 64-thread workgroup per
+ * row (up to 256 16-byte vectors), BLOCK = a 256-thread workgroup per row; segment 0 or n: no groups.
+ * DMXQ_ERR_BAD_ARG: null pointers, negative sizes, an invalid dtype, inverse without a format, in == out with dtypes of different
+ * widths.  DMXQ_ERR_UNSUPPORTED, nothing launched (the caller runs its chain, same bits): class 0, pointers that are not 16-byte
+ * aligned, other dtype pairs, precision outside 2 .. 22. */
+typedef enum { DMXQ_HADROW_NONE = 0, DMXQ_HADROW_WAVE = 1, DMXQ_HADROW_BLOCK = 2 } dmxq_hadamard_row_geometry;
+int dmxq_hadamard_row_class(int64_t n, int dtype_in, int64_t segment);
+int dmxq_hadamard_matrix(int m, int8_t* table);
+int dmxq_hadamard_row_qdq(const void* in, void* out, int dtype_in, int dtype_out, int64_t rows, int64_t n, int transpose, int inverse,
+                          int precision, int symmetric, int64_t segment, float* scale_out, int64_t* zero_point_out, void* stream);
 
 /* Dynamic integer cast (csrc/dynamic_quant.hip): every segment of `segment` consecutive elements of the contiguous
  * [n_segments, segment] tensor takes its scale and zero point from its OWN minimum and maximum, on every call, in ONE launch.  Not in
