@@ -875,6 +875,50 @@ def dynamic_fixed_qdq(x, segment, whole_rows, precision, fraction, clamp, symmet
     return out, sc, zp
 
 
+# ------------------------------------------------------------------------------------------------ dynamic casts along a non-last dimension
+def _cols_args(xc, dim, segment, what):
+    """x viewed as [outer, C, inner] around `dim` (non-negative) -> (outer, C, inner, the qparams' shape: x's with C / segment at dim)"""
+    if not 0 <= dim < xc.dim() or segment < 1 or xc.shape[dim] % segment != 0:
+        raise RuntimeError(f"{what}: dim must be a dimension of x and the segment must divide its extent")
+    C = xc.shape[dim]
+    outer = 1
+    for d in xc.shape[:dim]:
+        outer *= d
+    inner = 1
+    for d in xc.shape[dim + 1:]:
+        inner *= d
+    return outer, C, inner, tuple(xc.shape[:dim]) + (C // segment,) + tuple(xc.shape[dim + 1:])
+
+
+@_guarded
+def dynamic_fixed_qdq_cols(x, dim, segment, precision, fraction, clamp, symmetric, rounding, qmin, qmax, symmetric_qscheme, want_qparams,
+                           out_dtype=None):
+    """-> (out, scale float32, zero_point int64): the qparams in x's shape with C / segment at dim, empty unless want_qparams"""
+    xc = _prep(x, "dynamic_fixed_qdq_cols")
+    outer, C, inner, q_shape = _cols_args(xc, dim, segment, "dynamic_fixed_qdq_cols")
+    out = torch.empty(xc.shape, dtype=out_dtype or xc.dtype, device=xc.device)
+    sc = torch.empty(q_shape if want_qparams else 0, dtype=torch.float32, device=xc.device)
+    zp = torch.empty(q_shape if want_qparams else 0, dtype=torch.int64, device=xc.device)
+    check(lib().dmxq_dynamic_fixed_qdq_cols(ptr(xc), ptr(out), dtype_code(xc.dtype), dtype_code(out.dtype), outer, C, inner, segment, precision,
+                                            fraction, int(bool(clamp)), int(bool(symmetric)), rounding, qmin, qmax, int(bool(symmetric_qscheme)),
+                                            ptr(sc) if want_qparams else None, ptr(zp) if want_qparams else None, stream_of(xc)),
+          "dmxq_dynamic_fixed_qdq_cols")
+    return out, sc, zp
+
+
+@_guarded
+def dynamic_float_qdq_cols(x, dim, segment, man, exp, bias, flush_subnormal, rounding, pow2_scale, want_scale, out_dtype=None):
+    """-> (out, scale float32 in x's shape with C / segment at dim, empty unless want_scale)"""
+    xc = _prep(x, "dynamic_float_qdq_cols")
+    outer, C, inner, q_shape = _cols_args(xc, dim, segment, "dynamic_float_qdq_cols")
+    out = torch.empty(xc.shape, dtype=out_dtype or xc.dtype, device=xc.device)
+    sc = torch.empty(q_shape if want_scale else 0, dtype=torch.float32, device=xc.device)
+    check(lib().dmxq_dynamic_float_qdq_cols(ptr(xc), ptr(out), dtype_code(xc.dtype), dtype_code(out.dtype), outer, C, inner, segment, man, exp,
+                                            bias, int(bool(flush_subnormal)), rounding, int(bool(pow2_scale)), ptr(sc) if want_scale else None,
+                                            stream_of(xc)), "dmxq_dynamic_float_qdq_cols")
+    return out, sc
+
+
 # ------------------------------------------------------------------------------------------------ learned step size (backward)
 @_guarded
 def lsq_backward(x, g, scale, zero_point, segment, whole_rows, precision, rounding, qmin, qmax, grad_factor, want_dz, want_dx):

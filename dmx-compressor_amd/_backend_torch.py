@@ -58,6 +58,8 @@ _FAST_CALIBRATION_NAMES = {"hist_observe": "hist_observe", "hist_qparams": "hist
                            "dynamic_fixed_qdq": "dynamic_fixed_qdq",
                            # the dynamic scaled float cast: the same
                            "dynamic_float_qdq": "dynamic_float_qdq",
+                           # the two along a non-last dimension: the same
+                           "dynamic_fixed_qdq_cols": "dynamic_fixed_qdq_cols", "dynamic_float_qdq_cols": "dynamic_float_qdq_cols",
                            # the block-scaled float cast: the same
                            "block_scaled_float_qdq": "block_scaled_float_qdq", "block_scaled_tensor_scale": "block_scaled_tensor_scale",
                            # the learned step size backward: called from inside an autograd Function of the front end (_front.py)

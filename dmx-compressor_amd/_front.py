@@ -26,7 +26,7 @@ __all__ = [
     "HADAMARD_ROW_CHAIN_BY_DEFAULT",
     "dynamic_fixed_qdq", "dynamic_check", "dynamic_class", "DYNAMIC_GRANULARITIES", "DYNAMIC_CHAIN_BY_DEFAULT",
     "dynamic_float_qdq", "dynamic_float_check", "dynamic_float_class", "dynamic_float_fmax", "DYNAMIC_FLOAT_GRANULARITIES",
-    "DYNAMIC_FLOAT_CHAIN_BY_DEFAULT",
+    "DYNAMIC_FLOAT_CHAIN_BY_DEFAULT", "dynamic_cols_class", "DYNAMIC_COLS_CHAIN_BY_DEFAULT",
     "codebook_qdq", "codebook_check", "codebook_class", "codebook_accumulate", "codebook_fit", "CODEBOOKS", "NF4", "CODEBOOK_GRANULARITIES",
     "CODEBOOK_KERNEL_LEVELS", "CODEBOOK_CHAIN_BY_DEFAULT",
     "vq_qdq", "vq_check", "vq_grid", "vq_class", "vq_accumulate", "vq_fit", "VQ_DIMS", "VQ_CHAIN_BY_DEFAULT", "VQ_CHAIN_PIECE_ENTRIES",
@@ -1248,6 +1248,91 @@ def dynamic_class(segment: int, dtype: torch.dtype, whole_rows: bool) -> Optiona
     return _DYNAMIC_CLASS_NAMES.get(lib().dmxq_dynamic_class(dtype_code(dtype), int(segment), int(bool(whole_rows))))
 
 
+# ---- segments along a non-last dimension (csrc/dynamic_cols.hip), shared by dynamic_fixed_qdq and dynamic_float_qdq
+# Geometries of dmxq_dynamic_fixed_qdq_cols / dmxq_dynamic_float_qdq_cols (dynamic_cols_class) that fused=None sends to the transposing
+# route although the kernels take them: DYNAMIC_CHAIN_BY_DEFAULT's rule -- a class goes to the kernel by default only where
+# tools/bench_dynamic_cols.py MEASURED it faster than movedim().contiguous() -> the last-dim kernel -> movedim().contiguous() on the same
+# buffers; a class that is not gets listed here with its row.  profiles/r27_dynamic_cols.txt (bf16 unless noted, us per call, kernel
+# against the transposing route, and against the last-dim kernel on the same tensor -- the one-read one-write bound): cols_r8 keys
+# [8,32,4096,128] INT4 g32 dim -2 116.8 against 1034.7 (bound 94.8), [4096,4096] INT4 g16 dim 0 22.7 against 154.9 (18.1), g64 26.2 against
+# 155.6 (18.0); cols_r16 keys g128 154.5 against 1021.8 (94.2), Conv1D weight [4096,4096] INT4 g128 dim 0 21.8 against 154.6 (18.2),
+# activations [8192,4096] E4M3 g128 dim 0 45.8 against 290.2 (30.0), small [2048,768] g128 dim 0 INT4 15.4 against 29.5 (3.4: 24 workgroups
+# do not fill the device), E4M3 17.4 against 30.0 (3.8); cols_r16w16 [4096,4096] INT4 g256 dim 0 float32 30.2 against 168.8 (27.2), bf16 (half
+# vectors) 21.0 against 155.0 (18.2) -- every class is faster (1.7 x .. 8.9 x), none is listed.  Not measured: f16, f32 outside the g256
+# row, per_token columns, the symmetric scheme.
+DYNAMIC_COLS_CHAIN_BY_DEFAULT = frozenset()
+_dynamic_cols_routes = {"fused": 0, "chain": 0}
+_DYNAMIC_COLS_CLASS_NAMES = {7: "cols_r8", 8: "cols_r16", 9: "cols_r16w16"}   # dmxq_dynamic_cols_geometry (include/dmxq.h)
+
+
+def dynamic_cols_class(segment: int, dtype: torch.dtype, inner: int) -> Optional[str]:
+    """the geometry the column kernels pick for segments of `segment` indices along a non-last dimension of a `dtype` tensor whose
+    trailing dimensions hold `inner` elements, asked of the library itself (dmxq_dynamic_cols_class; no GPU involved), or None when they
+    refuse them: "cols_r8" (segments of 16 .. 64: segment / 8 waves, 8 rows per lane), "cols_r16" (128: 8 waves, 16 rows per lane),
+    "cols_r16w16" (256: 16 waves; a sixteen-bit lane moves half a vector).  inner must be a whole number of 16-byte vectors."""
+    from ._lib import dtype_code, lib
+    return _DYNAMIC_COLS_CLASS_NAMES.get(lib().dmxq_dynamic_cols_class(dtype_code(dtype), int(segment), int(inner)))
+
+
+def _cols_dim(x, dim, granularity, group_size, what):
+    """-> the non-negative dimension the segments run along, or None for the last one (the code that ran before `dim` existed); ValueError
+    before any GPU use: a dim outside the tensor's rank, per_tensor / per_tile with a dim, a group size that does not divide the extent"""
+    if isinstance(dim, bool) or not isinstance(dim, int) or not -x.dim() <= dim < x.dim():
+        raise ValueError(f"{what}: dim must be an integer in [{-x.dim()}, {x.dim() - 1}] for a {x.dim()}-d tensor, got {dim!r}")
+    d = dim % x.dim()
+    if d == x.dim() - 1:
+        return None
+    if granularity not in ("per_group", "per_token"):
+        raise ValueError(f"{what}: dim={dim} goes with 'per_group' / 'per_token' only, got {granularity!r}")
+    if granularity == "per_group" and x.shape[d] % group_size:
+        raise ValueError(f"{what}: dimension {dim} has {x.shape[d]} elements, not a multiple of the group size {group_size}")
+    return d
+
+
+def _dynamic_cols(x, d, granularity, group_size, out_dtype, want, fused, fmt_ok, kernel, last, q_dtypes, what):
+    """the dynamic cast with segments along dimension d (not the last): kernel(xc, S, want) is the raw column op, last(xt, want) the
+    last-dim front end on the transposed tensor (the definition, and the fallback).  -> y, or (y, *qparams) under `want`."""
+    require_gpu(x, what)
+    out_dtype = out_dtype or x.dtype
+    C = x.shape[d]
+    S = group_size if granularity == "per_group" else C
+
+    def run(xd):
+        xc = xd if xd.is_contiguous() else xd.contiguous()
+        q_shape = tuple(xc.shape[:d]) + (C // S if S else 0,) + tuple(xc.shape[d + 1:])
+        if xc.numel() == 0:
+            y = torch.empty(xc.shape, dtype=out_dtype, device=xc.device)
+            return (y,) + tuple(y.new_empty(q_shape, dtype=t) for t in q_dtypes) if want else y
+        if fused is not False:
+            inner = xc.numel() // (C * math.prod(xc.shape[:d]))
+            cls = dynamic_cols_class(S, xc.dtype, inner) if (fmt_ok and out_dtype == xc.dtype and xc.data_ptr() % 16 == 0) else None
+            if cls is None and fused:
+                raise NotImplementedError(f"{what}: no fused kernel for segments of {S} along dim {d} of a {tuple(xc.shape)} {xc.dtype} tensor -> "
+                                          f"{out_dtype} (base address {xc.data_ptr() % 16} mod 16)")
+            if cls is not None and fused is None and cls in DYNAMIC_COLS_CHAIN_BY_DEFAULT:
+                cls = None
+            if cls is not None:
+                try:
+                    out = kernel(xc, S, bool(want))
+                    _dynamic_cols_routes["fused"] += 1
+                    return tuple(out) if want else out[0]
+                except NotImplementedError:   # (DMXQ_ERR_UNSUPPORTED, nothing launched)
+                    if fused:
+                        raise
+        _dynamic_cols_routes["chain"] += 1
+        xt = xc.movedim(d, -1).contiguous()
+        out = last(xt, bool(want))
+        if not want:
+            return out.movedim(-1, d).contiguous()
+        qt = tuple(xt.shape[:-1]) + (C // S,)
+        return (out[0].movedim(-1, d).contiguous(),) + tuple(q.reshape(qt).movedim(-1, d).contiguous() for q in out[1:])
+
+    if x.requires_grad and torch.is_grad_enabled():
+        return _DynamicSTE.apply(x, run)
+    with torch.no_grad():
+        return run(x.detach())
+
+
 class _DynamicSTE(torch.autograd.Function):
     """the dynamic cast as a straight-through estimator (cast.py _FixedAffineCast: the scales are not differentiated either)"""
 
@@ -1268,7 +1353,8 @@ class _DynamicSTE(torch.autograd.Function):
 
 
 def dynamic_fixed_qdq(x, fmt, granularity: str = "per_token", group_size: Optional[int] = None, symmetric_qscheme: bool = False,
-                      out_dtype: Optional[torch.dtype] = None, return_qparams: bool = False, fused: Optional[bool] = None, seed: Optional[int] = None):
+                      out_dtype: Optional[torch.dtype] = None, return_qparams: bool = False, fused: Optional[bool] = None, seed: Optional[int] = None,
+                      dim: int = -1):
     """Integer Q->DQ with scales derived from the tensor itself on every call (not in the reference, whose integer casts
     need a calibration pass).  A segment is S consecutive elements along the last dim of the contiguous tensor: the whole row with
     "per_token" (per output channel of an [out, in] weight), `group_size` elements with "per_group" (it must divide the last dim), the
@@ -1287,11 +1373,28 @@ def dynamic_fixed_qdq(x, fmt, granularity: str = "per_token", group_size: Option
     its piece of the chain.
     return_qparams: (y, scale float32 [n_segments], zero_point int64 [n_segments]) on both routes.
     ValueError (before any GPU use): a format without an integer range, an unknown granularity, a group_size that does not divide the
-    last dim.  Autograd: a straight-through estimator."""
+    last dim.  Autograd: a straight-through estimator.
+    dim: the dimension the segments run along (default: the last).  Another dimension: per_group takes groups of group_size along it,
+    per_token its whole extent; by definition the call on x.movedim(dim, -1).contiguous(), moved back, bit for bit, each of scale and zero
+    point in x's shape with extent C / S at dim (_dynamic_cols: the kernel of csrc/dynamic_cols.hip or the transposing route)."""
     from .observer import get_qmin_qmax
     fmt, granularity, group_size = dynamic_check(fmt, granularity, group_size)
     if x.dim() < 1:
         raise ValueError("dynamic_fixed_qdq: expects a tensor with at least one dimension")
+    d = _cols_dim(x, dim, granularity, group_size, "dynamic_fixed_qdq")
+    if d is not None:
+        qmin, qmax = get_qmin_qmax(fmt)
+        ok = fmt.rounding == "nearest" and fmt.precision <= 22 and fmt.fraction == 0 and bool(fmt.clamp)   # (all the entry takes)
+
+        def kernel(xc, S, want):
+            return _ops.dynamic_fixed_qdq_cols(xc, d, S, fmt.precision, fmt.fraction, bool(fmt.clamp), bool(fmt.symmetric), ROUNDING_CODE[fmt.rounding],
+                                               qmin, qmax, bool(symmetric_qscheme), want, out_dtype or xc.dtype)
+
+        def last(xt, want):
+            return dynamic_fixed_qdq(xt, fmt, granularity, group_size, symmetric_qscheme, out_dtype, want, None, seed)
+
+        return _dynamic_cols(x, d, granularity, group_size, out_dtype, return_qparams, fused, ok, kernel, last, (torch.float32, torch.int64),
+                             "dynamic_fixed_qdq")
     L = x.shape[-1]
     if granularity == "per_group" and L % group_size:
         raise ValueError(f"dynamic_fixed_qdq: the last dimension has {L} elements, not a multiple of the group size {group_size}")
@@ -1607,7 +1710,7 @@ def _scale_from_amax(amax, fmax: float, pow2_scale: bool):
 
 def dynamic_float_qdq(x, fmt, granularity: str = "per_token", group_size: Optional[int] = None, pow2_scale: bool = False,
                       out_dtype: Optional[torch.dtype] = None, return_scale: bool = False, fused: Optional[bool] = None,
-                      seed: Optional[int] = None):
+                      seed: Optional[int] = None, dim: int = -1):
     """Low-bit float Q->DQ with a scale derived from the tensor itself on every call (not in the reference, whose float
     casts are unscaled): the FP8 recipe's per-token / per-group activations and per-channel / per-tile weights.  `fmt` is a signed
     FloatingPoint format with fewer than 8 exponent bits; fmax = 2^(2^(e-1)) (2 - 2^-m) is its largest output (480 for FP[1|4|3,7], 114688
@@ -1628,8 +1731,22 @@ def dynamic_float_qdq(x, fmt, granularity: str = "per_token", group_size: Option
     DYNAMIC_FLOAT_CHAIN_BY_DEFAULT; True: NotImplementedError instead of falling back; False: the chain.  seed: for a stochastic-rounding
     format (the chain only), as ops.float_qdq takes it.  return_scale: (y, scale) with scale float32 [n_segments], or [..., R/g, C/g] for
     tiles, on both routes.  ValueError (before any GPU use): a format that cannot be scaled, an unknown granularity, a group_size that does
-    not divide.  Autograd: a straight-through estimator.  Nothing is read back to the host."""
+    not divide.  Autograd: a straight-through estimator.  Nothing is read back to the host.
+    dim: the dimension the segments run along (default: the last), as in dynamic_fixed_qdq: per_group / per_token only, by definition the
+    call on x.movedim(dim, -1).contiguous() moved back, the scale in x's shape with extent C / S at dim."""
     fmt, granularity, group_size = dynamic_float_check(fmt, granularity, group_size)
+    d = _cols_dim(x, dim, granularity, group_size, "dynamic_float_qdq") if x.dim() >= 1 else None
+    if d is not None:
+        ok = fmt.rounding == "nearest" and fmt.mantissa <= 22
+
+        def kernel(xc, S, want):
+            return _ops.dynamic_float_qdq_cols(xc, d, S, fmt.mantissa, fmt.exponent, fmt.bias, bool(fmt.flush_subnormal), ROUNDING_CODE[fmt.rounding],
+                                               bool(pow2_scale), want, out_dtype or xc.dtype)
+
+        def last(xt, want):
+            return dynamic_float_qdq(xt, fmt, granularity, group_size, pow2_scale, out_dtype, want, None, seed)
+
+        return _dynamic_cols(x, d, granularity, group_size, out_dtype, return_scale, fused, ok, kernel, last, (torch.float32,), "dynamic_float_qdq")
     tile = granularity == "per_tile"
     if x.dim() < (2 if tile else 1):
         raise ValueError(f"dynamic_float_qdq: {granularity} expects a tensor with at least {2 if tile else 1} dimension(s)")

@@ -86,6 +86,9 @@ SIGNATURES = {
     "dmxq_dynamic_float_class": [_i32, _i32, _i64],
     "dmxq_dynamic_float_qdq": [_vp, _vp, _i32, _i32, _i32, _i64, _i64, _i64, _i64, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp],
     "dmxq_dynamic_fixed_qdq": [_vp, _vp, _i32, _i32, _i64, _i64, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp],
+    "dmxq_dynamic_cols_class": [_i32, _i64, _i64],
+    "dmxq_dynamic_fixed_qdq_cols": [_vp, _vp, _i32, _i32, _i64, _i64, _i64, _i64, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp],
+    "dmxq_dynamic_float_qdq_cols": [_vp, _vp, _i32, _i32, _i64, _i64, _i64, _i64, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp],
     "dmxq_channel_sumsq_workspace_bytes": [_i64, _i64],
     "dmxq_channel_sumsq_accumulate": [_vp, _i32, _i64, _i64, _vp, _vp, _vp],
     "dmxq_wanda_class": [_i32, _i64, _i32],

@@ -14,6 +14,7 @@ from torch.autograd import Function
 
 from . import ops
 from ._flags import HostFlags
+from ._lib import DmxqError
 from .format import FixedPoint, FloatingPoint, Format, Same
 from .observer import _PER_CHANNEL, _SYMMETRIC, DummyObserver, HistogramObserver, MinMaxObserver, ObserverBase
 
@@ -119,6 +120,49 @@ def _parse_dynamic(granularity, group_size=None):
     return granularity, group_size
 
 
+def _split_dim(setting, what):
+    """a dict setting of set_dynamic / set_scaling with "dim" -> (the setting without it, dim); every other setting passes through with
+    None.  dim: the dimension the segments run along (ops.dynamic_fixed_qdq / ops.dynamic_float_qdq), kept as spelled and normalised
+    against the tensor's rank at every forward.  Without other keys than "granularity" the rest is the granularity's name."""
+    if not isinstance(setting, dict) or "dim" not in setting:
+        return setting, None
+    d = dict(setting)
+    dim = d.pop("dim")
+    if isinstance(dim, bool) or not isinstance(dim, int):
+        raise ValueError(f"{what}: 'dim' must be an integer, got {dim!r}")
+    if set(d) == {"granularity"}:
+        d = d["granularity"]
+    return d, dim
+
+
+def _dim_is_last(dim, rank=None):
+    """whether `dim` names the last dimension: True / False, or None where only the tensor's rank can tell (a non-negative dim before
+    the first forward); ValueError for a dim outside a known rank"""
+    if dim is None or dim == -1:
+        return True
+    if rank is None:
+        return False if dim < -1 else None
+    if not -rank <= dim < rank:
+        raise ValueError(f"a dynamic setting with dim = {dim} on a {rank}-d tensor")
+    return dim % rank == rank - 1
+
+
+def _refuse_with_dim(what, dim, outliers=False, block_scale=False, granularity=None, pre_transform=None):
+    """the settings that do not go with segments along a dimension other than the last (DESIGN.md §8 "Dynamic casts along a non-last
+    dimension"): ValueError -- at set time where dim alone tells, else at the first forward"""
+    why = None
+    if outliers:
+        why = "'outliers' (ops.outlier_fixed_qdq selects inside runs of the last dimension)"
+    elif block_scale:
+        why = "'scale_format' (ops.block_scaled_float_qdq quantises the scales of runs of the last dimension)"
+    elif granularity not in (None, "per_group", "per_token"):
+        why = f"granularity {granularity!r} ('per_group' / 'per_token' only)"
+    elif pre_transform and ("hadamard" in pre_transform or "hadamard_row" in pre_transform):
+        why = "a 'hadamard' / 'hadamard_row' pre_transform (the rotation and the fused casts run along the last dimension)"
+    if why is not None:
+        raise ValueError(f"{what}: dim = {dim}, a dimension other than the last, does not go with {why}")
+
+
 _OUTLIER_KEYS = ("outliers", "outlier_format")
 
 
@@ -208,6 +252,10 @@ class CastTo(HostFlags, torch.nn.Module):
     #: None, or (granularity, group_size, pow2_scale): a float format is cast with a scale derived from every tensor itself (set_scaling;
     #: DESIGN.md §8).  A plain attribute as well.
     _scaling = None
+    #: None, or the "dim" of the set_dynamic / set_scaling setting as spelled: the dimension the segments run along (normalised against
+    #: the tensor's rank at every forward; DESIGN.md §8 "Dynamic casts along a non-last dimension").  Plain attributes as well.
+    _dynamic_dim = None
+    _scaling_dim = None
     #: None, or (scale_format, scale_max, tensor_scale) beside a per_group _scaling: the group scales are quantised to scale_format under
     #: one float32 scale per tensor (ops.block_scaled_float_qdq).  A plain attribute as well.
     _block_scale = None
@@ -313,6 +361,10 @@ class CastTo(HostFlags, torch.nn.Module):
                 if other is not None:
                     raise ValueError(msg)
             self.pre_transform["hadamard_row"] = _parse_hadamard_row(spec)
+        for dim in (self._dynamic_dim, self._scaling_dim):
+            if _dim_is_last(dim) is False and ("hadamard" in self.pre_transform or "hadamard_row" in self.pre_transform):
+                pt, self.pre_transform = self.pre_transform, {k: v for k, v in self.pre_transform.items() if not k.startswith("hadamard")}
+                _refuse_with_dim("CastTo.set_pre_transform", dim, pre_transform=pt)
 
     def set_dynamic(self, granularity=None, group_size=None):
         """Dynamic scales (not in the reference): with fake-quant on and the observer off, an integer format is cast with a
@@ -324,9 +376,16 @@ class CastTo(HostFlags, torch.nn.Module):
         set_format when the format comes later (a cast that is still SAME accepts the setting).
         Outliers (DESIGN.md §8 "Outlier-aware dynamic cast"): {"per_group": g, "outliers": k} or {"granularity": "per_token", "outliers": k},
         each optionally with "outlier_format" (None: the value itself; or a per-element FloatingPoint format), keep every segment's k largest
-        magnitudes at that precision and derive the scale from the rest (ops.outlier_fixed_qdq); "outliers": 0 is the plain setting."""
+        magnitudes at that precision and derive the scale from the rest (ops.outlier_fixed_qdq); "outliers": 0 is the plain setting.
+        Along another dimension (DESIGN.md §8 "Dynamic casts along a non-last dimension"): {"per_group": g, "dim": d} or {"granularity":
+        "per_token", "dim": d} take the groups / the whole extent along dimension d (ops.dynamic_fixed_qdq's dim), d normalised against
+        the tensor's rank at every forward.  With a d other than the last dimension "outliers", per_tensor and a "hadamard" /
+        "hadamard_row" pre_transform are refused: ValueError here where d alone tells (d < -1), else at the first forward."""
+        granularity, dim = _split_dim(granularity, "set_dynamic")
         granularity, out = _parse_outliers(granularity)
         dyn = _parse_dynamic(granularity, group_size)
+        if dim is not None and dyn is None:
+            raise ValueError(f"set_dynamic: 'dim' = {dim} without a granularity")
         if dyn is not None and self._codebook is not None:
             raise ValueError("CastTo.set_dynamic: " + _CODEBOOK_EXCLUSIVE)
         if dyn is not None and self._vq is not None:
@@ -342,8 +401,11 @@ class CastTo(HostFlags, torch.nn.Module):
             _, _, k_, ofmt_ = ops.outlier_check("XP[8,0](CSN)" if isinstance(self.format, Same) else self.format, dyn[1], out["k"],
                                                    out["outlier_format"], dyn[0], what="CastTo.set_dynamic")
             out = {"k": k_, "outlier_format": ofmt_} if k_ else None
+        if _dim_is_last(dim) is False:
+            _refuse_with_dim("CastTo.set_dynamic", dim, outliers=out is not None, granularity=dyn[0], pre_transform=self.pre_transform)
         self._dynamic = dyn
         self._outliers = out
+        self._dynamic_dim = dim
 
     @property
     def dynamic(self):
@@ -357,11 +419,29 @@ class CastTo(HostFlags, torch.nn.Module):
             d["outliers"] = self._outliers["k"]
             if self._outliers["outlier_format"] is not None:
                 d["outlier_format"] = repr(self._outliers["outlier_format"])
+            if self._dynamic_dim is not None:
+                d["dim"] = self._dynamic_dim
             return d
+        if self._dynamic_dim is not None:   # (with "dim": the dict spelling it was set in)
+            return {"per_group": dyn[1], "dim": self._dynamic_dim} if dyn[0] == "per_group" else {"granularity": dyn[0], "dim": self._dynamic_dim}
         return {"per_group": dyn[1]} if dyn[0] == "per_group" else dyn[0]
+
+    def refuse_groups_along_dim(self, what, rank):
+        """THE check of every consumer that reads a dynamic weight cast's groups as runs along the LAST dimension (GPTQ's dynamic path, AWQ
+        and the AWQ clip, HQQ, AdaRound, Wanda, folding): DmxqError where this cast's set_dynamic / set_scaling setting names another
+        dimension of a rank-`rank` weight; called before any state is touched"""
+        for name, dim, setting in (("weight_dynamic", self._dynamic_dim, self.dynamic), ("weight_scaling", self._scaling_dim, self.scaling)):
+            if setting is not None and dim is not None and not (-rank <= dim < rank and dim % rank == rank - 1):
+                raise DmxqError(f"{what} reads the weight cast's groups as runs along the last dimension; {name} = {setting!r} runs them "
+                                f"along dimension {dim} of the {rank}-d weight: clear \"dim\" first")
 
     def _dynamic_cast(self, x, out_dtype):
         g, gs = self._dynamic
+        if not _dim_is_last(self._dynamic_dim, x.dim()):   # segments along another dimension: the refusals the rank decides, then the op
+            _refuse_with_dim("CastTo with a dynamic setting", self._dynamic_dim, outliers=self._outliers is not None, granularity=g,
+                             pre_transform=self.pre_transform)
+            return ops.dynamic_fixed_qdq(x, self.format, g, gs, symmetric_qscheme=self.qscheme in _SYMMETRIC, out_dtype=out_dtype,
+                                         dim=self._dynamic_dim)
         if self._outliers is not None:
             return ops.outlier_fixed_qdq(x, self.format, gs, self._outliers["k"], symmetric_qscheme=self.qscheme in _SYMMETRIC,
                                          outlier_format=self._outliers["outlier_format"], granularity=g, out_dtype=out_dtype)
@@ -506,8 +586,11 @@ class CastTo(HostFlags, torch.nn.Module):
         "scale_max" and "tensor_scale" ("dynamic" -- the default --, None, a float or a one-element tensor) casts every group's scale to
         the float format Sf under one float32 scale per tensor -- ops.NVFP4 is the ready setting for FP[1|2|1,1](_N).  These keys go with
         per_group only and not with pow2_scale: ValueError otherwise."""
+        granularity, dim = _split_dim(granularity, "set_scaling")
         granularity, block = _split_block_scale(granularity)
         sc = _parse_scaling(granularity, group_size, pow2_scale)
+        if dim is not None and sc is None:
+            raise ValueError(f"set_scaling: 'dim' = {dim} without a granularity")
         if sc is not None and self._codebook is not None:
             raise ValueError("CastTo.set_scaling: " + _CODEBOOK_EXCLUSIVE)
         if sc is not None and self._vq is not None:
@@ -528,7 +611,9 @@ class CastTo(HostFlags, torch.nn.Module):
                 _, _, smax = ops.block_scaled_check(fmt, sc[1], block["scale_format"], block.get("scale_max"),
                                                     block.get("tensor_scale", "dynamic"), what="CastTo.set_scaling")
                 block = (block["scale_format"], smax, block.get("tensor_scale", "dynamic"))
-        self._scaling, self._block_scale = sc, block
+        if _dim_is_last(dim) is False:
+            _refuse_with_dim("CastTo.set_scaling", dim, block_scale=block is not None, granularity=sc[0], pre_transform=self.pre_transform)
+        self._scaling, self._block_scale, self._scaling_dim = sc, block, dim
 
     @property
     def scaling(self):
@@ -540,14 +625,21 @@ class CastTo(HostFlags, torch.nn.Module):
         g, gs, pow2 = sc
         if self._block_scale is not None:
             sf, smax, ts = self._block_scale
-            return {"per_group": gs, "scale_format": sf if isinstance(sf, str) else repr(sf), "scale_max": smax, "tensor_scale": ts}
+            out = {"per_group": gs, "scale_format": sf if isinstance(sf, str) else repr(sf), "scale_max": smax, "tensor_scale": ts}
+            return out if self._scaling_dim is None else dict(out, dim=self._scaling_dim)
         out = {g: gs} if g in ("per_group", "per_tile") else g
         if pow2:
             out = dict(out, pow2_scale=True) if isinstance(out, dict) else {"granularity": g, "pow2_scale": True}
+        if self._scaling_dim is not None:   # (with "dim": the dict spelling it was set in)
+            out = dict(out, dim=self._scaling_dim) if isinstance(out, dict) else {"granularity": g, "dim": self._scaling_dim}
         return out
 
     def _scaled_cast(self, x, out_dtype):
         g, gs, pow2 = self._scaling
+        if not _dim_is_last(self._scaling_dim, x.dim()):   # (as _dynamic_cast)
+            _refuse_with_dim("CastTo with a scaling setting", self._scaling_dim, block_scale=self._block_scale is not None, granularity=g,
+                             pre_transform=self.pre_transform)
+            return ops.dynamic_float_qdq(x, self.format, g, gs, pow2_scale=pow2, out_dtype=out_dtype, dim=self._scaling_dim)
         if self._block_scale is not None:
             sf, smax, ts = self._block_scale
             return ops.block_scaled_float_qdq(x, self.format, gs, sf, smax, ts, out_dtype=out_dtype)
@@ -876,6 +968,8 @@ class CastTo(HostFlags, torch.nn.Module):
         or per-group integer cast, the group a power of two 16 .. 256 dividing 2^k; the row length is validated here (ValueError)"""
         _, k = ops.hadamard_row_check(int(x.shape[-1]) if x.dim() else 0, "CastTo with a 'hadamard_row' pre_transform")
         dyn = self._dynamic
+        if dyn is not None and not _dim_is_last(self._dynamic_dim, x.dim()):
+            _refuse_with_dim("CastTo with a dynamic setting", self._dynamic_dim, pre_transform=self.pre_transform)
         if dyn is None or self._outliers is not None or self._scaling is not None or not isinstance(self.format, FixedPoint):
             return False
         g, gs = dyn
@@ -897,6 +991,9 @@ class CastTo(HostFlags, torch.nn.Module):
                 raise TypeError("CastTo with a torch.dtype format is torch.ao's stock FakeQuantize path, "
                                 "not part of the accelerated hot path")
             return self._quantize(x, x.dtype)
+        for dim in (self._dynamic_dim, self._scaling_dim):   # (a non-negative dim: only now does the rank tell; before any GPU use)
+            if dim is not None and not _dim_is_last(dim, x.dim()):
+                _refuse_with_dim("CastTo with a dynamic setting", dim, pre_transform=pt)
         had = pt.get("hadamard")
         if had is not None and len(pt) == 1 and d["_h_fake_quant_enabled"] and not d["_h_observer_enabled"] and isinstance(fmt, Format) \
                 and not isinstance(fmt, Same) and self._dynamic is None and self._scaling is None:   # (a dynamic / scaled cast: the step-by-step route below)
@@ -1058,8 +1155,9 @@ class CastToDict(torch.nn.ModuleDict):
     def set_dynamic(self, dynamic):
         """one setting (None, "per_token", "per_tensor", {"per_group": g}, or a dict with "outliers" as CastTo.set_dynamic takes it) for every
         cast, or a list / dict of settings over the casts the way set_pre_transform takes them"""
-        one = isinstance(dynamic, dict) and (set(dynamic) == {"per_group"} or ("outliers" in dynamic and set(dynamic) <= {
-            "per_group", "granularity", *_OUTLIER_KEYS})) and not set(dynamic) & set(self.keys())
+        one = isinstance(dynamic, dict) and (set(dynamic) - {"dim"} == {"per_group"} or (("outliers" in dynamic or "dim" in dynamic)
+                                                                                         and set(dynamic) <= {
+            "per_group", "granularity", "dim", *_OUTLIER_KEYS})) and not set(dynamic) & set(self.keys())
         if dynamic is None or isinstance(dynamic, str) or one:
             for c in self.values():
                 c.set_dynamic(dynamic)
@@ -1078,7 +1176,7 @@ class CastToDict(torch.nn.ModuleDict):
     def set_scaling(self, scaling):
         """one setting (None, "per_token", "per_tensor", {"per_group": g}, {"per_tile": g}, each dict optionally with "pow2_scale"; a
         per_group dict also with "scale_format" / "scale_max" / "tensor_scale", such as ops.NVFP4) for every cast, or a list / dict of settings over the casts the way set_dynamic takes them"""
-        one = isinstance(scaling, dict) and set(scaling) <= {"per_group", "per_tile", "granularity", "pow2_scale", *_BLOCK_SCALE_KEYS} \
+        one = isinstance(scaling, dict) and set(scaling) <= {"per_group", "per_tile", "granularity", "pow2_scale", "dim", *_BLOCK_SCALE_KEYS} \
             and not set(scaling) & set(self.keys())
         if scaling is None or isinstance(scaling, str) or one:
             for c in self.values():

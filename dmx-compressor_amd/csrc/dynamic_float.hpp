@@ -40,6 +40,21 @@ __device__ __forceinline__ void df_quotient_vec(const float (&x)[V], float (&q)[
   }
 }
 
+// the per-element-segment form (csrc/dynamic_cols.hip: element k of a lane's vector belongs to segment k of that lane): the same
+// quotient under V scales, the same cold redo
+template <int V>
+__device__ __forceinline__ void df_quotient_cols(const float (&x)[V], float (&q)[V], const DfSeg (&sg)[V], bool fast) {
+  bool ok = fast;
+#pragma unroll
+  for (int k = 0; k < V; k++) { q[k] = div_by_recip(x[k], sg[k].s, sg[k].rs); ok = ok && div_by_recip_ok(x[k]); }
+  if (__builtin_expect(__builtin_amdgcn_ballot_w64(!ok) != 0ull, 0)) {
+    if (!ok) {
+#pragma unroll
+      for (int k = 0; k < V; k++) q[k] = x[k] / sg[k].s;
+    }
+  }
+}
+
 // the maximum of a workgroup's waves (WAVES > 1): through LDS
 template <int WAVES>
 __device__ __forceinline__ uint32_t df_block_max(uint32_t m) {

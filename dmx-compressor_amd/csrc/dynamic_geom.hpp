@@ -22,6 +22,14 @@ inline int dyn_class(int64_t S, int V, bool whole_rows) {
   return nv <= 16 * kWave ? DMXQ_DYN_WAVE_ROW : DMXQ_DYN_BLOCK_ROW;
 }
 
+// Segments that run down a NON-LAST dimension (dynamic_cols.hip; dmxq_dynamic_cols_class): the contiguous tensor is [outer, C, inner], a
+// segment S consecutive indices along C at one (outer, inner) position.  A workgroup of S / R waves holds a tile of S rows x 64 vectors,
+// R rows per lane: R = 8 up to S = 64, 16 above (S = 256: sixteen waves; a sixteen-bit lane then takes half a vector).  `inner` must be whole 16-byte vectors.
+inline int dync_class(int64_t S, int V, int64_t inner) {
+  if (!dyn_pow2(S) || S < 16 || S > 256 || inner < V || inner % V != 0) return DMXQ_DYN_NONE;
+  return S <= 64 ? DMXQ_DYNC_R8 : (S == 128 ? DMXQ_DYNC_R16 : DMXQ_DYNC_R16W16);
+}
+
 // a g x g tile of the last two dims: 32, 64 or 128 (a tile's 16-byte vectors stay in the registers of a wave or a workgroup)
 inline int dyn_tile_class(int64_t g) { return (g == 32 || g == 64 || g == 128) ? DMXQ_DYN_TILE : DMXQ_DYN_NONE; }
 

@@ -61,13 +61,17 @@ struct DynSeg {
   }
 };
 
-// FixedOp<.., SIMPLE>::q with the IEEE division
-__device__ __forceinline__ float dyn_q_exact(float x, float sc, float z, const DynFmt& f) {
-  const float t = x / sc + z;
+// FixedOp<.., SIMPLE>::q from the quotient q = x / sc.  ZP0: the caller knows z == +0.0f, the + z and - z steps are skipped (exact:
+// common.hpp affine_int_pairs)
+template <bool ZP0 = false>
+__device__ __forceinline__ float dyn_q_of(float q, float sc, float z, const DynFmt& f) {
+  const float t = ZP0 ? q : q + z;
   float v = rintf((t + 0.5f) - 0.5f);
   v = v > f.t_max ? f.t_max : (v < f.t_min ? f.t_min : v);
-  return (v - z) * sc;
+  return (ZP0 ? v : v - z) * sc;
 }
+// ... with the IEEE division
+__device__ __forceinline__ float dyn_q_exact(float x, float sc, float z, const DynFmt& f) { return dyn_q_of(x / sc, sc, z, f); }
 
 // called by whole waves; the recipe is chosen per wave (every segment of the wave inside the reciprocal's range; every zero point 0)
 template <int V>
@@ -84,6 +88,45 @@ __device__ __forceinline__ void dyn_cast_vec(const float (&x)[V], float (&y)[V],
   } else {
 #pragma unroll
     for (int k = 0; k < V; k++) y[k] = dyn_q_exact(x[k], s.sc, s.z, f);
+  }
+}
+
+// THE PER-ELEMENT-SEGMENT FORMS (csrc/dynamic_cols.hip: the segments run down the rows of a tile, so element k of every 16-byte vector
+// of a lane belongs to segment k of that lane): V extrema side by side, and the cast of a vector under V (scale, zero point) pairs.
+template <int V>
+__device__ __forceinline__ void dyn_ext_add_cols(DynExt (&e)[V], const float (&x)[V]) {
+#pragma unroll
+  for (int k = 0; k < V; k++) e[k].FloatExtrema::add(x[k]);
+}
+
+// called by whole waves; the recipe is chosen per wave as in dyn_cast_vec.  The reciprocal quotient is common.hpp div_for_clamped_int per
+// element (the form affine_int_pairs packs for a shared scale: same bits for every finite quotient); a lane with an Inf / NaN quotient
+// redoes its vector with the division behind one cold wave-uniform branch.
+template <int V, bool ZP0>
+__device__ __forceinline__ bool dyn_recip_cols(const float (&x)[V], float (&y)[V], const DynSeg (&s)[V], const DynFmt& f) {
+  bool special = false;
+#pragma unroll
+  for (int k = 0; k < V; k++) {
+    const float q = div_for_clamped_int(x[k], Recip{s[k].sc, s[k].rs});
+    special = special || __builtin_amdgcn_classf(q, 0x001 | 0x002 | 0x004 | 0x200);   // sNaN, qNaN, -inf, +inf
+    y[k] = dyn_q_of<ZP0>(q, s[k].sc, s[k].z, f);
+  }
+  return special;
+}
+template <int V>
+__device__ __forceinline__ void dyn_cast_cols(const float (&x)[V], float (&y)[V], const DynSeg (&s)[V], bool all_fast, bool all_zp0,
+                                              const DynFmt& f) {
+  if (all_fast) {
+    const bool special = all_zp0 ? dyn_recip_cols<V, true>(x, y, s, f) : dyn_recip_cols<V, false>(x, y, s, f);
+    if (__builtin_expect(__builtin_amdgcn_ballot_w64(special) != 0ull, 0)) {
+      if (special) {
+#pragma unroll
+        for (int k = 0; k < V; k++) y[k] = dyn_q_exact(x[k], s[k].sc, s[k].z, f);
+      }
+    }
+  } else {
+#pragma unroll
+    for (int k = 0; k < V; k++) y[k] = dyn_q_exact(x[k], s[k].sc, s[k].z, f);
   }
 }
 

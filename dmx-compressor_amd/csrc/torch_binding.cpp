@@ -1062,6 +1062,60 @@ std::tuple<Tensor, Tensor, Tensor> dynamic_fixed_qdq_meta(const Tensor& x, int64
   return std::make_tuple(empty_like_shape(x, out_dtype), at::empty({n}, x.options().dtype(at::kFloat)), at::empty({n}, x.options().dtype(at::kLong)));
 }
 
+// ------------------------------------------------------------------------------------------------ dynamic casts along a non-last dimension
+// x: contiguous, viewed as [outer, C, inner] around `dim` (non-negative), C % segment == 0; the qparams have x's shape with C / segment
+// at dim (empty unless wanted).  DMXQ_ERR_UNSUPPORTED (NotImplementedError, nothing launched): the front end transposes.
+struct ColsArgs { int64_t outer, C, inner; std::vector<int64_t> q_shape; };
+ColsArgs cols_args(const Tensor& x, int64_t dim, int64_t segment, const char* what) {
+  TORCH_CHECK(dim >= 0 && dim < x.dim() && segment >= 1 && x.size(dim) % segment == 0, what,
+              ": dim must be a dimension of x and the segment must divide its extent");
+  ColsArgs a{1, x.size(dim), 1, std::vector<int64_t>(x.sizes().begin(), x.sizes().end())};
+  for (int64_t d = 0; d < dim; d++) a.outer *= x.size(d);
+  for (int64_t d = dim + 1; d < x.dim(); d++) a.inner *= x.size(d);
+  a.q_shape[dim] = a.C / segment;
+  return a;
+}
+std::tuple<Tensor, Tensor, Tensor> dynamic_fixed_qdq_cols(const Tensor& x, int64_t dim, int64_t segment, int64_t precision, int64_t fraction,
+                                                          bool clamp, bool symmetric, int64_t rounding, int64_t qmin, int64_t qmax,
+                                                          bool symmetric_qscheme, bool want_qparams, OptDtype out_dtype) {
+  const Tensor xc = prep(x, "dynamic_fixed_qdq_cols");
+  const ColsArgs a = cols_args(xc, dim, segment, "dynamic_fixed_qdq_cols");
+  Tensor out = empty_like_shape(xc, out_dtype);
+  Tensor sc = want_qparams ? at::empty(a.q_shape, xc.options().dtype(at::kFloat)) : at::empty({0}, xc.options().dtype(at::kFloat));
+  Tensor zp = want_qparams ? at::empty(a.q_shape, xc.options().dtype(at::kLong)) : at::empty({0}, xc.options().dtype(at::kLong));
+  Launch l(xc);
+  check(dmxq_dynamic_fixed_qdq_cols(xc.data_ptr(), out.data_ptr(), dt_code(xc.scalar_type()), dt_code(out.scalar_type()), a.outer, a.C, a.inner,
+                                    segment, (int)precision, (int)fraction, clamp ? 1 : 0, symmetric ? 1 : 0, (int)rounding, (int)qmin, (int)qmax,
+                                    symmetric_qscheme ? 1 : 0, want_qparams ? (float*)sc.data_ptr() : nullptr,
+                                    want_qparams ? (int64_t*)zp.data_ptr() : nullptr, l.stream), "dmxq_dynamic_fixed_qdq_cols");
+  return std::make_tuple(out, sc, zp);
+}
+std::tuple<Tensor, Tensor, Tensor> dynamic_fixed_qdq_cols_meta(const Tensor& x, int64_t dim, int64_t segment, int64_t, int64_t, bool, bool, int64_t,
+                                                               int64_t, int64_t, bool, bool want_qparams, OptDtype out_dtype) {
+  const ColsArgs a = cols_args(x, dim, segment, "dynamic_fixed_qdq_cols");
+  const std::vector<int64_t> none{0};
+  return std::make_tuple(empty_like_shape(x, out_dtype), at::empty(want_qparams ? a.q_shape : none, x.options().dtype(at::kFloat)),
+                         at::empty(want_qparams ? a.q_shape : none, x.options().dtype(at::kLong)));
+}
+std::tuple<Tensor, Tensor> dynamic_float_qdq_cols(const Tensor& x, int64_t dim, int64_t segment, int64_t man, int64_t exp, int64_t bias,
+                                                  bool flush_subnormal, int64_t rounding, bool pow2_scale, bool want_scale, OptDtype out_dtype) {
+  const Tensor xc = prep(x, "dynamic_float_qdq_cols");
+  const ColsArgs a = cols_args(xc, dim, segment, "dynamic_float_qdq_cols");
+  Tensor out = empty_like_shape(xc, out_dtype);
+  Tensor sc = want_scale ? at::empty(a.q_shape, xc.options().dtype(at::kFloat)) : at::empty({0}, xc.options().dtype(at::kFloat));
+  Launch l(xc);
+  check(dmxq_dynamic_float_qdq_cols(xc.data_ptr(), out.data_ptr(), dt_code(xc.scalar_type()), dt_code(out.scalar_type()), a.outer, a.C, a.inner,
+                                    segment, (int)man, (int)exp, (int)bias, flush_subnormal ? 1 : 0, (int)rounding, pow2_scale ? 1 : 0,
+                                    want_scale ? (float*)sc.data_ptr() : nullptr, l.stream), "dmxq_dynamic_float_qdq_cols");
+  return std::make_tuple(out, sc);
+}
+std::tuple<Tensor, Tensor> dynamic_float_qdq_cols_meta(const Tensor& x, int64_t dim, int64_t segment, int64_t, int64_t, int64_t, bool, int64_t, bool,
+                                                       bool want_scale, OptDtype out_dtype) {
+  const ColsArgs a = cols_args(x, dim, segment, "dynamic_float_qdq_cols");
+  const std::vector<int64_t> none{0};
+  return std::make_tuple(empty_like_shape(x, out_dtype), at::empty(want_scale ? a.q_shape : none, x.options().dtype(at::kFloat)));
+}
+
 // ------------------------------------------------------------------------------------------------ learned step size (backward)
 // x, g: contiguous, one shape, numel % segment == 0; scale, zero_point: float32 [n_segments]; whole_rows: 0 groups, 1 rows, 2 the whole
 // tensor (the partial rows' scratch is allocated here) -> (dx, empty unless want_dx: then nothing is stored; ds float32 [n_segments];
@@ -1552,6 +1606,8 @@ TORCH_LIBRARY(dmxq, m) {
   m.def("hadamard_row_qdq(Tensor x, bool transpose, bool inverse, int precision, int symmetric, int segment, bool want_qparams, ScalarType? out_dtype=None) -> (Tensor, Tensor, Tensor)");
   m.def("dynamic_fixed_qdq(Tensor x, int segment, bool whole_rows, int precision, int fraction, bool clamp, bool symmetric, int rounding, int qmin, int qmax, bool symmetric_qscheme, bool want_qparams, ScalarType? out_dtype=None) -> (Tensor, Tensor, Tensor)");
   m.def("dynamic_float_qdq(Tensor x, int mode, int segment, int man, int exp, int bias, bool flush_subnormal, int rounding, bool pow2_scale, bool want_scale, ScalarType? out_dtype=None) -> (Tensor, Tensor)");
+  m.def("dynamic_fixed_qdq_cols(Tensor x, int dim, int segment, int precision, int fraction, bool clamp, bool symmetric, int rounding, int qmin, int qmax, bool symmetric_qscheme, bool want_qparams, ScalarType? out_dtype=None) -> (Tensor, Tensor, Tensor)");
+  m.def("dynamic_float_qdq_cols(Tensor x, int dim, int segment, int man, int exp, int bias, bool flush_subnormal, int rounding, bool pow2_scale, bool want_scale, ScalarType? out_dtype=None) -> (Tensor, Tensor)");
   m.def("channel_sumsq(Tensor x, Tensor(a!) acc, Tensor(b!) scratch) -> ()");
   m.def("wanda_nm(Tensor w, Tensor act_norm, int K, int M, bool want_score, bool want_mask, bool want_y, ScalarType? mask_dtype=None, ScalarType? y_dtype=None) -> (Tensor, Tensor, Tensor)");
   m.def("channel_sumabs(Tensor x, Tensor(a!) acc, Tensor(b!) scratch) -> ()");
@@ -1580,7 +1636,8 @@ TORCH_LIBRARY(dmxq, m) {
   X(m, error_stats); X(m, cast_error); X(m, hadamard_qdq); X(m, dynamic_fixed_qdq); X(m, gptq_block_dynamic); X(m, dynamic_float_qdq); \
   X(m, channel_sumsq); X(m, wanda_nm); X(m, channel_sumabs); X(m, awq_group_error); X(m, block_scaled_float_qdq); X(m, block_scaled_tensor_scale); \
   X(m, lsq_backward); X(m, codebook_qdq); X(m, codebook_accumulate); X(m, hqq_qdq); X(m, outlier_fixed_qdq); X(m, awq_clip); \
-  X(m, adaround_forward); X(m, adaround_backward); X(m, vq_qdq); X(m, vq_accumulate); X(m, hadamard_row_qdq)
+  X(m, adaround_forward); X(m, adaround_backward); X(m, vq_qdq); X(m, vq_accumulate); X(m, hadamard_row_qdq); \
+  X(m, dynamic_fixed_qdq_cols); X(m, dynamic_float_qdq_cols)
 
 // "CUDA" is the dispatch key of HIP tensors in a ROCm build of PyTorch
 TORCH_LIBRARY_IMPL(dmxq, CUDA, m) {
@@ -1643,6 +1700,11 @@ PYBIND11_MODULE(dmxq_fast, m) {
         py::arg("want_qparams"), py::arg("out_dtype") = py::none());
   m.def("dynamic_float_qdq", &dynamic_float_qdq, py::arg("x"), py::arg("mode"), py::arg("segment"), py::arg("man"), py::arg("exp"), py::arg("bias"),
         py::arg("flush_subnormal"), py::arg("rounding"), py::arg("pow2_scale"), py::arg("want_scale"), py::arg("out_dtype") = py::none());
+  m.def("dynamic_fixed_qdq_cols", &dynamic_fixed_qdq_cols, py::arg("x"), py::arg("dim"), py::arg("segment"), py::arg("precision"), py::arg("fraction"),
+        py::arg("clamp"), py::arg("symmetric"), py::arg("rounding"), py::arg("qmin"), py::arg("qmax"), py::arg("symmetric_qscheme"),
+        py::arg("want_qparams"), py::arg("out_dtype") = py::none());
+  m.def("dynamic_float_qdq_cols", &dynamic_float_qdq_cols, py::arg("x"), py::arg("dim"), py::arg("segment"), py::arg("man"), py::arg("exp"),
+        py::arg("bias"), py::arg("flush_subnormal"), py::arg("rounding"), py::arg("pow2_scale"), py::arg("want_scale"), py::arg("out_dtype") = py::none());
   m.def("block_scaled_float_qdq", &block_scaled_float_qdq, py::arg("x"), py::arg("group"), py::arg("fmt"), py::arg("scale_fmt"), py::arg("scale_max"),
         py::arg("tensor_scale"), py::arg("want_scale"), py::arg("want_code"), py::arg("out_dtype") = py::none());
   m.def("block_scaled_tensor_scale", &block_scaled_tensor_scale);

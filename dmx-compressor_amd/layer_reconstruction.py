@@ -67,6 +67,14 @@ def refuse_outlier_weight_cast(module, what):
                                   "reproduce the cast without its outliers; clear the outliers (set_dynamic without \"outliers\") first")
 
 
+def refuse_cols_weight_cast(module, what):
+    """GPTQ, AWQ, the AWQ clip, Wanda, HQQ, AdaRound and folding on a module whose dynamic weight cast runs its groups along a dimension
+    other than the last (CastTo.set_dynamic / set_scaling with "dim"): DmxqError through the cast's ONE check, before any state is touched"""
+    wc = getattr(module, "weight_cast", None)
+    if wc is not None and getattr(module, "weight", None) is not None:
+        wc.refuse_groups_along_dim(what, module.weight.dim())
+
+
 class OptimalBrainCompressor:
     H = None
 
@@ -74,6 +82,7 @@ class OptimalBrainCompressor:
         refuse_learnable_weight_cast(module, "GPTQ")
         refuse_codebook_weight_cast(module, "GPTQ")
         refuse_vq_weight_cast(module, "GPTQ")
+        refuse_cols_weight_cast(module, "GPTQ")
         refuse_outlier_weight_cast(module, "GPTQ")
         self.module = module
         self.example_counter = 0
@@ -479,6 +488,7 @@ class WandaCalibrator:
         refuse_learnable_weight_cast(module, "Wanda")
         refuse_codebook_weight_cast(module, "Wanda")
         refuse_vq_weight_cast(module, "Wanda")
+        refuse_cols_weight_cast(module, "Wanda")
         self.module = module
         self.sumsq = sumsq
         self.n_tokens = int(n_tokens)
@@ -561,6 +571,7 @@ class AWQCalibrator:
         refuse_learnable_weight_cast(module, "AWQ")
         refuse_codebook_weight_cast(module, "AWQ")
         refuse_vq_weight_cast(module, "AWQ")
+        refuse_cols_weight_cast(module, "AWQ")
         refuse_outlier_weight_cast(module, "AWQ")   # (neither ops.awq_scaled_error nor its chain selects outliers)
         # the clip that follows the fuse: its refusals now, before any state is touched (SmoothQuant's own state is refuse_awq's matter)
         self.clip_plan = refuse_awq_clip(module, after_awq_scaling=True) if hyperparams.clip is not None else None
@@ -669,6 +680,7 @@ def refuse_awq_clip(module, after_awq_scaling: bool = False):
     if wc is None:
         raise DmxqError("AWQ clipping needs a weight cast: the module has none")
     refuse_vq_weight_cast(module, "AWQ clipping")
+    refuse_cols_weight_cast(module, "AWQ clipping")
     for what, setting in (("an outlier-aware", wc._outliers), ("a codebook", wc._codebook), ("a learnable", wc._learnable), ("a scaled float", wc._scaling)):
         if setting is not None:
             raise DmxqError(f"AWQ clipping with {what} weight cast is not supported: the search reproduces the plain per-group dynamic "
@@ -769,6 +781,7 @@ def refuse_hqq(module):
     refuse_learnable_weight_cast(module, "HQQ")
     refuse_codebook_weight_cast(module, "HQQ")
     refuse_vq_weight_cast(module, "HQQ")
+    refuse_cols_weight_cast(module, "HQQ")
     refuse_outlier_weight_cast(module, "HQQ")
     if wc.pre_transform:
         raise DmxqError(f"HQQ with a weight cast pre_transform {sorted(wc.pre_transform)} is not supported: the zero points would be solved "
@@ -825,6 +838,7 @@ def refuse_adaround(module):
     if wc is None:
         raise DmxqError("AdaRound needs a weight cast: the module has none")
     refuse_vq_weight_cast(module, "AdaRound")
+    refuse_cols_weight_cast(module, "AdaRound")
     for what, setting in (("an outlier-aware", wc._outliers), ("a codebook", wc._codebook), ("a learnable", wc._learnable), ("a scaled float", wc._scaling)):
         if setting is not None:
             raise DmxqError(f"AdaRound with {what} weight cast is not supported: it rounds on the grid of a plain integer cast; clear the "

@@ -556,10 +556,12 @@ class DmxModule(FastAttr, torch.nn.Module):
         return self.weight_sparsifier(self.weight) if self.weight_sparsifier is not None else self.weight
 
     def fold_weight_and_bias(self) -> None:
-        from .layer_reconstruction import refuse_codebook_weight_cast, refuse_learnable_weight_cast, refuse_vq_weight_cast
+        from .layer_reconstruction import (refuse_codebook_weight_cast, refuse_cols_weight_cast, refuse_learnable_weight_cast,
+                                           refuse_vq_weight_cast)
         refuse_learnable_weight_cast(self, "folding the weight")
         refuse_codebook_weight_cast(self, "folding the weight")
         refuse_vq_weight_cast(self, "folding the weight")
+        refuse_cols_weight_cast(self, "folding the weight")
         with torch.no_grad():
             if self.bias_cast is not None and not isinstance(self.bias_format, Same) and self.bias is not None:
                 self.bias.data = self.bias_cast(self.bias.data)

@@ -61,7 +61,8 @@ const char* dmxq_status_string(int status);
  * dmxq_codebook_qdq, dmxq_codebook_class, dmxq_codebook_accumulate, dmxq_codebook_workspace_bytes, dmxq_hqq_qdq, dmxq_hqq_class,
  * dmxq_outlier_fixed_qdq, dmxq_outlier_class, dmxq_awq_clip, dmxq_awq_clip_class, dmxq_adaround_forward, dmxq_adaround_backward,
  * dmxq_adaround_class, dmxq_adaround_scratch_bytes, dmxq_vq_qdq, dmxq_vq_class, dmxq_vq_accumulate, dmxq_vq_workspace_bytes,
- * dmxq_hadamard_row_qdq, dmxq_hadamard_row_class, dmxq_hadamard_matrix) leave it at 4: a caller built against 4 runs on
+ * dmxq_hadamard_row_qdq, dmxq_hadamard_row_class, dmxq_hadamard_matrix, dmxq_dynamic_cols_class, dmxq_dynamic_fixed_qdq_cols,
+ * dmxq_dynamic_float_qdq_cols) leave it at 4: a caller built against 4 runs on
  * this library unchanged.  4 = round 5: + dmxq_float_qdq_multi, dmxq_fixed_float_qdq_multi; 3 = round 4: + dmxq_weight_hypernet_multi,
  * dmxq_unary_cast_table, dmxq_lut16_apply.  Nothing was ever removed or changed: a caller built against version n runs on any library >= n. */
 int dmxq_abi_version(void);
@@ -661,6 +662,28 @@ int dmxq_dynamic_float_class(int dtype, int mode, int64_t segment);
 int dmxq_dynamic_float_qdq(const void* in, void* out, int dtype_in, int dtype_out, int mode, int64_t n_segments, int64_t segment,
                            int64_t rows, int64_t cols, int man_bits, int exp_bits, int exp_bias, int flush_subnormal, int rounding,
                            int pow2_scale, float* scale_out, void* stream);
+
+/* The two dynamic casts above with segments along a NON-LAST dimension (csrc/dynamic_cols.hip; DESIGN.md §8 "Dynamic casts along a
+ * non-last dimension"): KIVI's per-channel keys grouped along tokens, per-channel activations, [in, out] and conv weights grouped along
+ * input channels.  The contiguous tensor is viewed as [outer, C, inner]; a segment is `segment` consecutive indices along C at one
+ * (outer, inner) position, segment dividing C (segment == C: the whole column).  Per segment the arithmetic is dmxq_dynamic_fixed_qdq's /
+ * dmxq_dynamic_float_qdq's: the result is, bit for bit, that entry on the tensor with C moved last, moved back.  scale_out / zp_out: each
+ * NULL, or a DEVICE array in the layout [outer, C / segment, inner].  ONE launch, every element read once and written once, no workspace,
+ * no atomics, no host synchronisation: capturable.  in == out is NOT allowed (a tile's stores may pass another tile's loads).
+ * dmxq_dynamic_cols_class: the geometry the entries pick (no GPU involved; the same function makes the choice inside them): NONE =
+ * refused, R8 = segments of 16 .. 64 (a workgroup of segment / 8 waves, 8 rows per lane), R16 = 128 (8 waves, 16 rows per lane), R16W16 =
+ * 256 (16 waves; a sixteen-bit lane then moves 8 bytes, half a vector).  Taken: segment a power of two from 16 to 256, inner a whole number (>= 1) of 16-byte vectors (8 sixteen-bit or 4 fp32
+ * elements), dtype_in == dtype_out, nearest rounding, 16-byte aligned bases (and fraction 0, clamp, precision <= 22 / man_bits <= 22 as in
+ * the last-dim entries).  DMXQ_ERR_UNSUPPORTED, nothing launched (the caller transposes): anything else.  DMXQ_ERR_BAD_ARG: null data
+ * pointers, negative sizes, a segment that does not divide C, invalid dtype / rounding, qmax <= qmin, exp_bits outside 1 .. 7, in == out. */
+typedef enum { DMXQ_DYNC_R8 = 7, DMXQ_DYNC_R16 = 8, DMXQ_DYNC_R16W16 = 9 } dmxq_dynamic_cols_geometry;
+int dmxq_dynamic_cols_class(int dtype, int64_t segment, int64_t inner);
+int dmxq_dynamic_fixed_qdq_cols(const void* in, void* out, int dtype_in, int dtype_out, int64_t outer, int64_t C, int64_t inner,
+                                int64_t segment, int precision, int fraction, int clamp, int symmetric, int rounding, int qmin, int qmax,
+                                int symmetric_qscheme, float* scale_out, int64_t* zp_out, void* stream);
+int dmxq_dynamic_float_qdq_cols(const void* in, void* out, int dtype_in, int dtype_out, int64_t outer, int64_t C, int64_t inner,
+                                int64_t segment, int man_bits, int exp_bits, int exp_bias, int flush_subnormal, int rounding,
+                                int pow2_scale, float* scale_out, void* stream);
 
 /* Codebook casts (csrc/codebook.hip; DESIGN.md §8 "Codebook casts"): a small table of ARBITRARY levels under a per-segment absolute-maximum
  * scale -- NF4, Lloyd-Max / k-means tables -- in ONE launch, and the weighted Lloyd statistics that fit a table on the device.  Not in
