@@ -121,6 +121,25 @@ def bfp_unpack(mant, exps, precision, block_size, out_dtype):
 
 
 @_guarded
+def bfp_matmul(mant_a, exps_a, mant_w, exps_w, precision_a, precision_w, block_size, out_dtype):
+    """packed [M, K] / [M, K / B] x [N, K] / [N, K / B] -> [M, N] (csrc/bfp_matmul.hip); NotImplementedError: the front end's chain"""
+    for t in (mant_a, exps_a, mant_w, exps_w):
+        require_gpu(t, "bfp_matmul")
+    if (mant_a.dim() != 2 or mant_w.dim() != 2 or exps_a.dim() != 2 or exps_w.dim() != 2 or block_size < 1
+            or mant_a.dtype != torch.int8 or mant_w.dtype != torch.int8 or exps_a.dtype != torch.uint8 or exps_w.dtype != torch.uint8):
+        raise RuntimeError("bfp_matmul: expects 2-d int8 codes and uint8 exponents and a positive block size")
+    K = mant_a.shape[1]
+    nb = -(-K // block_size)
+    if mant_w.shape[1] != K or tuple(exps_a.shape) != (mant_a.shape[0], nb) or tuple(exps_w.shape) != (mant_w.shape[0], nb):
+        raise RuntimeError("bfp_matmul: operand shapes do not match ([M, K] / [M, K / B] and [N, K] / [N, K / B])")
+    ca, ea, cw, ew = mant_a.contiguous(), exps_a.contiguous(), mant_w.contiguous(), exps_w.contiguous()
+    out = torch.empty((ca.shape[0], cw.shape[0]), dtype=out_dtype, device=ca.device)
+    check(lib().dmxq_bfp_matmul(ptr(ca), ptr(ea), ptr(cw), ptr(ew), ptr(out), dtype_code(out_dtype), ca.shape[0], cw.shape[0], K, block_size,
+                                precision_a, precision_w, stream_of(ca)), "dmxq_bfp_matmul")
+    return out
+
+
+@_guarded
 def weight_hypernet(w, precision, block_size, symmetric, score, K, M, sq_scale, out_dtype=None, block_dim=-1):
     wc = _prep(w, "weight_hypernet")
     masked = score is not None and M != 0

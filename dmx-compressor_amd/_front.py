@@ -40,6 +40,8 @@ __all__ = [
     "awq_clip", "awq_clip_check", "awq_clip_class", "awq_clip_ratios", "awq_gram_blocks", "AWQ_CLIP_CHAIN_BY_DEFAULT", "AWQ_CLIP_MAX_RATIOS",
     "adaround_check", "adaround_class", "adaround_scratch_bytes", "adaround_init", "adaround_qdq", "adaround_backward",
     "ADAROUND_CHAIN_BY_DEFAULT",
+    "bfp_matmul", "bfp_matmul_packed", "bfp_matmul_check", "bfp_matmul_class", "BFP_MATMUL_CHAIN_BY_DEFAULT", "BFP_MATMUL_BLOCK_SIZES",
+    "BFP_MATMUL_CHAIN_PIECE_ENTRIES",
 ]
 
 _ops = None   # the raw namespace: set by bind()
@@ -117,6 +119,141 @@ def bfp_pack(x, precision: int, block_size: int, symmetric: bool = True):
 def bfp_unpack(mant, exps, precision: int, block_size: int, out_dtype: torch.dtype = torch.float32):
     require_gpu(mant, "bfp_unpack")
     return _ops.bfp_unpack(mant, exps, precision, block_size, out_dtype)
+
+
+# ---------------------------------------------------------------------------------------------------- BFP matmul
+# Kernel classes (bfp_matmul_class) that run the chain of torch operations unless fused=True asks for the kernel: none.  The chain is
+# the definition spelled in torch, slow by construction (an [M, N, K] product in pieces and a Python loop over the blocks); the kernel is
+# the only practical route wherever it applies.  profiles/r28_bfp_matmul.txt has the kernel against today's dequantise-then-matmul path.
+BFP_MATMUL_CHAIN_BY_DEFAULT = frozenset()
+BFP_MATMUL_BLOCK_SIZES = (32, 64, 128)
+BFP_MATMUL_CHAIN_PIECE_ENTRIES = 1 << 24   # entries of the chain's [rows, N, K] fp32 product per piece (64 MiB)
+_bfp_matmul_routes = {"fused": 0, "chain": 0}
+_BFP_MATMUL_CLASS_NAMES = {1: "mfma_b32", 2: "mfma_b64", 3: "mfma_b128"}   # dmxq_bfp_matmul_geometry (include/dmxq.h)
+
+
+def bfp_matmul_class(mant_a, mant_w, block_size: int) -> Optional[str]:
+    """the geometry the kernel picks for the packed call (codes mant_a [M, K], mant_w [N, K], blocks of block_size along K), asked of the
+    library itself (dmxq_bfp_matmul_class; no GPU involved), or None where the call runs the chain: a block size outside 32 / 64 / 128,
+    K % block_size != 0, or codes whose (contiguous) base is not 16-byte aligned.  "mfma_b32": one 16x16x32 MFMA per 16 x 16 tile and
+    block, "mfma_b64": one 16x16x64, "mfma_b128": two chained 16x16x64; a 128 x 128 output tile per workgroup in every class."""
+    from ._lib import lib
+    if mant_a.dim() != 2 or mant_w.dim() != 2:
+        return None
+    for c in (mant_a, mant_w):
+        if c.is_contiguous() and c.data_ptr() % 16:
+            return None
+    return _BFP_MATMUL_CLASS_NAMES.get(lib().dmxq_bfp_matmul_class(mant_a.shape[0], mant_w.shape[0], mant_a.shape[1], int(block_size)))
+
+
+def bfp_matmul_check(x, w, fmt_x, fmt_w=None):
+    """-> (fmt_x, fmt_w) as BlockFloatingPoint objects, or DmxqError before any launch: a format that is not BFP[p|8]{B}, p > 8 (codes
+    wider than int8), rounding other than nearest, two block sizes, w that is not [N, K], or x whose last dimension is not K."""
+    from .format import BlockFloatingPoint, Format
+    fmts = []
+    for name, f in (("fmt_x", fmt_x), ("fmt_w", fmt_x if fmt_w is None else fmt_w)):
+        try:
+            f = Format.from_shorthand(f) if isinstance(f, str) else f
+        except ValueError as e:
+            raise DmxqError(f"bfp_matmul: {name}: {e}") from None
+        if not isinstance(f, BlockFloatingPoint):
+            raise DmxqError(f"bfp_matmul: {name} must be a BlockFloatingPoint format (BFP[p|8]{{B}}), got {f!r}")
+        if f.precision > 8:
+            raise DmxqError(f"bfp_matmul: {name} = {f!r} has {f.precision}-bit mantissas; the packed codes are int8 (p <= 8)")
+        if f.rounding != "nearest":
+            raise DmxqError(f"bfp_matmul: {name} = {f!r} rounds {f.rounding}; the packed operands are rounded to nearest")
+        fmts.append(f)
+    if fmts[0].block_size != fmts[1].block_size:
+        raise DmxqError(f"bfp_matmul: the operands share one block size, got {fmts[0].block_size} and {fmts[1].block_size}")
+    if w.dim() != 2:
+        raise DmxqError(f"bfp_matmul: w must be [N, K], got {tuple(w.shape)}")
+    if x.dim() < 1 or x.shape[-1] != w.shape[1]:
+        raise DmxqError(f"bfp_matmul: x is {tuple(x.shape)}, its last dimension must be w's K = {w.shape[1]}")
+    return fmts[0], fmts[1]
+
+
+def _bfp_block_scale(exps, precision):
+    """uint8 shared exponents -> fp32 2^(e - 127 - (p - 2)); 0 -> 0 (the block adds nothing), 255 -> NaN"""
+    e = exps.to(torch.int32)
+    s = (e << 23).view(torch.float32) * (2.0 ** -(precision - 2))   # exact: a power of two >= 2^-132, denormals kept
+    return torch.where(e == 255, torch.full_like(s, float("nan")), s)
+
+
+def _bfp_matmul_chain(ca, ea, cw, ew, pa, pw, B, out_dtype):
+    """the definition in torch operations, same bits as the kernel: exact per-block integer sums in fp32 (every partial sum is an integer
+    below 2^24), the two multiplies by the shared exponents' powers of two, then the blocks added in ascending order"""
+    M, K = ca.shape
+    N, nb = cw.shape[0], ea.shape[1]
+    pad = nb * B - K                                       # a ragged last block: zero codes add nothing to its sum
+    a = torch.nn.functional.pad(ca.to(torch.float32), (0, pad)).view(M, nb, B)
+    w = torch.nn.functional.pad(cw.to(torch.float32), (0, pad)).view(N, nb, B)
+    sa, sw = _bfp_block_scale(ea, pa), _bfp_block_scale(ew, pw)
+    y = torch.zeros((M, N), dtype=torch.float32, device=ca.device)
+    rows = max(1, BFP_MATMUL_CHAIN_PIECE_ENTRIES // max(N * nb * B, 1))
+    for r0 in range(0, M, rows):
+        P = (a[r0:r0 + rows, None] * w[None]).sum(-1)                      # [rows, N, nb]
+        t = (P * sa[r0:r0 + rows, None, :]) * sw[None, :, :]
+        for j in range(nb):
+            y[r0:r0 + rows] += t[:, :, j]
+    return y.to(out_dtype)
+
+
+def bfp_matmul_packed(mant_a, exps_a, mant_w, exps_w, precision_a: int, precision_w: int, block_size: int,
+                      out_dtype: torch.dtype = torch.float32, fused: Optional[bool] = None):
+    """y = A W^T on packed BFP operands (ops.bfp_pack's: int8 codes [M, K] / [N, K], uint8 shared exponents [M, ceil(K / B)] /
+    [N, ceil(K / B)]) as a block-floating-point datapath computes it (DESIGN.md §8 "BFP matmul"): per block an exact integer dot
+    product, scaled by the two shared exponents, the blocks added in fp32 in ascending order; -> [M, N] of out_dtype.  A block with
+    exponent byte 0 in either operand adds nothing, 255 makes the element NaN.  Bit-reproducible.
+    fused=None: the int8-MFMA kernel (dmxq_bfp_matmul) where it applies (bfp_matmul_class) and its class is not listed in
+    BFP_MATMUL_CHAIN_BY_DEFAULT, else the chain of torch operations with the same bits; True: NotImplementedError instead of falling
+    back; False: the chain."""
+    for t in (mant_a, exps_a, mant_w, exps_w):
+        require_gpu(t, "bfp_matmul_packed")
+    B = int(block_size)
+    if mant_a.dim() != 2 or mant_w.dim() != 2 or mant_a.shape[1] != mant_w.shape[1] or B < 1:
+        raise DmxqError(f"bfp_matmul_packed: codes must be [M, K] and [N, K] with a positive block size, got {tuple(mant_a.shape)}, "
+                        f"{tuple(mant_w.shape)}, {block_size}")
+    nb = -(-mant_a.shape[1] // B)
+    if tuple(exps_a.shape) != (mant_a.shape[0], nb) or tuple(exps_w.shape) != (mant_w.shape[0], nb):
+        raise DmxqError(f"bfp_matmul_packed: exponents must be [M, {nb}] and [N, {nb}], got {tuple(exps_a.shape)}, {tuple(exps_w.shape)}")
+    if mant_a.dtype != torch.int8 or mant_w.dtype != torch.int8 or exps_a.dtype != torch.uint8 or exps_w.dtype != torch.uint8:
+        raise DmxqError("bfp_matmul_packed: codes are int8 and shared exponents uint8 (ops.bfp_pack)")
+    if not (2 <= precision_a <= 8 and 2 <= precision_w <= 8):
+        raise DmxqError(f"bfp_matmul_packed: precisions must lie in 2 .. 8, got {precision_a}, {precision_w}")
+    with torch.no_grad():
+        if fused is not False and mant_a.shape[0] and mant_w.shape[0]:
+            cls = bfp_matmul_class(mant_a, mant_w, B)
+            if cls is None and fused:
+                raise NotImplementedError(f"bfp_matmul_packed: no kernel for {tuple(mant_a.shape)} x {tuple(mant_w.shape)} codes in blocks of {B} "
+                                          f"(base addresses {mant_a.data_ptr() % 16}, {mant_w.data_ptr() % 16} mod 16)")
+            if cls is not None and fused is None and cls in BFP_MATMUL_CHAIN_BY_DEFAULT:
+                cls = None
+            if cls is not None:
+                try:
+                    y = _ops.bfp_matmul(mant_a, exps_a, mant_w, exps_w, int(precision_a), int(precision_w), B, out_dtype)
+                    _bfp_matmul_routes["fused"] += 1
+                    return y
+                except NotImplementedError:   # (DMXQ_ERR_UNSUPPORTED, nothing launched)
+                    if fused:
+                        raise
+        _bfp_matmul_routes["chain"] += 1
+        return _bfp_matmul_chain(mant_a, exps_a, mant_w, exps_w, int(precision_a), int(precision_w), B, out_dtype)
+
+
+def bfp_matmul(x, w, fmt_x, fmt_w=None, out_dtype: Optional[torch.dtype] = None, fused: Optional[bool] = None):
+    """x[..., K] times w[N, K]^T with both operands in block floating point along K (fmt_x, fmt_w: BFP[p|8]{B} objects or shorthands, one
+    block size, p <= 8, nearest rounding; fmt_w defaults to fmt_x): packs both with ops.bfp_pack and multiplies the packed operands
+    (bfp_matmul_packed).  -> [..., N] of out_dtype (default x.dtype).  Casting an operand first changes nothing: pack of a cast tensor
+    gives the same codes.  No gradient: the result is detached."""
+    fx, fw = bfp_matmul_check(x, w, fmt_x, fmt_w)
+    require_gpu(x, "bfp_matmul")
+    require_gpu(w, "bfp_matmul")
+    with torch.no_grad():
+        x2 = x.detach().reshape(-1, x.shape[-1])
+        ca, ea = bfp_pack(x2, fx.precision, fx.block_size, fx.symmetric)
+        cw, ew = bfp_pack(w.detach(), fw.precision, fw.block_size, fw.symmetric)
+        y = bfp_matmul_packed(ca, ea, cw, ew, fx.precision, fw.precision, fx.block_size, out_dtype or x.dtype, fused)
+    return y.reshape(tuple(x.shape[:-1]) + (w.shape[0],))
 
 
 def weight_hypernet(w, precision: int, block_size: int, symmetric: bool = True, score=None, K: int = 0, M: int = 0,

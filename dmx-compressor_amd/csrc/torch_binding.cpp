@@ -166,6 +166,37 @@ Tensor bfp_unpack_meta(const Tensor& mant, const Tensor&, int64_t, int64_t, at::
   return at::empty(mant.sizes(), mant.options().dtype(out_dtype));
 }
 
+// the BFP matmul on packed operands (csrc/bfp_matmul.hip): mant_a [M, K] int8 + exps_a [M, K / B] uint8, mant_w [N, K] + exps_w [N, K / B]
+// -> [M, N].  DMXQ_ERR_UNSUPPORTED (NotImplementedError, nothing launched): the front end runs its chain.
+void bfp_matmul_shapes(const Tensor& mant_a, const Tensor& exps_a, const Tensor& mant_w, const Tensor& exps_w, int64_t block_size) {
+  TORCH_CHECK(mant_a.dim() == 2 && mant_w.dim() == 2 && exps_a.dim() == 2 && exps_w.dim() == 2 && block_size >= 1,
+              "bfp_matmul: expects 2-d codes and exponents and a positive block size");
+  TORCH_CHECK(mant_a.scalar_type() == at::kChar && mant_w.scalar_type() == at::kChar && exps_a.scalar_type() == at::kByte &&
+              exps_w.scalar_type() == at::kByte, "bfp_matmul: codes are int8 and exponents uint8");
+  const int64_t K = mant_a.size(1), nb = (K + block_size - 1) / block_size;
+  TORCH_CHECK(mant_w.size(1) == K && exps_a.size(0) == mant_a.size(0) && exps_w.size(0) == mant_w.size(0) && exps_a.size(1) == nb &&
+              exps_w.size(1) == nb, "bfp_matmul: operand shapes do not match ([M, K] / [M, K / B] and [N, K] / [N, K / B])");
+}
+Tensor bfp_matmul(const Tensor& mant_a, const Tensor& exps_a, const Tensor& mant_w, const Tensor& exps_w, int64_t precision_a,
+                  int64_t precision_w, int64_t block_size, at::ScalarType out_dtype) {
+  TORCH_CHECK(mant_a.is_cuda() && exps_a.is_cuda() && mant_w.is_cuda() && exps_w.is_cuda(),
+              "bfp_matmul: tensors must be on the GPU (no CPU fallback)");
+  bfp_matmul_shapes(mant_a, exps_a, mant_w, exps_w, block_size);
+  const Tensor ca = mant_a.contiguous(), ea = exps_a.contiguous(), cw = mant_w.contiguous(), ew = exps_w.contiguous();
+  Tensor out = at::empty({ca.size(0), cw.size(0)}, ca.options().dtype(out_dtype));
+  Launch l(ca);
+  check(dmxq_bfp_matmul((const int8_t*)ca.data_ptr(), (const uint8_t*)ea.data_ptr(), (const int8_t*)cw.data_ptr(),
+                        (const uint8_t*)ew.data_ptr(), out.data_ptr(), dt_code(out_dtype), ca.size(0), cw.size(0), ca.size(1), block_size,
+                        (int)precision_a, (int)precision_w, l.stream), "dmxq_bfp_matmul");
+  return out;
+}
+Tensor bfp_matmul_meta(const Tensor& mant_a, const Tensor& exps_a, const Tensor& mant_w, const Tensor& exps_w, int64_t, int64_t,
+                       int64_t block_size, at::ScalarType out_dtype) {
+  bfp_matmul_shapes(mant_a, exps_a, mant_w, exps_w, block_size);
+  dt_code(out_dtype);
+  return at::empty({mant_a.size(0), mant_w.size(0)}, mant_a.options().dtype(out_dtype));
+}
+
 at::ScalarType hypernet_dtype(const Tensor& w, const OptTensor& score, int64_t M, OptDtype out_dtype) {
   const bool masked = score.has_value() && score->defined() && M != 0;
   return out_dtype.value_or(masked ? at::promote_types(w.scalar_type(), score->scalar_type()) : w.scalar_type());
@@ -1561,6 +1592,7 @@ TORCH_LIBRARY(dmxq, m) {
   m.def("bfp_qdq_multi(Tensor[] xs, int precision, int block_size, int block_dim=-1, bool symmetric=True, int rounding=2, ScalarType? out_dtype=None, int seed=0) -> Tensor[]");
   m.def("bfp_pack(Tensor x, int precision, int block_size, bool symmetric=True) -> (Tensor, Tensor)");
   m.def("bfp_unpack(Tensor mant, Tensor exps, int precision, int block_size, ScalarType out_dtype) -> Tensor");
+  m.def("bfp_matmul(Tensor mant_a, Tensor exps_a, Tensor mant_w, Tensor exps_w, int precision_a, int precision_w, int block_size, ScalarType out_dtype) -> Tensor");
   m.def("weight_hypernet(Tensor w, int precision, int block_size, bool symmetric, Tensor? score, int K, int M, Tensor? sq_scale, ScalarType? out_dtype=None, int block_dim=-1) -> Tensor");
   m.def("input_hypernet(Tensor x, Tensor sq_scale, int precision, int block_size, bool symmetric) -> Tensor");
   m.def("binary_cast(Tensor a, Tensor b, int op, int[] cast_a, int[] cast_b, int[] cast_out, int bfp_block=0, int bfp_precision=0) -> Tensor");
@@ -1637,7 +1669,7 @@ TORCH_LIBRARY(dmxq, m) {
   X(m, channel_sumsq); X(m, wanda_nm); X(m, channel_sumabs); X(m, awq_group_error); X(m, block_scaled_float_qdq); X(m, block_scaled_tensor_scale); \
   X(m, lsq_backward); X(m, codebook_qdq); X(m, codebook_accumulate); X(m, hqq_qdq); X(m, outlier_fixed_qdq); X(m, awq_clip); \
   X(m, adaround_forward); X(m, adaround_backward); X(m, vq_qdq); X(m, vq_accumulate); X(m, hadamard_row_qdq); \
-  X(m, dynamic_fixed_qdq_cols); X(m, dynamic_float_qdq_cols)
+  X(m, dynamic_fixed_qdq_cols); X(m, dynamic_float_qdq_cols); X(m, bfp_matmul)
 
 // "CUDA" is the dispatch key of HIP tensors in a ROCm build of PyTorch
 TORCH_LIBRARY_IMPL(dmxq, CUDA, m) {

@@ -392,8 +392,13 @@ class DmxModule(FastAttr, torch.nn.Module):
             self.weight_sparsifier.configure(sparseness=config["weight_sparseness"])
         if "approximation_function" in config:
             self.approximator.set_function(config["approximation_function"])
+        if "block_matmul" in config:
+            self.set_block_matmul(config["block_matmul"])
 
     transform = configure
+
+    def set_block_matmul(self, enabled: bool = True):
+        raise TypeError(f"{type(self).__name__} has no block matmul (ops.bfp_matmul): Linear only")
 
     # ------------------------------------------------------------------ views used by the harness
     @property
@@ -1085,7 +1090,44 @@ class Linear(DmxModule, torch.nn.Linear):
         if self.bias_cast is not None:
             self.bias_cast.block_dim = -1
 
+    #: opt-in (set_block_matmul / configure's "block_matmul"): the product of two BFP-cast operands runs as ops.bfp_matmul_packed -- per
+    #: block an exact integer dot product, the blocks added in fp32 in order (DESIGN.md §8 "BFP matmul") -- instead of torch.matmul
+    #: on the dequantised operands.  A plain attribute: no buffer, no state_dict key
+    block_matmul = False
+
+    def set_block_matmul(self, enabled: bool = True):
+        self.block_matmul = bool(enabled)
+
+    def _block_matmul_formats(self, _input):
+        """(input format, weight format) when this forward can run as a BFP matmul, else None: both casts plain BFP casts (switched on,
+        no pre_transform) along the last dimension with one block size the kernel takes, p <= 8, nearest rounding, and no gradient asked"""
+        from . import ops
+        from .format import BlockFloatingPoint
+        ic, wc = self.input_casts.input_cast, self.weight_cast
+        fi, fw = ic.format, wc.format
+        if not (isinstance(fi, BlockFloatingPoint) and isinstance(fw, BlockFloatingPoint)):
+            return None
+        if fi.block_size != fw.block_size or fi.block_size not in ops.BFP_MATMUL_BLOCK_SIZES:
+            return None
+        for c, f in ((ic, fi), (wc, fw)):
+            if (c.block_dim != -1 or f.precision > 8 or f.rounding != "nearest" or c.pre_transform or c._codebook is not None or c._vq is not None
+                    or not c._flag("fake_quant_enabled")):
+                return None
+        if torch.is_grad_enabled() and (_input.requires_grad or self.weight.requires_grad or (self.bias is not None and self.bias.requires_grad)):
+            return None
+        return fi, fw
+
     def _forward(self, _input):
+        _fmts = self._block_matmul_formats(_input) if self.block_matmul else None
+        if _fmts is not None:   # the operands are already cast: packing a cast tensor gives its codes back (ops.bfp_pack)
+            from . import ops
+            _fi, _fw = _fmts
+            _weight = self._weight_ro
+            _ca, _ea = ops.bfp_pack(_input.reshape(-1, _input.shape[-1]), _fi.precision, _fi.block_size, _fi.symmetric)
+            _cw, _ew = ops.bfp_pack(_weight, _fw.precision, _fw.block_size, _fw.symmetric)
+            _product = ops.bfp_matmul_packed(_ca, _ea, _cw, _ew, _fi.precision, _fw.precision, _fi.block_size, out_dtype=_weight.dtype)
+            _product = self.accum_cast(_product.reshape(tuple(_input.shape[:-1]) + (_weight.shape[0],)))
+            return torch.add(_product, self._bias_ro) if self.bias is not None else _product
         if isinstance(self.accum_format, Same):  # torch_modules.py:346-350
             _weight = self.weight_hypernet(self.weight, _input.dtype).to(_input.dtype)
             _bias = self._bias_ro  # (a property: one cast launch per evaluation)

@@ -62,7 +62,7 @@ const char* dmxq_status_string(int status);
  * dmxq_outlier_fixed_qdq, dmxq_outlier_class, dmxq_awq_clip, dmxq_awq_clip_class, dmxq_adaround_forward, dmxq_adaround_backward,
  * dmxq_adaround_class, dmxq_adaround_scratch_bytes, dmxq_vq_qdq, dmxq_vq_class, dmxq_vq_accumulate, dmxq_vq_workspace_bytes,
  * dmxq_hadamard_row_qdq, dmxq_hadamard_row_class, dmxq_hadamard_matrix, dmxq_dynamic_cols_class, dmxq_dynamic_fixed_qdq_cols,
- * dmxq_dynamic_float_qdq_cols) leave it at 4: a caller built against 4 runs on
+ * dmxq_dynamic_float_qdq_cols, dmxq_bfp_matmul, dmxq_bfp_matmul_class) leave it at 4: a caller built against 4 runs on
  * this library unchanged.  4 = round 5: + dmxq_float_qdq_multi, dmxq_fixed_float_qdq_multi; 3 = round 4: + dmxq_weight_hypernet_multi,
  * dmxq_unary_cast_table, dmxq_lut16_apply.  Nothing was ever removed or changed: a caller built against version n runs on any library >= n. */
 int dmxq_abi_version(void);
@@ -125,6 +125,23 @@ int dmxq_bfp_pack(const void* in, int dtype_in, int8_t* mant, uint8_t* exps, int
                   int64_t block_size, int precision, int symmetric, void* stream);
 int dmxq_bfp_unpack(const int8_t* mant, const uint8_t* exps, void* out, int dtype_out, int64_t rows, int64_t L,
                     int64_t block_size, int precision, void* stream);
+
+/* BFP matmul on the int8 matrix cores (csrc/bfp_matmul.hip; DESIGN.md §8 "BFP matmul"): y = A W^T on the packed operands of
+ * dmxq_bfp_pack, as a block-floating-point datapath computes it.  A: mant_a int8 [M, K] + exps_a uint8 [M, K / B] of precision prec_a,
+ * W: mant_w [N, K] + exps_w [N, K / B] of prec_w, both blocked along K with one block size B; out: [M, N] of dtype_out, contiguous.
+ * Per block j the integer P_j = sum ca * cw is exact; t_j = (float(P_j) * 2^(ea_j - 127 - (pa - 2))) * 2^(ew_j - 127 - (pw - 2));
+ * y = ((t_0 + t_1) + t_2) + ... in fp32 in ascending block order, then one nearest-even convert.  An exponent byte 0 in either operand
+ * makes the block add nothing (+0), 255 in either makes y[m, n] NaN.  ONE launch, no workspace, no atomics, no split-K: the same
+ * operands give the same bits on every call; capturable.
+ * dmxq_bfp_matmul_class: the geometry the entry picks (no GPU involved; the same function makes the choice inside it): NONE = refused,
+ * B32 / B64 / B128 = a 128 x 128 tile per workgroup with one 16x16x32, one 16x16x64, two chained 16x16x64 MFMA per block.
+ * Taken: B in {32, 64, 128}, K % B == 0, M, N, K >= 1, 2 <= prec_a, prec_w <= 8 (symmetric or asymmetric codes), 16-byte aligned code
+ * bases.  DMXQ_ERR_UNSUPPORTED, nothing launched (the caller runs its chain, same bits): anything else.  DMXQ_ERR_BAD_ARG: null
+ * pointers, negative sizes, an invalid dtype, B < 1.  M * N == 0: DMXQ_OK, nothing launched. */
+typedef enum { DMXQ_BFPMM_NONE = 0, DMXQ_BFPMM_B32 = 1, DMXQ_BFPMM_B64 = 2, DMXQ_BFPMM_B128 = 3 } dmxq_bfp_matmul_geometry;
+int dmxq_bfp_matmul_class(int64_t M, int64_t N, int64_t K, int64_t block_size);
+int dmxq_bfp_matmul(const int8_t* mant_a, const uint8_t* exps_a, const int8_t* mant_w, const uint8_t* exps_w, void* out,
+                    int dtype_out, int64_t M, int64_t N, int64_t K, int64_t block_size, int prec_a, int prec_w, void* stream);
 
 /* Low-bit floating point Q->DQ ("FP[s|e|m,bias](F|_ N|S)").
  * Replaces: numerical/format.py:208-233 FloatingPoint.cast -> quant_function.py:120-152 float_quantize
