@@ -16,6 +16,7 @@ from typing import Optional
 import torch
 
 from ._lib import DmxqError, ROUNDING_CODE, require_gpu
+from ._routing import DYNAMIC_CHAIN_MAX_SEGMENTS, DYNAMIC_CHAIN_PIECE, in_pieces, route, straight_through  # noqa: F401
 
 __all__ = [
     "bfp_qdq", "block_quantize", "bfp_qdq_multi", "bfp_pack", "bfp_unpack", "weight_hypernet", "weight_hypernet_multi", "input_hypernet", "binary_cast", "rope_cast", "relu_cast", "unary_cast", "unary_cast_table", "lut16_apply", "softmax_cast", "layernorm_cast", "rmsnorm_cast", "sbfp_qdq", "mxfp_qdq", "float_qdq", "float_qdq_multi", "fixed_qdq", "fixed_qdq_multi", "fixed_float_qdq_multi", "nm_mask", "nm_sparsify", "nm_mask_class", "topk_mask", "topk_sparsify", "bernoulli_mask", "group_minmax", "group_minmax_accumulate", "qparams", "channel_maxabs",
@@ -220,24 +221,15 @@ def bfp_matmul_packed(mant_a, exps_a, mant_w, exps_w, precision_a: int, precisio
         raise DmxqError("bfp_matmul_packed: codes are int8 and shared exponents uint8 (ops.bfp_pack)")
     if not (2 <= precision_a <= 8 and 2 <= precision_w <= 8):
         raise DmxqError(f"bfp_matmul_packed: precisions must lie in 2 .. 8, got {precision_a}, {precision_w}")
+    if not (mant_a.shape[0] and mant_w.shape[0]):
+        fused = False   # (an empty product: the chain, whatever was asked for)
+    cls = None if fused is False else bfp_matmul_class(mant_a, mant_w, B)
     with torch.no_grad():
-        if fused is not False and mant_a.shape[0] and mant_w.shape[0]:
-            cls = bfp_matmul_class(mant_a, mant_w, B)
-            if cls is None and fused:
-                raise NotImplementedError(f"bfp_matmul_packed: no kernel for {tuple(mant_a.shape)} x {tuple(mant_w.shape)} codes in blocks of {B} "
-                                          f"(base addresses {mant_a.data_ptr() % 16}, {mant_w.data_ptr() % 16} mod 16)")
-            if cls is not None and fused is None and cls in BFP_MATMUL_CHAIN_BY_DEFAULT:
-                cls = None
-            if cls is not None:
-                try:
-                    y = _ops.bfp_matmul(mant_a, exps_a, mant_w, exps_w, int(precision_a), int(precision_w), B, out_dtype)
-                    _bfp_matmul_routes["fused"] += 1
-                    return y
-                except NotImplementedError:   # (DMXQ_ERR_UNSUPPORTED, nothing launched)
-                    if fused:
-                        raise
-        _bfp_matmul_routes["chain"] += 1
-        return _bfp_matmul_chain(mant_a, exps_a, mant_w, exps_w, int(precision_a), int(precision_w), B, out_dtype)
+        return route(fused, cls, BFP_MATMUL_CHAIN_BY_DEFAULT, _bfp_matmul_routes,
+                     lambda: _ops.bfp_matmul(mant_a, exps_a, mant_w, exps_w, int(precision_a), int(precision_w), B, out_dtype),
+                     lambda: _bfp_matmul_chain(mant_a, exps_a, mant_w, exps_w, int(precision_a), int(precision_w), B, out_dtype),
+                     lambda: (f"bfp_matmul_packed: no kernel for {tuple(mant_a.shape)} x {tuple(mant_w.shape)} codes in blocks of {B} "
+                              f"(base addresses {mant_a.data_ptr() % 16}, {mant_w.data_ptr() % 16} mod 16)"))
 
 
 def bfp_matmul(x, w, fmt_x, fmt_w=None, out_dtype: Optional[torch.dtype] = None, fused: Optional[bool] = None):
@@ -1081,28 +1073,24 @@ def hadamard_qdq(x, size: int, fmt, block_dim: int = -1, inverse: bool = True, s
 
     def run(xd):
         xl = _to_last(xd, d)
-        if fused is not False:
-            fields = None if on_chain_only else _hadamard_fields(fmt, per_row)
-            if fields is None and fused:
-                raise NotImplementedError(f"hadamard_qdq: no fused kernel for {fmt!r}"
-                                          + (" with per-channel / per-group scales" if on_chain_only else ""))
-            if fields is not None and fused is None and fields[0] in HADAMARD_CHAIN_BY_DEFAULT:
-                fields = None
-            if fields is not None:
-                sc, zp = affine(xl) if fixed else (None, None)
-                if per_row and (sc.numel() != xl.numel() // max(xl.shape[-1], 1) or zp.numel() != sc.numel()):
-                    raise ValueError("hadamard_qdq: per_row needs one scale and one zero point per row")
-                try:
-                    return _from_last(_ops.hadamard_qdq(xl, size, bool(inverse), fields, sc, zp, out_dtype), d)
-                except NotImplementedError:   # (DMXQ_ERR_UNSUPPORTED, nothing launched: a block that does not divide size, ...)
-                    if fused:
-                        raise
-        r = _ops.hadamard_qdq(xl, size, False, [], None, None, torch.float32)
-        if inverse:
-            y = _ops.hadamard_qdq(cast(r, torch.float32), size, False, [], None, None, out_dtype)
-        else:
-            y = cast(r, out_dtype)
-        return _from_last(y, d)
+        fields = None if fused is False or on_chain_only else _hadamard_fields(fmt, per_row)
+
+        def kernel():   # (it may still refuse, with nothing launched: a block that does not divide size, ...)
+            sc, zp = affine(xl) if fixed else (None, None)
+            if per_row and (sc.numel() != xl.numel() // max(xl.shape[-1], 1) or zp.numel() != sc.numel()):
+                raise ValueError("hadamard_qdq: per_row needs one scale and one zero point per row")
+            return _from_last(_ops.hadamard_qdq(xl, size, bool(inverse), fields, sc, zp, out_dtype), d)
+
+        def chain():
+            r = _ops.hadamard_qdq(xl, size, False, [], None, None, torch.float32)
+            if inverse:
+                y = _ops.hadamard_qdq(cast(r, torch.float32), size, False, [], None, None, out_dtype)
+            else:
+                y = cast(r, out_dtype)
+            return _from_last(y, d)
+
+        return route(fused, None if fields is None else fields[0], HADAMARD_CHAIN_BY_DEFAULT, None, kernel, chain,
+                     lambda: f"hadamard_qdq: no fused kernel for {fmt!r}" + (" with per-channel / per-group scales" if on_chain_only else ""))
 
     if x.requires_grad and torch.is_grad_enabled():
         return _RotatedCast.apply(x, run, size, d, bool(inverse))
@@ -1201,21 +1189,13 @@ def _rotate_row_chain(v, transpose):
 def _rotate_row(x, d, transpose, out_dtype, fused=None):
     xl = _to_last(x.detach(), d)
     n = xl.shape[-1]
-    if fused is not False and xl.numel() and hadamard_row_class(n, xl.dtype) is not None and out_dtype in (xl.dtype, torch.float32):
-        xc = xl if xl.is_contiguous() else xl.contiguous()
-        if xc.data_ptr() % 16 == 0 and (fused or hadamard_row_class(n, xl.dtype) not in HADAMARD_ROW_CHAIN_BY_DEFAULT):
-            try:
-                y = _ops.hadamard_row_qdq(xc, bool(transpose), False, 0, 0, n, False, out_dtype)[0]
-                _hadamard_row_routes["fused"] += 1
-                return _from_last(y, d)
-            except NotImplementedError:   # (DMXQ_ERR_UNSUPPORTED, nothing launched)
-                if fused:
-                    raise
-    if fused:
-        raise NotImplementedError(f"hadamard_row: no fused kernel for rows of {n} {xl.dtype} elements -> {out_dtype} "
-                                  f"(base address {xl.data_ptr() % 16} mod 16)")
-    _hadamard_row_routes["chain"] += 1
-    return _from_last(_rotate_row_chain(xl.to(torch.float32), transpose).to(out_dtype), d)
+    cls = None if fused is False or not xl.numel() or out_dtype not in (xl.dtype, torch.float32) else hadamard_row_class(n, xl.dtype)
+    xc = xl if cls is None or xl.is_contiguous() else xl.contiguous()
+    return route(fused, cls if xc.data_ptr() % 16 == 0 else None, HADAMARD_ROW_CHAIN_BY_DEFAULT, _hadamard_row_routes,
+                 lambda: _from_last(_ops.hadamard_row_qdq(xc, bool(transpose), False, 0, 0, n, False, out_dtype)[0], d),
+                 lambda: _from_last(_rotate_row_chain(xl.to(torch.float32), transpose).to(out_dtype), d),
+                 lambda: (f"hadamard_row: no fused kernel for rows of {n} {xl.dtype} elements -> {out_dtype} "
+                          f"(base address {xl.data_ptr() % 16} mod 16)"))
 
 
 class _RowRotation(torch.autograd.Function):
@@ -1289,28 +1269,23 @@ def hadamard_row_dynamic_qdq(x, fmt, granularity: str = "per_token", group_size:
         if xc.numel() == 0:
             y = torch.empty(xc.shape, dtype=out_dtype, device=xc.device)
             return (y, y.new_empty(0, dtype=torch.float32), y.new_empty(0, dtype=torch.int64)) if return_qparams else y
-        if fused is not False:
-            cls = hadamard_row_class(n, xc.dtype, S) if (fmt.rounding == "nearest" and out_dtype == xc.dtype and 2 <= fmt.precision <= 22
-                                                         and xc.data_ptr() % 16 == 0) else None
-            if cls is None and fused:
-                raise NotImplementedError(f"hadamard_row_dynamic_qdq: no fused kernel for rows of {n} {xc.dtype} elements in segments of "
-                                          f"{S} -> {out_dtype} with {fmt!r} (base address {xc.data_ptr() % 16} mod 16)")
-            if cls is not None and fused is None and cls in HADAMARD_ROW_CHAIN_BY_DEFAULT:
-                cls = None
-            if cls is not None:
-                try:
-                    y, sc, zp = _ops.hadamard_row_qdq(xc, tr, inv, fmt.precision, (1 if sym else 0) | (2 if fmt.symmetric else 0), S,
-                                                      bool(return_qparams), out_dtype)
-                    _hadamard_row_routes["fused"] += 1
-                    return (y, sc, zp) if return_qparams else y
-                except NotImplementedError:   # (DMXQ_ERR_UNSUPPORTED, nothing launched)
-                    if fused:
-                        raise
-        _hadamard_row_routes["chain"] += 1
-        r = _rotate_row_chain(xc.to(torch.float32), tr)
-        q, sc, zp = dynamic_fixed_qdq(r, fmt, granularity, group_size, sym, torch.float32, True)
-        y = (_rotate_row_chain(q, not tr) if inv else q).to(out_dtype)
-        return (y, sc, zp) if return_qparams else y
+        cls = None if fused is False or not (fmt.rounding == "nearest" and out_dtype == xc.dtype and 2 <= fmt.precision <= 22
+                                             and xc.data_ptr() % 16 == 0) else hadamard_row_class(n, xc.dtype, S)
+
+        def kernel():
+            y, sc, zp = _ops.hadamard_row_qdq(xc, tr, inv, fmt.precision, (1 if sym else 0) | (2 if fmt.symmetric else 0), S,
+                                              bool(return_qparams), out_dtype)
+            return (y, sc, zp) if return_qparams else y
+
+        def chain():
+            r = _rotate_row_chain(xc.to(torch.float32), tr)
+            q, sc, zp = dynamic_fixed_qdq(r, fmt, granularity, group_size, sym, torch.float32, True)
+            y = (_rotate_row_chain(q, not tr) if inv else q).to(out_dtype)
+            return (y, sc, zp) if return_qparams else y
+
+        return route(fused, cls, HADAMARD_ROW_CHAIN_BY_DEFAULT, _hadamard_row_routes, kernel, chain,
+                     lambda: (f"hadamard_row_dynamic_qdq: no fused kernel for rows of {n} {xc.dtype} elements in segments of "
+                              f"{S} -> {out_dtype} with {fmt!r} (base address {xc.data_ptr() % 16} mod 16)"))
 
     if x.requires_grad and torch.is_grad_enabled():
         return _RowRotatedSTE.apply(x, run, tr, inv)
@@ -1342,8 +1317,6 @@ class _RowRotatedSTE(torch.autograd.Function):
 # ---------------------------------------------------------------------------------------------------- dynamic integer cast
 DYNAMIC_GRANULARITIES = ("per_token", "per_group", "per_tensor")
 DYNAMIC_MAX_ROW = 16384          # the longest segment dmxq_dynamic_fixed_qdq keeps in registers
-DYNAMIC_CHAIN_MAX_SEGMENTS = 65535   # groups of one dmxq_group_minmax call; more segments: the chain runs on pieces of ...
-DYNAMIC_CHAIN_PIECE = 32768          # ... this many segments (the kernel has no such limit)
 # Launch geometries of dmxq_dynamic_fixed_qdq (dynamic_class) that fused=None sends to the three-launch chain although the kernel takes
 # them.  The rule: a class goes to the kernel by default only where tools/bench_dynamic_quant.py MEASURED it faster than the chain on the
 # same buffers; a class that is not gets listed here with its row.  profiles/r12_dynamic_quant.txt (bf16 INT8, symmetric / affine, us per
@@ -1440,53 +1413,27 @@ def _dynamic_cols(x, d, granularity, group_size, out_dtype, want, fused, fmt_ok,
         if xc.numel() == 0:
             y = torch.empty(xc.shape, dtype=out_dtype, device=xc.device)
             return (y,) + tuple(y.new_empty(q_shape, dtype=t) for t in q_dtypes) if want else y
-        if fused is not False:
-            inner = xc.numel() // (C * math.prod(xc.shape[:d]))
-            cls = dynamic_cols_class(S, xc.dtype, inner) if (fmt_ok and out_dtype == xc.dtype and xc.data_ptr() % 16 == 0) else None
-            if cls is None and fused:
-                raise NotImplementedError(f"{what}: no fused kernel for segments of {S} along dim {d} of a {tuple(xc.shape)} {xc.dtype} tensor -> "
-                                          f"{out_dtype} (base address {xc.data_ptr() % 16} mod 16)")
-            if cls is not None and fused is None and cls in DYNAMIC_COLS_CHAIN_BY_DEFAULT:
-                cls = None
-            if cls is not None:
-                try:
-                    out = kernel(xc, S, bool(want))
-                    _dynamic_cols_routes["fused"] += 1
-                    return tuple(out) if want else out[0]
-                except NotImplementedError:   # (DMXQ_ERR_UNSUPPORTED, nothing launched)
-                    if fused:
-                        raise
-        _dynamic_cols_routes["chain"] += 1
-        xt = xc.movedim(d, -1).contiguous()
-        out = last(xt, bool(want))
-        if not want:
-            return out.movedim(-1, d).contiguous()
-        qt = tuple(xt.shape[:-1]) + (C // S,)
-        return (out[0].movedim(-1, d).contiguous(),) + tuple(q.reshape(qt).movedim(-1, d).contiguous() for q in out[1:])
+        inner = xc.numel() // (C * math.prod(xc.shape[:d]))
+        cls = None if fused is False or not (fmt_ok and out_dtype == xc.dtype
+                                             and xc.data_ptr() % 16 == 0) else dynamic_cols_class(S, xc.dtype, inner)
 
-    if x.requires_grad and torch.is_grad_enabled():
-        return _DynamicSTE.apply(x, run)
-    with torch.no_grad():
-        return run(x.detach())
+        def fused_cols():
+            out = kernel(xc, S, bool(want))
+            return tuple(out) if want else out[0]
 
+        def chain():
+            xt = xc.movedim(d, -1).contiguous()
+            out = last(xt, bool(want))
+            if not want:
+                return out.movedim(-1, d).contiguous()
+            qt = tuple(xt.shape[:-1]) + (C // S,)
+            return (out[0].movedim(-1, d).contiguous(),) + tuple(q.reshape(qt).movedim(-1, d).contiguous() for q in out[1:])
 
-class _DynamicSTE(torch.autograd.Function):
-    """the dynamic cast as a straight-through estimator (cast.py _FixedAffineCast: the scales are not differentiated either)"""
+        return route(fused, cls, DYNAMIC_COLS_CHAIN_BY_DEFAULT, _dynamic_cols_routes, fused_cols, chain,
+                     lambda: (f"{what}: no fused kernel for segments of {S} along dim {d} of a {tuple(xc.shape)} {xc.dtype} tensor -> "
+                              f"{out_dtype} (base address {xc.data_ptr() % 16} mod 16)"))
 
-    @staticmethod
-    def forward(ctx, x, run):
-        ctx.set_materialize_grads(False)
-        ctx.in_dtype = x.dtype
-        out = run(x.detach())
-        if isinstance(out, tuple):
-            ctx.mark_non_differentiable(*out[1:])
-        return out
-
-    @staticmethod
-    def backward(ctx, g, *_):
-        if g is not None and g.dtype != ctx.in_dtype:
-            g = g.to(ctx.in_dtype)
-        return g, None
+    return straight_through(x, run)
 
 
 def dynamic_fixed_qdq(x, fmt, granularity: str = "per_token", group_size: Optional[int] = None, symmetric_qscheme: bool = False,
@@ -1547,44 +1494,30 @@ def dynamic_fixed_qdq(x, fmt, granularity: str = "per_token", group_size: Option
         if xc.numel() == 0:
             y = torch.empty(xc.shape, dtype=out_dtype, device=xc.device)
             return (y, y.new_empty(0, dtype=torch.float32), y.new_empty(0, dtype=torch.int64)) if return_qparams else y
-        if fused is not False:
-            cls = dynamic_class(S, xc.dtype, whole_rows) if (fmt.rounding == "nearest" and out_dtype == xc.dtype and fmt.precision <= 22
-                                                             and xc.data_ptr() % 16 == 0) else None
-            if cls is None and fused:
-                raise NotImplementedError(f"dynamic_fixed_qdq: no fused kernel for segments of {S} {xc.dtype} elements -> {out_dtype} "
-                                          f"with {fmt!r} (base address {xc.data_ptr() % 16} mod 16)")
-            if cls is not None and fused is None and cls in DYNAMIC_CHAIN_BY_DEFAULT:
-                cls = None
-            if cls is not None:
-                try:
-                    y, sc, zp = _ops.dynamic_fixed_qdq(xc, S, whole_rows, fmt.precision, fmt.fraction, bool(fmt.clamp), bool(fmt.symmetric),
-                                                       ROUNDING_CODE[fmt.rounding], qmin, qmax, sym, bool(return_qparams), out_dtype)
-                    _dynamic_routes["fused"] += 1
-                    return (y, sc, zp) if return_qparams else y
-                except NotImplementedError:   # (DMXQ_ERR_UNSUPPORTED, nothing launched)
-                    if fused:
-                        raise
-        _dynamic_routes["chain"] += 1
-        x2 = xc.reshape(-1, S)
+        cls = None if fused is False or not (fmt.rounding == "nearest" and out_dtype == xc.dtype and fmt.precision <= 22
+                                             and xc.data_ptr() % 16 == 0) else dynamic_class(S, xc.dtype, whole_rows)
 
-        def three(part):
-            mn, mx = _ops.group_minmax(part, 0, 1)
-            sc, zp = _ops.qparams(mn, mx, qmin, qmax, sym)
-            return fixed_qdq(part, fmt.precision, fmt.fraction, fmt.clamp, fmt.symmetric, fmt.rounding, scale=sc, zero_point=zp, ch_axis=0,
-                             out_dtype=out_dtype, seed=seed), sc, zp
+        def kernel():
+            y, sc, zp = _ops.dynamic_fixed_qdq(xc, S, whole_rows, fmt.precision, fmt.fraction, bool(fmt.clamp), bool(fmt.symmetric),
+                                               ROUNDING_CODE[fmt.rounding], qmin, qmax, sym, bool(return_qparams), out_dtype)
+            return (y, sc, zp) if return_qparams else y
 
-        if x2.shape[0] <= DYNAMIC_CHAIN_MAX_SEGMENTS:
-            y, sc, zp = three(x2)
-        else:   # (dmxq_group_minmax takes 65535 groups: segments are independent, so the chain runs on pieces and the results are joined)
-            parts = [three(x2[i:i + DYNAMIC_CHAIN_PIECE]) for i in range(0, x2.shape[0], DYNAMIC_CHAIN_PIECE)]
-            y, sc, zp = (torch.cat([p[k] for p in parts]) for k in range(3))
-        y = y.reshape(xc.shape)
-        return (y, sc, zp) if return_qparams else y
+        def chain():
+            def three(part):
+                mn, mx = _ops.group_minmax(part, 0, 1)
+                sc, zp = _ops.qparams(mn, mx, qmin, qmax, sym)
+                return fixed_qdq(part, fmt.precision, fmt.fraction, fmt.clamp, fmt.symmetric, fmt.rounding, scale=sc, zero_point=zp, ch_axis=0,
+                                 out_dtype=out_dtype, seed=seed), sc, zp
 
-    if x.requires_grad and torch.is_grad_enabled():
-        return _DynamicSTE.apply(x, run)
-    with torch.no_grad():
-        return run(x.detach())
+            y, sc, zp = in_pieces(three, xc.reshape(-1, S), 3)
+            y = y.reshape(xc.shape)
+            return (y, sc, zp) if return_qparams else y
+
+        return route(fused, cls, DYNAMIC_CHAIN_BY_DEFAULT, _dynamic_routes, kernel, chain,
+                     lambda: (f"dynamic_fixed_qdq: no fused kernel for segments of {S} {xc.dtype} elements -> {out_dtype} "
+                              f"with {fmt!r} (base address {xc.data_ptr() % 16} mod 16)"))
+
+    return straight_through(x, run)
 
 
 # ---------------------------------------------------------------------------------------------------- learned step size (LSQ / LSQ+)
@@ -1688,39 +1621,34 @@ def lsq_backward(x, g, scale, zero_point, fmt, granularity: str = "per_token", g
         z = zero_point.detach().float().reshape(-1).contiguous()
         if xc.numel() == 0:
             return (torch.empty_like(xc) if want_dx else None), s.new_zeros(n_seg), (s.new_zeros(n_seg) if want_dz else None)
-        if fused is not False:
-            cls = lsq_class(S, xc.dtype, granularity) if (gc.dtype == xc.dtype and fmt.precision <= 22 and xc.data_ptr() % 16 == 0
-                                                           and gc.data_ptr() % 16 == 0) else None
-            if cls is None and fused:
-                raise NotImplementedError(f"lsq_backward: no fused kernel for segments of {S} {xc.dtype} elements ({granularity}) with a "
-                                          f"{gc.dtype} gradient and {fmt!r} (base addresses {xc.data_ptr() % 16} / {gc.data_ptr() % 16} mod 16)")
-            if cls is not None and fused is None and cls in LSQ_CHAIN_BY_DEFAULT:
-                cls = None
-            if cls is not None:
-                try:
-                    dx, ds, dz = _ops.lsq_backward(xc, gc, s, z, S, _LSQ_MODE[granularity], fmt.precision, ROUNDING_CODE[fmt.rounding], qmin, qmax,
-                                                   float(grad_factor), bool(want_dz), bool(want_dx))
-                    _lsq_routes["fused"] += 1
-                    return (dx if want_dx else None), ds, (dz if want_dz else None)
-                except NotImplementedError:   # (DMXQ_ERR_UNSUPPORTED, nothing launched)
-                    if fused:
-                        raise
-        _lsq_routes["chain"] += 1
-        # the definition, spelled in torch on the device
-        x2, g2 = xc.reshape(-1, S).float(), gc.reshape(-1, S).float()
-        sc, zq = s[:, None], _lsq_zq(z, qmin, qmax)[:, None]
-        v = x2 / sc + zq
-        r = torch.round((v + 0.5).double() - 0.5).float()
-        inside = (r >= qmin) & (r <= qmax)
-        q = torch.clamp(r, qmin, qmax)
-        dx = torch.where(inside, g2, torch.zeros_like(g2)).to(xc.dtype).reshape(xc.shape) if want_dx else None
-        ts = g2 * torch.where(inside, q - v, q - zq)
-        ds = (ts.sum(dim=1, dtype=torch.float64) * float(grad_factor)).float()
-        dz = None
-        if want_dz:
-            tz = torch.where(inside, torch.zeros_like(g2), -(g2 * sc))
-            dz = (tz.sum(dim=1, dtype=torch.float64) * float(grad_factor)).float()
-        return dx, ds, dz
+        cls = None if fused is False or not (gc.dtype == xc.dtype and fmt.precision <= 22 and xc.data_ptr() % 16 == 0
+                                             and gc.data_ptr() % 16 == 0) else lsq_class(S, xc.dtype, granularity)
+
+        def kernel():
+            dx, ds, dz = _ops.lsq_backward(xc, gc, s, z, S, _LSQ_MODE[granularity], fmt.precision, ROUNDING_CODE[fmt.rounding], qmin, qmax,
+                                           float(grad_factor), bool(want_dz), bool(want_dx))
+            return (dx if want_dx else None), ds, (dz if want_dz else None)
+
+        def chain():
+            # the definition, spelled in torch on the device
+            x2, g2 = xc.reshape(-1, S).float(), gc.reshape(-1, S).float()
+            sc, zq = s[:, None], _lsq_zq(z, qmin, qmax)[:, None]
+            v = x2 / sc + zq
+            r = torch.round((v + 0.5).double() - 0.5).float()
+            inside = (r >= qmin) & (r <= qmax)
+            q = torch.clamp(r, qmin, qmax)
+            dx = torch.where(inside, g2, torch.zeros_like(g2)).to(xc.dtype).reshape(xc.shape) if want_dx else None
+            ts = g2 * torch.where(inside, q - v, q - zq)
+            ds = (ts.sum(dim=1, dtype=torch.float64) * float(grad_factor)).float()
+            dz = None
+            if want_dz:
+                tz = torch.where(inside, torch.zeros_like(g2), -(g2 * sc))
+                dz = (tz.sum(dim=1, dtype=torch.float64) * float(grad_factor)).float()
+            return dx, ds, dz
+
+        return route(fused, cls, LSQ_CHAIN_BY_DEFAULT, _lsq_routes, kernel, chain,
+                     lambda: (f"lsq_backward: no fused kernel for segments of {S} {xc.dtype} elements ({granularity}) with a "
+                              f"{gc.dtype} gradient and {fmt!r} (base addresses {xc.data_ptr() % 16} / {gc.data_ptr() % 16} mod 16)"))
 
 
 class _LsqCast(torch.autograd.Function):
@@ -1905,53 +1833,41 @@ def dynamic_float_qdq(x, fmt, granularity: str = "per_token", group_size: Option
         if xc.numel() == 0:
             y = torch.empty(xc.shape, dtype=out_dtype, device=xc.device)
             return (y, y.new_empty(sc_shape if tile else 0, dtype=torch.float32)) if return_scale else y
-        if fused is not False:
-            cls = dynamic_float_class(S, xc.dtype, granularity) if (fmt.rounding == "nearest" and out_dtype == xc.dtype and fmt.mantissa <= 22
-                                                                    and xc.data_ptr() % 16 == 0) else None
-            if cls is None and fused:
-                raise NotImplementedError(f"dynamic_float_qdq: no fused kernel for {granularity} segments of {S} {xc.dtype} elements -> "
-                                          f"{out_dtype} with {fmt!r} (base address {xc.data_ptr() % 16} mod 16)")
-            if cls is not None and fused is None and cls in DYNAMIC_FLOAT_CHAIN_BY_DEFAULT:
-                cls = None
-            if cls is not None:
-                try:
-                    y, sc = _ops.dynamic_float_qdq(xc, mode, S, *fields, ROUNDING_CODE[fmt.rounding], bool(pow2_scale), bool(return_scale),
-                                                   out_dtype)
-                    _dynamic_float_routes["fused"] += 1
-                    return (y, sc) if return_scale else y
-                except NotImplementedError:   # (DMXQ_ERR_UNSUPPORTED, nothing launched)
-                    if fused:
-                        raise
-        _dynamic_float_routes["chain"] += 1
-        if tile:
-            B = xc.numel() // (xc.shape[-2] * L)
-            x2 = xc.reshape(B, xc.shape[-2] // S, S, L // S, S).permute(0, 1, 3, 2, 4).reshape(-1, S * S)
-        else:
-            x2 = xc.reshape(-1, S)
+        cls = None if fused is False or not (fmt.rounding == "nearest" and out_dtype == xc.dtype and fmt.mantissa <= 22
+                                             and xc.data_ptr() % 16 == 0) else dynamic_float_class(S, xc.dtype, granularity)
 
-        def chain(part):
-            mn, mx = _ops.group_minmax(part, 0, 1)
-            sc = _scale_from_amax(torch.maximum(mn.abs(), mx.abs()), fmax, pow2_scale)
-            q = _ops.scale_channels(part, sc, 0, True, torch.float32)
-            q = float_qdq(q, *fields, False, fmt.rounding, torch.float32, seed)
-            return _ops.scale_channels(q, sc, 0, False, out_dtype), sc
+        def kernel():
+            y, sc = _ops.dynamic_float_qdq(xc, mode, S, *fields, ROUNDING_CODE[fmt.rounding], bool(pow2_scale), bool(return_scale),
+                                           out_dtype)
+            return (y, sc) if return_scale else y
 
-        if x2.shape[0] <= DYNAMIC_CHAIN_MAX_SEGMENTS:
-            y, sc = chain(x2)
-        else:   # (dmxq_group_minmax takes 65535 groups: segments are independent, so the chain runs on pieces and the results are joined)
-            parts = [chain(x2[i:i + DYNAMIC_CHAIN_PIECE]) for i in range(0, x2.shape[0], DYNAMIC_CHAIN_PIECE)]
-            y, sc = (torch.cat([p[k] for p in parts]) for k in range(2))
-        if tile:
-            y = y.reshape(B, xc.shape[-2] // S, L // S, S, S).permute(0, 1, 3, 2, 4).reshape(xc.shape)
-            sc = sc.reshape(sc_shape)
-        else:
-            y = y.reshape(xc.shape)
-        return (y, sc) if return_scale else y
+        def chain():
+            if tile:
+                B = xc.numel() // (xc.shape[-2] * L)
+                x2 = xc.reshape(B, xc.shape[-2] // S, S, L // S, S).permute(0, 1, 3, 2, 4).reshape(-1, S * S)
+            else:
+                x2 = xc.reshape(-1, S)
 
-    if x.requires_grad and torch.is_grad_enabled():
-        return _DynamicSTE.apply(x, run)
-    with torch.no_grad():
-        return run(x.detach())
+            def piece(part):
+                mn, mx = _ops.group_minmax(part, 0, 1)
+                sc = _scale_from_amax(torch.maximum(mn.abs(), mx.abs()), fmax, pow2_scale)
+                q = _ops.scale_channels(part, sc, 0, True, torch.float32)
+                q = float_qdq(q, *fields, False, fmt.rounding, torch.float32, seed)
+                return _ops.scale_channels(q, sc, 0, False, out_dtype), sc
+
+            y, sc = in_pieces(piece, x2, 2)
+            if tile:
+                y = y.reshape(B, xc.shape[-2] // S, L // S, S, S).permute(0, 1, 3, 2, 4).reshape(xc.shape)
+                sc = sc.reshape(sc_shape)
+            else:
+                y = y.reshape(xc.shape)
+            return (y, sc) if return_scale else y
+
+        return route(fused, cls, DYNAMIC_FLOAT_CHAIN_BY_DEFAULT, _dynamic_float_routes, kernel, chain,
+                     lambda: (f"dynamic_float_qdq: no fused kernel for {granularity} segments of {S} {xc.dtype} elements -> "
+                              f"{out_dtype} with {fmt!r} (base address {xc.data_ptr() % 16} mod 16)"))
+
+    return straight_through(x, run)
 
 
 # ---------------------------------------------------------------------------------------------------- codebook casts
@@ -2106,15 +2022,10 @@ def _codebook_chain(x2, c, norm_t, want_lookup=True, out_dtype=None):
         u = _ops.scale_channels(part, sc, 0, True, torch.float32)
         idx = torch.bucketize(u, t, right=False)
         idx = torch.where(torch.isnan(u), z, idx)
-        y = _ops.scale_channels(c[idx], sc, 0, False, out_dtype) if want_lookup else sc
+        y = _ops.scale_channels(c[idx], sc, 0, False, out_dtype) if want_lookup else None
         return y, sc, u, idx
 
-    if x2.shape[0] <= DYNAMIC_CHAIN_MAX_SEGMENTS:
-        y, sc, u, idx = chain(x2)
-    else:   # (dmxq_group_minmax takes 65535 groups: segments are independent, so the chain runs on pieces and the results are joined)
-        parts = [chain(x2[i:i + DYNAMIC_CHAIN_PIECE]) for i in range(0, x2.shape[0], DYNAMIC_CHAIN_PIECE)]
-        y, sc, u, idx = (torch.cat([p[k] for p in parts]) for k in range(4))
-    return (y if want_lookup else None), sc, u, idx
+    return in_pieces(chain, x2, 4)
 
 
 def _codebook_norm_tensor(c, norm):
@@ -2162,30 +2073,21 @@ def codebook_qdq(x, codebook, granularity: str = "per_group", group_size: Option
             return pick(torch.empty(xc.shape, dtype=out_dtype, device=xc.device), torch.empty(0, dtype=torch.float32, device=xc.device),
                         torch.empty(xc.shape, dtype=torch.uint8, device=xc.device))
         c = _codebook_tensor(levels, xc.device)
-        if fused is not False:
-            cls = codebook_class(S, xc.dtype, mode == _DYNF_ROWS) if (K <= CODEBOOK_KERNEL_LEVELS and out_dtype == xc.dtype
-                                                                       and xc.data_ptr() % 16 == 0) else None
-            if cls is None and fused:
-                raise NotImplementedError(f"codebook_qdq: no fused kernel for {granularity} segments of {S} {xc.dtype} elements -> {out_dtype} "
-                                          f"with {K} levels (base address {xc.data_ptr() % 16} mod 16)")
-            if cls is not None and fused is None and cls in CODEBOOK_CHAIN_BY_DEFAULT:
-                cls = None
-            if cls is not None:
-                try:
-                    y, sc, idx = _ops.codebook_qdq(xc, mode, S, c, 0.0 if norm is None else norm, bool(return_scale), bool(return_index), out_dtype)
-                    _codebook_routes["fused"] += 1
-                    return pick(y, sc, idx)
-                except NotImplementedError:   # (DMXQ_ERR_UNSUPPORTED, nothing launched)
-                    if fused:
-                        raise
-        _codebook_routes["chain"] += 1
-        y, sc, _, idx = _codebook_chain(xc.reshape(-1, S), c, _codebook_norm_tensor(c, norm), True, out_dtype)
-        return pick(y.reshape(xc.shape), sc, idx.to(torch.uint8).reshape(xc.shape) if return_index else None)
+        cls = None if fused is False or not (K <= CODEBOOK_KERNEL_LEVELS and out_dtype == xc.dtype
+                                             and xc.data_ptr() % 16 == 0) else codebook_class(S, xc.dtype, mode == _DYNF_ROWS)
 
-    if x.requires_grad and torch.is_grad_enabled():
-        return _DynamicSTE.apply(x, run)
-    with torch.no_grad():
-        return run(x.detach())
+        def kernel():
+            return pick(*_ops.codebook_qdq(xc, mode, S, c, 0.0 if norm is None else norm, bool(return_scale), bool(return_index), out_dtype))
+
+        def chain():
+            y, sc, _, idx = _codebook_chain(xc.reshape(-1, S), c, _codebook_norm_tensor(c, norm), True, out_dtype)
+            return pick(y.reshape(xc.shape), sc, idx.to(torch.uint8).reshape(xc.shape) if return_index else None)
+
+        return route(fused, cls, CODEBOOK_CHAIN_BY_DEFAULT, _codebook_routes, kernel, chain,
+                     lambda: (f"codebook_qdq: no fused kernel for {granularity} segments of {S} {xc.dtype} elements -> {out_dtype} "
+                              f"with {K} levels (base address {xc.data_ptr() % 16} mod 16)"))
+
+    return straight_through(x, run)
 
 
 def codebook_accumulate(x, codebook, granularity: str = "per_group", group_size: Optional[int] = 64, norm: Optional[float] = None, acc=None,
@@ -2217,36 +2119,35 @@ def codebook_accumulate(x, codebook, granularity: str = "per_group", group_size:
         if xc.numel() == 0:
             return acc
         c = _codebook_tensor(levels, xc.device)
-        if fused is not False:
-            cls = codebook_class(S, xc.dtype, mode == _DYNF_ROWS) if (K <= CODEBOOK_KERNEL_LEVELS and xc.data_ptr() % 16 == 0) else None
-            if cls is None and fused:
-                raise NotImplementedError(f"codebook_accumulate: no fused kernel for {granularity} segments of {S} {xc.dtype} elements with {K} "
-                                          f"levels (base address {xc.data_ptr() % 16} mod 16)")
-            if cls is not None:
-                try:
-                    _ops.codebook_accumulate(xc, mode, S, c, 0.0 if norm is None else norm, acc, bool(accumulate))
-                    _codebook_accumulate_routes["fused"] += 1
-                    return acc
-                except NotImplementedError:   # (DMXQ_ERR_UNSUPPORTED, nothing launched)
-                    if fused:
-                        raise
-        _codebook_accumulate_routes["chain"] += 1
-        _, sc, u, idx = _codebook_chain(xc.reshape(-1, S), c, _codebook_norm_tensor(c, norm), False)
-        fin = torch.isfinite(u)
-        w = (sc.double() * sc.double())[:, None].expand_as(u)
-        zero = torch.zeros((), dtype=torch.float64, device=xc.device)
-        terms = torch.stack([torch.where(fin, w * u.double(), zero), torch.where(fin, w, zero), fin.double()], dim=-1).reshape(-1, 3)
-        # index_add_ adds with atomics: onto K rows alone every element of the tensor meets every other one (measured: seconds for 8 M
-        # elements), so the rows are kept in _CODEBOOK_ACC_REPLICAS copies, element i adding to copy i mod R, and the copies are summed
-        n = idx.numel()
-        R = min(_CODEBOOK_ACC_REPLICAS, n)
-        rows = idx.reshape(-1) + K * (torch.arange(n, device=xc.device) % R)
-        A = torch.zeros(R * K, 3, dtype=torch.float64, device=xc.device).index_add_(0, rows, terms).reshape(R, K, 3).sum(dim=0)
-        if accumulate:
-            acc += A
-        else:
-            acc.copy_(A)
-        return acc
+        cls = None if fused is False or not (K <= CODEBOOK_KERNEL_LEVELS
+                                             and xc.data_ptr() % 16 == 0) else codebook_class(S, xc.dtype, mode == _DYNF_ROWS)
+
+        def kernel():
+            _ops.codebook_accumulate(xc, mode, S, c, 0.0 if norm is None else norm, acc, bool(accumulate))
+            return acc
+
+        def chain():
+            _, sc, u, idx = _codebook_chain(xc.reshape(-1, S), c, _codebook_norm_tensor(c, norm), False)
+            fin = torch.isfinite(u)
+            w = (sc.double() * sc.double())[:, None].expand_as(u)
+            zero = torch.zeros((), dtype=torch.float64, device=xc.device)
+            terms = torch.stack([torch.where(fin, w * u.double(), zero), torch.where(fin, w, zero), fin.double()], dim=-1).reshape(-1, 3)
+            # index_add_ adds with atomics: onto K rows alone every element of the tensor meets every other one (measured: seconds for 8 M
+            # elements), so the rows are kept in _CODEBOOK_ACC_REPLICAS copies, element i adding to copy i mod R, and the copies are summed
+            n = idx.numel()
+            R = min(_CODEBOOK_ACC_REPLICAS, n)
+            rows = idx.reshape(-1) + K * (torch.arange(n, device=xc.device) % R)
+            A = torch.zeros(R * K, 3, dtype=torch.float64, device=xc.device).index_add_(0, rows, terms).reshape(R, K, 3).sum(dim=0)
+            if accumulate:
+                acc.add_(A)
+            else:
+                acc.copy_(A)
+            return acc
+
+        # (no *_CHAIN_BY_DEFAULT set of its own: the statistics pass goes to the kernel wherever codebook_qdq's kernel applies)
+        return route(fused, cls, (), _codebook_accumulate_routes, kernel, chain,
+                     lambda: (f"codebook_accumulate: no fused kernel for {granularity} segments of {S} {xc.dtype} elements with {K} "
+                              f"levels (base address {xc.data_ptr() % 16} mod 16)"))
 
 
 def codebook_fit(x, codebook="nf4", granularity: str = "per_group", group_size: Optional[int] = 64, norm: Optional[float] = None, iters: int = 8,
@@ -2474,15 +2375,10 @@ def _vq_chain(x2, c, norm_t, want_lookup=True, out_dtype=None):
         u = _ops.scale_channels(part, sc, 0, True, torch.float32)
         uv = u.reshape(-1, d)
         idx = torch.cat([_vq_choose(uv[i:i + step], c, z) for i in range(0, uv.shape[0], step)]) if uv.shape[0] > step else _vq_choose(uv, c, z)
-        y = _ops.scale_channels(c[idx].reshape(part.shape), sc, 0, False, out_dtype) if want_lookup else sc
+        y = _ops.scale_channels(c[idx].reshape(part.shape), sc, 0, False, out_dtype) if want_lookup else None
         return y, sc, u, idx.reshape(part.shape[0], -1)
 
-    if x2.shape[0] <= DYNAMIC_CHAIN_MAX_SEGMENTS:
-        y, sc, u, idx = chain(x2)
-    else:
-        parts = [chain(x2[i:i + DYNAMIC_CHAIN_PIECE]) for i in range(0, x2.shape[0], DYNAMIC_CHAIN_PIECE)]
-        y, sc, u, idx = (torch.cat([p[k] for p in parts]) for k in range(4))
-    return (y if want_lookup else None), sc, u, idx
+    return in_pieces(chain, x2, 4)
 
 
 def _vq_norm_tensor(c, norm):
@@ -2539,29 +2435,20 @@ def vq_qdq(x, codebook, granularity: str = "per_group", group_size: Optional[int
             return pick(torch.empty(xc.shape, dtype=out_dtype, device=xc.device), torch.empty(0, dtype=torch.float32, device=xc.device),
                         torch.empty(ishape, dtype=torch.uint8, device=xc.device))
         c = _vq_tensor(table, xc.device)
-        if fused is not False:
-            cls = _vq_kernel_class(xc, S, d, K, mode, out_dtype == xc.dtype)
-            if cls is None and fused:
-                raise NotImplementedError(f"vq_qdq: no fused kernel for {granularity} segments of {S} {xc.dtype} elements -> {out_dtype} "
-                                          f"with a [{K}, {d}] table (base address {xc.data_ptr() % 16} mod 16)")
-            if cls is not None and fused is None and cls in VQ_CHAIN_BY_DEFAULT:
-                cls = None
-            if cls is not None:
-                try:
-                    y, sc, idx = _ops.vq_qdq(xc, mode, S, c, 0.0 if norm is None else norm, bool(return_scale), bool(return_index), out_dtype)
-                    _vq_routes["fused"] += 1
-                    return pick(y, sc, idx)
-                except NotImplementedError:   # (DMXQ_ERR_UNSUPPORTED, nothing launched)
-                    if fused:
-                        raise
-        _vq_routes["chain"] += 1
-        y, sc, _, idx = _vq_chain(xc.reshape(-1, S), c, _vq_norm_tensor(c, norm), True, out_dtype)
-        return pick(y.reshape(xc.shape), sc, idx.to(torch.uint8).reshape(ishape) if return_index else None)
+        cls = None if fused is False else _vq_kernel_class(xc, S, d, K, mode, out_dtype == xc.dtype)
 
-    if x.requires_grad and torch.is_grad_enabled():
-        return _DynamicSTE.apply(x, run)
-    with torch.no_grad():
-        return run(x.detach())
+        def kernel():
+            return pick(*_ops.vq_qdq(xc, mode, S, c, 0.0 if norm is None else norm, bool(return_scale), bool(return_index), out_dtype))
+
+        def chain():
+            y, sc, _, idx = _vq_chain(xc.reshape(-1, S), c, _vq_norm_tensor(c, norm), True, out_dtype)
+            return pick(y.reshape(xc.shape), sc, idx.to(torch.uint8).reshape(ishape) if return_index else None)
+
+        return route(fused, cls, VQ_CHAIN_BY_DEFAULT, _vq_routes, kernel, chain,
+                     lambda: (f"vq_qdq: no fused kernel for {granularity} segments of {S} {xc.dtype} elements -> {out_dtype} "
+                              f"with a [{K}, {d}] table (base address {xc.data_ptr() % 16} mod 16)"))
+
+    return straight_through(x, run)
 
 
 def vq_accumulate(x, codebook, granularity: str = "per_group", group_size: Optional[int] = 64, norm: Optional[float] = None, acc=None,
@@ -2594,39 +2481,34 @@ def vq_accumulate(x, codebook, granularity: str = "per_group", group_size: Optio
         if xc.numel() == 0:
             return acc
         c = _vq_tensor(table, xc.device)
-        if fused is not False:
-            cls = _vq_kernel_class(xc, S, d, K, mode)
-            if cls is None and fused:
-                raise NotImplementedError(f"vq_accumulate: no fused kernel for {granularity} segments of {S} {xc.dtype} elements with a "
-                                          f"[{K}, {d}] table (base address {xc.data_ptr() % 16} mod 16)")
-            if cls is not None and fused is None and cls in VQ_CHAIN_BY_DEFAULT:
-                cls = None
-            if cls is not None:
-                try:
-                    _ops.vq_accumulate(xc, mode, S, c, 0.0 if norm is None else norm, acc, bool(accumulate))
-                    _vq_accumulate_routes["fused"] += 1
-                    return acc
-                except NotImplementedError:   # (DMXQ_ERR_UNSUPPORTED, nothing launched)
-                    if fused:
-                        raise
-        _vq_accumulate_routes["chain"] += 1
-        _, sc, u, idx = _vq_chain(xc.reshape(-1, S), c, _vq_norm_tensor(c, norm), False)
-        uv = u.reshape(-1, d)
-        fin = torch.isfinite(uv).all(dim=1, keepdim=True)
-        w = (sc.double() * sc.double())[:, None].expand(-1, S // d).reshape(-1, 1)
-        zero = torch.zeros((), dtype=torch.float64, device=xc.device)
-        terms = torch.cat([torch.where(fin, w * uv.double(), zero), torch.where(fin, w, zero), fin.double()], dim=1)
-        # index_add_ adds with atomics: onto K rows alone every vector meets every other one, so the rows are kept in R copies, vector i
-        # adding to copy i mod R, and the copies are summed (codebook_accumulate's form; R shrinks with K to bound the copies)
-        n = uv.shape[0]
-        R = max(1, min(_CODEBOOK_ACC_REPLICAS, 65536 // K, n))
-        rows = idx.reshape(-1) + K * (torch.arange(n, device=xc.device) % R)
-        A = torch.zeros(R * K, d + 2, dtype=torch.float64, device=xc.device).index_add_(0, rows, terms).reshape(R, K, d + 2).sum(dim=0)
-        if accumulate:
-            acc += A
-        else:
-            acc.copy_(A)
-        return acc
+        cls = None if fused is False else _vq_kernel_class(xc, S, d, K, mode)
+
+        def kernel():
+            _ops.vq_accumulate(xc, mode, S, c, 0.0 if norm is None else norm, acc, bool(accumulate))
+            return acc
+
+        def chain():
+            _, sc, u, idx = _vq_chain(xc.reshape(-1, S), c, _vq_norm_tensor(c, norm), False)
+            uv = u.reshape(-1, d)
+            fin = torch.isfinite(uv).all(dim=1, keepdim=True)
+            w = (sc.double() * sc.double())[:, None].expand(-1, S // d).reshape(-1, 1)
+            zero = torch.zeros((), dtype=torch.float64, device=xc.device)
+            terms = torch.cat([torch.where(fin, w * uv.double(), zero), torch.where(fin, w, zero), fin.double()], dim=1)
+            # index_add_ adds with atomics: onto K rows alone every vector meets every other one, so the rows are kept in R copies, vector i
+            # adding to copy i mod R, and the copies are summed (codebook_accumulate's form; R shrinks with K to bound the copies)
+            n = uv.shape[0]
+            R = max(1, min(_CODEBOOK_ACC_REPLICAS, 65536 // K, n))
+            rows = idx.reshape(-1) + K * (torch.arange(n, device=xc.device) % R)
+            A = torch.zeros(R * K, d + 2, dtype=torch.float64, device=xc.device).index_add_(0, rows, terms).reshape(R, K, d + 2).sum(dim=0)
+            if accumulate:
+                acc.add_(A)
+            else:
+                acc.copy_(A)
+            return acc
+
+        return route(fused, cls, VQ_CHAIN_BY_DEFAULT, _vq_accumulate_routes, kernel, chain,
+                     lambda: (f"vq_accumulate: no fused kernel for {granularity} segments of {S} {xc.dtype} elements with a "
+                              f"[{K}, {d}] table (base address {xc.data_ptr() % 16} mod 16)"))
 
 
 def _vq_update(c, A):
@@ -2645,13 +2527,9 @@ def _vq_sample_init(x, K, d, granularity, group_size, norm):
 
     def quotients(part):
         mn, mx = _ops.group_minmax(part, 0, 1)
-        return _ops.scale_channels(part, _scale_from_amax(torch.maximum(mn.abs(), mx.abs()), norm_t, False), 0, True, torch.float32)
+        return (_ops.scale_channels(part, _scale_from_amax(torch.maximum(mn.abs(), mx.abs()), norm_t, False), 0, True, torch.float32),)
 
-    if x2.shape[0] <= DYNAMIC_CHAIN_MAX_SEGMENTS:
-        u = quotients(x2)
-    else:
-        u = torch.cat([quotients(x2[i:i + DYNAMIC_CHAIN_PIECE]) for i in range(0, x2.shape[0], DYNAMIC_CHAIN_PIECE)])
-    uv = u.reshape(-1, d)
+    uv = in_pieces(quotients, x2, 1)[0].reshape(-1, d)
     n = uv.shape[0]
     pick = torch.tensor([(2 * i + 1) * n // (2 * K) for i in range(K)], dtype=torch.int64).to(xc.device)
     return uv[pick].contiguous()
@@ -2883,41 +2761,24 @@ def hqq_qdq(x, fmt, group_size: int = 64, lp_norm: float = 0.5, beta: float = 10
             e = torch.empty(0, dtype=torch.float32, device=xc.device)
             return pick(torch.empty(xc.shape, dtype=out_dtype, device=xc.device), e, e.clone(),
                         torch.empty(xc.shape, dtype=torch.uint8, device=xc.device))
-        if fused is not False:
-            cls = hqq_class(g, xc.dtype) if (lp_norm in HQQ_KERNEL_NORMS and out_dtype == xc.dtype and fmt.precision <= 22
-                                             and xc.data_ptr() % 16 == 0) else None
-            if cls is None and fused:
-                raise NotImplementedError(f"hqq_qdq: no fused kernel for groups of {g} {xc.dtype} elements -> {out_dtype} with {fmt!r} and "
-                                          f"lp_norm {lp_norm} (base address {xc.data_ptr() % 16} mod 16)")
-            if cls is not None and fused is None and cls in HQQ_CHAIN_BY_DEFAULT:
-                cls = None
-            if cls is not None:
-                try:
-                    y, sc, zero, codes = _ops.hqq_qdq(xc, g, ROUNDING_CODE[fmt.rounding], qmin, qmax, lp_norm, beta, kappa, iters,
-                                                      bool(return_qparams), bool(return_codes), out_dtype)
-                    _hqq_routes["fused"] += 1
-                    return pick(y, sc, zero, codes)
-                except NotImplementedError:   # (DMXQ_ERR_UNSUPPORTED, nothing launched)
-                    if fused:
-                        raise
-        _hqq_routes["chain"] += 1
-        x2 = xc.reshape(-1, g)
+        cls = None if fused is False or not (lp_norm in HQQ_KERNEL_NORMS and out_dtype == xc.dtype and fmt.precision <= 22
+                                             and xc.data_ptr() % 16 == 0) else hqq_class(g, xc.dtype)
 
-        def chain(part):
-            return _hqq_chain(part, qmin, qmax, lp_norm, beta, kappa, iters, out_dtype, return_codes)
+        def kernel():
+            y, sc, zero, codes = _ops.hqq_qdq(xc, g, ROUNDING_CODE[fmt.rounding], qmin, qmax, lp_norm, beta, kappa, iters,
+                                              bool(return_qparams), bool(return_codes), out_dtype)
+            return pick(y, sc, zero, codes)
 
-        if x2.shape[0] <= DYNAMIC_CHAIN_MAX_SEGMENTS:
-            y, sc, zero, codes = chain(x2)
-        else:   # (dmxq_group_minmax takes 65535 groups: groups are independent, so the chain runs on pieces and the results are joined)
-            parts = [chain(x2[i:i + DYNAMIC_CHAIN_PIECE]) for i in range(0, x2.shape[0], DYNAMIC_CHAIN_PIECE)]
-            y, sc, zero = (torch.cat([p[k] for p in parts]) for k in range(3))
-            codes = torch.cat([p[3] for p in parts]) if return_codes else None
-        return pick(y.reshape(xc.shape), sc, zero, codes.reshape(xc.shape) if return_codes else None)
+        def chain():
+            y, sc, zero, codes = in_pieces(lambda part: _hqq_chain(part, qmin, qmax, lp_norm, beta, kappa, iters, out_dtype, return_codes),
+                                           xc.reshape(-1, g), 4)
+            return pick(y.reshape(xc.shape), sc, zero, codes.reshape(xc.shape) if return_codes else None)
 
-    if x.requires_grad and torch.is_grad_enabled():
-        return _DynamicSTE.apply(x, run)
-    with torch.no_grad():
-        return run(x.detach())
+        return route(fused, cls, HQQ_CHAIN_BY_DEFAULT, _hqq_routes, kernel, chain,
+                     lambda: (f"hqq_qdq: no fused kernel for groups of {g} {xc.dtype} elements -> {out_dtype} with {fmt!r} and "
+                              f"lp_norm {lp_norm} (base address {xc.data_ptr() % 16} mod 16)"))
+
+    return straight_through(x, run)
 
 
 # ---------------------------------------------------------------------------------------------------- outlier-aware dynamic cast
@@ -3035,43 +2896,35 @@ def outlier_fixed_qdq(x, fmt, group_size: Optional[int] = None, k: int = 0, symm
                 return pick(y, y.new_empty(0, dtype=torch.float32), y.new_empty(0, dtype=torch.int64), idx, val)
             y, sc, zp = dynamic_fixed_qdq(xc, fmt, granularity, group_size if granularity == "per_group" else None, sym, out_dtype, True, fused)
             return pick(y, sc, zp, idx, val)
-        if fused is not False:
-            cls = outlier_class(S, xc.dtype) if (granularity == "per_group" and k <= OUTLIER_KERNEL_MAX_K and okernel and fmt.rounding == "nearest"
-                                                 and out_dtype == xc.dtype and fmt.precision <= 22 and xc.data_ptr() % 16 == 0) else None
-            if cls is None and fused:
-                raise NotImplementedError(f"outlier_fixed_qdq: no fused kernel for {granularity} segments of {S} {xc.dtype} elements -> "
-                                          f"{out_dtype} with {fmt!r}, k = {k} and outlier format {ofmt!r} (base address "
-                                          f"{xc.data_ptr() % 16} mod 16)")
-            if cls is not None and fused is None and cls in OUTLIER_CHAIN_BY_DEFAULT:
-                cls = None
-            if cls is not None:
-                try:
-                    y, sc, zp, idx, val = _ops.outlier_fixed_qdq(xc, S, k, fmt.precision, fmt.fraction, bool(fmt.clamp), bool(fmt.symmetric),
-                                                                 ROUNDING_CODE[fmt.rounding], qmin, qmax, sym, ofields, bool(return_qparams),
-                                                                 bool(return_outliers), out_dtype)
-                    _outlier_routes["fused"] += 1
-                    return pick(y, sc, zp, idx, val)
-                except NotImplementedError:   # (DMXQ_ERR_UNSUPPORTED, nothing launched)
-                    if fused:
-                        raise
-        _outlier_routes["chain"] += 1
-        x2 = xc.reshape(-1, S)
-        key = x2.float().abs().view(torch.int32)
-        order = torch.sort(key, dim=1, descending=True, stable=True).indices[:, :k]
-        mask = torch.zeros(x2.shape, dtype=torch.bool, device=x2.device).scatter_(1, order, True)
-        xin = torch.where(mask, torch.zeros((), dtype=x2.dtype, device=x2.device), x2)
-        y_in, sc, zp = dynamic_fixed_qdq(xin, fmt, "per_token", None, sym, out_dtype, True)
-        if ofmt is None:
-            ox = x2 if out_dtype == x2.dtype else x2.to(out_dtype)
-        else:
-            ox = float_qdq(x2, ofmt.mantissa, ofmt.exponent, ofmt.bias, bool(ofmt.flush_subnormal), bool(ofmt.unsigned), ofmt.rounding, out_dtype)
-        y = torch.where(mask, ox, y_in).reshape(xc.shape)
-        return pick(y, sc, zp, order.to(torch.int32), ox.gather(1, order) if return_outliers else None)
+        cls = None if fused is False or not (granularity == "per_group" and k <= OUTLIER_KERNEL_MAX_K and okernel and fmt.rounding == "nearest"
+                                             and out_dtype == xc.dtype and fmt.precision <= 22 and xc.data_ptr() % 16 == 0) else outlier_class(S, xc.dtype)
 
-    if x.requires_grad and torch.is_grad_enabled():
-        return _DynamicSTE.apply(x, run)
-    with torch.no_grad():
-        return run(x.detach())
+        def kernel():
+            y, sc, zp, idx, val = _ops.outlier_fixed_qdq(xc, S, k, fmt.precision, fmt.fraction, bool(fmt.clamp), bool(fmt.symmetric),
+                                                         ROUNDING_CODE[fmt.rounding], qmin, qmax, sym, ofields, bool(return_qparams),
+                                                         bool(return_outliers), out_dtype)
+            return pick(y, sc, zp, idx, val)
+
+        def chain():
+            x2 = xc.reshape(-1, S)
+            key = x2.float().abs().view(torch.int32)
+            order = torch.sort(key, dim=1, descending=True, stable=True).indices[:, :k]
+            mask = torch.zeros(x2.shape, dtype=torch.bool, device=x2.device).scatter_(1, order, True)
+            xin = torch.where(mask, torch.zeros((), dtype=x2.dtype, device=x2.device), x2)
+            y_in, sc, zp = dynamic_fixed_qdq(xin, fmt, "per_token", None, sym, out_dtype, True)
+            if ofmt is None:
+                ox = x2 if out_dtype == x2.dtype else x2.to(out_dtype)
+            else:
+                ox = float_qdq(x2, ofmt.mantissa, ofmt.exponent, ofmt.bias, bool(ofmt.flush_subnormal), bool(ofmt.unsigned), ofmt.rounding, out_dtype)
+            y = torch.where(mask, ox, y_in).reshape(xc.shape)
+            return pick(y, sc, zp, order.to(torch.int32), ox.gather(1, order) if return_outliers else None)
+
+        return route(fused, cls, OUTLIER_CHAIN_BY_DEFAULT, _outlier_routes, kernel, chain,
+                     lambda: (f"outlier_fixed_qdq: no fused kernel for {granularity} segments of {S} {xc.dtype} elements -> "
+                              f"{out_dtype} with {fmt!r}, k = {k} and outlier format {ofmt!r} (base address "
+                              f"{xc.data_ptr() % 16} mod 16)"))
+
+    return straight_through(x, run)
 
 
 # ---------------------------------------------------------------------------------------------------- block-scaled float cast
@@ -3228,61 +3081,47 @@ def block_scaled_float_qdq(x, fmt, group_size: int, scale_format, scale_max: Opt
             y = torch.empty(xc.shape, dtype=out_dtype, device=dev)
             e = y.new_empty(0, dtype=torch.float32)
             return (y, e, e.clone(), _one(1.0, dev)) if return_scale else y
-        cls = None
-        if fused is not False:
-            cls = block_scaled_float_class(g, xc.dtype) if (fmt.rounding == "nearest" and out_dtype == xc.dtype and fmt.mantissa <= 22
-                                                            and sf.mantissa <= 22 and xc.data_ptr() % 16 == 0) else None
-            if cls is None and fused:
-                raise NotImplementedError(f"block_scaled_float_qdq: no fused kernel for groups of {g} {xc.dtype} elements -> {out_dtype} "
-                                          f"with {fmt!r} under {sf!r} scales (base address {xc.data_ptr() % 16} mod 16)")
-            if cls is not None and fused is None and cls in BLOCK_SCALED_CHAIN_BY_DEFAULT:
-                cls = None
-        if cls is not None:
+        cls = None if fused is False or not (fmt.rounding == "nearest" and out_dtype == xc.dtype and fmt.mantissa <= 22 and sf.mantissa <= 22
+                                             and xc.data_ptr() % 16 == 0) else block_scaled_float_class(g, xc.dtype)
+
+        def kernel():
             # an absent and a given t go to the kernel as they are (it applies the t = 1 rule itself) unless the caller wants to see t
             if not return_scale and (tensor_scale is None or isinstance(tensor_scale, torch.Tensor)):
                 t = None if tensor_scale is None else tensor_scale.detach().reshape(1)
             else:
                 t = _bs_tensor_scale(xc, tensor_scale, fmax, scale_max, True)
-            try:
-                y, sc, sq = _ops.block_scaled_float_qdq(xc, g, [*fields, ROUNDING_CODE[fmt.rounding]], [*sfields, ROUNDING_CODE["nearest"]],
-                                                        scale_max, t, bool(return_scale), bool(return_scale), out_dtype)
-                _block_scaled_routes["fused"] += 1
-                return (y, sc, sq, t) if return_scale else y
-            except NotImplementedError:   # (DMXQ_ERR_UNSUPPORTED, nothing launched)
-                if fused:
-                    raise
-        _block_scaled_routes["chain"] += 1
-        t = _bs_tensor_scale(xc, tensor_scale, fmax, scale_max, False)
-        x2 = xc.reshape(-1, g)
-        fmax_t, smax_t = _one(fmax, dev), _one(scale_max, dev)
+            y, sc, sq = _ops.block_scaled_float_qdq(xc, g, [*fields, ROUNDING_CODE[fmt.rounding]], [*sfields, ROUNDING_CODE["nearest"]],
+                                                    scale_max, t, bool(return_scale), bool(return_scale), out_dtype)
+            return (y, sc, sq, t) if return_scale else y
 
-        def chain(part):
-            mn, mx = _ops.group_minmax(part, 0, 1)
-            c = _div_ieee(_div_ieee(torch.maximum(mn.abs(), mx.abs()), fmax_t), t)
-            sq = torch.minimum(float_qdq(c, *sfields, False, "nearest", torch.float32), smax_t.expand_as(c))
-            s = sq * t.expand_as(sq)
-            ok = _usable_scale(s)
-            s1 = torch.where(ok, s, torch.ones_like(s))
-            q = _ops.scale_channels(part, s1, 0, True, torch.float32)
-            q = float_qdq(q, *fields, False, fmt.rounding, torch.float32, seed)
-            y = _ops.scale_channels(q, s1, 0, False, out_dtype)
-            # an unusable group: zeros carrying the sign bit of float_q_E(x)
-            z = float_qdq(part, *fields, False, fmt.rounding, torch.float32, seed)
-            y = torch.where(ok[:, None], y, torch.copysign(torch.zeros_like(z), z).to(out_dtype))
-            return y, torch.where(ok, s, torch.zeros_like(s)), sq
+        def chain():
+            t = _bs_tensor_scale(xc, tensor_scale, fmax, scale_max, False)
+            fmax_t, smax_t = _one(fmax, dev), _one(scale_max, dev)
 
-        if x2.shape[0] <= DYNAMIC_CHAIN_MAX_SEGMENTS:
-            y, sc, sq = chain(x2)
-        else:   # (dmxq_group_minmax takes 65535 groups: groups are independent once t is known, so the chain runs on pieces)
-            parts = [chain(x2[i:i + DYNAMIC_CHAIN_PIECE]) for i in range(0, x2.shape[0], DYNAMIC_CHAIN_PIECE)]
-            y, sc, sq = (torch.cat([p[k] for p in parts]) for k in range(3))
-        y = y.reshape(xc.shape)
-        return (y, sc, sq, t) if return_scale else y
+            def piece(part):   # (groups are independent once t is known)
+                mn, mx = _ops.group_minmax(part, 0, 1)
+                c = _div_ieee(_div_ieee(torch.maximum(mn.abs(), mx.abs()), fmax_t), t)
+                sq = torch.minimum(float_qdq(c, *sfields, False, "nearest", torch.float32), smax_t.expand_as(c))
+                s = sq * t.expand_as(sq)
+                ok = _usable_scale(s)
+                s1 = torch.where(ok, s, torch.ones_like(s))
+                q = _ops.scale_channels(part, s1, 0, True, torch.float32)
+                q = float_qdq(q, *fields, False, fmt.rounding, torch.float32, seed)
+                y = _ops.scale_channels(q, s1, 0, False, out_dtype)
+                # an unusable group: zeros carrying the sign bit of float_q_E(x)
+                z = float_qdq(part, *fields, False, fmt.rounding, torch.float32, seed)
+                y = torch.where(ok[:, None], y, torch.copysign(torch.zeros_like(z), z).to(out_dtype))
+                return y, torch.where(ok, s, torch.zeros_like(s)), sq
 
-    if x.requires_grad and torch.is_grad_enabled():
-        return _DynamicSTE.apply(x, run)
-    with torch.no_grad():
-        return run(x.detach())
+            y, sc, sq = in_pieces(piece, xc.reshape(-1, g), 3)
+            y = y.reshape(xc.shape)
+            return (y, sc, sq, t) if return_scale else y
+
+        return route(fused, cls, BLOCK_SCALED_CHAIN_BY_DEFAULT, _block_scaled_routes, kernel, chain,
+                     lambda: (f"block_scaled_float_qdq: no fused kernel for groups of {g} {xc.dtype} elements -> {out_dtype} "
+                              f"with {fmt!r} under {sf!r} scales (base address {xc.data_ptr() % 16} mod 16)"))
+
+    return straight_through(x, run)
 
 
 # ---------------------------------------------------------------------------------------------------- Wanda
@@ -3381,27 +3220,22 @@ def _wanda(w, act_norm, K, M, want_score, want_mask, want_y, fused, out_dtype, w
         if wc.numel() == 0:
             e = lambda dt: torch.empty(wc.shape, dtype=dt, device=wc.device)
             return (e(torch.float32) if want_score else None, e(torch.float32) if want_mask else None, e(y_dtype) if want_y else None)
-        if fused is not False:
-            ok = wanda_class(wc.dtype, wc.shape[1], M) and wc.data_ptr() % 16 == 0 and an.data_ptr() % 16 == 0
-            if not ok and fused:
-                raise NotImplementedError(f"{what}: no one-pass kernel for groups of {M} in rows of {wc.shape[1]} {wc.dtype} elements "
-                                          f"(weight base address {wc.data_ptr() % 16} mod 16)")
-            if ok and fused is None and M in WANDA_CHAIN_BY_DEFAULT:
-                ok = False
-            if ok:
-                try:
-                    score, mask, y = _ops.wanda_nm(wc, an, int(K), int(M), bool(want_score), bool(want_mask), bool(want_y), None, y_dtype)
-                    _wanda_routes["fused"] += 1
-                    return (score if want_score else None), (mask if want_mask else None), (y if want_y else None)
-                except NotImplementedError:   # (DMXQ_ERR_UNSUPPORTED, nothing launched)
-                    if fused:
-                        raise
-        _wanda_routes["chain"] += 1
-        score = wc.float().abs() * an   # (the definition: one fp32 multiply per element)
-        mask = y = None
-        if want_mask or want_y:
-            mask, y = _nm(score, wc if want_y else None, K, M, -1, want_mask, want_y, None, y_dtype if want_y else None)
-        return (score if want_score else None), mask, y
+        key = None if fused is False or not (wanda_class(wc.dtype, wc.shape[1], M) and wc.data_ptr() % 16 == 0 and an.data_ptr() % 16 == 0) else M
+
+        def kernel():
+            score, mask, y = _ops.wanda_nm(wc, an, int(K), int(M), bool(want_score), bool(want_mask), bool(want_y), None, y_dtype)
+            return (score if want_score else None), (mask if want_mask else None), (y if want_y else None)
+
+        def chain():
+            score = wc.float().abs() * an   # (the definition: one fp32 multiply per element)
+            mask = y = None
+            if want_mask or want_y:
+                mask, y = _nm(score, wc if want_y else None, K, M, -1, want_mask, want_y, None, y_dtype if want_y else None)
+            return (score if want_score else None), mask, y
+
+        return route(fused, key, WANDA_CHAIN_BY_DEFAULT, _wanda_routes, kernel, chain,
+                     lambda: (f"{what}: no one-pass kernel for groups of {M} in rows of {wc.shape[1]} {wc.dtype} elements "
+                              f"(weight base address {wc.data_ptr() % 16} mod 16)"))
 
 
 def wanda_score(w, act_norm, fused: Optional[bool] = None):
@@ -3530,28 +3364,23 @@ def awq_scaled_error(w, s, fmt, group_size: int, symmetric_qscheme: bool = False
         if wc.numel() == 0:
             d = torch.empty(wc.shape, dtype=torch.float32, device=wc.device)
             return (d, torch.empty_like(wc)) if return_wq else d
-        if fused is not False:
-            ok = (fmt.rounding == "nearest" and fmt.precision <= 22 and awq_class(wc.dtype, wc.shape[1], group_size)
-                  and wc.data_ptr() % 16 == 0 and sc.data_ptr() % 16 == 0)
-            if not ok and fused:
-                raise NotImplementedError(f"awq_scaled_error: no one-launch kernel for groups of {group_size} in rows of {wc.shape[1]} {wc.dtype} "
-                                          f"elements with {fmt!r} (weight base address {wc.data_ptr() % 16} mod 16)")
-            if ok and fused is None and group_size in AWQ_CHAIN_BY_DEFAULT:
-                ok = False
-            if ok:
-                try:
-                    d, wq = _ops.awq_group_error(wc, sc, int(group_size), fmt.precision, fmt.fraction, bool(fmt.clamp), bool(fmt.symmetric),
-                                                 qmin, qmax, sym, bool(return_wq))
-                    _awq_routes["fused"] += 1
-                    return (d, wq) if return_wq else d
-                except NotImplementedError:   # (DMXQ_ERR_UNSUPPORTED, nothing launched)
-                    if fused:
-                        raise
-        _awq_routes["chain"] += 1
-        ws = _ops.scale_channels(wc, sc, -1, False, wc.dtype)
-        wq = dynamic_fixed_qdq(ws, fmt, "per_group", group_size, symmetric_qscheme=sym)
-        d = _ops.scale_channels(wq, sc, -1, True, torch.float32) - wc.float()
-        return (d, wq) if return_wq else d
+        key = None if fused is False or not (fmt.rounding == "nearest" and fmt.precision <= 22 and awq_class(wc.dtype, wc.shape[1], group_size)
+                                             and wc.data_ptr() % 16 == 0 and sc.data_ptr() % 16 == 0) else group_size
+
+        def kernel():
+            d, wq = _ops.awq_group_error(wc, sc, int(group_size), fmt.precision, fmt.fraction, bool(fmt.clamp), bool(fmt.symmetric),
+                                         qmin, qmax, sym, bool(return_wq))
+            return (d, wq) if return_wq else d
+
+        def chain():
+            ws = _ops.scale_channels(wc, sc, -1, False, wc.dtype)
+            wq = dynamic_fixed_qdq(ws, fmt, "per_group", group_size, symmetric_qscheme=sym)
+            d = _ops.scale_channels(wq, sc, -1, True, torch.float32) - wc.float()
+            return (d, wq) if return_wq else d
+
+        return route(fused, key, AWQ_CHAIN_BY_DEFAULT, _awq_routes, kernel, chain,
+                     lambda: (f"awq_scaled_error: no one-launch kernel for groups of {group_size} in rows of {wc.shape[1]} {wc.dtype} "
+                              f"elements with {fmt!r} (weight base address {wc.data_ptr() % 16} mod 16)"))
 
 
 class _full_fp32_matmul:
@@ -3766,28 +3595,23 @@ def awq_clip(w, blocks, fmt, group_size: int, ratios=None, symmetric_qscheme: bo
             return result(torch.empty(rows, G, dtype=torch.uint8, device=wc.device), torch.empty(rows, G, dtype=torch.float32, device=wc.device),
                           torch.empty(rows, G, n, dtype=torch.float32, device=wc.device))
         r = _awq_clip_device_ratios(ratios, wc.device)
-        if fused is not False:
-            ok = (fmt.precision <= 22 and awq_clip_class(wc.dtype, L, group_size)
-                  and all(t.data_ptr() % 16 == 0 for t in (wc, blocks, r, y)))
-            if not ok and fused:
-                raise NotImplementedError(f"awq_clip: no one-launch kernel for groups of {group_size} in rows of {L} {wc.dtype} elements with "
-                                          f"{fmt!r} (weight base address {wc.data_ptr() % 16} mod 16)")
-            if ok and fused is None and group_size in AWQ_CLIP_CHAIN_BY_DEFAULT:
-                ok = False
-            if ok:
-                try:
-                    best, clip, losses = _ops.awq_clip(wc, blocks.detach(), r, y, int(group_size), fmt.precision, fmt.fraction, bool(fmt.clamp),
-                                                       bool(fmt.symmetric), qmin, qmax, sym, bool(return_best), bool(return_clip),
-                                                       bool(return_losses))
-                    _awq_clip_routes["fused"] += 1
-                    return result(best, clip, losses)
-                except NotImplementedError:   # (DMXQ_ERR_UNSUPPORTED, nothing launched)
-                    if fused:
-                        raise
-        _awq_clip_routes["chain"] += 1
-        yc, best, clip, losses = _awq_clip_chain(wc, blocks.detach(), r, fmt, group_size, sym)
-        y.copy_(yc)
-        return result(best, clip, losses)
+        key = None if fused is False or not (fmt.precision <= 22 and awq_clip_class(wc.dtype, L, group_size)
+                                             and all(t.data_ptr() % 16 == 0 for t in (wc, blocks, r, y))) else group_size
+
+        def kernel():
+            best, clip, losses = _ops.awq_clip(wc, blocks.detach(), r, y, int(group_size), fmt.precision, fmt.fraction, bool(fmt.clamp),
+                                               bool(fmt.symmetric), qmin, qmax, sym, bool(return_best), bool(return_clip),
+                                               bool(return_losses))
+            return result(best, clip, losses)
+
+        def chain():
+            yc, best, clip, losses = _awq_clip_chain(wc, blocks.detach(), r, fmt, group_size, sym)
+            y.copy_(yc)
+            return result(best, clip, losses)
+
+        return route(fused, key, AWQ_CLIP_CHAIN_BY_DEFAULT, _awq_clip_routes, kernel, chain,
+                     lambda: (f"awq_clip: no one-launch kernel for groups of {group_size} in rows of {L} {wc.dtype} elements with "
+                              f"{fmt!r} (weight base address {wc.data_ptr() % 16} mod 16)"))
 
 
 # ---------------------------------------------------------------------------------------------------- AdaRound (learned weight rounding)
@@ -3900,30 +3724,22 @@ def _adaround_soft(V2):
 
 def _adaround_forward(wc, Vc, s, z, S, qmin, qmax, hard, out_dtype, fused, granularity):
     """y of the contiguous operands: the kernel where it applies, else the chain"""
-    if fused is not False:
-        cls = adaround_class(S, wc.dtype, granularity) if (out_dtype in (wc.dtype, torch.float32) and wc.data_ptr() % 16 == 0
-                                                            and Vc.data_ptr() % 16 == 0) else None
-        if cls is None and fused:
-            raise NotImplementedError(f"adaround_qdq: no fused kernel for segments of {S} {wc.dtype} elements with a {out_dtype} output "
-                                      f"(base addresses {wc.data_ptr() % 16} / {Vc.data_ptr() % 16} mod 16)")
-        if cls is not None and fused is None and cls in ADAROUND_CHAIN_BY_DEFAULT:
-            cls = None
-        if cls is not None:
-            try:
-                y = _ops.adaround_forward(wc, Vc, s, z, S, qmin, qmax, bool(hard), out_dtype)
-                _adaround_routes["fused"] += 1
-                return y
-            except NotImplementedError:   # (DMXQ_ERR_UNSUPPORTED, nothing launched)
-                if fused:
-                    raise
-    _adaround_routes["chain"] += 1
-    # the definition, spelled in torch on the device
-    w2, V2 = wc.reshape(-1, S).float(), Vc.reshape(-1, S)
-    sc, zq = s[:, None], z[:, None]
-    f = torch.floor(w2 / sc)
-    h = (V2 >= 0).to(torch.float32) if hard else _adaround_soft(V2)[2]
-    q = torch.clamp((f + h) + zq, qmin, qmax)
-    return ((q - zq) * sc).to(out_dtype).reshape(wc.shape)
+    cls = None if fused is False or not (out_dtype in (wc.dtype, torch.float32) and wc.data_ptr() % 16 == 0
+                                         and Vc.data_ptr() % 16 == 0) else adaround_class(S, wc.dtype, granularity)
+
+    def chain():
+        # the definition, spelled in torch on the device
+        w2, V2 = wc.reshape(-1, S).float(), Vc.reshape(-1, S)
+        sc, zq = s[:, None], z[:, None]
+        f = torch.floor(w2 / sc)
+        h = (V2 >= 0).to(torch.float32) if hard else _adaround_soft(V2)[2]
+        q = torch.clamp((f + h) + zq, qmin, qmax)
+        return ((q - zq) * sc).to(out_dtype).reshape(wc.shape)
+
+    return route(fused, cls, ADAROUND_CHAIN_BY_DEFAULT, _adaround_routes,
+                 lambda: _ops.adaround_forward(wc, Vc, s, z, S, qmin, qmax, bool(hard), out_dtype), chain,
+                 lambda: (f"adaround_qdq: no fused kernel for segments of {S} {wc.dtype} elements with a {out_dtype} output "
+                          f"(base addresses {wc.data_ptr() % 16} / {Vc.data_ptr() % 16} mod 16)"))
 
 
 def adaround_backward(w, V, g, scale, zero_point, fmt, granularity: str = "per_group", group_size: Optional[int] = None, beta: float = 2.0,
@@ -3967,46 +3783,41 @@ def adaround_backward(w, V, g, scale, zero_point, fmt, granularity: str = "per_g
 
         if wc.numel() == 0:
             return done(torch.empty(wc.shape, dtype=torch.float32, device=wc.device), torch.zeros((), dtype=torch.float64, device=wc.device))
-        if fused is not False:
-            cls = adaround_class(S, wc.dtype, granularity) if (gc.dtype in (wc.dtype, torch.float32) and wc.data_ptr() % 16 == 0
-                                                                and Vc.data_ptr() % 16 == 0 and gc.data_ptr() % 16 == 0) else None
-            if cls is None and fused:
-                raise NotImplementedError(f"adaround_backward: no fused kernel for segments of {S} {wc.dtype} elements with a {gc.dtype} "
-                                          f"gradient (base addresses {wc.data_ptr() % 16} / {Vc.data_ptr() % 16} / {gc.data_ptr() % 16} mod 16)")
-            if cls is not None and fused is None and cls in ADAROUND_CHAIN_BY_DEFAULT:
-                cls = None
-            if cls is not None:
-                try:
-                    dV, reg = _ops.adaround_backward(wc, Vc, gc, s, z, S, qmin, qmax, float(beta), float(reg_weight), want)
-                    _adaround_routes["fused"] += 1
-                    return done(dV, reg.reshape(()) if want else None)
-                except NotImplementedError:   # (DMXQ_ERR_UNSUPPORTED, nothing launched)
-                    if fused:
-                        raise
-        _adaround_routes["chain"] += 1
-        # the definition, spelled in torch on the device
-        w2, V2, g2 = wc.reshape(-1, S).float(), Vc.reshape(-1, S), gc.reshape(-1, S).float()
-        sc, zq = s[:, None], z[:, None]
-        fz = torch.floor(w2 / sc) + zq
-        cell = (fz >= qmin) & (fz <= qmax - 1)
-        sg, hr, h = _adaround_soft(V2)
-        in01 = (hr > 0) & (hr < 1)
-        dh = (sg * (1.0 - sg)) * ADAROUND_ZG
-        zero = torch.zeros_like(dh)
-        dV = torch.where(in01 & cell, (g2 * sc) * dh, zero)
-        reg = None
-        rw = _f32(reg_weight)
-        if rw != 0.0 or want:
-            b = torch.tensor(float(beta), dtype=torch.float32)
-            bm1, m2b = (b - 1.0).item(), (-2.0 * b).item()
-            t2 = 2.0 * h - 1.0
-            a = torch.abs(t2)
-            p1 = torch.pow(a, bm1)
-            if rw != 0.0:
-                dV = dV + torch.where(in01, rw * (((m2b * p1) * torch.sign(t2)) * dh), zero)
-            if want:
-                reg = (1.0 - p1 * a).sum(dtype=torch.float64)
-        return done(dV.reshape(wc.shape), reg)
+        cls = None if fused is False or not (gc.dtype in (wc.dtype, torch.float32) and wc.data_ptr() % 16 == 0 and Vc.data_ptr() % 16 == 0
+                                             and gc.data_ptr() % 16 == 0) else adaround_class(S, wc.dtype, granularity)
+
+        def kernel():
+            dV, reg = _ops.adaround_backward(wc, Vc, gc, s, z, S, qmin, qmax, float(beta), float(reg_weight), want)
+            return done(dV, reg.reshape(()) if want else None)
+
+        def chain():
+            # the definition, spelled in torch on the device
+            w2, V2, g2 = wc.reshape(-1, S).float(), Vc.reshape(-1, S), gc.reshape(-1, S).float()
+            sc, zq = s[:, None], z[:, None]
+            fz = torch.floor(w2 / sc) + zq
+            cell = (fz >= qmin) & (fz <= qmax - 1)
+            sg, hr, h = _adaround_soft(V2)
+            in01 = (hr > 0) & (hr < 1)
+            dh = (sg * (1.0 - sg)) * ADAROUND_ZG
+            zero = torch.zeros_like(dh)
+            dV = torch.where(in01 & cell, (g2 * sc) * dh, zero)
+            reg = None
+            rw = _f32(reg_weight)
+            if rw != 0.0 or want:
+                b = torch.tensor(float(beta), dtype=torch.float32)
+                bm1, m2b = (b - 1.0).item(), (-2.0 * b).item()
+                t2 = 2.0 * h - 1.0
+                a = torch.abs(t2)
+                p1 = torch.pow(a, bm1)
+                if rw != 0.0:
+                    dV = dV + torch.where(in01, rw * (((m2b * p1) * torch.sign(t2)) * dh), zero)
+                if want:
+                    reg = (1.0 - p1 * a).sum(dtype=torch.float64)
+            return done(dV.reshape(wc.shape), reg)
+
+        return route(fused, cls, ADAROUND_CHAIN_BY_DEFAULT, _adaround_routes, kernel, chain,
+                     lambda: (f"adaround_backward: no fused kernel for segments of {S} {wc.dtype} elements with a {gc.dtype} "
+                              f"gradient (base addresses {wc.data_ptr() % 16} / {Vc.data_ptr() % 16} / {gc.data_ptr() % 16} mod 16)"))
 
 
 class _AdaRoundCast(torch.autograd.Function):
