@@ -140,6 +140,44 @@ def bfp_matmul(mant_a, exps_a, mant_w, exps_w, precision_a, precision_w, block_s
 
 
 @_guarded
+def bfp_pack_cols(x, precision, block_size, symmetric=True):
+    """x[..., K, N] blocked along K -> codes [..., K, N], exps [..., K / B, N] (csrc/bfp_pack.hip); NotImplementedError: the transposing route"""
+    xc = _prep(x, "bfp_pack_cols")
+    if xc.dim() < 2 or block_size < 1:
+        raise RuntimeError("bfp_pack_cols: expects a tensor of at least two dimensions and a positive block size")
+    K, N = xc.shape[-2], xc.shape[-1]
+    if K % block_size:
+        _unsupported("bfp_pack_cols: a ragged last block")
+    mant = torch.empty(xc.shape, dtype=torch.int8, device=xc.device)
+    exps = torch.empty(tuple(xc.shape[:-2]) + (K // block_size, N), dtype=torch.uint8, device=xc.device)
+    check(lib().dmxq_bfp_pack_cols(ptr(xc), dtype_code(xc.dtype), ptr(mant), ptr(exps), xc.numel() // max(K * N, 1), K, N, block_size,
+                                   precision, int(symmetric), stream_of(xc)), "dmxq_bfp_pack_cols")
+    return mant, exps
+
+
+@_guarded
+def bfp_bmm(mant_a, exps_a, mant_w, exps_w, precision_a, precision_w, block_size, w_layout, out_dtype):
+    """packed [b, M, K] / [b, M, K / B] x ([b, N, K] / [b, N, K / B] (w_layout 0) or [b, K, N] / [b, K / B, N] (1)) -> [b, M, N]
+    (csrc/bfp_bmm.hip); NotImplementedError: the front end's chain"""
+    for t in (mant_a, exps_a, mant_w, exps_w):
+        require_gpu(t, "bfp_bmm")
+    if (mant_a.dim() != 3 or mant_w.dim() != 3 or exps_a.dim() != 3 or exps_w.dim() != 3 or block_size < 1 or w_layout not in (0, 1)
+            or mant_a.dtype != torch.int8 or mant_w.dtype != torch.int8 or exps_a.dtype != torch.uint8 or exps_w.dtype != torch.uint8):
+        raise RuntimeError("bfp_bmm: expects 3-d int8 codes and uint8 exponents, a positive block size and w_layout 0 or 1")
+    b, M, K = mant_a.shape
+    nb = -(-K // block_size)
+    N = mant_w.shape[2] if w_layout else mant_w.shape[1]
+    if (tuple(mant_w.shape) != ((b, K, N) if w_layout else (b, N, K)) or tuple(exps_a.shape) != (b, M, nb)
+            or tuple(exps_w.shape) != ((b, nb, N) if w_layout else (b, N, nb))):
+        raise RuntimeError("bfp_bmm: operand shapes do not match")
+    ca, ea, cw, ew = mant_a.contiguous(), exps_a.contiguous(), mant_w.contiguous(), exps_w.contiguous()
+    out = torch.empty((b, M, N), dtype=out_dtype, device=ca.device)
+    check(lib().dmxq_bfp_bmm(ptr(ca), ptr(ea), ptr(cw), ptr(ew), ptr(out), dtype_code(out_dtype), b, M, N, K, block_size, precision_a,
+                             precision_w, w_layout, stream_of(ca)), "dmxq_bfp_bmm")
+    return out
+
+
+@_guarded
 def weight_hypernet(w, precision, block_size, symmetric, score, K, M, sq_scale, out_dtype=None, block_dim=-1):
     wc = _prep(w, "weight_hypernet")
     masked = score is not None and M != 0

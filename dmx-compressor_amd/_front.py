@@ -43,6 +43,7 @@ __all__ = [
     "ADAROUND_CHAIN_BY_DEFAULT",
     "bfp_matmul", "bfp_matmul_packed", "bfp_matmul_check", "bfp_matmul_class", "BFP_MATMUL_CHAIN_BY_DEFAULT", "BFP_MATMUL_BLOCK_SIZES",
     "BFP_MATMUL_CHAIN_PIECE_ENTRIES",
+    "bfp_bmm", "bfp_bmm_packed", "bfp_bmm_class", "BFP_BMM_CHAIN_BY_DEFAULT", "BFP_BMM_MAX_BATCH",
 ]
 
 _ops = None   # the raw namespace: set by bind()
@@ -110,11 +111,33 @@ def bfp_qdq_multi(tensors, precision: int, block_size: int, block_dim: int = -1,
                                    _seed_arg(seed, rounding)))
 
 
-def bfp_pack(x, precision: int, block_size: int, symmetric: bool = True):
+_bfp_pack_cols_routes = {"fused": 0, "chain": 0}
+
+
+def bfp_pack(x, precision: int, block_size: int, symmetric: bool = True, block_dim: int = -1, fused: Optional[bool] = None):
     """Packed on-wire BFP of a tensor blocked along its last dim: (int8 mantissa codes, same shape; uint8 shared
-    exponents, [..., ceil(L / block_size)]).  bfp_unpack(*bfp_pack(x)) == bfp_qdq(x)."""
+    exponents, [..., ceil(L / block_size)]).  bfp_unpack(*bfp_pack(x)) == bfp_qdq(x).
+    block_dim=-2: x[..., K, N] blocked along K, the layout of an attention layer's V (ops.bfp_bmm's "kn" operand): codes [..., K, N],
+    exponents [..., ceil(K / block_size), N]; by definition the last-dim pack of x.transpose(-1, -2), transposed back, bit for bit.  One
+    launch (dmxq_bfp_pack_cols) for block sizes 32 / 64 / 128 with K a multiple, N whole 16-byte vectors and an aligned base, the
+    transposing route otherwise; fused=True: NotImplementedError instead, False: the transposing route."""
     require_gpu(x, "bfp_pack")
-    return _ops.bfp_pack(x, precision, block_size, symmetric)
+    if block_dim == -1 or (x.dim() and block_dim == x.dim() - 1):
+        return _ops.bfp_pack(x, precision, block_size, symmetric)
+    if x.dim() < 2 or block_dim not in (-2, x.dim() - 2):
+        raise DmxqError(f"bfp_pack: block_dim must be -1 or -2 (of at least two dimensions), got {block_dim} for {tuple(x.shape)}")
+    B = int(block_size)
+    epl = 4 if x.dtype == torch.float32 else 8
+    ok = (fused is not False and B in BFP_MATMUL_BLOCK_SIZES and x.shape[-2] % B == 0 and x.shape[-1] % epl == 0 and x.numel() > 0
+          and not (x.is_contiguous() and x.data_ptr() % 16))
+
+    def transposing():
+        c, e = _ops.bfp_pack(x.transpose(-1, -2).contiguous(), precision, B, symmetric)
+        return c.transpose(-1, -2).contiguous(), e.transpose(-1, -2).contiguous()
+
+    return route(fused, "cols" if ok else None, frozenset(), _bfp_pack_cols_routes,
+                 lambda: tuple(_ops.bfp_pack_cols(x, precision, B, symmetric)), transposing,
+                 lambda: f"bfp_pack: no column kernel for {tuple(x.shape)} {x.dtype} in blocks of {B} (base {x.data_ptr() % 16} mod 16)")
 
 
 def bfp_unpack(mant, exps, precision: int, block_size: int, out_dtype: torch.dtype = torch.float32):
@@ -246,6 +269,109 @@ def bfp_matmul(x, w, fmt_x, fmt_w=None, out_dtype: Optional[torch.dtype] = None,
         cw, ew = bfp_pack(w.detach(), fw.precision, fw.block_size, fw.symmetric)
         y = bfp_matmul_packed(ca, ea, cw, ew, fx.precision, fw.precision, fx.block_size, out_dtype or x.dtype, fused)
     return y.reshape(tuple(x.shape[:-1]) + (w.shape[0],))
+
+
+# ---------------------------------------------------------------------------------------------------- batched BFP matmul
+# Kernel classes (bfp_bmm_class) that run the chain unless fused=True asks for the kernel: none (profiles/r30_bfp_bmm.txt; the chain is
+# _bfp_matmul_chain per batch element, slow by construction).
+BFP_BMM_CHAIN_BY_DEFAULT = frozenset()
+BFP_BMM_MAX_BATCH = 65535   # grid.z of one launch: larger batches run in pieces
+_bfp_bmm_routes = {"fused": 0, "chain": 0}
+_BFP_BMM_LAYOUTS = {"nk": 0, "kn": 1}
+
+
+def bfp_bmm_class(mant_a, mant_w, block_size: int, w_layout: str = "nk") -> Optional[str]:
+    """the geometry the batched kernel picks for codes mant_a [batch, M, K] and mant_w ([batch, N, K] in "nk", [batch, K, N] in "kn"),
+    asked of the library (dmxq_bfp_bmm_class; no GPU involved): "<layout>_b<block size>_n<N tile width>", e.g. "kn_b64_n64" (the 64-wide
+    tile serves N <= 64), or None where the call runs the chain: a block size outside 32 / 64 / 128, K % block_size != 0, "kn" with
+    N % 4 != 0, or a contiguous base that is not 16-byte (mant_w in "kn": 4-byte) aligned."""
+    from ._lib import lib
+    if mant_a.dim() != 3 or mant_w.dim() != 3 or w_layout not in _BFP_BMM_LAYOUTS:
+        return None
+    kn = _BFP_BMM_LAYOUTS[w_layout]
+    for c, al in ((mant_a, 16), (mant_w, 4 if kn else 16)):
+        if c.is_contiguous() and c.data_ptr() % al:
+            return None
+    N = mant_w.shape[2] if kn else mant_w.shape[1]
+    v = lib().dmxq_bfp_bmm_class(min(mant_a.shape[0], BFP_BMM_MAX_BATCH), mant_a.shape[1], N, mant_a.shape[2], int(block_size), kn)
+    if v == 0:
+        return None
+    v -= 1
+    return f"{('nk', 'kn')[v // 6]}_b{BFP_MATMUL_BLOCK_SIZES[(v // 2) % 3]}_n{64 if v & 1 else 128}"
+
+
+def bfp_bmm_packed(mant_a, exps_a, mant_w, exps_w, precision_a: int, precision_w: int, block_size: int, w_layout: str = "nk",
+                   out_dtype: torch.dtype = torch.float32, fused: Optional[bool] = None):
+    """Batched y[b] = A[b] W[b]^T ("nk": W codes [.., N, K], exponents [.., N, K / B]) or A[b] W[b] ("kn": codes [.., K, N], exponents
+    [.., K / B, N]: ops.bfp_pack(w, ..., block_dim=-2)) on packed BFP operands, each batch element as bfp_matmul_packed defines the
+    product.  A: codes [.., M, K], exponents [.., M, K / B]; the leading dimensions of all four are equal and come back
+    on the result [.., M, N]; 2-D operands are a batch of one.  fused as in bfp_matmul_packed: the kernel (dmxq_bfp_bmm) where
+    bfp_bmm_class names one, else _bfp_matmul_chain per batch element (on W transposed in "kn")."""
+    for t in (mant_a, exps_a, mant_w, exps_w):
+        require_gpu(t, "bfp_bmm_packed")
+    B = int(block_size)
+    if w_layout not in _BFP_BMM_LAYOUTS:
+        raise DmxqError(f"bfp_bmm_packed: w_layout must be 'nk' or 'kn', got {w_layout!r}")
+    kn = _BFP_BMM_LAYOUTS[w_layout]
+    if mant_a.dim() < 2 or mant_w.dim() != mant_a.dim() or B < 1:
+        raise DmxqError(f"bfp_bmm_packed: codes must be [.., M, K] and [.., N, K] / [.., K, N] of one rank with a positive block size, "
+                        f"got {tuple(mant_a.shape)}, {tuple(mant_w.shape)}, {block_size}")
+    lead, (M, K) = tuple(mant_a.shape[:-2]), mant_a.shape[-2:]
+    N = mant_w.shape[-1] if kn else mant_w.shape[-2]
+    nb = -(-K // B)
+    if tuple(mant_w.shape) != lead + ((K, N) if kn else (N, K)):
+        raise DmxqError(f"bfp_bmm_packed: {w_layout!r} codes of w must be {lead + ((K, N) if kn else (N, K))}, got {tuple(mant_w.shape)} "
+                        f"(equal leading dimensions, one K)")
+    if tuple(exps_a.shape) != lead + (M, nb) or tuple(exps_w.shape) != lead + ((nb, N) if kn else (N, nb)):
+        raise DmxqError(f"bfp_bmm_packed: exponents must be {lead + (M, nb)} and {lead + ((nb, N) if kn else (N, nb))}, got "
+                        f"{tuple(exps_a.shape)}, {tuple(exps_w.shape)}")
+    if mant_a.dtype != torch.int8 or mant_w.dtype != torch.int8 or exps_a.dtype != torch.uint8 or exps_w.dtype != torch.uint8:
+        raise DmxqError("bfp_bmm_packed: codes are int8 and shared exponents uint8 (ops.bfp_pack)")
+    if not (2 <= precision_a <= 8 and 2 <= precision_w <= 8):
+        raise DmxqError(f"bfp_bmm_packed: precisions must lie in 2 .. 8, got {precision_a}, {precision_w}")
+    pa, pw = int(precision_a), int(precision_w)
+    ca, ea, cw, ew = (t.reshape((-1,) + tuple(t.shape[-2:])) for t in (mant_a, exps_a, mant_w, exps_w))
+    batch = ca.shape[0]
+    if not (batch and M and N):
+        fused = False   # (an empty product: the chain, whatever was asked for)
+    cls = None if fused is False else bfp_bmm_class(ca, cw, B, w_layout)
+
+    def kernel():
+        parts = [_ops.bfp_bmm(ca[i:i + BFP_BMM_MAX_BATCH], ea[i:i + BFP_BMM_MAX_BATCH], cw[i:i + BFP_BMM_MAX_BATCH],
+                              ew[i:i + BFP_BMM_MAX_BATCH], pa, pw, B, kn, out_dtype) for i in range(0, batch, BFP_BMM_MAX_BATCH)]
+        return parts[0] if len(parts) == 1 else torch.cat(parts)
+
+    def chain():
+        y = torch.empty((batch, M, N), dtype=out_dtype, device=ca.device)
+        for b in range(batch):
+            wb, eb = (cw[b].T.contiguous(), ew[b].T.contiguous()) if kn else (cw[b], ew[b])
+            y[b] = _bfp_matmul_chain(ca[b], ea[b], wb, eb, pa, pw, B, out_dtype)
+        return y
+
+    with torch.no_grad():
+        y = route(fused, cls, BFP_BMM_CHAIN_BY_DEFAULT, _bfp_bmm_routes, kernel, chain,
+                  lambda: (f"bfp_bmm_packed: no kernel for {tuple(mant_a.shape)} x {tuple(mant_w.shape)} {w_layout!r} codes in blocks of {B} "
+                           f"(base addresses {mant_a.data_ptr() % 16}, {mant_w.data_ptr() % 16} mod 16)"))
+    return y.reshape(lead + (M, N))
+
+
+def bfp_bmm(x, w, fmt_x, fmt_w=None, w_layout: str = "nk", out_dtype: Optional[torch.dtype] = None, fused: Optional[bool] = None):
+    """Batched x[.., M, K] times w[.., N, K]^T ("nk") or w[.., K, N] ("kn"), both operands in block floating point along K (formats as
+    ops.bfp_matmul: one block size, p <= 8, nearest rounding; fmt_w defaults to fmt_x): packs x along its last and w along its K
+    dimension (ops.bfp_pack, block_dim=-2 in "kn") and multiplies the packed operands (bfp_bmm_packed).  Equal leading dimensions;
+    -> [.., M, N] of out_dtype (default x.dtype).  No gradient: the result is detached."""
+    if w_layout not in _BFP_BMM_LAYOUTS:
+        raise DmxqError(f"bfp_bmm: w_layout must be 'nk' or 'kn', got {w_layout!r}")
+    kn = _BFP_BMM_LAYOUTS[w_layout]
+    if x.dim() < 2 or w.dim() != x.dim() or tuple(w.shape[:-2]) != tuple(x.shape[:-2]) or w.shape[-2 if kn else -1] != x.shape[-1]:
+        raise DmxqError(f"bfp_bmm: x {tuple(x.shape)} and w {tuple(w.shape)} ({w_layout!r}) need equal leading dimensions and one K")
+    fx, fw = bfp_matmul_check(x.reshape(-1, x.shape[-1]), w.new_empty((0, x.shape[-1])), fmt_x, fmt_w)
+    require_gpu(x, "bfp_bmm")
+    require_gpu(w, "bfp_bmm")
+    with torch.no_grad():
+        ca, ea = bfp_pack(x.detach(), fx.precision, fx.block_size, fx.symmetric)
+        cw, ew = bfp_pack(w.detach(), fw.precision, fw.block_size, fw.symmetric, block_dim=-2 if kn else -1)
+        return bfp_bmm_packed(ca, ea, cw, ew, fx.precision, fw.precision, fx.block_size, w_layout, out_dtype or x.dtype, fused)
 
 
 def weight_hypernet(w, precision: int, block_size: int, symmetric: bool = True, score=None, K: int = 0, M: int = 0,

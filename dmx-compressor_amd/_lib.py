@@ -31,6 +31,9 @@ SIGNATURES = {
     "dmxq_bfp_unpack": [_vp, _vp, _vp, _i32, _i64, _i64, _i64, _i32, _vp],
     "dmxq_bfp_matmul_class": [_i64, _i64, _i64, _i64],
     "dmxq_bfp_matmul": [_vp, _vp, _vp, _vp, _vp, _i32, _i64, _i64, _i64, _i64, _i32, _i32, _vp],
+    "dmxq_bfp_pack_cols": [_vp, _i32, _vp, _vp, _i64, _i64, _i64, _i64, _i32, _i32, _vp],
+    "dmxq_bfp_bmm_class": [_i64, _i64, _i64, _i64, _i64, _i32],
+    "dmxq_bfp_bmm": [_vp, _vp, _vp, _vp, _vp, _i32, _i64, _i64, _i64, _i64, _i64, _i32, _i32, _i32, _vp],
     "dmxq_weight_hypernet": [_vp, _i32, _vp, _i32, _i32, _i32, _vp, _vp, _i32, _i64, _i64, _i64, _i32, _i32, _vp],
     "dmxq_weight_hypernet_multi": [_vp, _i64, _i32, _i32, _i32, _i32, _i32, _i64, _i32, _i32, _vp],
     "dmxq_weight_hypernet_strided": [_vp, _i32, _vp, _i32, _i32, _i32, _vp, _vp, _i32, _i64, _i64, _i64, _i64, _i32, _i32, _vp],

@@ -173,6 +173,100 @@ __global__ __launch_bounds__(T) void bfp_pack_rows_kernel(const void* __restrict
   }
 }
 
+// blocks running DOWN a non-contiguous dimension: x[ob, B, N] (ob = outer * K / B blocks of B rows) -> codes [ob, B, N], exps [ob, N].
+// Lanes run along the contiguous N, one 16-byte vector of EPL columns per lane; a lane owns EPL whole blocks.  It walks the B rows of
+// its blocks twice, kColsRows loads in flight: pass 1 takes the per-column maximum on the magnitude bits (16-bit inputs: v_pk_max_u16
+// on the masked dwords), pass 2 reads the rows again (from L2) and emits the codes by the magic-add difference of
+// bfp_pack_rows_kernel, each column with its own block parameters -- the same functions on the same maxima, so the same bits as the
+// row packer on the transposed tensor.  Never B x EPL values in registers.  Columns the magic add does not cover (denormal, huge or
+// non-finite maxima) are redone by the literal form behind one cold branch.
+constexpr int kColsRows = 8;
+template <int DTI>
+__device__ __forceinline__ void cols_max(u32x4& m, const u32x4& v) {
+  constexpr uint32_t mask = DTI == DMXQ_F32 ? 0x7FFFFFFFu : 0x7FFF7FFFu;
+#pragma unroll
+  for (int j = 0; j < 4; j++) {
+    const uint32_t a = v[j] & mask;
+    if (DTI == DMXQ_F32) m[j] = max(m[j], a);
+    else m[j] = __builtin_bit_cast(uint32_t, __builtin_elementwise_max(__builtin_bit_cast(u16x2, (uint32_t)m[j]), __builtin_bit_cast(u16x2, a)));
+  }
+}
+template <int DTI, bool ASYM>
+__global__ __launch_bounds__(kThreads) void bfp_pack_cols_kernel(const void* __restrict__ in, int8_t* __restrict__ mant,
+                                                                uint8_t* __restrict__ exps, int64_t total /*ob * n_vec*/, int n_vec,
+                                                                int B, int64_t N, int wl, int asym) {
+  constexpr int EPL = 16 / Elem<DTI>::bytes;
+  constexpr bool SINGLE = DTI != DMXQ_F32;
+  const int64_t t = (int64_t)blockIdx.x * kThreads + threadIdx.x;
+  if (t >= total) return;
+  const int64_t ob = t / n_vec, e0 = ob * B * N + (t % n_vec) * EPL;   // element index of (row 0 of the block, this lane's first column)
+  const int eb = Elem<DTI>::bytes;
+  u32x4 mx = {0u, 0u, 0u, 0u};
+  for (int r0 = 0; r0 < B; r0 += kColsRows) {
+    u32x4 raw[kColsRows];
+#pragma unroll
+    for (int r = 0; r < kColsRows; r++) raw[r] = load_raw16<false>(in, (e0 + (int64_t)(r0 + r) * N) * eb);
+#pragma unroll
+    for (int r = 0; r < kColsRows; r++) cols_max<DTI>(mx, raw[r]);
+  }
+  uint32_t mb[EPL];
+  BfpBlockParams p[EPL];
+  bool slow[EPL], any_slow = false;
+  int Eb[EPL];
+#pragma unroll
+  for (int k = 0; k < EPL; k++) {
+    if (DTI == DMXQ_F32) mb[k] = mx[k % 4];
+    else {
+      const uint32_t h = (k & 1) ? mx[(k / 2) % 4] >> 16 : mx[(k / 2) % 4] & 0xFFFFu;
+      mb[k] = DTI == DMXQ_BF16 ? h << 16 : f2u((float)__builtin_bit_cast(_Float16, (uint16_t)h));
+    }
+    Eb[k] = (int)((mb[k] & 0x7F800000u) >> 23);
+    slow[k] = !(bfp_fast_ok(mb[k], wl) && Eb[k] != 0 && Eb[k] != 255);
+    any_slow |= slow[k];
+    p[k] = bfp_block_params<ASYM, true>(mb[k], wl);
+  }
+  const int cmax = (1 << (wl - 1)) - 1;
+  for (int r0 = 0; r0 < B; r0 += kColsRows) {
+    u32x4 raw[kColsRows];
+#pragma unroll
+    for (int r = 0; r < kColsRows; r++) raw[r] = load_raw16<false>(in, (e0 + (int64_t)(r0 + r) * N) * eb);
+#pragma unroll
+    for (int r = 0; r < kColsRows; r++) {
+      float x[EPL];
+      widen<DTI, EPL>(raw[r], x);
+      int code[EPL];
+#pragma unroll
+      for (int k = 0; k < EPL; k++) {   // pack_codes_fast, one block per column
+        const uint32_t kb = f2u(p[k].K);
+        if constexpr (SINGLE) {
+          const int ci = (int)(f2u(x[k] + p[k].K) - kb);
+          code[k] = ci < (ASYM ? -cmax - 1 : -cmax) ? (ASYM ? -cmax - 1 : -cmax) : (ci > cmax ? cmax : ci);
+        } else {
+          const int ci = (int)(f2u((x[k] + p[k].base) + p[k].M) - kb);
+          const int c = ci < -cmax ? -cmax : (ci > cmax ? cmax : ci);
+          code[k] = (ASYM && x[k] <= p[k].thr) ? -cmax - 1 : c;
+        }
+      }
+      if (__builtin_expect(any_slow, 0)) {
+#pragma unroll
+        for (int k = 0; k < EPL; k++)
+          if (slow[k]) {
+            const float x1[1] = {x[k]};
+            int c1[1];
+            pack_codes_literal<1>(x1, mb[k], wl, asym, c1);
+            code[k] = c1[0];
+          }
+      }
+      int8_t* dst = mant + e0 + (int64_t)(r0 + r) * N;
+      if constexpr (EPL == 8) *(u32x2*)dst = u32x2{pack4_codes(code[0], code[1], code[2], code[3]), pack4_codes(code[4], code[5], code[6], code[EPL - 1])};
+      else *(uint32_t*)dst = pack4_codes(code[0], code[1], code[2], code[3]);
+    }
+  }
+  uint8_t* de = exps + ob * N + (t % n_vec) * EPL;
+  if constexpr (EPL == 8) *(u32x2*)de = u32x2{pack4_codes(Eb[0], Eb[1], Eb[2], Eb[3]), pack4_codes(Eb[4], Eb[5], Eb[6], Eb[EPL - 1])};
+  else *(uint32_t*)de = pack4_codes(Eb[0], Eb[1], Eb[2], Eb[3]);
+}
+
 // generic: one lane per block (any L / B, ragged tails, unaligned)
 template <int DTI>
 __global__ __launch_bounds__(kThreads) void bfp_pack_generic_kernel(const void* __restrict__ in, int8_t* __restrict__ mant,
@@ -385,6 +479,31 @@ extern "C" int dmxq_bfp_pack(const void* in, int dtype_in, int8_t* mant, uint8_t
     else if (dtype_in == DMXQ_F16) DMXQ_LAUNCH(bfp_pack_generic_kernel<DMXQ_F16>, dim3(grid), dim3(kThreads), 0, s, in, mant, exps, rows, L, B, precision, asym);
     else DMXQ_LAUNCH(bfp_pack_generic_kernel<DMXQ_BF16>, dim3(grid), dim3(kThreads), 0, s, in, mant, exps, rows, L, B, precision, asym);
   }
+  return launch_status();
+}
+
+extern "C" int dmxq_bfp_pack_cols(const void* in, int dtype_in, int8_t* mant, uint8_t* exps, int64_t outer, int64_t K, int64_t N,
+                                  int64_t block_size, int precision, int symmetric, void* stream) {
+  if (!valid_dtype(dtype_in) || outer < 0 || K < 0 || N < 0 || block_size < 1) return DMXQ_ERR_BAD_ARG;
+  if (precision < 2 || precision > 8) return DMXQ_ERR_UNSUPPORTED;
+  if (outer * K * N == 0) return DMXQ_OK;
+  if (!in || !mant || !exps) return DMXQ_ERR_BAD_ARG;
+  const int epl = dtype_in == DMXQ_F32 ? 4 : 8;
+  const int64_t B = block_size;
+  if ((B != 32 && B != 64 && B != 128) || K % B != 0 || N % epl != 0 || N / epl > 0x7FFFFFFF || !aligned16(in) ||
+      (reinterpret_cast<uintptr_t>(mant) & 7u) != 0 || (reinterpret_cast<uintptr_t>(exps) & 7u) != 0)
+    return DMXQ_ERR_UNSUPPORTED;
+  const int64_t total = outer * (K / B) * (N / epl), wgs = (total + kThreads - 1) / kThreads;
+  if (wgs > 0x7FFFFFFF) return DMXQ_ERR_UNSUPPORTED;
+  hipStream_t s = (hipStream_t)stream;
+  const int asym = symmetric ? 0 : 1;
+#define DMXQ_PC(DT_, A_) DMXQ_LAUNCH((bfp_pack_cols_kernel<DT_, A_>), dim3((unsigned)wgs), dim3(kThreads), 0, s, in, mant, exps, total, (int)(N / epl), (int)B, N, precision, asym)
+#define DMXQ_PCA(DT_) do { if (asym) DMXQ_PC(DT_, true); else DMXQ_PC(DT_, false); } while (0)
+  if (dtype_in == DMXQ_F32) DMXQ_PCA(DMXQ_F32);
+  else if (dtype_in == DMXQ_F16) DMXQ_PCA(DMXQ_F16);
+  else DMXQ_PCA(DMXQ_BF16);
+#undef DMXQ_PC
+#undef DMXQ_PCA
   return launch_status();
 }
 

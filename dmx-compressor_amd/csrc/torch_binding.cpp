@@ -197,6 +197,64 @@ Tensor bfp_matmul_meta(const Tensor& mant_a, const Tensor& exps_a, const Tensor&
   return at::empty({mant_a.size(0), mant_w.size(0)}, mant_a.options().dtype(out_dtype));
 }
 
+// the column-blocked pack (csrc/bfp_pack.hip): x[..., K, N] blocked along K -> codes [..., K, N] + exps [..., K / B, N].
+// DMXQ_ERR_UNSUPPORTED or a ragged last block (NotImplementedError, nothing launched): the front end transposes and packs rows.
+std::vector<int64_t> exps_cols_shape(const Tensor& x, int64_t block_size) {
+  TORCH_CHECK(x.dim() >= 2 && block_size >= 1, "bfp_pack_cols: expects a tensor of at least two dimensions and a positive block size");
+  std::vector<int64_t> sh(x.sizes().begin(), x.sizes().end());
+  TORCH_CHECK_NOT_IMPLEMENTED(sh[sh.size() - 2] % block_size == 0, "bfp_pack_cols: a ragged last block");
+  sh[sh.size() - 2] /= block_size;
+  return sh;
+}
+std::tuple<Tensor, Tensor> bfp_pack_cols(const Tensor& x, int64_t precision, int64_t block_size, bool symmetric) {
+  const Tensor xc = prep(x, "bfp_pack_cols");
+  Tensor exps = at::empty(exps_cols_shape(xc, block_size), xc.options().dtype(at::kByte));
+  Tensor mant = at::empty(xc.sizes(), xc.options().dtype(at::kChar));
+  const int64_t K = xc.size(-2), N = xc.size(-1), outer = K * N ? xc.numel() / (K * N) : 0;
+  Launch l(xc);
+  check(dmxq_bfp_pack_cols(xc.data_ptr(), dt_code(xc.scalar_type()), (int8_t*)mant.data_ptr(), (uint8_t*)exps.data_ptr(), outer, K, N,
+                           block_size, (int)precision, symmetric, l.stream), "dmxq_bfp_pack_cols");
+  return {mant, exps};
+}
+std::tuple<Tensor, Tensor> bfp_pack_cols_meta(const Tensor& x, int64_t, int64_t block_size, bool) {
+  return {at::empty(x.sizes(), x.options().dtype(at::kChar)), at::empty(exps_cols_shape(x, block_size), x.options().dtype(at::kByte))};
+}
+
+// the batched BFP matmul (csrc/bfp_bmm.hip): mant_a [b, M, K] + exps_a [b, M, K / B]; w_layout 0: mant_w [b, N, K] + exps_w [b, N, K / B],
+// 1: mant_w [b, K, N] + exps_w [b, K / B, N] -> [b, M, N].  DMXQ_ERR_UNSUPPORTED (NotImplementedError): the front end runs its chain.
+int64_t bfp_bmm_shapes(const Tensor& mant_a, const Tensor& exps_a, const Tensor& mant_w, const Tensor& exps_w, int64_t block_size,
+                       int64_t w_layout) {
+  TORCH_CHECK(mant_a.dim() == 3 && mant_w.dim() == 3 && exps_a.dim() == 3 && exps_w.dim() == 3 && block_size >= 1 &&
+              (w_layout == 0 || w_layout == 1), "bfp_bmm: expects 3-d codes and exponents, a positive block size and w_layout 0 or 1");
+  TORCH_CHECK(mant_a.scalar_type() == at::kChar && mant_w.scalar_type() == at::kChar && exps_a.scalar_type() == at::kByte &&
+              exps_w.scalar_type() == at::kByte, "bfp_bmm: codes are int8 and exponents uint8");
+  const int64_t b = mant_a.size(0), M = mant_a.size(1), K = mant_a.size(2), nb = (K + block_size - 1) / block_size;
+  const int64_t N = mant_w.size(w_layout ? 2 : 1);
+  TORCH_CHECK(mant_w.size(0) == b && mant_w.size(w_layout ? 1 : 2) == K && exps_a.size(0) == b && exps_a.size(1) == M &&
+              exps_a.size(2) == nb && exps_w.size(0) == b && exps_w.size(w_layout ? 1 : 2) == nb && exps_w.size(w_layout ? 2 : 1) == N,
+              "bfp_bmm: operand shapes do not match");
+  return N;
+}
+Tensor bfp_bmm(const Tensor& mant_a, const Tensor& exps_a, const Tensor& mant_w, const Tensor& exps_w, int64_t precision_a,
+               int64_t precision_w, int64_t block_size, int64_t w_layout, at::ScalarType out_dtype) {
+  TORCH_CHECK(mant_a.is_cuda() && exps_a.is_cuda() && mant_w.is_cuda() && exps_w.is_cuda(),
+              "bfp_bmm: tensors must be on the GPU (no CPU fallback)");
+  const int64_t N = bfp_bmm_shapes(mant_a, exps_a, mant_w, exps_w, block_size, w_layout);
+  const Tensor ca = mant_a.contiguous(), ea = exps_a.contiguous(), cw = mant_w.contiguous(), ew = exps_w.contiguous();
+  Tensor out = at::empty({ca.size(0), ca.size(1), N}, ca.options().dtype(out_dtype));
+  Launch l(ca);
+  check(dmxq_bfp_bmm((const int8_t*)ca.data_ptr(), (const uint8_t*)ea.data_ptr(), (const int8_t*)cw.data_ptr(),
+                     (const uint8_t*)ew.data_ptr(), out.data_ptr(), dt_code(out_dtype), ca.size(0), ca.size(1), N, ca.size(2), block_size,
+                     (int)precision_a, (int)precision_w, (int)w_layout, l.stream), "dmxq_bfp_bmm");
+  return out;
+}
+Tensor bfp_bmm_meta(const Tensor& mant_a, const Tensor& exps_a, const Tensor& mant_w, const Tensor& exps_w, int64_t, int64_t,
+                    int64_t block_size, int64_t w_layout, at::ScalarType out_dtype) {
+  const int64_t N = bfp_bmm_shapes(mant_a, exps_a, mant_w, exps_w, block_size, w_layout);
+  dt_code(out_dtype);
+  return at::empty({mant_a.size(0), mant_a.size(1), N}, mant_a.options().dtype(out_dtype));
+}
+
 at::ScalarType hypernet_dtype(const Tensor& w, const OptTensor& score, int64_t M, OptDtype out_dtype) {
   const bool masked = score.has_value() && score->defined() && M != 0;
   return out_dtype.value_or(masked ? at::promote_types(w.scalar_type(), score->scalar_type()) : w.scalar_type());
@@ -1593,6 +1651,8 @@ TORCH_LIBRARY(dmxq, m) {
   m.def("bfp_pack(Tensor x, int precision, int block_size, bool symmetric=True) -> (Tensor, Tensor)");
   m.def("bfp_unpack(Tensor mant, Tensor exps, int precision, int block_size, ScalarType out_dtype) -> Tensor");
   m.def("bfp_matmul(Tensor mant_a, Tensor exps_a, Tensor mant_w, Tensor exps_w, int precision_a, int precision_w, int block_size, ScalarType out_dtype) -> Tensor");
+  m.def("bfp_pack_cols(Tensor x, int precision, int block_size, bool symmetric=True) -> (Tensor, Tensor)");
+  m.def("bfp_bmm(Tensor mant_a, Tensor exps_a, Tensor mant_w, Tensor exps_w, int precision_a, int precision_w, int block_size, int w_layout, ScalarType out_dtype) -> Tensor");
   m.def("weight_hypernet(Tensor w, int precision, int block_size, bool symmetric, Tensor? score, int K, int M, Tensor? sq_scale, ScalarType? out_dtype=None, int block_dim=-1) -> Tensor");
   m.def("input_hypernet(Tensor x, Tensor sq_scale, int precision, int block_size, bool symmetric) -> Tensor");
   m.def("binary_cast(Tensor a, Tensor b, int op, int[] cast_a, int[] cast_b, int[] cast_out, int bfp_block=0, int bfp_precision=0) -> Tensor");
@@ -1669,7 +1729,7 @@ TORCH_LIBRARY(dmxq, m) {
   X(m, channel_sumsq); X(m, wanda_nm); X(m, channel_sumabs); X(m, awq_group_error); X(m, block_scaled_float_qdq); X(m, block_scaled_tensor_scale); \
   X(m, lsq_backward); X(m, codebook_qdq); X(m, codebook_accumulate); X(m, hqq_qdq); X(m, outlier_fixed_qdq); X(m, awq_clip); \
   X(m, adaround_forward); X(m, adaround_backward); X(m, vq_qdq); X(m, vq_accumulate); X(m, hadamard_row_qdq); \
-  X(m, dynamic_fixed_qdq_cols); X(m, dynamic_float_qdq_cols); X(m, bfp_matmul)
+  X(m, dynamic_fixed_qdq_cols); X(m, dynamic_float_qdq_cols); X(m, bfp_matmul); X(m, bfp_pack_cols); X(m, bfp_bmm)
 
 // "CUDA" is the dispatch key of HIP tensors in a ROCm build of PyTorch
 TORCH_LIBRARY_IMPL(dmxq, CUDA, m) {

@@ -398,7 +398,7 @@ class DmxModule(FastAttr, torch.nn.Module):
     transform = configure
 
     def set_block_matmul(self, enabled: bool = True):
-        raise TypeError(f"{type(self).__name__} has no block matmul (ops.bfp_matmul): Linear only")
+        raise TypeError(f"{type(self).__name__} has no block matmul (ops.bfp_matmul, ops.bfp_bmm): Linear and ActActMatMul only")
 
     # ------------------------------------------------------------------ views used by the harness
     @property
@@ -1266,7 +1266,49 @@ class ActActMatMul(DmxModule):
         for c in self.input_casts.values():             # torch.matmul takes any strides: no contiguous copy of q / k^T / v views
             c.keep_layout = True
 
+    #: opt-in (set_block_matmul / configure's "block_matmul"): the product of two BFP-cast operands runs as ops.bfp_bmm_packed (DESIGN.md
+    #: §8 "Batched BFP matmul") instead of torch.matmul on the dequantised operands.  A plain attribute: no buffer, no state_dict key
+    block_matmul = False
+
+    def set_block_matmul(self, enabled: bool = True):
+        self.block_matmul = bool(enabled)
+
+    def _block_matmul_plan(self, _input, multiplier):
+        """(input format, multiplier format, w_layout) when this forward can run as a batched BFP matmul, else None: both casts plain BFP
+        casts (switched on, no pre_transform, codebook or VQ, nearest rounding, p <= 8) with one block size the kernel takes, the input
+        blocked along -1 and the multiplier along -2, equal leading dimensions, no gradient asked, and a multiplier that is contiguous
+        ("kn": P V) or the transposed view of a contiguous tensor ("nk": Q K^T, no copy)"""
+        from . import ops
+        from .format import BlockFloatingPoint
+        ic, mc = self.input_casts.input_cast, self.input_casts.multiplier_cast
+        fi, fm = ic.format, mc.format
+        if not (isinstance(fi, BlockFloatingPoint) and isinstance(fm, BlockFloatingPoint)):
+            return None
+        if fi.block_size != fm.block_size or fi.block_size not in ops.BFP_MATMUL_BLOCK_SIZES:
+            return None
+        for c, f, d in ((ic, fi, -1), (mc, fm, -2)):
+            if (c.block_dim != d or f.precision > 8 or f.rounding != "nearest" or c.pre_transform or c._codebook is not None or c._vq is not None
+                    or not c._flag("fake_quant_enabled")):
+                return None
+        if _input.dim() < 2 or multiplier.dim() != _input.dim() or _input.shape[:-2] != multiplier.shape[:-2] or _input.shape[-1] != multiplier.shape[-2]:
+            return None
+        if torch.is_grad_enabled() and (_input.requires_grad or multiplier.requires_grad):
+            return None
+        if multiplier.transpose(-1, -2).is_contiguous():
+            return fi, fm, "nk"
+        return (fi, fm, "kn") if multiplier.is_contiguous() else None
+
     def _forward(self, _input, multiplier):
+        _plan = self._block_matmul_plan(_input, multiplier) if self.block_matmul else None
+        if _plan is not None:   # the operands are already cast: packing a cast tensor gives its codes back (ops.bfp_pack)
+            from . import ops
+            _fi, _fm, _layout = _plan
+            _ca, _ea = ops.bfp_pack(_input, _fi.precision, _fi.block_size, _fi.symmetric)
+            if _layout == "nk":
+                _cw, _ew = ops.bfp_pack(multiplier.transpose(-1, -2), _fm.precision, _fm.block_size, _fm.symmetric)
+            else:
+                _cw, _ew = ops.bfp_pack(multiplier, _fm.precision, _fm.block_size, _fm.symmetric, block_dim=-2)
+            return ops.bfp_bmm_packed(_ca, _ea, _cw, _ew, _fi.precision, _fm.precision, _fi.block_size, _layout, out_dtype=_input.dtype)
         return torch.matmul(_input, multiplier)
 
 

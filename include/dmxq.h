@@ -62,7 +62,7 @@ const char* dmxq_status_string(int status);
  * dmxq_outlier_fixed_qdq, dmxq_outlier_class, dmxq_awq_clip, dmxq_awq_clip_class, dmxq_adaround_forward, dmxq_adaround_backward,
  * dmxq_adaround_class, dmxq_adaround_scratch_bytes, dmxq_vq_qdq, dmxq_vq_class, dmxq_vq_accumulate, dmxq_vq_workspace_bytes,
  * dmxq_hadamard_row_qdq, dmxq_hadamard_row_class, dmxq_hadamard_matrix, dmxq_dynamic_cols_class, dmxq_dynamic_fixed_qdq_cols,
- * dmxq_dynamic_float_qdq_cols, dmxq_bfp_matmul, dmxq_bfp_matmul_class) leave it at 4: a caller built against 4 runs on
+ * dmxq_dynamic_float_qdq_cols, dmxq_bfp_matmul, dmxq_bfp_matmul_class, dmxq_bfp_pack_cols, dmxq_bfp_bmm, dmxq_bfp_bmm_class) leave it at 4: a caller built against 4 runs on
  * this library unchanged.  4 = round 5: + dmxq_float_qdq_multi, dmxq_fixed_float_qdq_multi; 3 = round 4: + dmxq_weight_hypernet_multi,
  * dmxq_unary_cast_table, dmxq_lut16_apply.  Nothing was ever removed or changed: a caller built against version n runs on any library >= n. */
 int dmxq_abi_version(void);
@@ -142,6 +142,27 @@ typedef enum { DMXQ_BFPMM_NONE = 0, DMXQ_BFPMM_B32 = 1, DMXQ_BFPMM_B64 = 2, DMXQ
 int dmxq_bfp_matmul_class(int64_t M, int64_t N, int64_t K, int64_t block_size);
 int dmxq_bfp_matmul(const int8_t* mant_a, const uint8_t* exps_a, const int8_t* mant_w, const uint8_t* exps_w, void* out,
                     int dtype_out, int64_t M, int64_t N, int64_t K, int64_t block_size, int prec_a, int prec_w, void* stream);
+
+/* Column-blocked pack (csrc/bfp_pack.hip): x[outer, K, N] blocked along K, the NON-contiguous dimension -> mant int8 [outer, K, N] +
+ * exps uint8 [outer, K / B, N]; bit for bit dmxq_bfp_pack of the transposed tensor, transposed back.  ONE launch: lanes along N, a
+ * 16-byte vector of columns per lane, the B rows of a block read twice (maxima, then codes).  Taken: B in {32, 64, 128}, K % B == 0,
+ * N a multiple of the 16-byte vector (8 sixteen-bit / 4 float32 elements), `in` 16-byte and mant / exps 8-byte aligned,
+ * 2 <= precision <= 8.  DMXQ_ERR_UNSUPPORTED, nothing launched (the caller transposes and calls dmxq_bfp_pack): anything else. */
+int dmxq_bfp_pack_cols(const void* in, int dtype_in, int8_t* mant, uint8_t* exps, int64_t outer, int64_t K, int64_t N,
+                       int64_t block_size, int precision, int symmetric, void* stream);
+
+/* Batched BFP matmul, W in either layout (csrc/bfp_bmm.hip; DESIGN.md §8 "Batched BFP matmul"): per batch element the product
+ * dmxq_bfp_matmul defines.  A: mant_a [batch, M, K] + exps_a [batch, M, K / B].  w_layout NK: mant_w [batch, N, K] + exps_w
+ * [batch, N, K / B] (dmxq_bfp_pack); KN: mant_w [batch, K, N] + exps_w [batch, K / B, N] (dmxq_bfp_pack_cols).  out [batch, M, N].
+ * dmxq_bfp_bmm_class: NONE = refused, else 1 + 2 * (3 * w_layout + {B = 32: 0, 64: 1, 128: 2}) + (N <= 64: the 64-wide N tile).
+ * Taken: 1 <= batch <= 65535 (grid.z: the caller splits), B in {32, 64, 128}, K % B == 0, 2 <= prec <= 8, mant_a 16-byte aligned;
+ * NK: mant_w 16-byte aligned; KN: N % 4 == 0 and mant_w 4-byte aligned.  DMXQ_ERR_UNSUPPORTED, nothing launched: anything else.
+ * DMXQ_ERR_BAD_ARG: null pointers, negative sizes, an invalid dtype or layout, B < 1.  batch * M * N == 0: DMXQ_OK. */
+typedef enum { DMXQ_BFPBMM_NK = 0, DMXQ_BFPBMM_KN = 1 } dmxq_bfp_bmm_layout;
+enum { DMXQ_BFPBMM_NONE = 0 };
+int dmxq_bfp_bmm_class(int64_t batch, int64_t M, int64_t N, int64_t K, int64_t block_size, int w_layout);
+int dmxq_bfp_bmm(const int8_t* mant_a, const uint8_t* exps_a, const int8_t* mant_w, const uint8_t* exps_w, void* out, int dtype_out,
+                 int64_t batch, int64_t M, int64_t N, int64_t K, int64_t block_size, int prec_a, int prec_w, int w_layout, void* stream);
 
 /* Low-bit floating point Q->DQ ("FP[s|e|m,bias](F|_ N|S)").
  * Replaces: numerical/format.py:208-233 FloatingPoint.cast -> quant_function.py:120-152 float_quantize
