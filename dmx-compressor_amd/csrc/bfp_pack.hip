@@ -40,6 +40,12 @@ __device__ __forceinline__ void pack_codes_fast(const float (&x)[EPL], uint32_t 
 __device__ __forceinline__ uint32_t pack4_codes(int c0, int c1, int c2, int c3) {
   return __builtin_amdgcn_perm((uint32_t)c1, (uint32_t)c0, 0x0c0c0400u) | __builtin_amdgcn_perm((uint32_t)c3, (uint32_t)c2, 0x04000c0cu);
 }
+// 2^-(e-(p-2)), the reciprocal of the block's quantum.  Its biased exponent is 127 - (Eb - 127 - (wl - 2)) >= 0, and 0 only for
+// Eb = 254 at wl = 2 (quantum 2^127): there the reciprocal 2^-127 is a DENORMAL, which an exponent field of 0 does not spell
+__device__ __forceinline__ float pack_inv_quantum(uint32_t Eb, int wl) {
+  const int ie = 127 - ((int)Eb - 127 - (wl - 2));
+  return ie > 0 ? u2f((uint32_t)ie << 23) : u2f(0x00400000u);
+}
 // the literal form, for the blocks bfp_fast_ok does not cover and the zero / denormal / Inf / NaN maxima (all-zero codes)
 template <int EPL>
 __device__ __forceinline__ void pack_codes_literal(const float (&x)[EPL], uint32_t mb, int wl, int asym, int (&code)[EPL]) {
@@ -49,7 +55,7 @@ __device__ __forceinline__ void pack_codes_literal(const float (&x)[EPL], uint32
     for (int k = 0; k < EPL; k++) code[k] = 0;
     return;
   }
-  const float inv_quantum = u2f((uint32_t)(127 - ((int)Eb - 127 - (wl - 2))) << 23);  // 2^-(e-(p-2))
+  const float inv_quantum = pack_inv_quantum(Eb, wl);
   const BfpBlockParams p = bfp_block_params<true, false>(mb, wl);
 #pragma unroll
   for (int k = 0; k < EPL; k++) {
@@ -286,7 +292,7 @@ __global__ __launch_bounds__(kThreads) void bfp_pack_generic_kernel(const void* 
       for (int64_t i = 0; i < len; i++) mant[e0 + i] = 0;
       continue;
     }
-    const float inv_quantum = u2f((uint32_t)(127 - ((int)Eb - 127 - (wl - 2))) << 23);
+    const float inv_quantum = pack_inv_quantum(Eb, wl);
     const BfpBlockParams ps = bfp_block_params<false, false>(mb, wl), pa = bfp_block_params<true, false>(mb, wl);
     for (int64_t i = 0; i < len; i++) {
       const float x = load1<DTI>(in, e0 + i);

@@ -7,7 +7,8 @@ import copy
 import pytest
 import torch
 
-from _data import make, mismatches_nan_aware, ulp_of
+from _bfp_mm_ref import ref_and_bound_bmm as _ref_and_bound
+from _data import make, mismatches_nan_aware
 
 pytestmark = pytest.mark.gpu
 BLOCKS = (32, 64, 128)
@@ -23,20 +24,6 @@ def _operands(dev, layout, batch, M, N, K, kind="heavy"):
 
 def _pack(ops, x, w, layout, pa, pw, B, sym_a=True):
     return ops.bfp_pack(x, pa, B, sym_a), ops.bfp_pack(w, pw, B, True, block_dim=-2 if layout == "kn" else -1)
-
-
-def _ref_and_bound(ops, A, W, layout, pa, pw, B, out_dtype=torch.float32):
-    """the float64 batched product of the unpacked operands (unpack to float32 is exact) and (nb - 1) 2^-24 sum_j |t_j| (1 + 2^-20), plus
-    half an ulp of a 16-bit output"""
-    a = ops.bfp_unpack(*A, pa, B, torch.float32).double()
-    cw, ew = (t.transpose(-1, -2).contiguous() for t in W) if layout == "kn" else W
-    w = ops.bfp_unpack(cw, ew, pw, B, torch.float32).double()                                           # [batch, N, K]
-    nb = -(-a.shape[-1] // B)
-    ref = (a @ w.transpose(-1, -2)).cpu()
-    a, w = (torch.nn.functional.pad(t, (0, nb * B - t.shape[-1])).view(t.shape[0], -1, nb, B) for t in (a, w))
-    t_abs = torch.einsum("bmjk,bnjk->bmnj", a, w).abs().sum(-1).cpu()
-    bound = (nb - 1) * 2.0 ** -24 * t_abs * (1 + 2.0 ** -20)
-    return ref, bound if out_dtype == torch.float32 else bound + 0.5 * ulp_of(ref, out_dtype)
 
 
 @pytest.mark.parametrize("shape", range(len(SHAPES)))

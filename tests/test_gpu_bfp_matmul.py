@@ -4,6 +4,7 @@ operations bit for bit (special blocks included), the front end's properties, an
 import pytest
 import torch
 
+from _bfp_mm_ref import ref_and_bound_mm as _ref_and_bound
 from _data import make, mismatches_nan_aware, ulp_of
 
 pytestmark = pytest.mark.gpu
@@ -15,18 +16,6 @@ SHAPES = (lambda B: (1, 16, B), lambda B: (17, 33, 3 * B), lambda B: (130, 257, 
 def _packed(ops, dev, M, N, K, B, pa, pw, kind="heavy", sym_a=True):
     x, w = make(kind, (M, K), seed=M + K).to(dev), make("normal", (N, K), seed=N + K + 1).to(dev)
     return x, w, ops.bfp_pack(x, pa, B, sym_a), ops.bfp_pack(w, pw, B, True)
-
-
-def _ref_and_bound(ops, A, W, pa, pw, B, out_dtype=torch.float32):
-    """the float64 product of the unpacked operands (unpack to float32 is exact) and (nb - 1) 2^-24 sum_j |t_j| (1 + 2^-20), plus half
-    an ulp of a 16-bit output: nb - 1 ordered fp32 additions of exact block terms"""
-    a, w = ops.bfp_unpack(*A, pa, B, torch.float32).double(), ops.bfp_unpack(*W, pw, B, torch.float32).double()
-    nb = -(-a.shape[1] // B)
-    ref = (a @ w.T).cpu()
-    a, w = (torch.nn.functional.pad(t, (0, nb * B - t.shape[1])).view(-1, nb, B) for t in (a, w))   # (a ragged last block: zeros)
-    t_abs = torch.einsum("mjk,njk->mnj", a, w).abs().sum(-1).cpu()
-    bound = (nb - 1) * 2.0 ** -24 * t_abs * (1 + 2.0 ** -20)
-    return ref, bound if out_dtype == torch.float32 else bound + 0.5 * ulp_of(ref, out_dtype)
 
 
 @pytest.mark.parametrize("shape", range(len(SHAPES)))
