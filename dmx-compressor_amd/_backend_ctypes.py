@@ -140,6 +140,51 @@ def bfp_matmul(mant_a, exps_a, mant_w, exps_w, precision_a, precision_w, block_s
 
 
 @_guarded
+def dynamic_fixed_pack(x, segment, whole_rows, precision, symmetric, qmin, qmax):
+    """x viewed as [numel / segment, segment] -> (int8 codes of x's shape, float32 scale [numel / segment]) (csrc/dynamic_pack.hip);
+    NotImplementedError: the front end's chain"""
+    xc = _prep(x, "dynamic_fixed_pack")
+    if segment < 1 or xc.numel() % segment:
+        raise RuntimeError("dynamic_fixed_pack: the segment must divide the number of elements")
+    n = xc.numel() // segment
+    codes = torch.empty(xc.shape, dtype=torch.int8, device=xc.device)
+    scale = torch.empty((n,), dtype=torch.float32, device=xc.device)
+    check(lib().dmxq_dynamic_fixed_pack(ptr(xc), dtype_code(xc.dtype), ptr(codes), ptr(scale), n, segment, int(bool(whole_rows)), precision,
+                                        int(bool(symmetric)), qmin, qmax, stream_of(xc)), "dmxq_dynamic_fixed_pack")
+    return codes, scale
+
+
+def _int_matmul_groups(codes_a, scale_a, codes_w, scale_w, group_size):
+    """-> (group_a, group_w) of the C entry, or RuntimeError: int8 [M, K] / [N, K] codes, float32 scales [rows] or [rows, K / group_size]"""
+    if (codes_a.dim() != 2 or codes_w.dim() != 2 or codes_a.dtype != torch.int8 or codes_w.dtype != torch.int8 or group_size < 0
+            or scale_a.dtype != torch.float32 or scale_w.dtype != torch.float32 or codes_a.shape[1] != codes_w.shape[1]):
+        raise RuntimeError("int_matmul: expects int8 codes [M, K] and [N, K], float32 scales and a group size >= 0")
+    K, groups = codes_a.shape[1], []
+    for c, s in ((codes_a, scale_a), (codes_w, scale_w)):
+        if tuple(s.shape) == (c.shape[0],):
+            groups.append(0)
+        elif group_size > 0 and K % group_size == 0 and tuple(s.shape) == (c.shape[0], K // group_size):
+            groups.append(group_size)
+        else:
+            raise RuntimeError("int_matmul: a scale must be [rows] or [rows, K / group_size]")
+    return groups
+
+
+@_guarded
+def int_matmul(codes_a, scale_a, codes_w, scale_w, group_size, out_dtype):
+    """codes [M, K] / [N, K] with scales [rows] or [rows, K / group_size] -> [M, N] (csrc/int_matmul.hip); NotImplementedError: the
+    front end's chain"""
+    for t in (codes_a, scale_a, codes_w, scale_w):
+        require_gpu(t, "int_matmul")
+    ga, gw = _int_matmul_groups(codes_a, scale_a, codes_w, scale_w, group_size)
+    ca, sa, cw, sw = codes_a.contiguous(), scale_a.contiguous(), codes_w.contiguous(), scale_w.contiguous()
+    out = torch.empty((ca.shape[0], cw.shape[0]), dtype=out_dtype, device=ca.device)
+    check(lib().dmxq_int_matmul(ptr(ca), ptr(sa), ptr(cw), ptr(sw), ptr(out), dtype_code(out_dtype), ca.shape[0], cw.shape[0], ca.shape[1],
+                                ga, gw, stream_of(ca)), "dmxq_int_matmul")
+    return out
+
+
+@_guarded
 def bfp_pack_cols(x, precision, block_size, symmetric=True):
     """x[..., K, N] blocked along K -> codes [..., K, N], exps [..., K / B, N] (csrc/bfp_pack.hip); NotImplementedError: the transposing route"""
     xc = _prep(x, "bfp_pack_cols")

@@ -44,6 +44,8 @@ __all__ = [
     "bfp_matmul", "bfp_matmul_packed", "bfp_matmul_check", "bfp_matmul_class", "BFP_MATMUL_CHAIN_BY_DEFAULT", "BFP_MATMUL_BLOCK_SIZES",
     "BFP_MATMUL_CHAIN_PIECE_ENTRIES",
     "bfp_bmm", "bfp_bmm_packed", "bfp_bmm_class", "BFP_BMM_CHAIN_BY_DEFAULT", "BFP_BMM_MAX_BATCH",
+    "dynamic_int_pack", "int_matmul", "int_matmul_packed", "int_matmul_check", "int_matmul_class", "INT_MATMUL_CHAIN_BY_DEFAULT",
+    "INT_MATMUL_GROUP_SIZES",
 ]
 
 _ops = None   # the raw namespace: set by bind()
@@ -1644,6 +1646,190 @@ def dynamic_fixed_qdq(x, fmt, granularity: str = "per_token", group_size: Option
                               f"with {fmt!r} (base address {xc.data_ptr() % 16} mod 16)"))
 
     return straight_through(x, run)
+
+
+# ---------------------------------------------------------------------------------------------------- integer matmul
+# Kernel classes (int_matmul_class) that run the chain of torch operations unless fused=True asks for the kernel: none.
+# DYNAMIC_CHAIN_BY_DEFAULT's rule -- a class is listed only where a measurement found the chain faster on the same buffers -- and the
+# chain is the definition spelled in torch (float64 products, a Python loop over the groups): slow by construction.
+# tools/bench_int_matmul.py has the kernel against today's two dynamic casts + bf16 matmul.
+INT_MATMUL_CHAIN_BY_DEFAULT = frozenset()
+INT_MATMUL_GROUP_SIZES = (32, 64, 128)
+_int_matmul_routes = {"fused": 0, "chain": 0}
+_int_pack_routes = {"fused": 0, "chain": 0}
+_INT_MATMUL_CLASS_NAMES = {1: "row", 2: "group"}   # dmxq_int_matmul_geometry (include/dmxq.h)
+
+
+def _int_matmul_format(f, name):
+    """-> the FixedPoint format of an integer matmul operand, or DmxqError: XP[p,0] clamped, nearest rounding, p <= 8"""
+    from .format import FixedPoint, Format
+    try:
+        f = Format.from_shorthand(f) if isinstance(f, str) else f
+    except ValueError as e:
+        raise DmxqError(f"int_matmul: {name}: {e}") from None
+    if not isinstance(f, FixedPoint) or f.fraction != 0 or not f.clamp:
+        raise DmxqError(f"int_matmul: {name} must be a clamped FixedPoint format without fraction bits (XP[p,0](C..)), got {f!r}")
+    if not 2 <= f.precision <= 8:
+        raise DmxqError(f"int_matmul: {name} = {f!r} has {f.precision}-bit codes; the packed codes are int8 (2 <= p <= 8)")
+    if f.rounding != "nearest":
+        raise DmxqError(f"int_matmul: {name} = {f!r} rounds {f.rounding}; the packed operands are rounded to nearest")
+    return f
+
+
+def int_matmul_check(x, w, fmt_x, fmt_w=None):
+    """-> (fmt_x, fmt_w) as FixedPoint objects, or DmxqError before any launch: a format that is not a clamped XP[p,0] (a BFP format, say),
+    p > 8 (codes wider than int8), rounding other than nearest, w that is not [N, K], or x whose last dimension is not K."""
+    fx, fw = _int_matmul_format(fmt_x, "fmt_x"), _int_matmul_format(fmt_x if fmt_w is None else fmt_w, "fmt_w")
+    if w.dim() != 2:
+        raise DmxqError(f"int_matmul: w must be [N, K], got {tuple(w.shape)}")
+    if x.dim() < 1 or x.shape[-1] != w.shape[1]:
+        raise DmxqError(f"int_matmul: x is {tuple(x.shape)}, its last dimension must be w's K = {w.shape[1]}")
+    return fx, fw
+
+
+def dynamic_int_pack(x, fmt, granularity: str = "per_token", group_size: Optional[int] = None, fused: Optional[bool] = None):
+    """The symmetric dynamic integer cast of x as packed operands (DESIGN.md §8 "Integer matmul"): -> (int8 codes of x's shape,
+    float32 scale [..., 1 per row] for "per_token" / [..., L / group_size] for "per_group").  fmt: a clamped nearest-rounding XP[p,0],
+    p <= 8.  scale is dynamic_fixed_qdq(x, ..., symmetric_qscheme=True)'s, codes the integers it multiplies by the scale: for a float32
+    x, codes.float() * scale is that cast.  A sixteen-bit x packs as x.float().  No gradient.
+    fused=None: one launch (dmxq_dynamic_fixed_pack) for segments of a power of two from 16 to 256, or rows of whole 32-byte units up
+    to 16384 elements, of a 16-byte aligned tensor; else the chain -- the scale from dynamic_fixed_qdq(x.float(), return_qparams=True),
+    the codes from the same IEEE division in torch -- with the same result; True: NotImplementedError instead; False: the chain."""
+    from ._lib import dtype_code, lib
+    from .observer import get_qmin_qmax
+    f = _int_matmul_format(fmt, "fmt")
+    if granularity not in ("per_token", "per_group"):
+        raise DmxqError(f"dynamic_int_pack: granularity must be 'per_token' or 'per_group', got {granularity!r}")
+    dynamic_check(f, granularity, group_size, what="dynamic_int_pack")
+    if x.dim() < 1 or (granularity == "per_group" and x.shape[-1] % group_size):
+        raise ValueError(f"dynamic_int_pack: the last dimension of {tuple(x.shape)} must be a multiple of the group size {group_size}")
+    require_gpu(x, "dynamic_int_pack")
+    qmin, qmax = get_qmin_qmax(f)
+    L = x.shape[-1]
+    S = L if granularity == "per_token" else group_size
+    whole_rows = granularity == "per_token"
+    with torch.no_grad():
+        xc = x.detach().contiguous()
+        q_shape = tuple(xc.shape[:-1]) + ((L // S,) if not whole_rows else ())
+        if xc.numel() == 0:
+            return torch.empty(xc.shape, dtype=torch.int8, device=xc.device), torch.empty(q_shape, dtype=torch.float32, device=xc.device)
+        cls = None if fused is False or xc.data_ptr() % 16 else _DYNAMIC_CLASS_NAMES.get(
+            lib().dmxq_dynamic_pack_class(dtype_code(xc.dtype), int(S), int(whole_rows)))
+
+        def chain():
+            xf = xc.float()
+            _, sc, _ = dynamic_fixed_qdq(xf, f, granularity, group_size, True, None, True)
+            v = torch.round((xf.reshape(-1, S) / sc[:, None] + 0.5) - 0.5).clamp(float(qmin), float(qmax))   # (a NaN stays one ...)
+            return torch.nan_to_num(v, nan=0.0).to(torch.int8).reshape(xc.shape), sc                       # (... and packs to 0)
+
+        codes, sc = route(fused, cls, frozenset(), _int_pack_routes,
+                          lambda: tuple(_ops.dynamic_fixed_pack(xc, S, whole_rows, f.precision, bool(f.symmetric), qmin, qmax)), chain,
+                          lambda: (f"dynamic_int_pack: no kernel for segments of {S} {xc.dtype} elements (base address "
+                                   f"{xc.data_ptr() % 16} mod 16)"))
+        return codes, sc.reshape(q_shape)
+
+
+def _int_matmul_groups(codes_a, scale_a, codes_w, scale_w, group_size, what):
+    """-> (group_a, group_w): 0 for a per-row scale [rows], G for [rows, K / G]; DmxqError for anything else"""
+    if codes_a.dim() != 2 or codes_w.dim() != 2 or codes_a.shape[1] != codes_w.shape[1]:
+        raise DmxqError(f"{what}: codes must be [M, K] and [N, K], got {tuple(codes_a.shape)}, {tuple(codes_w.shape)}")
+    if codes_a.dtype != torch.int8 or codes_w.dtype != torch.int8 or scale_a.dtype != torch.float32 or scale_w.dtype != torch.float32:
+        raise DmxqError(f"{what}: codes are int8 and scales float32 (ops.dynamic_int_pack)")
+    G, K, out = int(group_size or 0), codes_a.shape[1], []
+    if G < 0 or (G and K % G):
+        raise DmxqError(f"{what}: the group size must divide K = {K}, got {group_size!r}")
+    for name, c, s in (("scale_a", codes_a, scale_a), ("scale_w", codes_w, scale_w)):
+        if tuple(s.shape) == (c.shape[0],):
+            out.append(0)
+        elif G and tuple(s.shape) == (c.shape[0], K // G):
+            out.append(G)
+        else:
+            raise DmxqError(f"{what}: {name} must be [{c.shape[0]}]" + (f" or [{c.shape[0]}, {K // G}]" if G else "") + f", got {tuple(s.shape)}")
+    if G and not any(out):
+        raise DmxqError(f"{what}: group_size = {G} with two per-row scales")
+    return out[0], out[1]
+
+
+def int_matmul_class(codes_a, codes_w, group_a: int = 0, group_w: int = 0) -> Optional[str]:
+    """the class the kernel picks for the packed call (codes [M, K] and [N, K]; group_a / group_w: 0 = one scale per row, G = one per G
+    codes along K), asked of the library itself (dmxq_int_matmul_class; no GPU involved), or None where the call runs the chain.
+    "row": both scales per row, 16 <= K <= 131072, K % 16 == 0 -- one int32 accumulator over all of K; "group": weight scales per
+    G in INT_MATMUL_GROUP_SIZES with K % G == 0, activation scales per row or per the same G.  None: everything else, and codes whose
+    (contiguous) base is not 16-byte aligned."""
+    from ._lib import lib
+    if codes_a.dim() != 2 or codes_w.dim() != 2:
+        return None
+    for c in (codes_a, codes_w):
+        if c.is_contiguous() and c.data_ptr() % 16:
+            return None
+    return _INT_MATMUL_CLASS_NAMES.get(lib().dmxq_int_matmul_class(codes_a.shape[0], codes_w.shape[0], codes_a.shape[1], int(group_a), int(group_w)))
+
+
+def _int_matmul_chain(ca, sa, cw, sw, G, out_dtype):
+    """the definition in torch operations.  Per-row scales: the integer product in float64 (exact below 2^53), its nearest-even
+    conversion to float32 (the int32 convert's result), the two multiplies -- the kernel's bits.  Groups: per-group float64 products,
+    scaled and added in fp32 in ascending order; torch promises no fused multiply-add, so this is the kernel's value up to the
+    rounding of the products (DESIGN.md §8 has the bound both are held to)."""
+    M, K = ca.shape
+    N = cw.shape[0]
+    if sa.dim() == 1 and sw.dim() == 1:
+        P = (ca.to(torch.float64) @ cw.to(torch.float64).t()).to(torch.float32)
+        return ((P * sa[:, None]) * sw[None, :]).to(out_dtype)
+    ng = K // G
+    a, w = ca.to(torch.float64).view(M, ng, G), cw.to(torch.float64).view(N, ng, G)
+    acc = torch.zeros((M, N), dtype=torch.float32, device=ca.device)
+    for g in range(ng):
+        p = (a[:, g] @ w[:, g].t()).to(torch.float32)
+        if sa.dim() == 2:
+            p = p * sa[:, g, None]
+        acc = acc + p * (sw[:, g] if sw.dim() == 2 else sw)[None, :]
+    return (acc if sa.dim() == 2 else acc * sa[:, None]).to(out_dtype)
+
+
+def int_matmul_packed(codes_a, scale_a, codes_w, scale_w, group_size: Optional[int] = None, out_dtype: torch.dtype = torch.float32,
+                      fused: Optional[bool] = None):
+    """y = A W^T on packed integer operands (ops.dynamic_int_pack's: int8 codes [M, K] / [N, K], float32 scales [rows] or
+    [rows, K / group_size]) as a W8A8 / W4A8 datapath computes it (DESIGN.md §8 "Integer matmul") -> [M, N] of out_dtype.
+    Two per-row scales: y = (float(P) * sa[m]) * sw[n] with P the exact int32 dot product over all of K.  Grouped weight scales
+    (activation scales per row or grouped alike): per group the exact integer P_g, acc = fma(float(P_g) [* sa[m, g]], sw[n, g], acc)
+    in ascending g, [y = acc * sa[m]].  Bit-reproducible.
+    fused=None: the int8-MFMA kernel (dmxq_int_matmul) where it applies (int_matmul_class) and its class is not listed in
+    INT_MATMUL_CHAIN_BY_DEFAULT, else the chain of torch operations (per-row scales: the same bits); True: NotImplementedError instead
+    of falling back; False: the chain."""
+    for t in (codes_a, scale_a, codes_w, scale_w):
+        require_gpu(t, "int_matmul_packed")
+    ga, gw = _int_matmul_groups(codes_a, scale_a, codes_w, scale_w, group_size, "int_matmul_packed")
+    G = int(group_size or 0)
+    if not (codes_a.shape[0] and codes_w.shape[0]):
+        fused = False   # (an empty product: the chain, whatever was asked for)
+    cls = None if fused is False else int_matmul_class(codes_a, codes_w, ga, gw)
+    with torch.no_grad():
+        return route(fused, cls, INT_MATMUL_CHAIN_BY_DEFAULT, _int_matmul_routes,
+                     lambda: _ops.int_matmul(codes_a, scale_a, codes_w, scale_w, G, out_dtype),
+                     lambda: _int_matmul_chain(codes_a, scale_a, codes_w, scale_w, G, out_dtype),
+                     lambda: (f"int_matmul_packed: no kernel for {tuple(codes_a.shape)} x {tuple(codes_w.shape)} codes with scale groups "
+                              f"{ga} / {gw} (base addresses {codes_a.data_ptr() % 16}, {codes_w.data_ptr() % 16} mod 16)"))
+
+
+def int_matmul(x, w, fmt_x, fmt_w=None, granularity_x: str = "per_token", granularity_w: str = "per_token",
+               group_size: Optional[int] = None, out_dtype: Optional[torch.dtype] = None, fused: Optional[bool] = None):
+    """x[..., K] times w[N, K]^T with both operands in dynamic symmetric integer quantisation along K (fmt_x, fmt_w: clamped
+    nearest-rounding XP[p,0] objects or shorthands, p <= 8; fmt_w defaults to fmt_x; each granularity "per_token" -- one scale per row --
+    or "per_group" with the shared group_size): packs both with ops.dynamic_int_pack and multiplies the packed operands
+    (int_matmul_packed, which takes `fused`).  -> [..., N] of out_dtype (default x.dtype).  The operands are the UNCAST tensors: a
+    dequantised integer tensor does not re-pack to its own codes.  No gradient: the result is detached."""
+    fx, fw = int_matmul_check(x, w, fmt_x, fmt_w)
+    require_gpu(x, "int_matmul")
+    require_gpu(w, "int_matmul")
+    grouped = "per_group" in (granularity_x, granularity_w)
+    if grouped != (group_size is not None):
+        raise DmxqError(f"int_matmul: group_size goes with a 'per_group' granularity, got {granularity_x!r}, {granularity_w!r}, {group_size!r}")
+    with torch.no_grad():
+        x2 = x.detach().reshape(-1, x.shape[-1])
+        ca, sa = dynamic_int_pack(x2, fx, granularity_x, group_size if granularity_x == "per_group" else None)
+        cw, sw = dynamic_int_pack(w.detach(), fw, granularity_w, group_size if granularity_w == "per_group" else None)
+        y = int_matmul_packed(ca, sa, cw, sw, group_size, out_dtype or x.dtype, fused)
+    return y.reshape(tuple(x.shape[:-1]) + (w.shape[0],))
 
 
 # ---------------------------------------------------------------------------------------------------- learned step size (LSQ / LSQ+)

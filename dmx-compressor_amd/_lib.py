@@ -34,6 +34,10 @@ SIGNATURES = {
     "dmxq_bfp_pack_cols": [_vp, _i32, _vp, _vp, _i64, _i64, _i64, _i64, _i32, _i32, _vp],
     "dmxq_bfp_bmm_class": [_i64, _i64, _i64, _i64, _i64, _i32],
     "dmxq_bfp_bmm": [_vp, _vp, _vp, _vp, _vp, _i32, _i64, _i64, _i64, _i64, _i64, _i32, _i32, _i32, _vp],
+    "dmxq_dynamic_pack_class": [_i32, _i64, _i32],
+    "dmxq_dynamic_fixed_pack": [_vp, _i32, _vp, _vp, _i64, _i64, _i32, _i32, _i32, _i32, _i32, _vp],
+    "dmxq_int_matmul_class": [_i64, _i64, _i64, _i64, _i64],
+    "dmxq_int_matmul": [_vp, _vp, _vp, _vp, _vp, _i32, _i64, _i64, _i64, _i64, _i64, _vp],
     "dmxq_weight_hypernet": [_vp, _i32, _vp, _i32, _i32, _i32, _vp, _vp, _i32, _i64, _i64, _i64, _i32, _i32, _vp],
     "dmxq_weight_hypernet_multi": [_vp, _i64, _i32, _i32, _i32, _i32, _i32, _i64, _i32, _i32, _vp],
     "dmxq_weight_hypernet_strided": [_vp, _i32, _vp, _i32, _i32, _i32, _vp, _vp, _i32, _i64, _i64, _i64, _i64, _i32, _i32, _vp],

@@ -15,7 +15,7 @@ LIB = os.path.join(HERE, "lib", "libdmxq.so")
 TORCH_LIB = os.path.join(HERE, "lib", "dmxq_torch.so")
 # "file.hip" or "file.hip#N": the file compiled with -DDMXQ_EW_PART=N into file_pN.o (elementwise.hip: three objects, approx.hip: two, in parallel);
 # the slowest compilations first (gptq.hip: 18 unrolled kernels; gptq_dynamic.hip: 5 more)
-SOURCES = ["vq.hip", "gptq.hip", "gptq_dynamic.hip", "hist_observer.hip", "error_stats.hip", "bfp.hip#1", "approx.hip#3", "approx.hip#5", "approx.hip#1", "approx.hip#2", "approx.hip#4", "elementwise.hip#2", "elementwise.hip#1", "elementwise.hip#3", "bfp_cols.hip#1", "bfp_cols.hip#2", "bfp_cols.hip#3", "bfp.hip#2", "bfp.hip#3", "bfp_urows.hip", "bfp_smallinner.hip", "bfp_slab.hip", "blockfmt.hip", "bfp_pack.hip", "hypernet.hip", "hypernet_multi.hip", "nm_mask.hip", "topk.hip", "reduce.hip", "unary.hip", "act_cast.hip", "lut16.hip", "fixed_multi.hip", "rope.hip", "hadamard.hip", "hadamard_row.hip", "dynamic_quant.hip", "dynamic_float.hip", "wanda.hip", "awq.hip", "block_scaled_float.hip", "lsq.hip", "codebook.hip", "hqq.hip", "outlier_quant.hip", "awq_clip.hip", "adaround.hip", "dynamic_cols.hip", "bfp_matmul.hip", "bfp_bmm.hip"]
+SOURCES = ["vq.hip", "gptq.hip", "gptq_dynamic.hip", "hist_observer.hip", "error_stats.hip", "bfp.hip#1", "approx.hip#3", "approx.hip#5", "approx.hip#1", "approx.hip#2", "approx.hip#4", "elementwise.hip#2", "elementwise.hip#1", "elementwise.hip#3", "bfp_cols.hip#1", "bfp_cols.hip#2", "bfp_cols.hip#3", "bfp.hip#2", "bfp.hip#3", "bfp_urows.hip", "bfp_smallinner.hip", "bfp_slab.hip", "blockfmt.hip", "bfp_pack.hip", "hypernet.hip", "hypernet_multi.hip", "nm_mask.hip", "topk.hip", "reduce.hip", "unary.hip", "act_cast.hip", "lut16.hip", "fixed_multi.hip", "rope.hip", "hadamard.hip", "hadamard_row.hip", "dynamic_quant.hip", "dynamic_float.hip", "wanda.hip", "awq.hip", "block_scaled_float.hip", "lsq.hip", "codebook.hip", "hqq.hip", "outlier_quant.hip", "awq_clip.hip", "adaround.hip", "dynamic_cols.hip", "bfp_matmul.hip", "bfp_bmm.hip", "dynamic_pack.hip", "int_matmul.hip"]
 # bit-exact fp32: no fast-math, no fma contraction; fp32 denormals stay on (gfx950 default).
 # --offload-compress (round 5): the gfx950 code objects are stored zstd-compressed inside the fat binary and unpacked by the HIP runtime at
 # load: libdmxq.so 88 MB -> 17 MB (what a gpurun snapshot pushes, what a wheel would ship), load time and kernels unchanged
@@ -80,7 +80,13 @@ NO_SCRATCH = {"lut16.hip": ["lut16_apply_kernel"], "fixed_multi.hip": ["stream_m
               "bfp_bmm.hip": ["bfp_bmm_kernel"],
               # the column-blocked pack: a lane's per-column maxima and block parameters stay in registers between its two passes over
               # the B rows; the rows themselves are read twice, never held (csrc/bfp_pack.hip)
-              "bfp_pack.hip": ["bfp_pack_cols_kernel"]}
+              "bfp_pack.hip": ["bfp_pack_cols_kernel"],
+              # the dynamic pack: a lane's raw units (up to 16 vectors) stay in registers between the extrema pass and the codes
+              # (csrc/dynamic_pack.hip)
+              "dynamic_pack.hip": ["dynp_group_kernel", "dynp_rows_kernel"],
+              # the integer matmul: a wave's 64 x 64 int32 (class row) or fp32 (class group) accumulators stay in registers through
+              # the K loop (csrc/int_matmul.hip)
+              "int_matmul.hip": ["int_matmul_kernel"]}
 
 
 # per-source flags: csrc/hadamard_row.hip is built without the packed fp32 instructions (v_pk_add / mul / fma_f32): the shared cast body
@@ -91,7 +97,8 @@ NO_SCRATCH = {"lut16.hip": ["lut16_apply_kernel"], "fixed_multi.hip": ["stream_m
 EXTRA_FLAGS = {"hadamard_row.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
                "dynamic_cols.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
                "bfp_matmul.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
-               "bfp_bmm.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
+               "bfp_bmm.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
+               "int_matmul.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
 
 
 def _check_no_scratch(src, remarks_file):
@@ -111,7 +118,7 @@ def _check_no_scratch(src, remarks_file):
                                    f"wrong; the multi-tensor kernels: every wave of a launch pays for a spilling body; "
                                    f"the error statistics: the format table must stay in registers; the Hadamard rotation: a lane's vector "
                                    f"must stay in registers; the dynamic cast: a segment's vectors must stay in registers; GPTQ with dynamic scales: a "
-                                   f"microblock must stay in registers; Wanda: the accumulators and a unit's scores must stay in registers; AWQ: a lane's slots must stay in registers; the block-scaled float cast: a lane's vectors must stay in registers; the learned step size backward: a lane's vectors and accumulators must stay in registers; the codebook cast: a lane's vectors, the table and the accumulators must stay in registers; HQQ: a lane's vector must stay in registers through the iterations; the outlier-aware cast: a lane's vector and its marks must stay in registers through the selection rounds; the AWQ clip search: a lane's weights, errors and sums must stay in registers through the candidates; AdaRound: a lane's units must stay in registers through expf and powf; the vector codebook cast: a lane's vectors and a batch's running choices must stay in registers; the full-row rotation: a lane's vectors and a column must stay in registers; the dynamic casts along a non-last dimension: a lane's rows and per-column qparams must stay in registers; the BFP matmul, 2-D and batched: a wave's accumulators must stay in registers; the column-blocked pack: a lane's per-column parameters must stay in registers) -- build.py NO_SCRATCH")
+                                   f"microblock must stay in registers; Wanda: the accumulators and a unit's scores must stay in registers; AWQ: a lane's slots must stay in registers; the block-scaled float cast: a lane's vectors must stay in registers; the learned step size backward: a lane's vectors and accumulators must stay in registers; the codebook cast: a lane's vectors, the table and the accumulators must stay in registers; HQQ: a lane's vector must stay in registers through the iterations; the outlier-aware cast: a lane's vector and its marks must stay in registers through the selection rounds; the AWQ clip search: a lane's weights, errors and sums must stay in registers through the candidates; AdaRound: a lane's units must stay in registers through expf and powf; the vector codebook cast: a lane's vectors and a batch's running choices must stay in registers; the full-row rotation: a lane's vectors and a column must stay in registers; the dynamic casts along a non-last dimension: a lane's rows and per-column qparams must stay in registers; the BFP matmul, 2-D and batched: a wave's accumulators must stay in registers; the column-blocked pack: a lane's per-column parameters must stay in registers; the dynamic pack: a lane's units must stay in registers; the integer matmul: a wave's accumulators must stay in registers) -- build.py NO_SCRATCH")
     if not seen:
         raise RuntimeError(f"{src}: no kernel matching {wanted} in the compiler's resource remarks: the NO_SCRATCH check did not run")
 

@@ -197,6 +197,62 @@ Tensor bfp_matmul_meta(const Tensor& mant_a, const Tensor& exps_a, const Tensor&
   return at::empty({mant_a.size(0), mant_w.size(0)}, mant_a.options().dtype(out_dtype));
 }
 
+// the dynamic integer cast as packed operands (csrc/dynamic_pack.hip): x viewed as [numel / segment, segment] -> int8 codes of x's shape
+// + float32 scale [numel / segment].  DMXQ_ERR_UNSUPPORTED (NotImplementedError, nothing launched): the front end runs its chain.
+std::tuple<Tensor, Tensor> dynamic_fixed_pack(const Tensor& x, int64_t segment, bool whole_rows, int64_t precision, bool symmetric, int64_t qmin,
+                                              int64_t qmax) {
+  const Tensor xc = prep(x, "dynamic_fixed_pack");
+  TORCH_CHECK(segment >= 1 && xc.numel() % segment == 0, "dynamic_fixed_pack: the segment must divide the number of elements");
+  const int64_t n = xc.numel() / segment;
+  Tensor codes = at::empty(xc.sizes(), xc.options().dtype(at::kChar));
+  Tensor scale = at::empty({n}, xc.options().dtype(at::kFloat));
+  Launch l(xc);
+  check(dmxq_dynamic_fixed_pack(xc.data_ptr(), dt_code(xc.scalar_type()), (int8_t*)codes.data_ptr(), (float*)scale.data_ptr(), n, segment,
+                                whole_rows ? 1 : 0, (int)precision, symmetric ? 1 : 0, (int)qmin, (int)qmax, l.stream), "dmxq_dynamic_fixed_pack");
+  return {codes, scale};
+}
+std::tuple<Tensor, Tensor> dynamic_fixed_pack_meta(const Tensor& x, int64_t segment, bool, int64_t, bool, int64_t, int64_t) {
+  TORCH_CHECK(segment >= 1 && x.numel() % segment == 0, "dynamic_fixed_pack: the segment must divide the number of elements");
+  return {at::empty(x.sizes(), x.options().dtype(at::kChar)), at::empty({x.numel() / segment}, x.options().dtype(at::kFloat))};
+}
+
+// the integer matmul on packed operands (csrc/int_matmul.hip): codes [M, K] / [N, K] int8, scales float32 [rows] or [rows, K / group_size]
+// -> [M, N].  DMXQ_ERR_UNSUPPORTED (NotImplementedError, nothing launched): the front end runs its chain.
+std::pair<int64_t, int64_t> int_matmul_groups(const Tensor& codes_a, const Tensor& scale_a, const Tensor& codes_w, const Tensor& scale_w,
+                                              int64_t group_size) {
+  TORCH_CHECK(codes_a.dim() == 2 && codes_w.dim() == 2 && codes_a.scalar_type() == at::kChar && codes_w.scalar_type() == at::kChar &&
+              group_size >= 0 && scale_a.scalar_type() == at::kFloat && scale_w.scalar_type() == at::kFloat &&
+              codes_a.size(1) == codes_w.size(1), "int_matmul: expects int8 codes [M, K] and [N, K], float32 scales and a group size >= 0");
+  const int64_t K = codes_a.size(1);
+  int64_t g[2];
+  const Tensor* cs[2][2] = {{&codes_a, &scale_a}, {&codes_w, &scale_w}};
+  for (int i = 0; i < 2; i++) {
+    const Tensor &c = *cs[i][0], &s = *cs[i][1];
+    if (s.dim() == 1 && s.size(0) == c.size(0)) g[i] = 0;
+    else if (group_size > 0 && K % group_size == 0 && s.dim() == 2 && s.size(0) == c.size(0) && s.size(1) == K / group_size) g[i] = group_size;
+    else TORCH_CHECK(false, "int_matmul: a scale must be [rows] or [rows, K / group_size]");
+  }
+  return {g[0], g[1]};
+}
+Tensor int_matmul(const Tensor& codes_a, const Tensor& scale_a, const Tensor& codes_w, const Tensor& scale_w, int64_t group_size,
+                  at::ScalarType out_dtype) {
+  TORCH_CHECK(codes_a.is_cuda() && scale_a.is_cuda() && codes_w.is_cuda() && scale_w.is_cuda(),
+              "int_matmul: tensors must be on the GPU (no CPU fallback)");
+  const auto g = int_matmul_groups(codes_a, scale_a, codes_w, scale_w, group_size);
+  const Tensor ca = codes_a.contiguous(), sa = scale_a.contiguous(), cw = codes_w.contiguous(), sw = scale_w.contiguous();
+  Tensor out = at::empty({ca.size(0), cw.size(0)}, ca.options().dtype(out_dtype));
+  Launch l(ca);
+  check(dmxq_int_matmul((const int8_t*)ca.data_ptr(), (const float*)sa.data_ptr(), (const int8_t*)cw.data_ptr(), (const float*)sw.data_ptr(),
+                        out.data_ptr(), dt_code(out_dtype), ca.size(0), cw.size(0), ca.size(1), g.first, g.second, l.stream), "dmxq_int_matmul");
+  return out;
+}
+Tensor int_matmul_meta(const Tensor& codes_a, const Tensor& scale_a, const Tensor& codes_w, const Tensor& scale_w, int64_t group_size,
+                       at::ScalarType out_dtype) {
+  int_matmul_groups(codes_a, scale_a, codes_w, scale_w, group_size);
+  dt_code(out_dtype);
+  return at::empty({codes_a.size(0), codes_w.size(0)}, codes_a.options().dtype(out_dtype));
+}
+
 // the column-blocked pack (csrc/bfp_pack.hip): x[..., K, N] blocked along K -> codes [..., K, N] + exps [..., K / B, N].
 // DMXQ_ERR_UNSUPPORTED or a ragged last block (NotImplementedError, nothing launched): the front end transposes and packs rows.
 std::vector<int64_t> exps_cols_shape(const Tensor& x, int64_t block_size) {
@@ -1653,6 +1709,8 @@ TORCH_LIBRARY(dmxq, m) {
   m.def("bfp_matmul(Tensor mant_a, Tensor exps_a, Tensor mant_w, Tensor exps_w, int precision_a, int precision_w, int block_size, ScalarType out_dtype) -> Tensor");
   m.def("bfp_pack_cols(Tensor x, int precision, int block_size, bool symmetric=True) -> (Tensor, Tensor)");
   m.def("bfp_bmm(Tensor mant_a, Tensor exps_a, Tensor mant_w, Tensor exps_w, int precision_a, int precision_w, int block_size, int w_layout, ScalarType out_dtype) -> Tensor");
+  m.def("dynamic_fixed_pack(Tensor x, int segment, bool whole_rows, int precision, bool symmetric, int qmin, int qmax) -> (Tensor, Tensor)");
+  m.def("int_matmul(Tensor codes_a, Tensor scale_a, Tensor codes_w, Tensor scale_w, int group_size, ScalarType out_dtype) -> Tensor");
   m.def("weight_hypernet(Tensor w, int precision, int block_size, bool symmetric, Tensor? score, int K, int M, Tensor? sq_scale, ScalarType? out_dtype=None, int block_dim=-1) -> Tensor");
   m.def("input_hypernet(Tensor x, Tensor sq_scale, int precision, int block_size, bool symmetric) -> Tensor");
   m.def("binary_cast(Tensor a, Tensor b, int op, int[] cast_a, int[] cast_b, int[] cast_out, int bfp_block=0, int bfp_precision=0) -> Tensor");
@@ -1729,7 +1787,8 @@ TORCH_LIBRARY(dmxq, m) {
   X(m, channel_sumsq); X(m, wanda_nm); X(m, channel_sumabs); X(m, awq_group_error); X(m, block_scaled_float_qdq); X(m, block_scaled_tensor_scale); \
   X(m, lsq_backward); X(m, codebook_qdq); X(m, codebook_accumulate); X(m, hqq_qdq); X(m, outlier_fixed_qdq); X(m, awq_clip); \
   X(m, adaround_forward); X(m, adaround_backward); X(m, vq_qdq); X(m, vq_accumulate); X(m, hadamard_row_qdq); \
-  X(m, dynamic_fixed_qdq_cols); X(m, dynamic_float_qdq_cols); X(m, bfp_matmul); X(m, bfp_pack_cols); X(m, bfp_bmm)
+  X(m, dynamic_fixed_qdq_cols); X(m, dynamic_float_qdq_cols); X(m, bfp_matmul); X(m, bfp_pack_cols); X(m, bfp_bmm); \
+  X(m, dynamic_fixed_pack); X(m, int_matmul)
 
 // "CUDA" is the dispatch key of HIP tensors in a ROCm build of PyTorch
 TORCH_LIBRARY_IMPL(dmxq, CUDA, m) {

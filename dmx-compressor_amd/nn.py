@@ -1117,6 +1117,66 @@ class Linear(DmxModule, torch.nn.Linear):
             return None
         return fi, fw
 
+    def _int_matmul_plan(self, input):
+        """((input format, granularity, group size), (weight ...)) when this forward can run as an integer matmul (ops.int_matmul_packed),
+        else None: both casts dynamic symmetric integer casts (set_dynamic per_token, or per_group with one G the kernel takes -- the
+        weight's, shared by a per_group input) along the last dimension, XP[p,0] clamped with nearest rounding and p <= 8, fake-quant on
+        and the observer off, no outliers / pre_transform / codebook / VQ / learned or stored-scale state in play, a dense weight with a
+        SAME storage cast, no SmoothQuant and no calibrator (OBC, Wanda, AWQ, AWQ clip, AdaRound) attached, no gradient asked"""
+        from . import ops
+        from .format import FixedPoint
+        from .observer import _SYMMETRIC
+        if not isinstance(input, torch.Tensor) or not input.is_cuda or input.dim() < 1 or input.numel() == 0 or torch.compiler.is_compiling():
+            return None
+        if len(self.input_casts) != 1 or self.weight_cast is None:
+            return None
+        plan = []
+        for c in (self.input_casts.input_cast, self.weight_cast):
+            f, dyn = c.format, c._dynamic
+            if (not isinstance(f, FixedPoint) or dyn is None or dyn[0] not in ("per_token", "per_group") or c._dynamic_dim not in (None, -1)
+                    or f.fraction != 0 or not f.clamp or not 2 <= f.precision <= 8 or f.rounding != "nearest" or c.qscheme not in _SYMMETRIC
+                    or c._outliers is not None or c.pre_transform or c._codebook is not None or c._vq is not None or c._learnable is not None
+                    or c._scaling is not None or not c._flag("fake_quant_enabled") or c._flag("observer_enabled")):
+                return None
+            plan.append((f, dyn[0], dyn[1]))
+        (_, gi, gsi), (_, gw, gsw) = plan
+        if (gw == "per_group" and gsw not in ops.INT_MATMUL_GROUP_SIZES) or (gi == "per_group" and (gw != "per_group" or gsi != gsw)):
+            return None
+        if input.shape[-1] != self.weight.shape[1] or (gw == "per_group" and self.weight.shape[1] % gsw):
+            return None
+        sq, st, sp = self.smoothquant, self.weight_storage_cast, self.weight_sparsifier
+        if sq is not None and (sq._flag("enabled") or sq._flag("dynamic") or sq.calibrating):
+            return None
+        if st is not None and not (isinstance(st.format, Same) and not st.pre_transform):
+            return None
+        if sp is not None and not isinstance(sp.sparseness, Dense):
+            return None
+        if any(o is not None for o in (self.obc, self.wanda, self.awq, self.awq_clipper, self.adarounder)):
+            return None
+        if torch.is_grad_enabled() and (input.requires_grad or self.weight.requires_grad or (self.bias is not None and self.bias.requires_grad)):
+            return None
+        return tuple(plan)
+
+    def _fused_forward(self, input, *args, **kwargs):
+        """block_matmul with two dynamic symmetric integer casts (_int_matmul_plan): the UNCAST input and weight are packed
+        (ops.dynamic_int_pack -- casting first would quantise twice: a dequantised integer tensor does not re-pack to its own codes) and
+        multiplied as integers (ops.int_matmul_packed; DESIGN.md §8 "Integer matmul"), then accum_cast, bias and output casts as ever.
+        Like the BFP route of _forward, and unlike every other _fused_forward, this opt-in CHANGES the product by design: the integer
+        dot product of a W8A8 / W4A8 datapath instead of a bf16 matmul on dequantised values."""
+        plan = self._int_matmul_plan(input) if self.block_matmul and not args and not kwargs else None
+        if plan is None:
+            return None
+        from . import ops
+        (fi, gi, gsi), (fw, gw, gsw) = plan
+        _weight = self.weight.detach()
+        _ca, _sa = ops.dynamic_int_pack(input.detach().reshape(-1, input.shape[-1]), fi, gi, gsi)
+        _cw, _sw = ops.dynamic_int_pack(_weight, fw, gw, gsw)
+        _product = ops.int_matmul_packed(_ca, _sa, _cw, _sw, gsw if gw == "per_group" else None, out_dtype=_weight.dtype)
+        _product = self.accum_cast(_product.reshape(tuple(input.shape[:-1]) + (_weight.shape[0],)))
+        _output = torch.add(_product, self._bias_ro) if self.bias is not None else _product
+        output = _output if self._output_cast_absorbed(_output) else self.output_casts(_output, output=True)
+        return output.to(input.dtype) if self.align_boundary_dtype else output
+
     def _forward(self, _input):
         _fmts = self._block_matmul_formats(_input) if self.block_matmul else None
         if _fmts is not None:   # the operands are already cast: packing a cast tensor gives its codes back (ops.bfp_pack)

@@ -62,7 +62,8 @@ const char* dmxq_status_string(int status);
  * dmxq_outlier_fixed_qdq, dmxq_outlier_class, dmxq_awq_clip, dmxq_awq_clip_class, dmxq_adaround_forward, dmxq_adaround_backward,
  * dmxq_adaround_class, dmxq_adaround_scratch_bytes, dmxq_vq_qdq, dmxq_vq_class, dmxq_vq_accumulate, dmxq_vq_workspace_bytes,
  * dmxq_hadamard_row_qdq, dmxq_hadamard_row_class, dmxq_hadamard_matrix, dmxq_dynamic_cols_class, dmxq_dynamic_fixed_qdq_cols,
- * dmxq_dynamic_float_qdq_cols, dmxq_bfp_matmul, dmxq_bfp_matmul_class, dmxq_bfp_pack_cols, dmxq_bfp_bmm, dmxq_bfp_bmm_class) leave it at 4: a caller built against 4 runs on
+ * dmxq_dynamic_float_qdq_cols, dmxq_bfp_matmul, dmxq_bfp_matmul_class, dmxq_bfp_pack_cols, dmxq_bfp_bmm, dmxq_bfp_bmm_class,
+ * dmxq_dynamic_fixed_pack, dmxq_dynamic_pack_class, dmxq_int_matmul, dmxq_int_matmul_class) leave it at 4: a caller built against 4 runs on
  * this library unchanged.  4 = round 5: + dmxq_float_qdq_multi, dmxq_fixed_float_qdq_multi; 3 = round 4: + dmxq_weight_hypernet_multi,
  * dmxq_unary_cast_table, dmxq_lut16_apply.  Nothing was ever removed or changed: a caller built against version n runs on any library >= n. */
 int dmxq_abi_version(void);
@@ -163,6 +164,38 @@ enum { DMXQ_BFPBMM_NONE = 0 };
 int dmxq_bfp_bmm_class(int64_t batch, int64_t M, int64_t N, int64_t K, int64_t block_size, int w_layout);
 int dmxq_bfp_bmm(const int8_t* mant_a, const uint8_t* exps_a, const int8_t* mant_w, const uint8_t* exps_w, void* out, int dtype_out,
                  int64_t batch, int64_t M, int64_t N, int64_t K, int64_t block_size, int prec_a, int prec_w, int w_layout, void* stream);
+
+/* Dynamic integer cast as PACKED operands (csrc/dynamic_pack.hip; DESIGN.md §8 "Integer matmul"): in [n_segments, segment] contiguous ->
+ * int8 codes of the same shape + float32 scale[n_segments], ONE launch.  Symmetric scheme only (zero point 0), the clamped
+ * nearest-rounding format XP[precision,0] (symmetric: its "(CS.)" / "(CA.)" flag; qmin / qmax: observer.get_qmin_qmax):
+ * scale = what dmxq_dynamic_fixed_qdq(symmetric_qscheme = 1) writes to scale_out, bit for bit (a NaN in the segment: eps; an Inf:
+ * Inf); code = the clamped integer that cast multiplies by the scale, so that for float32 input codes * scale is the cast itself
+ * (its -0 results are +0).  An element whose quotient x / scale is NaN packs to 0, every other one to what the clamp gives.
+ * dmxq_dynamic_pack_class: dmxq_dynamic_class's geometries (DMXQ_DYN_*) with a lane's unit of TWO 16-byte vectors: segment a power
+ * of two 16 .. 256, or -- whole_rows -- a multiple of 16 sixteen-bit / 8 float32 elements up to 16384.
+ * Taken: those segments, 2 <= precision <= 8, `in` and `codes` 16-byte aligned.  DMXQ_ERR_UNSUPPORTED, nothing launched (the caller
+ * runs its chain): anything else.  DMXQ_ERR_BAD_ARG: null pointers, negative sizes, an invalid dtype, precision < 1, qmax <= qmin. */
+int dmxq_dynamic_pack_class(int dtype, int64_t segment, int whole_rows);
+int dmxq_dynamic_fixed_pack(const void* in, int dtype_in, int8_t* codes, float* scale, int64_t n_segments, int64_t segment,
+                            int whole_rows, int precision, int symmetric, int qmin, int qmax, void* stream);
+
+/* Dynamic-scale integer matmul on the int8 matrix cores (csrc/int_matmul.hip; DESIGN.md §8 "Integer matmul"): y = A W^T on
+ * codes_a int8 [M, K] + scale_a float32, codes_w int8 [N, K] + scale_w float32; out [M, N] of dtype_out, contiguous.
+ * group_a / group_w: 0 = one scale per row (scale [M] / [N]), G = one per G codes along K (scale [M, K / G] / [N, K / G]).
+ * DMXQ_INTMM_ROW (group_a = group_w = 0, 16 <= K <= 131072, K % 16 == 0): P = sum over all of K of ca * cw in ONE int32 (exact:
+ *   127 * 127 * 131072 < 2^31); y = (float(P) * sa[m]) * sw[n]: one nearest-even int -> fp32 convert, the two fp32 multiplies in
+ *   that order, one nearest-even convert to dtype_out.
+ * DMXQ_INTMM_GROUP (group_w = G in {32, 64, 128}, K % G == 0, group_a = 0 or G): per group g the exact integer P_g from a zero
+ *   accumulator; group_a = 0: acc = fma(float(P_g), sw[n, g], acc) in ascending g from +0, y = acc * sa[m]; group_a = G:
+ *   acc = fma(float(P_g) * sa[m, g], sw[n, g], acc), y = acc; then one nearest-even convert.
+ * ONE launch, no workspace, no atomics, no split-K: bit-reproducible; capturable.
+ * dmxq_int_matmul_class: the class the entry picks (no GPU involved; it sees no pointers), NONE = refused: any other group pair, K
+ * outside the class's range, M > 65535 * 128 or N > 0x7FFFFF00.  DMXQ_ERR_UNSUPPORTED, nothing launched (the caller runs its chain):
+ * class NONE, code bases not 16-byte aligned.  DMXQ_ERR_BAD_ARG: null pointers, negative sizes, an invalid dtype.  M * N == 0: DMXQ_OK. */
+typedef enum { DMXQ_INTMM_NONE = 0, DMXQ_INTMM_ROW = 1, DMXQ_INTMM_GROUP = 2 } dmxq_int_matmul_geometry;
+int dmxq_int_matmul_class(int64_t M, int64_t N, int64_t K, int64_t group_a, int64_t group_w);
+int dmxq_int_matmul(const int8_t* codes_a, const float* scale_a, const int8_t* codes_w, const float* scale_w, void* out, int dtype_out,
+                    int64_t M, int64_t N, int64_t K, int64_t group_a, int64_t group_w, void* stream);
 
 /* Low-bit floating point Q->DQ ("FP[s|e|m,bias](F|_ N|S)").
  * Replaces: numerical/format.py:208-233 FloatingPoint.cast -> quant_function.py:120-152 float_quantize
